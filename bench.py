@@ -22,23 +22,34 @@ step order from a dedicated thread while later steps run.
 job, frame i on rank i mod N (64 / N frames per rank and step), the step's label blocks gathered to rank 0 in ONE RCCL gather;
 `scaling` is then "strong" and `value` still the whole job's points per second.
 
+A plain run does what `value` needs and no more: set-up, the W warm-up steps, the K timed steps, the label check of the last
+timed step against the oracle's committed hashes (it voids `value`, below), the outputs if ``--dump-outputs`` asks for them, and
+the JSON line.  ``--full`` adds the measurements marked (--full) below, each in runs of its own after the timed region; without
+it their fields are null.
+``--dump-outputs DIR``: after the timed steps, DIR/labels.npy holds what the timed path returned for the frames of its last step:
+the per-point labels, [frames, k] float32 (region id; -1 = F3DS_NO_LABEL; float64 for frames of 2^24 points or more), k = every
+point when the block fits in 60 MB, else a fixed seeded sample of point positions (ascending, the same in every frame).  The
+frames are seeded, so two builds run with the same arguments can be compared output for output.  With N ranks rank 0 writes
+its own frames.
+
 The JSON line also carries
   value              -- whole-job Mpoints/s with the frames resident in HBM when the timed region starts and the
                         labels left in HBM (the bench contract of this build: a PCIe-inclusive rate is never `value`);
                         `value_hbm_resident` repeats it under an explicit name;
-  value_host_io      -- the metric as SURVEY.md 8d words it (host buffer in -> per-point labels in a host buffer):
+  value_host_io      -- (--full) the metric as SURVEY.md 8d words it (host buffer in -> per-point labels in a host buffer):
                         the same loop with the frames in pinned host memory and the labels delivered to pinned host
                         memory, PCIe both ways inside the timed region; `value_survey_8d` repeats its number at top level;
-  config5_batch_latency_ms -- BASELINE config 5 as literally stated, from an idle GPU: wall time of ONE batch of 64 frames
+  single_frame_latency_ms -- (--full) one frame at a time on one stream, nothing else in flight;
+  config5_batch_latency_ms -- (--full) BASELINE config 5 as literally stated, from an idle GPU: wall time of ONE batch of 64 frames
                         as one call on one GPU (the N=1 shape) and of ONE call of 8 frames (what each GPU runs at N=8);
-  roofline           -- the dominant kernel is the merge loop (k_batched<d_merge_*>: first by total kernel time in the
+  roofline           -- (--full) the dominant kernel is the merge loop (k_batched<d_merge_*>: first by total kernel time in the
                         rocprofv3 trace of this same command, the newest profiles/r*_kernel_stats.csv); its launch duration is
                         measured live by a pair of HIP events around that one dispatch on the call's stream inside
                         libf3ds (f3ds_result.ms_stage[5]) and averaged over the timed region's calls.  achieved =
                         20 B/point x points per launch / mean launch duration, against the 8 TB/s HBM3E peak;
                         `stages` = the same figure for every stage of a call (sequences of many launches);
                         `whole_path` = the timed region as a whole, with the PMC-measured HBM traffic of all kernels;
-  cpu_baseline       -- the CPU oracle (kind "port": the reference needs PCL/OpenCV and cannot be built here) on the
+  cpu_baseline       -- (--full) the CPU oracle (kind "port": the reference needs PCL/OpenCV and cannot be built here) on the
                         same workload, rank 0 at N=1 only: one frame on one core (the reference is single-threaded)
                         through the libm-linked build of the oracle -- what a PCL/OpenCV build calls; its labels are
                         first checked against the shared-math build's, whose time is reported beside it --, and
@@ -58,6 +69,7 @@ FRAMES_PER_STEP = 64              # BASELINE.json config 5: a batch of 64 synthe
 STAGES = ["voxelise", "neighbours+normals", "seeds", "sweeps", "summaries+adjacency+weights", "merge", "labels"]
 ALG_BYTES_PER_POINT = 20          # 16 B read of {x,y,z,rgba} + 4 B label write
 HBM_PEAK_GBS = 8000.0             # MI355X HBM3E (guides/MI355X_MICROARCH.md)
+DUMP_BYTES = 60 * 10**6           # --dump-outputs: most bytes of labels written (64 MB at most with the file's header)
 
 
 def parse_args():
@@ -69,12 +81,32 @@ def parse_args():
     ap.add_argument("--groups", type=int, default=6, help="batch calls in flight per GPU (libf3ds lends each a stream of its own; measured 4: 2 080, 6: 2 200, 7: 1 990, 8: 1 820 Mpoints/s at --steps 20)")
     ap.add_argument("--width", type=int, default=1000)
     ap.add_argument("--height", type=int, default=1000)
-    ap.add_argument("--host-io-steps", type=int, default=-1, help="steps of the pinned-host-in / host-out pass (default min(steps, 12); 0 = skip)")
+    ap.add_argument("--host-io-steps", type=int, default=-1, help="(--full) steps of the pinned-host-in / host-out pass (default min(steps, 12); 0 = skip)")
     ap.add_argument("--host-io-groups", type=int, default=0, help="batch calls in flight in the host-in / host-out pass (0 = as --groups): a call is longer there by its PCIe copies")
     ap.add_argument("--strong", action="store_true", help="strong scaling: one 64-frame batch per step for the whole job, frame i on rank i mod N (BASELINE config 5 as written); default: weak, 64 frames per step on every rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--skip-latency", action="store_true", help="no lone-frame / one-batch latency runs after the timed region (profile runs: only the timed loop's launches in the trace)")
-    return ap.parse_args()
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU oracle baseline")
+    ap.add_argument("--skip-latency", action="store_true", help="(--full) no lone-frame / one-batch latency runs after the timed region (profile runs: only the timed loop's launches in the trace)")
+    ap.add_argument("--full", action="store_true", help="also the measurements beside `value`: host-in / host-out pass, latencies, roofline, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last step's labels to DIR/labels.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(directory, labels, seed=0):
+    """--dump-outputs: the per-point labels of the last timed step, [frames, points] int32 (F3DS_NO_LABEL reads as -1), as DIR/labels.npy.
+    Region ids are below the frame's point count, so float32 holds them exactly under 2^24 points (float64 from there).  A block larger
+    than DUMP_BYTES keeps every frame and a fixed sample of point positions (seeded, ascending, the same in every frame)."""
+    import numpy as np
+    frames, n = labels.shape
+    dt = np.dtype(np.float32 if n < (1 << 24) else np.float64)
+    k = min(n, max(1, DUMP_BYTES // (dt.itemsize * frames)))
+    cols = np.arange(n) if k == n else np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+    out = np.ascontiguousarray(labels[:, cols]).astype(dt)
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "labels.npy"), out)
+    return out
 
 
 def cpu_baseline_record(npts, cpu_s, sm_s, main_s, libm_same, host_cpus):
@@ -244,7 +276,7 @@ def main():
     if os.environ.get("F3DS_BENCH_MEMINFO"):                      # development: HBM in use after warm-up (contexts are grow-only)
         free, total = torch.cuda.mem_get_info(dev)
         print("rank %d: %.1f GB of %.1f GB HBM in use" % (rank, (total - free) / 2**30, total / 2**30), file=sys.stderr, flush=True)
-    mode["record"] = True
+    mode["record"] = args.full          # per-stage device times of the timed calls: the roofline (--full)
     t0 = time.perf_counter()
     plan = pipe.run(args.steps)
     barrier()
@@ -254,9 +286,13 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # the labels of the last timed step (its block of the ring), read back once: the label check below and --dump-outputs
+    last_block = label_blocks[(args.steps - 1) % n_blocks].cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_block)
 
-    # the same loop, frames from pinned host memory, labels into pinned host memory (PCIe inside the timed region)
-    hio_steps = min(args.steps, 12) if args.host_io_steps < 0 else args.host_io_steps
+    # (--full) the same loop, frames from pinned host memory, labels into pinned host memory (PCIe inside the timed region)
+    hio_steps = 0 if not args.full else min(args.steps, 12) if args.host_io_steps < 0 else args.host_io_steps
     host_io = None
     if hio_steps > 0:
         host_frames.extend(torch.from_numpy(f).pin_memory() for f in frames_host)
@@ -322,7 +358,7 @@ def main():
     try:
         import hashlib
         gold = json.load(open(os.path.join(ROOT, "tests", "golden", "oracle_golden_big.json")))
-        blk = label_blocks[(args.steps - 1) % n_blocks].cpu().numpy()
+        blk = last_block
         checked, bad = 0, []
         if npts == 1000 * 1000 and not os.environ.get("F3DS_BENCH_THRESHOLD"):      # (another threshold gives other labels: such a run is void anyway, below)
             with ThreadPoolExecutor(16) as ex:
@@ -346,18 +382,19 @@ def main():
         parity = {"error": repr(e)}
 
     merge_layouts = {}      # which merge kernel every call group's last batch call ran (before the lone frames below overwrite it)
-    for grp in ctxs[:ngroups]:
+    for grp in ctxs[:ngroups] if args.full else []:
         try:
             lay = grp[0].merge_layout()
             merge_layouts[lay] = merge_layouts.get(lay, 0) + 1
         except Exception:
             pass
-    # single-frame latency (one stream, nothing else in flight) for the record
+    # (--full) single-frame latency (one stream, nothing else in flight) for the record
+    skip_latency = args.skip_latency or not args.full
     barrier()
     tl = time.perf_counter()
-    for s in range(0 if args.skip_latency else 3):
+    for s in range(0 if skip_latency else 3):
         ctxs[0][0].segment(frames_dev[s].data_ptr(), prm, labels_out=label_blocks[0][0].data_ptr(), n=npts, on_device=True)
-    latency_ms = (time.perf_counter() - tl) / 3 * 1e3 if not args.skip_latency else 0.0
+    latency_ms = (time.perf_counter() - tl) / 3 * 1e3 if not skip_latency else 0.0
     res = ctxs[0][0].result
     # BASELINE config 5 as literally stated ("a batch of 64 frames sharded over 8 GPUs"), from an idle GPU: ONE batch of 64 frames as one
     # call on this GPU (N = 1), and ONE call of 8 frames (each GPU's share at N = 8); frames and labels in HBM; median of 3 after one untimed call
@@ -371,7 +408,7 @@ def main():
             times.append((time.perf_counter() - t1) * 1e3)
         return sorted(times[1:])[1]
     batch_latency = None
-    if nbatch >= FRAMES_PER_STEP and FPS == FRAMES_PER_STEP and not args.skip_latency:      # (a --strong rank at N > 1 holds fewer than 64 frames)
+    if nbatch >= FRAMES_PER_STEP and FPS == FRAMES_PER_STEP and not skip_latency:      # (a --strong rank at N > 1 holds fewer than 64 frames)
         b64, b8 = one_call_ms(FPS), one_call_ms(8)
         batch_latency = {"one_batch_of_64_frames_one_gpu": round(b64, 3), "one_call_of_8_frames": round(b8, 3),
                          "mpoints_per_s_64": round(FPS * npts / b64 / 1e3, 1), "mpoints_per_s_8": round(8 * npts / b8 / 1e3, 1),
@@ -433,7 +470,7 @@ def main():
                     "stages": stages,
                     "stage_ms_per_call": {STAGES[i]: round(mean_stage[i], 4) for i in range(7)}}
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             from conftest import CpuChecker
             import hashlib
             # The baseline is timed on the libm-linked build of the oracle (glibc log / exp / cbrt / atan2 ...: what a real PCL / OpenCV build calls);
@@ -490,7 +527,7 @@ def main():
         if invalid:
             value = None
         line = {"metric": "Mpoints/sec segmented end-to-end, 1M-pt RGB-D frames", "value": round(value, 3) if value is not None else None, "invalid": invalid, "unit": "Mpoints/s", "n_gpus": world,
-                "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
+                "steps": args.steps, "warmup": args.warmup, "full": args.full, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
                 "scaling": "strong" if args.strong else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                 "config": {"workload": ("step = ONE batch of %d distinct synthetic %dx%d (%d-point) XYZRGBA frames for the whole job, frame i on rank i mod N (BASELINE config 5 as written, seeds 1000..1063), "
                                         "-v 0.008 -s 0.08 --AL --CVX -t %g, frames resident in HBM" % (world * FPS, args.width, args.height, npts, prm.threshold)) if args.strong else
@@ -507,9 +544,9 @@ def main():
                 "value_survey_8d": host_io["value"] if host_io else None,
                 "value_note": "`value`: frames resident in HBM, labels left in HBM (the bench contract: a PCIe-inclusive rate is never `value`); `value_survey_8d` = `value_host_io.value`: "
                               "pinned host buffer in -> labels in a pinned host buffer, the metric as SURVEY.md 8d words it",
-                "value_host_io": host_io, "labels_checked": parity, "single_frame_latency_ms": round(latency_ms, 3), "config5_batch_latency_ms": batch_latency,
+                "value_host_io": host_io, "labels_checked": parity, "single_frame_latency_ms": round(latency_ms, 3) if args.full else None, "config5_batch_latency_ms": batch_latency,
                 "strong_scaling_estimate": strong_estimate(batch_latency, npts),
-                "library": lib_text, "roofline": roofline, "cpu_baseline": cpu}
+                "library": lib_text, "roofline": roofline if args.full else None, "cpu_baseline": cpu}
     for grp in ctxs:
         for c in grp:
             c.close()

@@ -234,6 +234,27 @@ def test_bench_cpu_baseline_is_voided_when_the_libm_oracle_disagrees():
     assert bench.strong_estimate(None, 1000000) is None
 
 
+def test_bench_dump_outputs_is_exact_bounded_and_repeatable(tmp_path):
+    """bench.py --dump-outputs: the last step's labels as float32 (F3DS_NO_LABEL as -1, region ids exact); a small block whole, a
+    bench-sized block as a seeded sample of point positions shared by every frame, under 64 MB, the same sample on every run."""
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    rng = np.random.default_rng(5)
+    small = rng.integers(-1, 300, size=(64, 19200)).astype(np.int32)
+    out = bench.dump_outputs(str(tmp_path / "a"), small)
+    got = np.load(tmp_path / "a" / "labels.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.astype(np.float64)) and np.array_equal(out, got)
+    big = np.broadcast_to(np.arange(1000000, dtype=np.int32) - 1, (64, 1000000))      # label = point position - 1
+    bench.dump_outputs(str(tmp_path / "b"), big)
+    bench.dump_outputs(str(tmp_path / "c"), big)
+    b, c = np.load(tmp_path / "b" / "labels.npy"), np.load(tmp_path / "c" / "labels.npy")
+    assert b.dtype == np.float32 and b.shape[0] == 64 and 100000 < b.shape[1] < 1000000 and np.array_equal(b, c)
+    assert os.path.getsize(tmp_path / "b" / "labels.npy") <= 64 * 10**6
+    cols = b[0].astype(np.int64) + 1         # the sampled positions: distinct, ascending, the same in every frame
+    assert np.all(b == b[0]) and np.all(np.diff(cols) > 0) and cols[0] >= 0 and cols[-1] < 1000000
+
+
 def _strong_worker(rank, world, port, n_steps, q):
     """bench.py --strong on CPU tensors: ONE batch of 8 frames per step for the whole job, frame i on rank i mod N; every rank runs its 8 / N frames through
     the step pipeline and the step's label blocks go to rank 0 in one gather, where block r row k is global frame k * N + r of that step."""

@@ -1202,10 +1202,12 @@ def test_bench_distributed_bookkeeping_with_one_forced_rank(tmp_path):
     import sys
     env = dict(os.environ, F3DS_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64", "--groups", "2", "--width", "160", "--height", "120",
-                        "--host-io-steps", "0", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900)
+                        "--host-io-steps", "0", "--no-cpu-baseline", "--full", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode in (0, 1), r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["steps"] == 2 and line["unit"] == "Mpoints/s" and line["scaling"] == "weak"
+    lab = np.load(tmp_path / "out" / "labels.npy")          # --dump-outputs: the last step's 64 frames, every point (small frames)
+    assert lab.dtype == np.float32 and lab.shape == (64, 160 * 120) and lab.min() >= -1 and lab.max() < 160 * 120
     assert "RCCL gather" in line["config"]["label_gather"] and line["config"]["frames_timed"] == 128
     assert line["roofline"]["kernel"].startswith("k_batched<d_merge") and line["library"].startswith("f3ds 1.2.0 src:")
     # 160x120 frames are not BASELINE's workload: the line carries no `value`, the rate sits under what_if_value
@@ -1222,7 +1224,7 @@ def test_bench_strong_mode_with_one_forced_rank(tmp_path):
     import sys
     env = dict(os.environ, F3DS_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--strong", "--steps", "2", "--warmup", "1", "--batch", "64", "--groups", "2", "--width", "160",
-                        "--height", "120", "--host-io-steps", "0", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900)
+                        "--height", "120", "--host-io-steps", "0", "--no-cpu-baseline", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode in (0, 1), r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["scaling"] == "strong" and line["config"]["frames_timed"] == 128 and line["config"]["frames_per_step_per_gpu"] == 64
