@@ -140,6 +140,11 @@ def load_library(path=None):
     lib.f3ds_cluster_supervoxels.argtypes = [vp, ctypes.POINTER(SupervoxelSet), vp, sz, ctypes.POINTER(Params), vp, vp, ctypes.POINTER(Result)]
     lib.f3ds_cluster_supervoxels.restype = ctypes.c_int
     lib.f3ds_get_regions.argtypes = [vp, vp, vp, vp, vp, vp, sz, ctypes.POINTER(sz)]; lib.f3ds_get_regions.restype = ctypes.c_int
+    if hasattr(lib, "f3ds_labels_at_thresholds"):      # (hierarchy levels; F3DS_LIB may point at an older build during A/B runs)
+        lib.f3ds_labels_at_thresholds.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]; lib.f3ds_labels_at_thresholds.restype = ctypes.c_int
+        lib.f3ds_labels_at_thresholds_batch.argtypes = [ctypes.POINTER(vp), ctypes.c_int, vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.c_int, vp]
+        lib.f3ds_labels_at_thresholds_batch.restype = ctypes.c_int
+        lib.f3ds_get_merge_tree.argtypes = [vp, vp, vp, vp, sz, ctypes.POINTER(sz)]; lib.f3ds_get_merge_tree.restype = ctypes.c_int
     lib.f3ds_get_region_voxels.argtypes = [vp, vp, vp, vp, sz, ctypes.POINTER(sz)]; lib.f3ds_get_region_voxels.restype = ctypes.c_int
     lib.f3ds_multi_create.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]; lib.f3ds_multi_create.restype = ctypes.c_int
     lib.f3ds_multi_destroy.argtypes = [vp]; lib.f3ds_multi_destroy.restype = None
@@ -362,6 +367,37 @@ class Context:
         labels = np.empty(int(self.result.n_points) or self._n, np.uint32)      # f3ds_recluster writes one label per point of the frame
         _check(self.lib, self.lib.f3ds_recluster(self.handle, ctypes.byref(params), labels.ctypes.data, 0, ctypes.byref(self.result)))
         return labels
+
+    def _level_count(self):
+        return int(self.result.n_points) or self._n
+
+    def labels_at_thresholds(self, thresholds, out=None, on_device=False):
+        """f3ds_labels_at_thresholds: the labels of every threshold t <= T of the last cluster run (segment / recluster /
+        cluster_supervoxels at T) from that run's merge log, without merging again.  Returns (labels, n_regions): labels is a
+        (k, n) uint32 array whose row l equals recluster(threshold=t_l), n_regions a (k,) uint32 array.  ``on_device``: ``out`` is a
+        device buffer of k * n uint32 (a torch tensor or a pointer) written in place, and labels is ``out``."""
+        t = np.ascontiguousarray(np.atleast_1d(np.asarray(thresholds, np.float32)).ravel())
+        k, n = len(t), self._level_count()
+        nreg = np.zeros(max(k, 1), np.uint32)
+        if on_device:
+            ptr = _device_ptr(out)
+            labels = out
+        else:
+            labels = np.empty((k, n), np.uint32) if out is None else out
+            if not (isinstance(labels, np.ndarray) and labels.dtype == np.uint32 and labels.flags.c_contiguous and labels.size == k * n):
+                raise ValueError("out must be a contiguous uint32 array of k * n = %d entries" % (k * n))
+            ptr = labels.ctypes.data
+        _check(self.lib, self.lib.f3ds_labels_at_thresholds(self.handle, t.ctypes.data, k, ptr, 1 if on_device else 0, nreg.ctypes.data))
+        return labels, nreg[:k]
+
+    def merge_tree(self):
+        """f3ds_get_merge_tree: the merges of the last cluster run in the order performed, as (survivor, absorbed, weight) arrays of
+        supervoxel labels (the caller's keys after cluster_supervoxels) and float32 weights."""
+        n = ctypes.c_size_t()
+        _check(self.lib, self.lib.f3ds_get_merge_tree(self.handle, None, None, None, 0, ctypes.byref(n)))
+        a = np.zeros(n.value, np.uint32); b = np.zeros(n.value, np.uint32); w = np.zeros(n.value, np.float32)
+        _check(self.lib, self.lib.f3ds_get_merge_tree(self.handle, a.ctypes.data, b.ctypes.data, w.ctypes.data, n.value, ctypes.byref(n)))
+        return a, b, w
 
     def evaluate(self, truth_point_labels):
         """Scores of the current segmentation against per-point ground-truth labels (Testing::eval_performance)."""
@@ -717,6 +753,38 @@ def segment_batch(ctxs, points, params, labels_out=None, n=None, on_device=False
     for c, r in zip(ctxs, results):
         ctypes.memmove(ctypes.byref(c.result), ctypes.byref(r), ctypes.sizeof(Result))
     return out
+
+
+def _device_ptr(buf):
+    """device address of a torch tensor / an integer pointer"""
+    if buf is None:
+        raise ValueError("on_device needs a device output buffer")
+    return ctypes.c_void_p(buf.data_ptr() if hasattr(buf, "data_ptr") else int(buf))
+
+
+def labels_at_thresholds_batch(ctxs, thresholds, out=None, on_device=False):
+    """f3ds_labels_at_thresholds_batch: Context.labels_at_thresholds for every context at once (one GPU, one dispatch per kernel).
+    Returns (list of (k, n_i) uint32 label arrays, (len(ctxs), k) uint32 region counts).  ``on_device``: ``out`` is a list of device
+    buffers (torch tensors or pointers) of k * n_i uint32 each, written in place and returned."""
+    lib = load_library()
+    t = np.ascontiguousarray(np.atleast_1d(np.asarray(thresholds, np.float32)).ravel())
+    k, m = len(t), len(ctxs)
+    vp = ctypes.c_void_p
+    handles = (vp * m)(*[c.handle for c in ctxs])
+    if on_device:
+        if out is None or len(out) != m:
+            raise ValueError("on_device needs one device output buffer per context")
+        labels = list(out)
+        lp = (vp * m)(*[_device_ptr(o) for o in out])
+    else:
+        labels = [np.empty((k, c._level_count()), np.uint32) for c in ctxs] if out is None else list(out)
+        for c, o in zip(ctxs, labels):
+            if not (isinstance(o, np.ndarray) and o.dtype == np.uint32 and o.flags.c_contiguous and o.size == k * c._level_count()):
+                raise ValueError("out[i] must be a contiguous uint32 array of k * n_i entries")
+        lp = (vp * m)(*[vp(o.ctypes.data) for o in labels])
+    nreg = np.zeros((max(m, 1), max(k, 1)), np.uint32)
+    _check(lib, lib.f3ds_labels_at_thresholds_batch(handles, m, t.ctypes.data, k, lp, 1 if on_device else 0, nreg.ctypes.data))
+    return labels, nreg[:m, :k]
 
 
 def segment(points, params=None, device=0):

@@ -6,7 +6,8 @@
 // Added (additive): -o <pcd> coloured voxel cloud (Clustering::get_colored_cloud), --labels <file>
 // per-point uint32 region ids, --gpu <id>, --gpus <N> (label files only: the files are sharded over N GPUs, file i on GPU i mod N, one host thread per
 // GPU, labels gathered on GPU 0 over RCCL: f3ds_multi_*), --dump <dir> (what visualize() draws, as PCD files), --refine <n> (refineSupervoxels, :369-375), --stream <depth> (label files only: the files go through the frame
-// pipeline f3ds_stream_*, reading ahead of the GPU, no evaluation).  Without -t the threshold is chosen by the ground-truth sweep
+// pipeline f3ds_stream_*, reading ahead of the GPU, no evaluation), --levels <t1,t2,...> (with -p and --labels: <file>.L<i> at each t_i <= -t, from the
+// one merge run: f3ds_labels_at_thresholds).  Without -t the threshold is chosen by the ground-truth sweep
 // (all_thresh 0.8..1 step 0.005 + best_thresh, :428-437) and the <-f name>_*.csv score files are written
 // (:471, manageAllPerformances); every file is scored against its `label` field (:462-463).
 #include <algorithm>
@@ -86,9 +87,36 @@ int main(int argc, char** argv) {
                " --dump <dir>                   (voxel centroids, supervoxel normals, adjacency graph, refined cloud as PCD: what the viewer shows) \n\t"
                " --stream <depth>               (with -t and --labels: files through the frame pipeline, <depth> in flight) \n\t"
                " --refine <iterations>          (refineSupervoxels as main() does with 3, :369-375; with -o also <out.pcd>.refined) \n\t"
+               " --levels <t1,t2,...>           (with -p and --labels: also <file>.L<i>, the labels at threshold t_i <= -t (default: the largest), from one merge run) \n\t"
                " --bench <frames>               (no input files: <frames> synthetic 1M-point RGB-D frames through the path, with --gpus N sharded and pipelined; prints Mpoints/s) \n",
                argv[0]);
         return 1;
+    }
+    // --levels: the labels at several thresholds from one merge run (f3ds_labels_at_thresholds).  Its argument errors are found here,
+    // before any device call.
+    std::vector<float> levels;
+    if (find_switch(argc, argv, "--levels")) {
+        std::string spec;
+        parse(argc, argv, "--levels", spec);
+        for (size_t pos = 0; pos <= spec.size();) {
+            const size_t end = spec.find(',', pos) == std::string::npos ? spec.size() : spec.find(',', pos);
+            const std::string tok = spec.substr(pos, end - pos);
+            char* stop = nullptr;
+            const float t = tok.empty() ? 0.0f : strtof(tok.c_str(), &stop);
+            if (tok.empty() || *stop != '\0' || !std::isfinite(t)) { fprintf(stderr, "--levels takes a comma-separated list of finite thresholds\n"); return 1; }
+            levels.push_back(t);
+            pos = end + 1;
+        }
+        float t_run = 0;
+        const bool t_given = find_switch(argc, argv, "-t");
+        if (t_given) parse(argc, argv, "-t", t_run);
+        if (find_switch(argc, argv, "-d") || find_switch(argc, argv, "--gpus") || find_switch(argc, argv, "--stream") || find_switch(argc, argv, "--bench") ||
+            !find_switch(argc, argv, "-p") || !find_switch(argc, argv, "--labels")) {
+            fprintf(stderr, "--levels needs -p <pcd-file> and --labels <file>, and does not take -d, --gpus, --stream or --bench\n");
+            return 1;
+        }
+        for (const float t : levels)
+            if (t_given && t > t_run) { fprintf(stderr, "--levels: threshold %g is above -t %g (levels come from the merge run to -t)\n", t, t_run); return 1; }
     }
     verbose = find_switch(argc, argv, "--V");
     const bool disable_transform = find_switch(argc, argv, "--NT");
@@ -114,10 +142,11 @@ int main(int argc, char** argv) {
         fprintf(stderr, "No input file or directory specified\n");
         return 1;
     }
-    const bool thresh_specified = find_switch(argc, argv, "-t");
+    const bool thresh_specified = find_switch(argc, argv, "-t") || !levels.empty();      // (--levels without -t: the run goes to the largest level)
     f3ds_params prm;
     f3ds_default_params(&prm);
     float thresh = 0;
+    if (!levels.empty() && !find_switch(argc, argv, "-t")) thresh = *std::max_element(levels.begin(), levels.end());
     if (thresh_specified) { parse(argc, argv, "-t", thresh); DEBUG("Using threshold: %f\n", thresh); }
     else DEBUG("Using automatic threshold\n");
     if (find_switch(argc, argv, "-v")) parse(argc, argv, "-v", prm.voxel_res);
@@ -375,6 +404,19 @@ int main(int argc, char** argv) {
                 FILE* f = fopen((out_labels + suffix).c_str(), "wb");
                 if (!f || fwrite(labels.data(), 4, n, f) != n) { fprintf(stderr, "writing %s failed\n", out_labels.c_str()); if (f) fclose(f); f3ds_destroy(ctx); return 1; }
                 fclose(f);
+                if (!levels.empty()) {      // <file>.L<i>: byte-identical to the --labels file of a -t t_i run
+                    const int K = (int)levels.size();
+                    std::vector<uint32_t> lv((size_t)K * n);
+                    rc = f3ds_labels_at_thresholds(ctx, levels.data(), K, lv.data(), 0, nullptr);
+                    if (rc == F3DS_ERR_LOGIC && res.n_voxels == 0) { std::fill(lv.begin(), lv.end(), F3DS_NO_LABEL); rc = F3DS_OK; }      // (a frame without voxels: every level is its labels)
+                    if (rc) { fprintf(stderr, "f3ds_labels_at_thresholds: %s %s\n", f3ds_strerror(rc), f3ds_last_hip_error()); f3ds_destroy(ctx); return 1; }
+                    for (int l = 0; l < K; ++l) {
+                        const std::string name = out_labels + suffix + ".L" + std::to_string(l);
+                        FILE* g = fopen(name.c_str(), "wb");
+                        if (!g || fwrite(lv.data() + (size_t)l * n, 4, n, g) != n) { fprintf(stderr, "writing %s failed\n", name.c_str()); if (g) fclose(g); f3ds_destroy(ctx); return 1; }
+                        fclose(g);
+                    }
+                }
             }
         }
         if (!dump_dir.empty()) {

@@ -11,6 +11,7 @@
 //                d_edge_deltas, d_lambda / d_cdf_*, d_edge_weights
 //   5 merge      d_inc_build, d_merge_il_t<4 or 8 waves, per-edge arrays in LDS or L2> (one persistent workgroup per frame), d_merge (global memory)
 //   6 labels     d_relabel (union-find relabel in LDS + per-point label write; d_region_ids + d_point_labels beyond 12 k supervoxels)
+//   levels       (f3ds_labels_at_thresholds, off the segment path) d_level_log, d_level_prefix, d_level_labels | d_level_tables + d_level_points (f3ds_levels.inc)
 // Every frame RECORDS its kernel calls; flush() zips the records of a batch into one dispatch per kernel (grid.y = frame).
 //
 // Layout in HBM: points stay as the caller's 16-byte records (one global_load_dwordx4 per lane);
@@ -21,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <atomic>
 #include <map>
 #include <chrono>
@@ -38,10 +40,12 @@
 #include "f3ds_glasbey.h"
 #include "f3ds_eval.h"
 #include "f3ds_dev.h"
+#include "f3ds_levels.h"
 
 using namespace f3ds;
 
 #include "f3ds_kernels.inc"
+#include "f3ds_levels.inc"
 
 // ================================================================================================
 // batched launch machinery
@@ -109,7 +113,7 @@ const int g_inc_shift = [] { const char* e = dev_getenv("F3DS_INC_SHIFT"); retur
 // call of the library (f3ds_segment_batch, f3ds_recluster, f3ds_refine_supervoxels) into this per-thread struct -- not per frame on the hot path,
 // where hundreds of getenv() scans per call would also race with a setenv from another thread.  Tests still see per-call values.
 struct Switches {
-    bool direct_labels = false, copy_stream = true, copy_duplex = false, split_voxel_accum = false, sweep_tiles = true, merge_spec = true, force_global_merge = false, no_stream_pool = false, sort_pairs = false, host_prof = false, trace_err = false, vox_hash = true, vox_tiles_forced = false;
+    bool direct_labels = false, copy_stream = true, copy_duplex = false, split_voxel_accum = false, sweep_tiles = true, merge_spec = true, force_global_merge = false, no_stream_pool = false, sort_pairs = false, host_prof = false, trace_err = false, vox_hash = true, vox_tiles_forced = false, levels_global = false;
     int normals_threads = 0, merge_nw = 0, merge_keys = -1; uint32_t tile_holes = 0, ilist_slack = 32, r_rounds = F3DS_R_ROUNDS; long relabel_lds_cap = -1;
     void read() {
         auto on = [](const char* n) { return dev_getenv(n) != nullptr; };
@@ -123,6 +127,7 @@ struct Switches {
         { const long v = num("F3DS_MERGE_NW", 0); merge_nw = v == 4 ? 4 : (v ? 8 : 0); }
         { const char* e = dev_getenv("F3DS_MERGE_KEYS"); merge_keys = !e ? -1 : (!strcmp(e, "lds") ? 2 : (!strcmp(e, "global") ? 1 : 0)); }
         relabel_lds_cap = num("F3DS_RELABEL_LDS_CAP", -1);
+        levels_global = num("F3DS_LEVELS_GLOBAL", 0) != 0;      // (tests: the hierarchy levels take the global-table form on small frames too)
         { const long v = num("F3DS_R_ROUNDS_RUN", F3DS_R_ROUNDS); r_rounds = v >= 1 && v <= F3DS_R_ROUNDS ? (uint32_t)v : (uint32_t)F3DS_R_ROUNDS; }
         { const long v = num("F3DS_ILIST_SLACK", 32); ilist_slack = v >= 1 && v <= 32 ? (uint32_t)v : 32u; }      // tests: a short incident-list pool (the merge stage then reruns with a larger one)
     }
@@ -192,8 +197,9 @@ struct f3ds_ctx {
     Buf tstamp, tround, hdirty, htiles, htcnt, vwl, vwl2, vtmask, glut, truth_pts, tsum, tcol, tlab, ctab, csize, eroot, eincl;      // ground-truth evaluation
     Buf hcnt, pslot, vlist;      // stage 0, tile path: per (tile, entry) point count / list base / leaf ordinal; per point its (entry, rank in tile); per-leaf point lists
     Buf u_src, u_voff, u_xyz, u_rgba, u_cent, u_nrm;      // f3ds_cluster_supervoxels: the caller's supervoxels as uploaded
-    Buf deltas, skeys0, skeys1, svals0, svals1, cdf_hist, cdf, root, rrank, pool, rstart, rnleaf, rcap, tile_n1, tile_ord, tile_slots, ilist, istart, ilen, icap, rincl;      // (rincl stays last: f3ds_destroy walks pts..rincl)
+    Buf deltas, skeys0, skeys1, svals0, svals1, cdf_hist, cdf, root, rrank, pool, rstart, rnleaf, rcap, tile_n1, tile_ord, tile_slots, ilist, istart, ilen, icap, lv_into, lv_at, lv_pfx, lv_thr, lv_tab, lv_nreg, lv_out, rincl;      // (rincl stays last: f3ds_destroy walks pts..rincl)
     std::vector<uint32_t> tsize;       // voxels per truth label (evaluation)
+    float cluster_T = 0.0f;            // threshold of the last cluster run: f3ds_labels_at_thresholds serves levels t <= cluster_T from its merge log
     // f3ds_cluster_supervoxels: the state is caller-supplied supervoxels (no points, no voxel grid).  user_label[h] = the caller's label of internal
     // supervoxel h (h = rank in ascending label + 1; [0] = 0), user_row[h] = its row in the caller's arrays; empty after f3ds_segment
     bool user_mode = false;
@@ -1039,6 +1045,7 @@ int run_cluster(Batch& b, const f3ds_params* prm, uint32_t* const* labels_of, co
         c->res.lambda = prm->merging == F3DS_ADAPTIVE_LAMBDA ? (c->E ? c->h_dc->lambda : __builtin_nanf("")) : c->host_lambda;
         c->prm.color_metric = prm->color_metric; c->prm.geom_metric = prm->geom_metric; c->prm.merging = prm->merging;
         c->prm.lambda = prm->lambda; c->prm.bins = prm->bins; c->prm.threshold = prm->threshold;
+        c->cluster_T = prm->threshold;
         c->have_frame = true;
     }
     return F3DS_OK;
@@ -1916,4 +1923,123 @@ extern "C" int f3ds_auto_threshold(f3ds_ctx* c, const f3ds_params* prm, const ui
     if (best_score) *best_score = bp;
     p.threshold = bt;
     return f3ds_recluster(c, &p, point_labels, labels_on_device, result);
+}
+
+// ------------------------------------------------------------------------------------------------
+// hierarchy levels: the labels of K thresholds t_l <= T from the merge log of the last cluster run to T (f3ds_levels.h / .inc).  Reads
+// the frame state and leaves it as it was: only the lv_* scratch is written.
+// ------------------------------------------------------------------------------------------------
+namespace {
+int check_levels(const f3ds_ctx* c, const float* thr, int K) {
+    if (!c->have_frame) return F3DS_ERR_LOGIC;
+    for (int l = 0; l < K; ++l) if (thr[l] > c->cluster_T) return F3DS_ERR_OUT_OF_RANGE;
+    for (int l = 0; l < K; ++l) if (!std::isfinite(thr[l])) return F3DS_ERR_ARG;      // (-inf; NaN is refused before)
+    return F3DS_OK;
+}
+int levels_record(f3ds_ctx* c, const float* d_thr, uint32_t K, bool lds_form, uint32_t* d_out, uint32_t* nreg) {
+    const uint32_t S0 = c->S0, n = c->n, nm = c->res.n_merges, Kp = (K + 3u) & ~3u;
+    uint32_t *into, *at, *pfx;
+    ENSURE(c->lv_into, uint32_t, S0 + 1, into); ENSURE(c->lv_at, uint32_t, S0 + 1, at); ENSURE(c->lv_pfx, uint32_t, (size_t)K * 2, pfx);      // (prefixes, then their order)
+    const uint32_t* ord = pfx + K;
+    const uint32_t* merges = (const uint32_t*)c->merges.p;
+    rec_fill(c, at, LV_NOT_ABSORBED, (size_t)(S0 + 1) * 4);
+    rec<d_level_log>(c, grid_for(nm, 256), 0u, nm, S0, merges, into, at);
+    rec<d_level_prefix>(c, 1u, 0u, nm, merges, K, d_thr, pfx, pfx + K);
+    const unsigned char* alive0 = (const unsigned char*)c->ralive0.p;
+    const int* pt_voxel = (const int*)c->pt_voxel.p; const uint32_t* owner = (const uint32_t*)c->owner0.p;
+    if (lds_form) {
+        const uint32_t gx = std::min(grid_for(n, 256), grid_wide(n, 4096));      // (every workgroup builds the tables: as d_relabel)
+        rec<d_level_labels>(c, gx, (S0 + 1u) * Kp * 4u, n, pt_voxel, owner, S0, K, Kp, alive0, (const uint32_t*)into, (const uint32_t*)at, (const uint32_t*)pfx, ord, d_out, nreg);
+    } else {
+        uint32_t* tab; ENSURE(c->lv_tab, uint32_t, (size_t)(S0 + 1) * Kp, tab);
+        rec<d_level_tables>(c, 1u, 0u, S0, K, Kp, alive0, (const uint32_t*)into, (const uint32_t*)at, (const uint32_t*)pfx, ord, tab, nreg);
+        rec<d_level_points>(c, grid_for(n, 256), 0u, n, K, Kp, pt_voxel, owner, (const uint32_t*)tab, d_out);
+    }
+    return F3DS_OK;
+}
+// all contexts on one device, one dispatch per kernel for the batch (grid.y = frame)
+int run_levels(f3ds_ctx** ctxs, int nctx, const float* thr, int K, uint32_t* const* point_labels, int labels_on_device, uint32_t* n_regions) {
+    g_sw.read();
+    f3ds_ctx* o = ctxs[0];
+    HIPCHECK(hipSetDevice(o->device));
+    Batch b; b.owner = o; b.st = o->stream; g_grid_cap = grid_cap_for_batch(nctx); g_batch_frames = nctx;
+    for (int i = 0; i < nctx; ++i) {
+        f3ds_ctx* c = ctxs[i];
+        if (c->stream != b.st) HIPCHECK(hipStreamSynchronize(c->stream));      // (the frame state is read on the owner's stream)
+        c->cmds.clear(); c->blob.clear(); c->pend.clear(); c->ops.n = 0; c->ops_grid = 0;
+        b.fr.push_back(c);
+    }
+    // the thresholds (shared by every frame) go up once, the region counts of all frames come back in one copy: both in the owner's scratch
+    float* d_thr; uint32_t* d_nreg;
+    { int rc = ensure<float>(o, o->lv_thr, (size_t)K, &d_thr); if (rc) return rc; rc = ensure<uint32_t>(o, o->lv_nreg, (size_t)nctx * K, &d_nreg); if (rc) return rc; }
+    HIPCHECK(hipMemcpyAsync(d_thr, thr, (size_t)K * 4, hipMemcpyHostToDevice, b.st));
+    const uint32_t Kp = ((uint32_t)K + 3u) & ~3u;
+    bool lds_form = !g_sw.levels_global;      // one form for the whole batch: its frames record identical command shapes
+    for (f3ds_ctx* c : b.fr) if ((uint64_t)(c->S0 + 1u) * Kp * 4u > LV_LDS_BYTES) lds_form = false;
+    for (int i = 0; i < nctx; ++i) {
+        f3ds_ctx* c = ctxs[i];
+        uint32_t* d_out;
+        if (labels_on_device) d_out = point_labels[i];
+        else ENSURE(c->lv_out, uint32_t, (size_t)c->n * K, d_out);
+        const int rc = levels_record(c, d_thr, (uint32_t)K, lds_form, d_out, d_nreg + (size_t)i * K);
+        if (rc) return rc;
+    }
+    int rc = flush(b);
+    if (rc) return rc;
+    std::vector<uint32_t> nreg((size_t)nctx * K);
+    HIPCHECK(hipMemcpyAsync(nreg.data(), d_nreg, nreg.size() * 4, hipMemcpyDeviceToHost, b.st));
+    if (!labels_on_device) {
+        // host outputs as run_cluster copies labels: through the device's copy stream once the labels exist (async into pinned memory), done before the call returns
+        hipStream_t dl = g_sw.copy_stream ? copy_stream_of(o->device, g_sw.copy_duplex ? 1 : 0) : nullptr;
+        if (dl) {
+            for (int k = 1; k < 3; ++k) if (!o->ev_copy[k]) HIPCHECK(hipEventCreateWithFlags(&o->ev_copy[k], hipEventDisableTiming));
+            HIPCHECK(hipEventRecord(o->ev_copy[1], b.st));
+            HIPCHECK(hipEventSynchronize(o->ev_copy[1]));
+        }
+        for (int i = 0; i < nctx; ++i)
+            if (ctxs[i]->n) HIPCHECK(hipMemcpyAsync(point_labels[i], ctxs[i]->lv_out.p, (size_t)ctxs[i]->n * K * 4, hipMemcpyDeviceToHost, dl ? dl : b.st));
+        if (dl) { HIPCHECK(hipEventRecord(o->ev_copy[2], dl)); HIPCHECK(hipEventSynchronize(o->ev_copy[2])); }
+    }
+    HIPCHECK(hipStreamSynchronize(b.st));
+    HIPCHECK(hipGetLastError());
+    if (n_regions) memcpy(n_regions, nreg.data(), nreg.size() * 4);
+    return F3DS_OK;
+}
+}  // namespace
+
+extern "C" int f3ds_labels_at_thresholds(f3ds_ctx* c, const float* thresholds, int k, uint32_t* point_labels, int labels_on_device, uint32_t* n_regions) {
+    uint32_t* lp[1] = {point_labels};
+    return f3ds_labels_at_thresholds_batch(&c, 1, thresholds, k, lp, labels_on_device, n_regions);
+}
+
+extern "C" int f3ds_labels_at_thresholds_batch(f3ds_ctx** ctxs, int nctx, const float* thresholds, int k, uint32_t* const* point_labels, int labels_on_device,
+                                               uint32_t* n_regions) {
+    if (!ctxs || nctx < 1 || !thresholds || k < 1 || !point_labels) return F3DS_ERR_ARG;
+    for (int l = 0; l < k; ++l) if (thresholds[l] != thresholds[l]) return F3DS_ERR_ARG;
+    for (int i = 0; i < nctx; ++i) {
+        if (!ctxs[i] || !point_labels[i] || ctxs[i]->device != ctxs[0]->device) return F3DS_ERR_ARG;
+        for (int j = 0; j < i; ++j) if (ctxs[j] == ctxs[i]) return F3DS_ERR_ARG;      // (one context holds one frame's scratch)
+    }
+    for (int i = 0; i < nctx; ++i) { const int rc = check_levels(ctxs[i], thresholds, k); if (rc) return rc; }
+    return run_levels(ctxs, nctx, thresholds, k, point_labels, labels_on_device, n_regions);
+}
+
+extern "C" int f3ds_get_merge_tree(f3ds_ctx* c, uint32_t* survivor, uint32_t* absorbed, float* weight, size_t cap, size_t* n_out) {
+    if (!c) return F3DS_ERR_ARG;
+    if (!c->have_frame) return F3DS_ERR_LOGIC;
+    HIPCHECK(hipSetDevice(c->device));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    const size_t nm = c->res.n_merges;
+    if (n_out) *n_out = nm;
+    if (!survivor && !absorbed && !weight) return F3DS_OK;
+    if (cap < nm) return F3DS_ERR_CAPACITY;
+    std::vector<uint32_t> u;
+    const int rc = fetch(c, c->merges, nm * 3, u);
+    if (rc) return rc;
+    for (size_t i = 0; i < nm; ++i) {
+        if (survivor) survivor[i] = label_out(c, u[i * 3]);
+        if (absorbed) absorbed[i] = label_out(c, u[i * 3 + 1]);
+        if (weight) memcpy(&weight[i], &u[i * 3 + 2], 4);
+    }
+    return F3DS_OK;
 }

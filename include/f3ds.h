@@ -290,6 +290,33 @@ int f3ds_auto_threshold(f3ds_ctx* ctx, const f3ds_params* params, const uint32_t
                         size_t cap, size_t* n_out, float* best_threshold, f3ds_performance* best_score,
                         uint32_t* point_labels, int labels_on_device, f3ds_result* result);
 
+/* ---- hierarchy levels: the segmentation at many thresholds from ONE merge run -------------------------------------------
+ * Clustering::cluster(state, t) merges the cheapest adjacency while its weight is below t (src/clustering.cpp:384-401); no merge
+ * depends on t, so the run to t <= T is a prefix of the run to T (all_thresh relies on it, :691-728).  The "cluster run" of a
+ * context is the latest of f3ds_segment, f3ds_segment_batch, f3ds_recluster and f3ds_cluster_supervoxels, at its threshold T.
+ * Level l (threshold t_l, any order, repeats allowed, finite and <= T) applies the logged merges before the FIRST merge i whose
+ * weight fails w_i < t_l (logged weights are not monotone: a count of weights below t_l is not the same); a t_l equal to a logged
+ * weight stops at that merge.  Level l is bit-equal to f3ds_recluster with the run's params and threshold = t_l: the same labels
+ * (F3DS_NO_LABEL included), region count and merge count.  The context's state does not change (regions, voxel cloud,
+ * adjacency, F3DS_DBG_* arrays and a later f3ds_recluster behave as if the call never happened).
+ * point_labels: k * n words, level-major (level l's n labels at point_labels + l * n); n = the frame's points, or its input
+ * voxels after f3ds_cluster_supervoxels (like that call's voxel_labels).  labels_on_device: a device buffer written in place;
+ * host buffers go through the device's copy stream like f3ds_segment_batch's labels (asynchronous when pinned) and are complete
+ * when the call returns.  n_regions (k words, may be NULL): regions per level.  One merge-log pass, one prefix pass and one
+ * label pass on the device (csrc/f3ds_levels.inc): K levels cost about one relabel, not K merge loops.
+ * Errors: F3DS_ERR_ARG for a NULL pointer, k < 1 or a NaN / infinite threshold; F3DS_ERR_OUT_OF_RANGE for t_l > T;
+ * F3DS_ERR_LOGIC before any cluster run (a frame without voxels included), as f3ds_recluster. */
+int f3ds_labels_at_thresholds(f3ds_ctx* ctx, const float* thresholds, int k, uint32_t* point_labels, int labels_on_device,
+                              uint32_t* n_regions /* k, may be NULL */);
+/* the same for every context of a batch (one GPU, one dispatch per kernel for all frames, grid.y = frame): point_labels[i] belongs
+ * to ctxs[i] (k * n_i words); n_regions (nctx * k words, context-major, may be NULL).  Every threshold must be <= each context's T. */
+int f3ds_labels_at_thresholds_batch(f3ds_ctx** ctxs, int nctx, const float* thresholds, int k, uint32_t* const* point_labels,
+                                    int labels_on_device, uint32_t* n_regions /* nctx * k, may be NULL */);
+/* the dendrogram: the merges of the last cluster run in the order performed -- survivor[i] took absorbed[i] at weight[i] -- as
+ * supervoxel labels (the label space of f3ds_get_supervoxels / F3DS_DBG_SV_REGION; the caller's keys after
+ * f3ds_cluster_supervoxels).  Any output may be NULL; n_out receives the merge count (F3DS_ERR_CAPACITY if cap is smaller). */
+int f3ds_get_merge_tree(f3ds_ctx* ctx, uint32_t* survivor, uint32_t* absorbed, float* weight, size_t cap, size_t* n_out);
+
 /* SupervoxelClustering::refineSupervoxels(num_itr, refined_supervoxel_clusters) (src/supervoxel_clustering.cpp:369-375) on
  * the supervoxels of the last f3ds_segment call: num_itr times { normals again from the owned two-ring, reseed every
  * supervoxel at the voxel nearest to its centroid, expand again }.  As in the reference, the refined supervoxels feed
