@@ -2,7 +2,10 @@
 //
 // Stage map (kernel functors d_<name> live in f3ds_kernels.inc; reference citations are in include/f3ds.h,
 // csrc/f3ds_numerics.h, csrc/f3ds_algo.h):
-//   0 voxelise   d_bbox -> d_grid -> d_keys -> radix sort -> d_heads/scan/d_segstart -> d_point_gather -> d_voxel_accum
+//   0 voxelise   d_bbox -> d_grid, then one of two paths:
+//                tile path (batches): d_tile_keys -> radix sort of the tile descriptors -> d_desc_part / d_desc_offsets / d_desc_apply -> d_tile_place -> d_voxel_list_accum (-> d_vox_hash)
+//                sort path (lone frames, refused frames): d_keys -> radix sort of the points -> d_seg_count / scan / d_seg_write -> d_voxel_gather_accum
+//                (F3DS_SPLIT_VOXEL_ACCUM, development: the sort path as d_heads / scan / d_segstart -> d_point_gather -> d_voxel_accum)
 //   1 neighbours d_neighbors (hash probe of the 27 cells), d_normals_t<384 | 256 threads> (two-ring ordered covariance, LDS tile)
 //   2 seeds      d_chunkbox, d_seed_grow, d_seed_keys, radix sort, d_cell_hash, d_seed_nn, d_seed_filter
 //   3 sweeps     per sweep: d_sweep_begin, d_sweep_R_first (pre-pass | round 0), d_sweep_R_round x2 | d_sweep_R + d_sweep_R_tail, d_sweep_claim,
@@ -58,6 +61,9 @@ using namespace f3ds;
 // ================================================================================================
 namespace {
 
+thread_local std::string g_last_hip_error;
+#define HIPCHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_last_hip_error = std::string(#expr) + ": " + hipGetErrorString(e_); return F3DS_ERR_HIP; } } while (0)
+
 template <class... Ts> struct ArgPack;
 template <> struct ArgPack<> {};
 template <class T, class... Ts> struct ArgPack<T, Ts...> { T head; ArgPack<Ts...> tail; };
@@ -90,7 +96,11 @@ template <class K> using pack_of = typename op_traits<decltype(&K::operator())>:
 
 inline void fill_pack(ArgPack<>&) {}
 template <class T, class... Ts, class A, class... As>
-inline void fill_pack(ArgPack<T, Ts...>& p, A a, As... as) { p.head = (T)a; fill_pack(p.tail, as...); }
+inline void fill_pack(ArgPack<T, Ts...>& p, A a, As... as) {
+    static_assert(std::is_convertible<A, T>::value && !(std::is_pointer<T>::value && std::is_integral<A>::value),
+                  "rec<K>(): an argument does not convert implicitly to the kernel's parameter type (wrong element type, swapped arguments?)");
+    p.head = a; fill_pack(p.tail, as...);
+}
 
 typedef hipError_t (*LaunchFn)(uint32_t gx, uint32_t nf, uint32_t lds, hipStream_t st, const void* dargs);
 template <class K>
@@ -100,7 +110,7 @@ hipError_t launch_fn(uint32_t gx, uint32_t nf, uint32_t lds, hipStream_t st, con
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_batched<K, Pack>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((k_batched<K, Pack>), dim3(gx ? gx : 1u, nf), dim3(K::BLOCK), lds, st, (const Pack*)dargs);
+    hipLaunchKernelGGL((k_batched<K, Pack>), dim3(gx ? gx : 1u, nf), dim3(K::BLOCK), lds, st, static_cast<const Pack*>(dargs));
     return hipGetLastError();
 }
 struct Cmd { LaunchFn fn; uint32_t gx, lds, bytes, off; };
@@ -135,7 +145,28 @@ struct Switches {
 thread_local Switches g_sw;
 // where the per-edge arrays of a 4-wave merge loop live when the call shares the device with other batch calls: 0 = global memory (52 KB of LDS per
 // workgroup: two fit a unit, and a voxel-normal workgroup beside them), 2 = LDS (up to 140 KB).  F3DS_MERGE_SHARED_RES=0|2 (A/B runs), read once.
-const int g_merge_shared_res = [] { const char* e = dev_getenv("F3DS_MERGE_SHARED_RES"); return e && atoi(e) == 2 ? 2 : (e && atoi(e) == 0 ? 0 : 0); }();
+const int g_merge_shared_res = [] { const char* e = dev_getenv("F3DS_MERGE_SHARED_RES"); return e && atoi(e) == 2 ? 2 : 0; }();
+
+// Device scratch of a context: typed, grow-only buffers (ensure(), below).  F3DS_SCRATCH is THE list of them: it declares the members of f3ds_ctx, numbers their slots in
+// the device-wide high-water table, and is what pregrow_scratch() and f3ds_destroy() walk.  A new buffer is one X(element type, name) here and nothing else.
+#define F3DS_SCRATCH(X) \
+    X(P16, pts) X(P16, spts) X(uint64_t, keys0) X(uint64_t, keys1) X(uint32_t, vals0) X(uint32_t, vals1) X(uint32_t, flags) X(uint32_t, incl) X(uint32_t, tiles) X(uint32_t, hist) X(uint32_t, seg_start) X(int, pt_voxel) X(uint32_t, labels) \
+    X(uint32_t, vkey) X(uint32_t, vcount) X(float, vf) X(int, nbr) X(int, nbrT) X(uint64_t, hkeys) X(uint32_t, hvals) X(float, boxes) X(uint32_t, ckey) X(uint32_t, cell_start) X(uint64_t, chk) X(uint32_t, chv) X(uint32_t, chvals) X(int, seed_orig) X(uint32_t, keep) X(int, seed_kept) \
+    X(uint32_t, owner0) X(uint32_t, ownR) X(float, dist0) X(unsigned char, R) X(float, hc) X(uint32_t, hcount) X(uint32_t, hlo) X(uint32_t, hhi) X(int, ghost_vox) X(unsigned char, ghost_active) X(unsigned char, ghost_done) X(uint32_t, ghost_head) X(uint32_t, ghost_next) \
+    X(uint32_t, loff) X(float, rows) X(int, row_voxel) X(float, racc0) X(uint32_t, rcnt0) X(float, rrec0) X(unsigned char, ralive0) X(uint64_t, ehk) X(uint64_t, ekeys0) X(uint64_t, ekeys1) X(uint32_t, evals0) X(uint32_t, evals1) X(uint32_t, ea0) X(uint32_t, eb0) \
+    X(uint32_t, ea) X(uint32_t, eb) X(float, ew) X(uint32_t, eku) X(int, ehist) X(unsigned char, ealive) X(uint32_t, ev_epoch) X(uint32_t, ev_key) X(int, ev_prev) X(float, racc) X(uint32_t, rcnt) X(float, rrec) X(unsigned char, ralive) X(uint32_t, rhead) X(uint32_t, rtail) X(uint32_t, lnext) X(uint32_t, parent) X(uint32_t, markA) X(uint32_t, markB) X(uint32_t, tl) X(uint32_t, merges) \
+    /* refineSupervoxels works on copies */ X(float, r_vf) X(uint32_t, r_owner) X(float, r_dist) X(float, r_hc) X(uint32_t, r_hcount) X(uint32_t, r_hlo) X(uint32_t, r_hhi) X(int, r_gvox) X(unsigned char, r_gact) X(unsigned char, r_gdone) X(uint32_t, r_ghead) X(uint32_t, r_gnext) X(uint32_t, r_tl) X(uint32_t, r_tcnt) X(int, r_seed) X(uint32_t, r_L) \
+    X(uint32_t, tstamp) X(uint32_t, tround) X(uint32_t, hdirty) X(uint32_t, htiles) X(uint32_t, htcnt) X(uint32_t, vwl) X(uint32_t, vwl2) X(uint32_t, vtmask) \
+    /* ground-truth evaluation */ X(uint32_t, glut) X(uint32_t, truth_pts) X(uint32_t, tsum) X(uint32_t, tcol) X(uint32_t, tlab) X(uint32_t, ctab) X(uint32_t, csize) X(uint32_t, eroot) X(uint32_t, eincl) \
+    /* stage 0, tile path: per (tile, entry) point count / list base / leaf ordinal; per point its (entry, rank in tile); per-leaf point lists */ X(uint32_t, hcnt) X(uint32_t, pslot) X(uint32_t, vlist) \
+    /* f3ds_cluster_supervoxels: the caller's supervoxels as uploaded */ X(uint32_t, u_src) X(uint32_t, u_voff) X(float, u_xyz) X(uint32_t, u_rgba) X(float, u_cent) X(float, u_nrm) \
+    X(float, deltas) X(uint64_t, skeys0) X(uint64_t, skeys1) X(uint32_t, svals0) X(uint32_t, svals1) X(uint32_t, cdf_hist) X(float, cdf) X(uint32_t, root) X(uint32_t, rincl) X(uint32_t, rrank) X(uint2, pool) X(uint32_t, rstart) X(uint32_t, rnleaf) X(uint32_t, rcap) X(uint32_t, tile_n1) X(uint32_t, tile_ord) X(uint32_t, tile_slots) X(uint32_t, ilist) X(uint32_t, istart) X(uint32_t, ilen) X(uint32_t, icap) \
+    /* hierarchy levels */ X(uint32_t, lv_into) X(uint32_t, lv_at) X(uint32_t, lv_pfx) X(float, lv_thr) X(uint32_t, lv_tab) X(uint32_t, lv_nreg) X(uint32_t, lv_out)
+template <class T> struct Scratch { T* p = nullptr; size_t cap = 0; int slot = -1; };      // cap: bytes allocated; slot: position in F3DS_SCRATCH
+#define F3DS_SCRATCH_SLOT(T, name) S_##name,
+#define F3DS_SCRATCH_MEMBER(T, name) Scratch<T> name{nullptr, 0, S_##name};
+#define F3DS_SCRATCH_VISIT(T, name) if (const int rc_ = f(name)) return rc_;
+enum ScratchSlot { F3DS_SCRATCH(F3DS_SCRATCH_SLOT) N_SCRATCH };
 
 }  // namespace
 
@@ -187,17 +218,9 @@ struct f3ds_ctx {
     int idxbits = -1;                  // >= 0: the sorted point keys carry the point index in their low bits
     uint32_t* user_labels = nullptr;   // device label buffer of the caller for the current call (else c->labels + copy)
     MergeDev mdev; MergeLds mlds; float host_lambda = 0.5f;
-    // device scratch (grow-only)
-    Buf pts, spts, keys0, keys1, vals0, vals1, flags, incl, tiles, hist, seg_start, pt_voxel, labels;
-    Buf vkey, vcount, vf, nbr, nbrT, hkeys, hvals, boxes, ckey, cell_start, chk, chv, chvals, seed_orig, keep, seed_kept;
-    Buf owner0, owner1, ownR, dist0, dist1, R, hc, hcount, hlo, hhi, ghost_vox, ghost_active, ghost_done, ghost_head, ghost_next;
-    Buf loff, rows, row_voxel, racc0, rcnt0, rrec0, ralive0, ehk, ekeys0, ekeys1, evals0, evals1, ea0, eb0;
-    Buf ea, eb, ew, eku, ehist, ealive, ev_epoch, ev_key, ev_prev, racc, rcnt, rrec, ralive, rhead, rtail, lnext, parent, markA, markB, tl, merges;
-    Buf r_vf, r_owner, r_dist, r_hc, r_hcount, r_hlo, r_hhi, r_gvox, r_gact, r_gdone, r_ghead, r_gnext, r_tl, r_tcnt, r_seed, r_L;      // refineSupervoxels works on copies
-    Buf tstamp, tround, hdirty, htiles, htcnt, vwl, vwl2, vtmask, glut, truth_pts, tsum, tcol, tlab, ctab, csize, eroot, eincl;      // ground-truth evaluation
-    Buf hcnt, pslot, vlist;      // stage 0, tile path: per (tile, entry) point count / list base / leaf ordinal; per point its (entry, rank in tile); per-leaf point lists
-    Buf u_src, u_voff, u_xyz, u_rgba, u_cent, u_nrm;      // f3ds_cluster_supervoxels: the caller's supervoxels as uploaded
-    Buf deltas, skeys0, skeys1, svals0, svals1, cdf_hist, cdf, root, rrank, pool, rstart, rnleaf, rcap, tile_n1, tile_ord, tile_slots, ilist, istart, ilen, icap, lv_into, lv_at, lv_pfx, lv_thr, lv_tab, lv_nreg, lv_out, rincl;      // (rincl stays last: f3ds_destroy walks pts..rincl)
+    // device scratch (grow-only): one typed member per entry of F3DS_SCRATCH; each_scratch(f) calls f on every one of them until one returns non-zero
+    F3DS_SCRATCH(F3DS_SCRATCH_MEMBER)
+    template <class F> int each_scratch(F&& f) { F3DS_SCRATCH(F3DS_SCRATCH_VISIT) return 0; }
     std::vector<uint32_t> tsize;       // voxels per truth label (evaluation)
     float cluster_T = 0.0f;            // threshold of the last cluster run: f3ds_labels_at_thresholds serves levels t <= cluster_T from its merge log
     // f3ds_cluster_supervoxels: the state is caller-supplied supervoxels (no points, no voxel grid).  user_label[h] = the caller's label of internal
@@ -212,8 +235,8 @@ namespace {
 // reallocated before the flush (the dispatch would write into freed memory).  rec<>() notes the address of every pointer-typed
 // argument (and, for the few struct arguments -- SweepFrame, MergeDev, MergeLds --, every 8-byte word of the struct, which is
 // where their pointer members sit); scalar arguments are never mistaken for addresses.  Checked on every regrow.
-bool referenced_by_pending_calls(const f3ds_ctx* c, const Buf& b) {
-    const uintptr_t lo = (uintptr_t)b.p, hi = lo + b.cap;
+bool referenced_by_pending_calls(const f3ds_ctx* c, const void* mem, size_t cap) {
+    const uintptr_t lo = (uintptr_t)mem, hi = lo + cap;
     for (const uintptr_t w : c->pend) if (w >= lo && w < hi) return true;
     for (uint32_t k = 0; k < c->ops.n; ++k) {      // (fills / copies recorded and not yet merged into a call)
         const uintptr_t d = (uintptr_t)c->ops.dst[k], sp = (uintptr_t)c->ops.src[k];
@@ -233,61 +256,53 @@ template <class A> inline void note_arg(f3ds_ctx* c, const A& a) {
 // while nothing recorded refers to the buffer -- goes straight to the mark (if that is within 4x of its own request), so that
 // a pool of contexts fed with frames of varying size stops allocating after every context has been used twice (hipFree waits for the whole device: a
 // regrow in steady state stalls every batch in flight).
-std::atomic<size_t> g_scratch_hwm[16][160];
+std::atomic<size_t> g_scratch_hwm[16][N_SCRATCH];
 std::atomic<unsigned long long> g_scratch_allocs{0};      // hipMalloc calls for scratch so far (F3DS_HOST_PROF prints it per batch)
 template <class T>
-int ensure(f3ds_ctx* c, Buf& b, size_t count, T** out) {
+int regrow(Scratch<T>& b, size_t mark) {      // trades the allocation for one of mark + 25 % + 64 bytes: the contents are lost
+    g_scratch_allocs.fetch_add(1, std::memory_order_relaxed);
+    if (b.p) { HIPCHECK(hipFree(b.p)); b.p = nullptr; b.cap = 0; }
+    const size_t want = mark + mark / 4 + 64;
+    HIPCHECK(hipMalloc(&b.p, want));
+    b.cap = want;
+    return F3DS_OK;
+}
+template <class T>
+int ensure(f3ds_ctx* c, Scratch<T>& b, size_t count, T** out) {
     size_t bytes = count * sizeof(T);
     if (bytes < 256) bytes = 256;
     size_t target = bytes;
-    const ptrdiff_t slot = &b - &c->pts;
-    if (slot >= 0 && slot < 160) {
-        std::atomic<size_t>& hwm = g_scratch_hwm[c->device & 15][slot];
-        size_t seen = hwm.load(std::memory_order_relaxed);
-        while (seen < bytes && !hwm.compare_exchange_weak(seen, bytes, std::memory_order_relaxed)) {}
-        if (seen > target && seen <= 4 * bytes) target = seen;      // (a frame of another scale altogether does not size this one)
-    }
+    std::atomic<size_t>& hwm = g_scratch_hwm[c->device & 15][b.slot];
+    size_t seen = hwm.load(std::memory_order_relaxed);
+    while (seen < bytes && !hwm.compare_exchange_weak(seen, bytes, std::memory_order_relaxed)) {}
+    if (seen > target && seen <= 4 * bytes) target = seen;      // (a frame of another scale altogether does not size this one)
     // ENSURE is an idempotent getter while the buffer covers the request: contents are only ever discarded when the request does not
     // fit (the caller is about to overwrite the buffer anyway).  The device-wide mark sizes such a regrow; buffers that are merely
     // below the mark are brought up to it by pregrow_scratch() at the start of a segment call, when no buffer holds frame state.
     if (b.cap < bytes) {
-        if (b.p && (!c->cmds.empty() || c->ops.n) && referenced_by_pending_calls(c, b)) {
+        if (b.p && (!c->cmds.empty() || c->ops.n) && referenced_by_pending_calls(c, b.p, b.cap)) {
             fprintf(stderr, "f3ds: internal error: regrowing a buffer that a recorded kernel call refers to\n");
             return F3DS_ERR_LOGIC;
         }
-        g_scratch_allocs.fetch_add(1, std::memory_order_relaxed);
         static const bool trace = dev_getenv("F3DS_TRACE_ALLOC") != nullptr;
-        if (trace && b.p) fprintf(stderr, "f3ds: regrow slot %td: cap %zu, request %zu, mark %zu, pending calls %zu\n", slot, b.cap, bytes, target, c->cmds.size());
-        if (b.p) { HIPCHECK(hipFree(b.p)); b.p = nullptr; b.cap = 0; }
-        size_t want = target + target / 4 + 64;
-        HIPCHECK(hipMalloc(&b.p, want));
-        b.cap = want;
+        if (trace && b.p) fprintf(stderr, "f3ds: regrow slot %d: cap %zu, request %zu, mark %zu, pending calls %zu\n", b.slot, b.cap, bytes, target, c->cmds.size());
+        if (const int rc = regrow(b, target)) return rc;
     }
-    *out = reinterpret_cast<T*>(b.p);
+    *out = b.p;
     return F3DS_OK;
 }
 // Start of a segment call: nothing is recorded and no buffer holds state of a frame that will be read again (the call starts a new
 // frame), so this is the one moment a context may trade a buffer for a larger one without losing anything.  Every allocated buffer
-// that is below the device-wide mark of its slot (within 4x) goes to the mark: a pool of contexts fed with frames of varying size
-// stops allocating once every context has been used twice (hipFree waits for the whole device: a regrow in steady state stalls
-// every batch in flight).
+// that is below the device-wide mark of its slot (within 4x) goes to the mark (see g_scratch_hwm).
 int pregrow_scratch(f3ds_ctx* c) {
-    Buf* bufs = &c->pts;
-    const size_t nb = (reinterpret_cast<char*>(&c->rincl) - reinterpret_cast<char*>(&c->pts)) / sizeof(Buf) + 1;
-    for (size_t i = 0; i < nb && i < 160; ++i) {
-        Buf& b = bufs[i];
-        if (!b.p) continue;
-        const size_t mark = g_scratch_hwm[c->device & 15][i].load(std::memory_order_relaxed);
-        if (b.cap >= mark || mark > 4 * b.cap) continue;
-        g_scratch_allocs.fetch_add(1, std::memory_order_relaxed);
-        HIPCHECK(hipFree(b.p)); b.p = nullptr; b.cap = 0;
-        const size_t want = mark + mark / 4 + 64;
-        HIPCHECK(hipMalloc(&b.p, want));
-        b.cap = want;
-    }
-    return F3DS_OK;
+    return c->each_scratch([c](auto& b) -> int {
+        if (!b.p) return F3DS_OK;
+        const size_t mark = g_scratch_hwm[c->device & 15][b.slot].load(std::memory_order_relaxed);
+        if (b.cap >= mark || mark > 4 * b.cap) return F3DS_OK;
+        return regrow(b, mark);
+    });
 }
-#define ENSURE(buf, T, count, ptr) do { int rc_ = ensure<T>(c, buf, (size_t)(count), &ptr); if (rc_) return rc_; } while (0)
+#define ENSURE(buf, count, ptr) do { int rc_ = ensure(c, buf, (size_t)(count), &ptr); if (rc_) return rc_; } while (0)
 
 // Workgroups per frame of a wide kernel.  A launch covers all frames of the batch (grid.y = frame), so a frame gets its
 // share of a launch-wide budget of ~3 k workgroups (12 per CU) and the kernels loop (grid-stride) over the rest: with
@@ -346,12 +361,14 @@ inline void rec_op(f3ds_ctx* c, void* dst, const void* src, uint32_t value, size
     if (c->ops.n == (uint32_t)MULTI_OPS) flush_ops(c);
     MultiOp& m = c->ops;
     if (m.n == 0) memset(&m, 0, sizeof m);
-    m.dst[m.n] = (uint32_t*)dst; m.src[m.n] = (const uint32_t*)src; m.val[m.n] = value; m.words[m.n] = words; m.n++;
+    m.dst[m.n] = static_cast<uint32_t*>(dst); m.src[m.n] = static_cast<const uint32_t*>(src); m.val[m.n] = value; m.words[m.n] = words; m.n++;      // (d_multi_op fills / copies any buffer word by word)
     const uint32_t g = grid_for(words, 256);
     if (g > c->ops_grid) c->ops_grid = g;
 }
-inline void rec_fill(f3ds_ctx* c, void* p, uint32_t value, size_t bytes) { rec_op(c, p, nullptr, value, bytes); }
+inline void rec_fill(f3ds_ctx* c, void* dst, uint32_t value, size_t bytes) { rec_op(c, dst, nullptr, value, bytes); }
 inline void rec_copy(f3ds_ctx* c, void* dst, const void* src, size_t bytes) { rec_op(c, dst, src, 0u, bytes); }
+// forget everything recorded and not launched
+inline void reset_recording(f3ds_ctx* c) { c->cmds.clear(); c->blob.clear(); c->pend.clear(); c->ops.n = 0; c->ops_grid = 0; }
 
 // a batch: the frames that are still being processed together, one stream, one argument arena
 struct Batch {
@@ -369,6 +386,12 @@ static int trace_err(int code, const char* where, const f3ds_ctx* c) {
     return code;
 }
 static inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// wait for an event / a stream; the time goes to the call's "waiting for the GPU" account
+inline hipError_t timed_sync(hipEvent_t e) { const double t0 = now_ms(); const hipError_t r = hipEventSynchronize(e); g_t_wait += now_ms() - t0; return r; }
+inline hipError_t timed_sync(hipStream_t st) { const double t0 = now_ms(); const hipError_t r = hipStreamSynchronize(st); g_t_wait += now_ms() - t0; return r; }
+// A stage that runs again starts from cleared counters: the listed fields of DevCounters go to zero on the device (in stream order) and in the host's copy
+template <class F> int clear_counter(f3ds_ctx* c, hipStream_t st, F DevCounters::*f) { c->h_dc->*f = 0; HIPCHECK(hipMemsetAsync(&(c->d_dc->*f), 0, sizeof(F), st)); return F3DS_OK; }
+template <class... Fs> int clear_counters(f3ds_ctx* c, hipStream_t st, Fs DevCounters::*... f) { int rc = F3DS_OK; (void)((rc = clear_counter(c, st, f)) || ...); return rc; }
 // zip the recorded calls of all live frames into batched dispatches
 int flush(Batch& b, hipEvent_t before_launch = nullptr) {      // before_launch: recorded after the argument upload, right before the first dispatch
     if (b.fr.empty()) return F3DS_OK;
@@ -390,8 +413,8 @@ int flush(Batch& b, hipEvent_t before_launch = nullptr) {      // before_launch:
         }
         o->args_cap = total * 2;
         for (int k = 0; k < 2; ++k) {
-            HIPCHECK(hipHostMalloc((void**)&o->h_args[k], o->args_cap, hipHostMallocDefault));
-            HIPCHECK(hipMalloc((void**)&o->d_args[k], o->args_cap));
+            HIPCHECK(hipHostMalloc(&o->h_args[k], o->args_cap, hipHostMallocDefault));
+            HIPCHECK(hipMalloc(&o->d_args[k], o->args_cap));
             if (!o->ev_args[k]) HIPCHECK(hipEventCreateWithFlags(&o->ev_args[k], hipEventDisableTiming));
         }
     }
@@ -399,7 +422,7 @@ int flush(Batch& b, hipEvent_t before_launch = nullptr) {      // before_launch:
     // end of the last dispatch that reads a pair, so the host packs and launches stage k+1 while stage k still runs: the only wait here is
     // for the flush before the previous one, which is long over (round 2 synchronised the stream at every flush).
     const int fl = o->args_flip; o->args_flip ^= 1;
-    if (o->args_used[fl]) { const double t0 = now_ms(); HIPCHECK(hipEventSynchronize(o->ev_args[fl])); g_t_wait += now_ms() - t0; }
+    if (o->args_used[fl]) HIPCHECK(timed_sync(o->ev_args[fl]));
     unsigned char* const h_args = o->h_args[fl]; unsigned char* const d_args = o->d_args[fl];
     const double tl0 = now_ms();
     for (size_t j = 0; j < ncmd; ++j)
@@ -416,7 +439,7 @@ int flush(Batch& b, hipEvent_t before_launch = nullptr) {      // before_launch:
         HIPCHECK(b.fr[0]->cmds[j].fn(gx, nf, lds, b.st, d_args + off[j]));
     }
     HIPCHECK(hipEventRecord(o->ev_args[fl], b.st)); o->args_used[fl] = true;
-    for (f3ds_ctx* c : b.fr) { c->cmds.clear(); c->blob.clear(); c->pend.clear(); c->ops.n = 0; c->ops_grid = 0; }
+    for (f3ds_ctx* c : b.fr) reset_recording(c);
     g_t_launch += now_ms() - tl0;
     return F3DS_OK;
 }
@@ -434,14 +457,14 @@ int flush_sync(Batch& b) {
             if (o->d_dcblk) HIPCHECK(hipFree(o->d_dcblk));
             if (o->h_dcblk) HIPCHECK(hipHostFree(o->h_dcblk));
             o->dcblk_cap = nf * 2;
-            HIPCHECK(hipMalloc((void**)&o->d_dcblk, o->dcblk_cap * sizeof(DevCounters)));
-            HIPCHECK(hipHostMalloc((void**)&o->h_dcblk, o->dcblk_cap * sizeof(DevCounters), hipHostMallocDefault));
+            HIPCHECK(hipMalloc(&o->d_dcblk, o->dcblk_cap * sizeof(DevCounters)));
+            HIPCHECK(hipHostMalloc(&o->h_dcblk, o->dcblk_cap * sizeof(DevCounters), hipHostMallocDefault));
         }
-        for (size_t i = 0; i < nf; ++i) rec<d_dc_gather>(b.fr[i], 1u, 0u, (const DevCounters*)b.fr[i]->d_dc, o->d_dcblk + i);
+        for (size_t i = 0; i < nf; ++i) rec<d_dc_gather>(b.fr[i], 1u, 0u, b.fr[i]->d_dc, o->d_dcblk + i);
         if ((rc = flush(b))) return rc;
         HIPCHECK(hipMemcpyAsync(o->h_dcblk, o->d_dcblk, nf * sizeof(DevCounters), hipMemcpyDeviceToHost, b.st));
     }
-    { const double t0 = now_ms(); HIPCHECK(hipStreamSynchronize(b.st)); g_t_wait += now_ms() - t0; }
+    HIPCHECK(timed_sync(b.st));
     HIPCHECK(hipGetLastError());
     if (nf > 1) for (size_t i = 0; i < nf; ++i) *b.fr[i]->h_dc = b.owner->h_dcblk[i];
     return F3DS_OK;
@@ -452,10 +475,10 @@ int flush_sync(Batch& b) {
 int scan_u32(f3ds_ctx* c, const uint32_t* in, uint32_t* out, uint32_t n) {
     const uint32_t nt = n ? (n + SCAN_TILE - 1) / SCAN_TILE : 1u;
     uint32_t* tiles;
-    ENSURE(c->tiles, uint32_t, nt, tiles);
+    ENSURE(c->tiles, nt, tiles);
     rec<d_scan_tiles>(c, nt, 0u, in, out, tiles, n);
     rec<d_scan_single>(c, 1u, 0u, tiles, nt);
-    rec<d_scan_add>(c, nt, 0u, out, (const uint32_t*)tiles, n);
+    rec<d_scan_add>(c, nt, 0u, out, tiles, n);
     return F3DS_OK;
 }
 // stable sort of (key,val) pairs on the low `total_bits` bits (the same for every frame of a batch)
@@ -467,14 +490,14 @@ int radix_sort(f3ds_ctx* c, uint64_t* k0, uint32_t* v0, uint64_t* k1, uint32_t* 
     const int per = (total_bits + passes - 1) / passes;
     const uint32_t nb = n ? (n + RS_TILE - 1) / RS_TILE : 1u;
     uint32_t* hist;
-    ENSURE(c->hist, uint32_t, (size_t)RS_BINS * nb, hist);
+    ENSURE(c->hist, (size_t)RS_BINS * nb, hist);
     int shift = 0;
     for (int p = 0; p < passes; ++p) {
         const int bits = (total_bits - shift) < per ? (total_bits - shift) : per;
-        rec<d_radix_hist>(c, nb, 0u, (const uint64_t*)k0, n, base_shift + shift, bits, hist, nb, n_dev);
+        rec<d_radix_hist>(c, nb, 0u, k0, n, base_shift + shift, bits, hist, nb, n_dev);
         rec<d_scan_single>(c, 1u, 0u, hist, (uint32_t)((1u << bits) * nb));
-        if (v0) rec<d_radix_scatter>(c, nb, 0u, (const uint64_t*)k0, (const uint32_t*)v0, k1, v1, n, base_shift + shift, bits, (const uint32_t*)hist, nb, n_dev);
-        else rec<d_radix_scatter_k>(c, nb, 0u, (const uint64_t*)k0, k1, n, base_shift + shift, bits, (const uint32_t*)hist, nb);      // payload in the key's low bits
+        if (v0) rec<d_radix_scatter>(c, nb, 0u, k0, v0, k1, v1, n, base_shift + shift, bits, hist, nb, n_dev);
+        else rec<d_radix_scatter_k>(c, nb, 0u, k0, k1, n, base_shift + shift, bits, hist, nb);      // payload in the key's low bits
         std::swap(k0, k1); std::swap(v0, v1);
         shift += bits;
     }
@@ -494,28 +517,28 @@ int seg_bbox(f3ds_ctx* c) {
 int seg_sort(f3ds_ctx* c, int sort_bits, int idxbits) {      // idxbits >= 0: (code << idxbits) | index in one array; -1: (key, index) pairs
     const uint32_t n = c->n;
     uint64_t *k0, *k1; uint32_t *v0 = nullptr, *v1 = nullptr, *flags, *incl, *seg_start; int* pt_voxel;
-    ENSURE(c->keys0, uint64_t, n, k0); ENSURE(c->keys1, uint64_t, n, k1);
-    if (idxbits < 0) { ENSURE(c->vals0, uint32_t, n, v0); ENSURE(c->vals1, uint32_t, n, v1); }
-    ENSURE(c->flags, uint32_t, n, flags); ENSURE(c->incl, uint32_t, n, incl); ENSURE(c->seg_start, uint32_t, (size_t)n + 1, seg_start);
-    ENSURE(c->pt_voxel, int, n, pt_voxel);
+    ENSURE(c->keys0, n, k0); ENSURE(c->keys1, n, k1);
+    if (idxbits < 0) { ENSURE(c->vals0, n, v0); ENSURE(c->vals1, n, v1); }
+    ENSURE(c->flags, n, flags); ENSURE(c->incl, n, incl); ENSURE(c->seg_start, (size_t)n + 1, seg_start);
+    ENSURE(c->pt_voxel, n, pt_voxel);
     c->idxbits = idxbits;
     const int ks = idxbits < 0 ? 0 : idxbits;
-    rec<d_keys>(c, grid_for(n, 256), 0u, c->d_pts, n, c->fa, (const GridInfo*)c->d_grid, k0, v0, ks);
+    rec<d_keys>(c, grid_for(n, 256), 0u, c->d_pts, n, c->fa, c->d_grid, k0, v0, ks);
     c->vs = nullptr;
     int rc = radix_sort(c, k0, v0, k1, v1, n, sort_bits, &c->ks, &c->vs, ks);
     if (rc) return rc;
     const uint64_t invalid = 1ull << (3 * c->h_dc->depth);
     if (g_sw.split_voxel_accum) {      // development: round 2's chain (d_point_gather reads the rank array)
-        rec<d_heads>(c, grid_for(n, 256), 0u, (const uint64_t*)c->ks, n, invalid, flags, ks);
+        rec<d_heads>(c, grid_for(n, 256), 0u, c->ks, n, invalid, flags, ks);
         if ((rc = scan_u32(c, flags, incl, n))) return rc;
-        rec<d_segstart>(c, grid_for(n, 256), 0u, (const uint64_t*)c->ks, (const uint32_t*)flags, (const uint32_t*)incl, n, invalid, seg_start, &c->d_dc->n_voxels, &c->d_dc->n_valid, ks);
+        rec<d_segstart>(c, grid_for(n, 256), 0u, c->ks, flags, incl, n, invalid, seg_start, &c->d_dc->n_voxels, &c->d_dc->n_valid, ks);
         return F3DS_OK;
     }
     const uint32_t nt = n ? (n + SCAN_TILE - 1) / SCAN_TILE : 1u;
-    uint32_t* tiles; ENSURE(c->tiles, uint32_t, nt, tiles);
-    rec<d_seg_count>(c, nt, 0u, (const uint64_t*)c->ks, n, invalid, ks, tiles);
+    uint32_t* tiles; ENSURE(c->tiles, nt, tiles);
+    rec<d_seg_count>(c, nt, 0u, c->ks, n, invalid, ks, tiles);
     rec<d_scan_single>(c, 1u, 0u, tiles, nt);
-    rec<d_seg_write>(c, nt, 0u, (const uint64_t*)c->ks, n, invalid, ks, (const uint32_t*)tiles, seg_start, &c->d_dc->n_voxels, &c->d_dc->n_valid);
+    rec<d_seg_write>(c, nt, 0u, c->ks, n, invalid, ks, tiles, seg_start, &c->d_dc->n_voxels, &c->d_dc->n_valid);
     return F3DS_OK;
 }
 // stage 0b + 0c without sorting the points (f3ds_kernels.inc, "stage 0 without sorting the points"): per-tile LDS grouping, sort of the tiles' descriptors, per-leaf
@@ -531,22 +554,21 @@ int seg_vox_tiles(f3ds_ctx* c, int code_bits, int tile_bits) {      // (code_bit
     c->vox_cap = capV;
     uint64_t *k0, *k1; uint32_t *ploc, *v0, *v1, *part, *vkey, *vcount, *seg_start, *list; uint2* bo_te; float* vf; int* pt_voxel;
     const uint32_t nchunks = (dcap + DS_CHUNK - 1u) / DS_CHUNK;
-    ENSURE(c->pslot, uint32_t, n, ploc); ENSURE(c->keys0, uint64_t, dcap, k0); ENSURE(c->keys1, uint64_t, dcap, k1); ENSURE(c->vals0, uint32_t, dcap, v0); ENSURE(c->vals1, uint32_t, dcap, v1);
-    { uint32_t* w; ENSURE(c->hcnt, uint32_t, (size_t)ntiles * VT_TAB * 2 + 2u * nchunks, w); bo_te = reinterpret_cast<uint2*>(w); part = w + (size_t)ntiles * VT_TAB * 2; }
-    ENSURE(c->vkey, uint32_t, (size_t)capV * 3, vkey); ENSURE(c->vcount, uint32_t, capV, vcount); ENSURE(c->vf, float, (size_t)capV * 12, vf);
-    ENSURE(c->seg_start, uint32_t, (size_t)capV + 1, seg_start); ENSURE(c->vlist, uint32_t, n, list); ENSURE(c->pt_voxel, int, n, pt_voxel);
-    { uint32_t *f, *incl; ENSURE(c->flags, uint32_t, capV, f); ENSURE(c->incl, uint32_t, capV, incl); }      // (the seed stage scans V / C flags through them without asking)
+    ENSURE(c->pslot, n, ploc); ENSURE(c->keys0, dcap, k0); ENSURE(c->keys1, dcap, k1); ENSURE(c->vals0, dcap, v0); ENSURE(c->vals1, dcap, v1);
+    { uint32_t* w; ENSURE(c->hcnt, (size_t)ntiles * VT_TAB * 2 + 2u * nchunks, w); bo_te = reinterpret_cast<uint2*>(w); part = w + (size_t)ntiles * VT_TAB * 2; }      // ONE allocation, two views: the tiles' (base, entry) tables as uint2 pairs, then the chunk partials as words
+    ENSURE(c->vkey, (size_t)capV * 3, vkey); ENSURE(c->vcount, capV, vcount); ENSURE(c->vf, (size_t)capV * 12, vf);
+    ENSURE(c->seg_start, (size_t)capV + 1, seg_start); ENSURE(c->vlist, n, list); ENSURE(c->pt_voxel, n, pt_voxel);
+    { uint32_t *f, *incl; ENSURE(c->flags, capV, f); ENSURE(c->incl, capV, incl); }      // (the seed stage scans V / C flags through them without asking)
     c->idxbits = -1; c->ks = nullptr; c->vs = nullptr;
-    rec<d_tile_keys>(c, std::min<uint32_t>(ntiles, (uint32_t)g_grid_cap * 16u), 0u, c->d_pts, n, c->fa, (const GridInfo*)c->d_grid, ploc, k0, v0, dcap, tile_bits, c->d_dc);
+    rec<d_tile_keys>(c, std::min<uint32_t>(ntiles, (uint32_t)g_grid_cap * 16u), 0u, c->d_pts, n, c->fa, c->d_grid, ploc, k0, v0, dcap, tile_bits, c->d_dc);
     uint64_t* ks; uint32_t* vs;
     int rc = radix_sort(c, k0, v0, k1, v1, dcap, code_bits + tile_bits, &ks, &vs, VT_CNT_BITS, &c->d_dc->seg_count);      // (the bits above the count field)
     if (rc) return rc;
-    rec<d_desc_part>(c, nchunks, 0u, (const uint64_t*)ks, dcap, tile_bits, part, (const DevCounters*)c->d_dc);
+    rec<d_desc_part>(c, nchunks, 0u, ks, dcap, tile_bits, part, c->d_dc);
     rec<d_desc_offsets>(c, 1u, 0u, part, dcap, capV, seg_start, c->d_dc);
-    rec<d_desc_apply>(c, nchunks, 0u, (const uint64_t*)ks, (const uint32_t*)vs, dcap, capV, tile_bits, c->fa, (const GridInfo*)c->d_grid, (const uint32_t*)part, bo_te,
-                      seg_start, vkey, (const DevCounters*)c->d_dc);
-    rec<d_tile_place>(c, std::min<uint32_t>(ntiles, (uint32_t)g_grid_cap * 16u), 0u, (const uint32_t*)ploc, n, (const uint2*)bo_te, list, pt_voxel, (const DevCounters*)c->d_dc);
-    rec<d_voxel_list_accum>(c, std::min<uint32_t>(grid_wide(capV, 256), std::max<uint32_t>(64u, grid_wide(n / 8u, 256))), 0u, c->d_pts, list, (const uint32_t*)seg_start, c->fa, vf, vcount, c->d_dc, capV);
+    rec<d_desc_apply>(c, nchunks, 0u, ks, vs, dcap, capV, tile_bits, c->fa, c->d_grid, part, bo_te, seg_start, vkey, c->d_dc);
+    rec<d_tile_place>(c, std::min<uint32_t>(ntiles, (uint32_t)g_grid_cap * 16u), 0u, ploc, n, bo_te, list, pt_voxel, c->d_dc);
+    rec<d_voxel_list_accum>(c, std::min<uint32_t>(grid_wide(capV, 256), std::max<uint32_t>(64u, grid_wide(n / 8u, 256))), 0u, c->d_pts, list, seg_start, c->fa, vf, vcount, c->d_dc, capV);
     c->vox_hashed = true;
     return F3DS_OK;
 }
@@ -557,28 +579,24 @@ int seg_voxels(f3ds_ctx* c) {
     if (c->vox_hashed) {      // the leaf sums exist already (seg_vox_tiles): the leaf keys go into the hash table, then the neighbour search
         const uint32_t hc2 = pow2_ge((size_t)V * 2 + 16);
         c->hmask = hc2 - 1;
-        ENSURE(c->nbr, int, (size_t)V * 27, nbr); ENSURE(c->nbrT, int, (size_t)V * 27, nbrT); ENSURE(c->hkeys, uint64_t, hc2, hkeys); ENSURE(c->hvals, uint32_t, hc2, hvals);
+        ENSURE(c->nbr, (size_t)V * 27, nbr); ENSURE(c->nbrT, (size_t)V * 27, nbrT); ENSURE(c->hkeys, hc2, hkeys); ENSURE(c->hvals, hc2, hvals);
         rec_fill(c, hkeys, 0xFFFFFFFFu, (size_t)hc2 * 8);
-        rec<d_vox_hash>(c, 1u, 0u, (const uint32_t*)c->vkey.p, V, (const GridInfo*)c->d_grid, hkeys, hvals, c->hmask);
-        rec<d_neighbors>(c, grid_wide((size_t)V * 27, 256), 0u, (const uint32_t*)c->vkey.p, (const DevCounters*)c->d_dc, (const GridInfo*)c->d_grid, (const uint64_t*)hkeys, (const uint32_t*)hvals,
-                         c->hmask, nbr, nbrT);
+        rec<d_vox_hash>(c, 1u, 0u, c->vkey.p, V, c->d_grid, hkeys, hvals, c->hmask);
+        rec<d_neighbors>(c, grid_wide((size_t)V * 27, 256), 0u, c->vkey.p, c->d_dc, c->d_grid, hkeys, hvals, c->hmask, nbr, nbrT);
         return F3DS_OK;
     }
     const uint32_t hcap = pow2_ge((size_t)V * 2 + 16);
     c->hmask = hcap - 1;
-    ENSURE(c->vkey, uint32_t, (size_t)V * 3, vkey); ENSURE(c->vcount, uint32_t, V, vcount); ENSURE(c->vf, float, (size_t)V * 12, vf);
-    ENSURE(c->nbr, int, (size_t)V * 27, nbr); ENSURE(c->nbrT, int, (size_t)V * 27, nbrT); ENSURE(c->hkeys, uint64_t, hcap, hkeys); ENSURE(c->hvals, uint32_t, hcap, hvals);
+    ENSURE(c->vkey, (size_t)V * 3, vkey); ENSURE(c->vcount, V, vcount); ENSURE(c->vf, (size_t)V * 12, vf);
+    ENSURE(c->nbr, (size_t)V * 27, nbr); ENSURE(c->nbrT, (size_t)V * 27, nbrT); ENSURE(c->hkeys, hcap, hkeys); ENSURE(c->hvals, hcap, hvals);
     rec_fill(c, hkeys, 0xFFFFFFFFu, (size_t)hcap * 8);
     if (g_sw.split_voxel_accum) {      // development: round 2's two kernels (a sorted copy of the frame in between)
-        P16* spts; ENSURE(c->spts, P16, n, spts);
-        rec<d_point_gather>(c, grid_wide(n, 256), 0u, c->d_pts, (const uint32_t*)c->vs, (const uint64_t*)c->ks, c->idxbits < 0 ? 0 : c->idxbits, (const uint32_t*)c->incl.p, n, (const DevCounters*)c->d_dc, spts, (int*)c->pt_voxel.p);
-        rec<d_voxel_accum>(c, grid_wide(V, 256), 0u, (const P16*)spts, (const uint64_t*)c->ks, c->idxbits < 0 ? 0 : c->idxbits, (const uint32_t*)c->seg_start.p, (const DevCounters*)c->d_dc, c->fa,
-                           (const GridInfo*)c->d_grid, vkey, vcount, vf, hkeys, hvals, c->hmask);
+        P16* spts; ENSURE(c->spts, n, spts);
+        rec<d_point_gather>(c, grid_wide(n, 256), 0u, c->d_pts, c->vs, c->ks, c->idxbits < 0 ? 0 : c->idxbits, c->incl.p, n, c->d_dc, spts, c->pt_voxel.p);
+        rec<d_voxel_accum>(c, grid_wide(V, 256), 0u, spts, c->ks, c->idxbits < 0 ? 0 : c->idxbits, c->seg_start.p, c->d_dc, c->fa, c->d_grid, vkey, vcount, vf, hkeys, hvals, c->hmask);
     } else
-        rec<d_voxel_gather_accum>(c, grid_wide(V, 256), 0u, c->d_pts, (const uint32_t*)c->vs, (const uint64_t*)c->ks, c->idxbits < 0 ? 0 : c->idxbits, (const uint32_t*)c->seg_start.p, n,
-                                  (const DevCounters*)c->d_dc, c->fa, (const GridInfo*)c->d_grid, vkey, vcount, vf, hkeys, hvals, c->hmask, (int*)c->pt_voxel.p);
-    rec<d_neighbors>(c, grid_wide((size_t)V * 27, 256), 0u, (const uint32_t*)vkey, (const DevCounters*)c->d_dc, (const GridInfo*)c->d_grid, (const uint64_t*)hkeys, (const uint32_t*)hvals,
-                     c->hmask, nbr, nbrT);
+        rec<d_voxel_gather_accum>(c, grid_wide(V, 256), 0u, c->d_pts, c->vs, c->ks, c->idxbits < 0 ? 0 : c->idxbits, c->seg_start.p, n, c->d_dc, c->fa, c->d_grid, vkey, vcount, vf, hkeys, hvals, c->hmask, c->pt_voxel.p);
+    rec<d_neighbors>(c, grid_wide((size_t)V * 27, 256), 0u, vkey, c->d_dc, c->d_grid, hkeys, hvals, c->hmask, nbr, nbrT);
     return F3DS_OK;
 }
 // stage 1b: voxel normals -- ONE launch per batch call, bracketed by its own pair of events (f3ds_result.ms_stage[7]: besides the merge
@@ -586,7 +604,7 @@ int seg_voxels(f3ds_ctx* c) {
 int seg_normals(f3ds_ctx* c) {
     const uint32_t nt = (c->V + NT_TILE - 1) / NT_TILE;
     uint32_t *tn1, *tord, *tslots;      // the tiles' one-ring tables, built on the way for the sweeps (d_sweep_R_pre, d_sweep_claim)
-    ENSURE(c->tile_n1, uint32_t, nt, tn1); ENSURE(c->tile_ord, uint32_t, (size_t)nt * NT_RING1, tord); ENSURE(c->tile_slots, uint32_t, (size_t)nt * SW_SLOT_WORDS * NT_TILE, tslots);
+    ENSURE(c->tile_n1, nt, tn1); ENSURE(c->tile_ord, (size_t)nt * NT_RING1, tord); ENSURE(c->tile_slots, (size_t)nt * SW_SLOT_WORDS * NT_TILE, tslots);
     // One workgroup per tile by default.  F3DS_NORMALS_WGS=<n> (experiment): a launch-wide budget of n workgroups, each walking a run of
     // tiles -- placed once, a 72 KB six-wave workgroup then keeps its compute unit instead of competing for one per tile.  With six calls in flight the
     // launch drops from 50-100 ms to 30 ms and the sweeps of the other calls grow by as much (2 140-2 155 vs 2 170 Mpoints/s on one box); alone it is
@@ -601,34 +619,34 @@ int seg_normals(f3ds_ctx* c) {
     const int nthr_env = g_sw.normals_threads;
     const uint32_t holes = g_sw.tile_holes;
     if (nthr_env ? nthr_env == 256 : g_batch_frames >= 16)
-        rec<d_normals_t<256>>(c, std::min(nt, share), 0u, (float*)c->vf.p, (const int*)c->nbr.p, (const DevCounters*)c->d_dc, tn1, tord, tslots, holes);
+        rec<d_normals_t<256>>(c, std::min(nt, share), 0u, c->vf.p, c->nbr.p, c->d_dc, tn1, tord, tslots, holes);
     else
-        rec<d_normals_t<384>>(c, std::min(nt, share), 0u, (float*)c->vf.p, (const int*)c->nbr.p, (const DevCounters*)c->d_dc, tn1, tord, tslots, holes);
+        rec<d_normals_t<384>>(c, std::min(nt, share), 0u, c->vf.p, c->nbr.p, c->d_dc, tn1, tord, tslots, holes);
     return F3DS_OK;
 }
 // stage 2a: seed grid growth
 int seg_seed_grid(f3ds_ctx* c) {
     const uint32_t V = c->V;
-    float* boxes; const float* vf = (const float*)c->vf.p;
+    float* boxes; const float* vf = c->vf.p;
     const uint32_t nchunks = (V + SEED_CHUNK - 1) / SEED_CHUNK;
-    ENSURE(c->boxes, float, (size_t)nchunks * 6, boxes);
-    rec<d_chunkbox>(c, nchunks, 0u, (const float*)vf, (const DevCounters*)c->d_dc, boxes);
-    rec<d_seed_grow>(c, 1u, 0u, (const float*)vf, (const float*)boxes, c->d_dc, c->prm.seed_res, c->d_sgrid);
+    ENSURE(c->boxes, (size_t)nchunks * 6, boxes);
+    rec<d_chunkbox>(c, nchunks, 0u, vf, c->d_dc, boxes);
+    rec<d_seed_grow>(c, 1u, 0u, vf, boxes, c->d_dc, c->prm.seed_res, c->d_sgrid);
     return F3DS_OK;
 }
 // stage 2b: seed cells (sort voxels by cell)
 int seg_seed_cells(f3ds_ctx* c, int sort_bits, int max_sdepth) {
     const uint32_t V = c->V;
-    uint32_t *ckey, *cell_start, *v0, *v1; uint64_t *k0 = (uint64_t*)c->keys0.p, *k1 = (uint64_t*)c->keys1.p;
-    ENSURE(c->vals0, uint32_t, V, v0); ENSURE(c->vals1, uint32_t, V, v1);
-    ENSURE(c->ckey, uint32_t, (size_t)V * 3, ckey); ENSURE(c->cell_start, uint32_t, (size_t)V + 1, cell_start);
-    rec<d_seed_keys>(c, grid_for(V, 256), 0u, (const float*)c->vf.p, (const DevCounters*)c->d_dc, (const SeedGrid*)c->d_sgrid, ckey, k0, v0);
+    uint32_t *ckey, *cell_start, *v0, *v1; uint64_t *k0 = c->keys0.p, *k1 = c->keys1.p;
+    ENSURE(c->vals0, V, v0); ENSURE(c->vals1, V, v1);
+    ENSURE(c->ckey, (size_t)V * 3, ckey); ENSURE(c->cell_start, (size_t)V + 1, cell_start);
+    rec<d_seed_keys>(c, grid_for(V, 256), 0u, c->vf.p, c->d_dc, c->d_sgrid, ckey, k0, v0);
     int rc = radix_sort(c, k0, v0, k1, v1, V, sort_bits, &c->cks, &c->cvs);
     if (rc) return rc;
     const uint64_t climit = max_sdepth >= 21 ? 0xFFFFFFFFFFFFFFFFull : (1ull << (3 * max_sdepth));
-    rec<d_heads>(c, grid_for(V, 256), 0u, (const uint64_t*)c->cks, V, climit, (uint32_t*)c->flags.p, 0);
-    if ((rc = scan_u32(c, (const uint32_t*)c->flags.p, (uint32_t*)c->incl.p, V))) return rc;
-    rec<d_segstart>(c, grid_for(V, 256), 0u, (const uint64_t*)c->cks, (const uint32_t*)c->flags.p, (const uint32_t*)c->incl.p, V, climit, cell_start, &c->d_dc->n_cells, &c->d_dc->seg_count, 0);
+    rec<d_heads>(c, grid_for(V, 256), 0u, c->cks, V, climit, c->flags.p, 0);
+    if ((rc = scan_u32(c, c->flags.p, c->incl.p, V))) return rc;
+    rec<d_segstart>(c, grid_for(V, 256), 0u, c->cks, c->flags.p, c->incl.p, V, climit, cell_start, &c->d_dc->n_cells, &c->d_dc->seg_count, 0);
     return F3DS_OK;
 }
 // stage 2c: nearest voxel per cell, radius filter, kept seeds
@@ -636,25 +654,23 @@ int seg_seeds(f3ds_ctx* c) {
     const uint32_t V = c->V, C = c->C;
     uint32_t *sorted_vox, *chvals, *keep; uint64_t* chk; int *seed_orig, *seed_kept;
     const uint32_t ccap = pow2_ge((size_t)C * 2 + 16);
-    ENSURE(c->chv, uint32_t, V, sorted_vox); ENSURE(c->chk, uint64_t, ccap, chk); ENSURE(c->chvals, uint32_t, ccap, chvals);
-    ENSURE(c->seed_orig, int, C, seed_orig); ENSURE(c->seed_kept, int, C, seed_kept); ENSURE(c->keep, uint32_t, C, keep);
+    ENSURE(c->chv, V, sorted_vox); ENSURE(c->chk, ccap, chk); ENSURE(c->chvals, ccap, chvals);
+    ENSURE(c->seed_orig, C, seed_orig); ENSURE(c->seed_kept, C, seed_kept); ENSURE(c->keep, C, keep);
     rec_copy(c, sorted_vox, c->cvs, (size_t)V * 4);      // the sort buffers are reused later
     rec_fill(c, chk, 0xFFFFFFFFu, (size_t)ccap * 8);
-    const uint32_t* ckey = (const uint32_t*)c->ckey.p; const uint32_t* cell_start = (const uint32_t*)c->cell_start.p; const float* vf = (const float*)c->vf.p;
-    rec<d_cell_hash>(c, grid_for(C, 256), 0u, ckey, (const uint32_t*)sorted_vox, cell_start, (const DevCounters*)c->d_dc, chk, chvals, ccap - 1);
-    rec<d_seed_nn>(c, (C + 3u) / 4u, 0u, vf, ckey, (const uint32_t*)sorted_vox, cell_start, (const DevCounters*)c->d_dc, (const SeedGrid*)c->d_sgrid, (const uint64_t*)chk, (const uint32_t*)chvals,
-                   ccap - 1, seed_orig);
-    rec<d_seed_filter>(c, (C + 3u) / 4u, 0u, vf, ckey, (const uint32_t*)sorted_vox, cell_start, (const DevCounters*)c->d_dc, (const SeedGrid*)c->d_sgrid, (const uint64_t*)chk, (const uint32_t*)chvals, ccap - 1,
-                       (const int*)seed_orig, a_radius_sq(c->prm.seed_res), a_min_points(c->prm.seed_res, c->prm.voxel_res), keep);
-    int rc = scan_u32(c, keep, (uint32_t*)c->incl.p, C);
+    const uint32_t* ckey = c->ckey.p; const uint32_t* cell_start = c->cell_start.p; const float* vf = c->vf.p;
+    rec<d_cell_hash>(c, grid_for(C, 256), 0u, ckey, sorted_vox, cell_start, c->d_dc, chk, chvals, ccap - 1);
+    rec<d_seed_nn>(c, (C + 3u) / 4u, 0u, vf, ckey, sorted_vox, cell_start, c->d_dc, c->d_sgrid, chk, chvals, ccap - 1, seed_orig);
+    rec<d_seed_filter>(c, (C + 3u) / 4u, 0u, vf, ckey, sorted_vox, cell_start, c->d_dc, c->d_sgrid, chk, chvals, ccap - 1, seed_orig, a_radius_sq(c->prm.seed_res), a_min_points(c->prm.seed_res, c->prm.voxel_res), keep);
+    int rc = scan_u32(c, keep, c->incl.p, C);
     if (rc) return rc;
-    rec<d_seed_compact>(c, grid_for(C, 256), 0u, (const int*)seed_orig, (const uint32_t*)keep, (const uint32_t*)c->incl.p, c->d_dc, seed_kept);
+    rec<d_seed_compact>(c, grid_for(C, 256), 0u, seed_orig, keep, c->incl.p, c->d_dc, seed_kept);
     return F3DS_OK;
 }
 // stage 3: helpers and all label-propagation sweeps
 // The state a run of sweeps works on: extract's own (ctx members) or the copy refineSupervoxels continues from
 struct SweepBufs {
-    Buf *owner, *dist, *hc, *hcount, *hlo, *hhi, *ghost_vox, *ghost_active, *ghost_done, *ghost_head, *ghost_next, *htiles, *htcnt;
+    Scratch<uint32_t> *owner; Scratch<float> *dist, *hc; Scratch<uint32_t> *hcount, *hlo, *hhi; Scratch<int>* ghost_vox; Scratch<unsigned char> *ghost_active, *ghost_done; Scratch<uint32_t> *ghost_head, *ghost_next, *htiles, *htcnt;
     const float* vf;        // voxel features (refine: the copy with the refined normals)
     const int* seeds;       // S0 seed voxels (refine: -1 for helpers erased earlier)
     bool reseed;            // refine: centroids are kept, helpers without a seed stay empty
@@ -663,16 +679,16 @@ int seg_sweeps_on(f3ds_ctx* c, const SweepBufs& sb) {
     const uint32_t V = c->V, S0 = c->S0;
     const f3ds_params& prm = c->prm;
     uint32_t *owner0, *ownR, *hcount, *hlo, *hhi, *ghost_head, *ghost_next; float *dist0, *hc; unsigned char *R, *ghost_active, *ghost_done; int* ghost_vox;
-    ENSURE(*sb.owner, uint32_t, V, owner0); ENSURE(c->ownR, uint32_t, V, ownR); ENSURE(*sb.dist, float, V, dist0);
-    ENSURE(c->R, unsigned char, V, R); ENSURE(*sb.hc, float, (size_t)(S0 + 1) * 12, hc); ENSURE(*sb.hcount, uint32_t, S0 + 1, hcount);
-    ENSURE(*sb.hlo, uint32_t, S0 + 1, hlo); ENSURE(*sb.hhi, uint32_t, S0 + 1, hhi); ENSURE(*sb.ghost_vox, int, S0 + 1, ghost_vox);
-    ENSURE(*sb.ghost_active, unsigned char, S0 + 1, ghost_active); ENSURE(*sb.ghost_done, unsigned char, S0 + 1, ghost_done);
-    ENSURE(*sb.ghost_head, uint32_t, V, ghost_head); ENSURE(*sb.ghost_next, uint32_t, S0 + 1, ghost_next);
+    ENSURE(*sb.owner, V, owner0); ENSURE(c->ownR, V, ownR); ENSURE(*sb.dist, V, dist0);
+    ENSURE(c->R, V, R); ENSURE(*sb.hc, (size_t)(S0 + 1) * 12, hc); ENSURE(*sb.hcount, S0 + 1, hcount);
+    ENSURE(*sb.hlo, S0 + 1, hlo); ENSURE(*sb.hhi, S0 + 1, hhi); ENSURE(*sb.ghost_vox, S0 + 1, ghost_vox);
+    ENSURE(*sb.ghost_active, S0 + 1, ghost_active); ENSURE(*sb.ghost_done, S0 + 1, ghost_done);
+    ENSURE(*sb.ghost_head, V, ghost_head); ENSURE(*sb.ghost_next, S0 + 1, ghost_next);
     const uint32_t T = (V + 63u) / 64u;
     uint32_t *tiles4, *trr, *hD;
-    ENSURE(c->tstamp, uint32_t, (size_t)4 * T, tiles4); ENSURE(c->tround, uint32_t, (size_t)(F3DS_R_ROUNDS - 1) * T, trr); ENSURE(c->hdirty, uint32_t, S0 + 1, hD);
-    uint32_t *tl, *tcnt; ENSURE(*sb.htiles, uint32_t, (size_t)(S0 + 1) * HT_CAP, tl); ENSURE(*sb.htcnt, uint32_t, S0 + 1, tcnt);
-    uint32_t *wl, *wl2, *tmask; ENSURE(c->vwl, uint32_t, V, wl); ENSURE(c->vwl2, uint32_t, V, wl2); ENSURE(c->vtmask, uint32_t, V, tmask);
+    ENSURE(c->tstamp, (size_t)4 * T, tiles4); ENSURE(c->tround, (size_t)(F3DS_R_ROUNDS - 1) * T, trr); ENSURE(c->hdirty, S0 + 1, hD);
+    uint32_t *tl, *tcnt; ENSURE(*sb.htiles, (size_t)(S0 + 1) * HT_CAP, tl); ENSURE(*sb.htcnt, S0 + 1, tcnt);
+    uint32_t *wl, *wl2, *tmask; ENSURE(c->vwl, V, wl); ENSURE(c->vwl2, V, wl2); ENSURE(c->vtmask, V, tmask);
     rec_fill(c, tiles4, 0u, (size_t)4 * T * 4);
     rec_fill(c, trr, 0u, (size_t)(F3DS_R_ROUNDS - 1) * T * 4);
     rec_fill(c, hD, 0u, (size_t)(S0 + 1) * 4);
@@ -682,22 +698,22 @@ int seg_sweeps_on(f3ds_ctx* c, const SweepBufs& sb) {
     { const float fmax = F3DS_FLT_MAX; uint32_t bits; memcpy(&bits, &fmax, 4); rec_fill(c, dist0, bits, (size_t)V * 4); }
     if (sb.reseed) {
         rec<d_reseed_own>(c, grid_for(S0, 256), 0u, sb.seeds, S0, owner0);
-        rec<d_reseed_init>(c, grid_for(S0 + 1, 256), 0u, sb.seeds, S0, (const uint32_t*)owner0, ghost_vox, ghost_active, ghost_done, hlo, hhi, hcount, tl, tcnt);
+        rec<d_reseed_init>(c, grid_for(S0 + 1, 256), 0u, sb.seeds, S0, owner0, ghost_vox, ghost_active, ghost_done, hlo, hhi, hcount, tl, tcnt);
     } else {
         rec<d_helper_own>(c, grid_for(S0, 256), 0u, sb.seeds, S0, owner0);
-        rec<d_helper_init>(c, grid_for(S0 + 1, 256), 0u, sb.seeds, S0, (const uint32_t*)owner0, ghost_vox, ghost_active, ghost_done, hlo, hhi, hcount, hc, tl, tcnt);
+        rec<d_helper_init>(c, grid_for(S0 + 1, 256), 0u, sb.seeds, S0, owner0, ghost_vox, ghost_active, ghost_done, hlo, hhi, hcount, hc, tl, tcnt);
     }
-    const int* nbrT = (const int*)c->nbrT.p; const float* vf = sb.vf;
+    const int* nbrT = c->nbrT.p; const float* vf = sb.vf;
     SweepFrame a;
-    a.sv = SweepView{(int)V, nbrT, vf, owner0, dist0, hc, ghost_head, ghost_next, (const uint32_t*)&c->d_dc->n_ghosts, prm.seed_res, prm.w_normal, prm.w_color, prm.w_spatial, (const int*)c->nbr.p};
+    a.sv = SweepView{(int)V, nbrT, vf, owner0, dist0, hc, ghost_head, ghost_next, &c->d_dc->n_ghosts, prm.seed_res, prm.w_normal, prm.w_color, prm.w_spatial, c->nbr.p};
     a.R = R; a.ownR = ownR; a.owner_out = owner0; a.dist_out = dist0;
     a.ghost_done = ghost_done; a.ghost_active = ghost_active; a.ghost_vox = ghost_vox; a.ghost_head = ghost_head; a.ghost_next = ghost_next;
     a.hlo = hlo; a.hhi = hhi; a.hcount = hcount; a.hc = hc; a.dc = c->d_dc; a.S0 = S0;
     a.tR0 = tiles4; a.tR1 = tiles4 + T; a.tC0 = tiles4 + 2 * (size_t)T; a.tC1 = tiles4 + 3 * (size_t)T; a.tRr = trr; a.hD = hD; a.T = T; a.tl = tl; a.tcnt = tcnt; a.wl = wl; a.wl2 = wl2; a.tmask = tmask;
     a.thr = g_inc_shift >= 32 ? 0xFFFFFFFFu : (g_inc_shift < 0 ? 0u : V >> g_inc_shift);
     if (!g_sw.sweep_tiles) a.tile_n1 = nullptr;      // development: F3DS_SWEEP_TILES=0 keeps the sweeps on their global-gather path (A/B, tests)
-    else a.tile_n1 = (const uint32_t*)c->tile_n1.p;
-    a.tile_ord = (const uint32_t*)c->tile_ord.p; a.tile_slots = (const uint32_t*)c->tile_slots.p;
+    else a.tile_n1 = c->tile_n1.p;
+    a.tile_ord = c->tile_ord.p; a.tile_slots = c->tile_slots.p;
     for (uint32_t t = 0; t < c->res.sweeps; ++t) {
         if (a_sweep_needs_clear(t)) rec_fill(c, R, 0u, V);
         rec<d_sweep_begin>(c, 1u, 0u, a, t);
@@ -716,47 +732,43 @@ int seg_sweeps_on(f3ds_ctx* c, const SweepBufs& sb) {
     return F3DS_OK;
 }
 int seg_sweeps(f3ds_ctx* c) {
-    SweepBufs sb{&c->owner0, &c->dist0, &c->hc, &c->hcount, &c->hlo, &c->hhi, &c->ghost_vox, &c->ghost_active, &c->ghost_done, &c->ghost_head, &c->ghost_next,
-                 &c->htiles, &c->htcnt, (const float*)c->vf.p, (const int*)c->seed_kept.p, false};
+    SweepBufs sb{&c->owner0, &c->dist0, &c->hc, &c->hcount, &c->hlo, &c->hhi, &c->ghost_vox, &c->ghost_active, &c->ghost_done, &c->ghost_head, &c->ghost_next, &c->htiles, &c->htcnt, c->vf.p, c->seed_kept.p, false};
     return seg_sweeps_on(c, sb);
 }
 // stage 4a: supervoxel payload rows, adjacency set
 int seg_supervoxels(f3ds_ctx* c) {
     const uint32_t V = c->V, S0 = c->S0;
     uint32_t *loff, *rcnt0, *ev0, *ev1; float *rows, *racc0, *rrec0; int* row_voxel; unsigned char* ralive0; uint64_t *ehk, *ek0, *ek1;
-    ENSURE(c->loff, uint32_t, S0 + 2, loff);
-    int rc = scan_u32(c, (const uint32_t*)c->hcount.p, loff + 1, S0 + 1);     // loff[h+1] = inclusive => loff[h] = exclusive
+    ENSURE(c->loff, S0 + 2, loff);
+    int rc = scan_u32(c, c->hcount.p, loff + 1, S0 + 1);     // loff[h+1] = inclusive => loff[h] = exclusive
     if (rc) return rc;
     rec_fill(c, loff, 0u, 4);
-    ENSURE(c->rows, float, ((size_t)V + S0 + 1) * 12, rows); ENSURE(c->row_voxel, int, (size_t)V + S0 + 1, row_voxel);      // ghosts add at most S0 rows
-    ENSURE(c->racc0, float, (size_t)(S0 + 1) * 12, racc0); ENSURE(c->rcnt0, uint32_t, S0 + 1, rcnt0); ENSURE(c->rrec0, float, (size_t)(S0 + 1) * 16, rrec0);
-    ENSURE(c->ralive0, unsigned char, S0 + 1, ralive0);
+    ENSURE(c->rows, ((size_t)V + S0 + 1) * 12, rows); ENSURE(c->row_voxel, (size_t)V + S0 + 1, row_voxel);      // ghosts add at most S0 rows
+    ENSURE(c->racc0, (size_t)(S0 + 1) * 12, racc0); ENSURE(c->rcnt0, S0 + 1, rcnt0); ENSURE(c->rrec0, (size_t)(S0 + 1) * 16, rrec0);
+    ENSURE(c->ralive0, S0 + 1, ralive0);
     rec_fill(c, ralive0, 0u, S0 + 1);
     rec_fill(c, rcnt0, 0u, (size_t)(S0 + 1) * 4);
     rec<d_sv_fill>(c, S0 ? (S0 + 3u) / 4u : 1u, 0u,      // (four helpers per workgroup, one per row of its wave)
-                   (const float*)c->vf.p, (const uint32_t*)c->owner0.p, S0, (const uint32_t*)c->hlo.p, (const uint32_t*)c->hhi.p, (const int*)c->ghost_vox.p,
-                   (const unsigned char*)c->ghost_active.p, (const uint32_t*)c->hcount.p, (const uint32_t*)loff, (const float*)c->hc.p, rows, row_voxel, racc0, rcnt0, rrec0, ralive0,
-                   c->d_dc, (const uint32_t*)c->htiles.p, (const uint32_t*)c->htcnt.p, V);
+                   c->vf.p, c->owner0.p, S0, c->hlo.p, c->hhi.p, c->ghost_vox.p, c->ghost_active.p, c->hcount.p, loff, c->hc.p, rows, row_voxel, racc0, rcnt0, rrec0, ralive0, c->d_dc, c->htiles.p, c->htcnt.p, V);
     const uint32_t ecap = (uint32_t)std::min<uint64_t>((uint64_t)S0 * c->edge_mult + 1024u, 0x7fffffffu);
     const uint32_t ehcap = pow2_ge((size_t)ecap * 2);
-    ENSURE(c->ehk, uint64_t, ehcap, ehk);
-    ENSURE(c->ekeys0, uint64_t, ecap, ek0); ENSURE(c->ekeys1, uint64_t, ecap, ek1); ENSURE(c->evals0, uint32_t, ecap, ev0); ENSURE(c->evals1, uint32_t, ecap, ev1);
+    ENSURE(c->ehk, ehcap, ehk);
+    ENSURE(c->ekeys0, ecap, ek0); ENSURE(c->ekeys1, ecap, ek1); ENSURE(c->evals0, ecap, ev0); ENSURE(c->evals1, ecap, ev1);
     rec_fill(c, ehk, 0xFFFFFFFFu, (size_t)ehcap * 8);
-    rec<d_edges>(c, grid_for(V, 256), 0u, V, S0, (const int*)c->nbrT.p, (const uint32_t*)c->owner0.p, ehk, ehcap - 1, ek0, ecap, c->d_dc);
-    rec<d_edges_ghost>(c, grid_for(S0, 256), 0u, V, S0, (const int*)c->ghost_vox.p, (const unsigned char*)c->ghost_active.p, (const int*)c->nbrT.p, (const uint32_t*)c->owner0.p, ehk,
-                       ehcap - 1, ek0, ecap, c->d_dc);
+    rec<d_edges>(c, grid_for(V, 256), 0u, V, S0, c->nbrT.p, c->owner0.p, ehk, ehcap - 1, ek0, ecap, c->d_dc);
+    rec<d_edges_ghost>(c, grid_for(S0, 256), 0u, V, S0, c->ghost_vox.p, c->ghost_active.p, c->nbrT.p, c->owner0.p, ehk, ehcap - 1, ek0, ecap, c->d_dc);
     return F3DS_OK;
 }
 // stage 4b: sorted edge list
 int seg_edge_sort(f3ds_ctx* c, int sort_bits) {
     const uint32_t E = c->E, S0 = c->S0;
-    uint32_t *ea0, *eb0; ENSURE(c->ea0, uint32_t, E, ea0); ENSURE(c->eb0, uint32_t, E, eb0);
+    uint32_t *ea0, *eb0; ENSURE(c->ea0, E, ea0); ENSURE(c->eb0, E, eb0);
     uint32_t* evs;
-    { uint32_t* h; ENSURE(c->hist, uint32_t, (size_t)RS_BINS * (((size_t)E * 2 + RS_TILE - 1) / RS_TILE + 1), h); }      // also holds the 2E-delta sort of seg_cluster_front, recorded before this one is flushed
-    rec<d_iota>(c, grid_for(E, 256), 0u, (uint32_t*)c->evals0.p, E);
-    int rc = radix_sort(c, (uint64_t*)c->ekeys0.p, (uint32_t*)c->evals0.p, (uint64_t*)c->ekeys1.p, (uint32_t*)c->evals1.p, E, sort_bits, &c->eks, &evs);
+    { uint32_t* h; ENSURE(c->hist, (size_t)RS_BINS * (((size_t)E * 2 + RS_TILE - 1) / RS_TILE + 1), h); }      // also holds the 2E-delta sort of seg_cluster_front, recorded before this one is flushed
+    rec<d_iota>(c, grid_for(E, 256), 0u, c->evals0.p, E);
+    int rc = radix_sort(c, c->ekeys0.p, c->evals0.p, c->ekeys1.p, c->evals1.p, E, sort_bits, &c->eks, &evs);
     if (rc) return rc;
-    rec<d_edge_init>(c, grid_for(E, 256), 0u, (const uint64_t*)c->eks, E, S0, ea0, eb0);
+    rec<d_edge_init>(c, grid_for(E, 256), 0u, c->eks, E, S0, ea0, eb0);
     return F3DS_OK;
 }
 // d_merge_il_t<NW, RES>: LDS a frame with E adjacencies needs (merge_il_offsets, f3ds_kernels.inc) and whether the kernel can take it
@@ -803,16 +815,16 @@ int seg_cluster_front(f3ds_ctx* c, const f3ds_params* prm, int kind) {
     memset(&m, 0, sizeof m);
     m.E = E; m.S0 = S0; m.threshold = prm->threshold; m.dc = c->d_dc;
     { const uint64_t cap = (uint64_t)E * c->ev_mult + 4096u; m.ev_cap = cap > 0x7fffffffull ? 0x7fffffffu : (uint32_t)cap; }      // weight-history events: grown on demand (run_cluster)
-    ENSURE(c->ea, uint32_t, E, m.ea); ENSURE(c->eb, uint32_t, E, m.eb); ENSURE(c->ew, float, ((size_t)E + 2047) & ~(size_t)2047, m.ew); /* d_merge: weights; d_merge_cw_t<., 0>: endpoints */ ENSURE(c->eku, uint32_t, ((size_t)E + 2047) & ~(size_t)2047, m.eku);      // (Ecap of the widest merge kernel)
-    ENSURE(c->ehist, int, E, m.ehist); ENSURE(c->ealive, unsigned char, E, m.ealive);
-    ENSURE(c->ev_epoch, uint32_t, m.ev_cap, m.ev_epoch); ENSURE(c->ev_key, uint32_t, m.ev_cap, m.ev_key); ENSURE(c->ev_prev, int, m.ev_cap, m.ev_prev);
-    ENSURE(c->racc, float, (size_t)(S0 + 1) * 12, m.racc); ENSURE(c->rrec, float, (size_t)(S0 + 1) * 16, m.rrec);
-    ENSURE(c->rcnt, uint32_t, S0 + 1, m.rcnt); ENSURE(c->ralive, unsigned char, S0 + 1, m.ralive);
-    ENSURE(c->rhead, uint32_t, S0 + 1, m.rhead); ENSURE(c->rtail, uint32_t, S0 + 1, m.rtail); ENSURE(c->lnext, uint32_t, S0 + 1, m.lnext);
-    ENSURE(c->parent, uint32_t, S0 + 1, m.parent); ENSURE(c->markA, uint32_t, S0 + 1, m.markA); ENSURE(c->markB, uint32_t, S0 + 1, m.markB);
-    ENSURE(c->tl, uint32_t, E, m.tl); ENSURE(c->merges, uint32_t, (size_t)(S0 + 1) * 3, m.merges);
-    m.loff = (const uint32_t*)c->loff.p; m.llen = (const uint32_t*)c->hcount.p; m.rows = (const float*)c->rows.p;
-    float* deltas; ENSURE(c->deltas, float, (size_t)E * 2, deltas);
+    ENSURE(c->ea, E, m.ea); ENSURE(c->eb, E, m.eb); ENSURE(c->ew, ((size_t)E + 2047) & ~(size_t)2047, m.ew); /* d_merge: weights; d_merge_cw_t<., 0>: endpoints */ ENSURE(c->eku, ((size_t)E + 2047) & ~(size_t)2047, m.eku);      // (Ecap of the widest merge kernel)
+    ENSURE(c->ehist, E, m.ehist); ENSURE(c->ealive, E, m.ealive);
+    ENSURE(c->ev_epoch, m.ev_cap, m.ev_epoch); ENSURE(c->ev_key, m.ev_cap, m.ev_key); ENSURE(c->ev_prev, m.ev_cap, m.ev_prev);
+    ENSURE(c->racc, (size_t)(S0 + 1) * 12, m.racc); ENSURE(c->rrec, (size_t)(S0 + 1) * 16, m.rrec);
+    ENSURE(c->rcnt, S0 + 1, m.rcnt); ENSURE(c->ralive, S0 + 1, m.ralive);
+    ENSURE(c->rhead, S0 + 1, m.rhead); ENSURE(c->rtail, S0 + 1, m.rtail); ENSURE(c->lnext, S0 + 1, m.lnext);
+    ENSURE(c->parent, S0 + 1, m.parent); ENSURE(c->markA, S0 + 1, m.markA); ENSURE(c->markB, S0 + 1, m.markB);
+    ENSURE(c->tl, E, m.tl); ENSURE(c->merges, (size_t)(S0 + 1) * 3, m.merges);
+    m.loff = c->loff.p; m.llen = c->hcount.p; m.rows = c->rows.p;
+    float* deltas; ENSURE(c->deltas, (size_t)E * 2, deltas);
     // working copies of the supervoxel state (a second cluster() call starts from the same initial state)
     rec_copy(c, m.racc, c->racc0.p, (size_t)(S0 + 1) * 12 * 4);
     rec_copy(c, m.rrec, c->rrec0.p, (size_t)(S0 + 1) * 16 * 4);
@@ -824,8 +836,8 @@ int seg_cluster_front(f3ds_ctx* c, const f3ds_params* prm, int kind) {
     merge_il_layout(E, S0, use_lds ? mk_waves(kind) : 8, use_lds ? mk_res(kind) : 0, &xl);
     uint32_t logS = 1; while ((1u << logS) < S0 + 2u) ++logS;
     xl.pool_cap = (S0 + 1u) * (4u * logS + 8u) * c->pool_mult;
-    ENSURE(c->pool, uint2, xl.pool_cap, xl.pool); ENSURE(c->rstart, uint32_t, S0 + 1, xl.rstart); ENSURE(c->rnleaf, uint32_t, S0 + 1, xl.rnleaf);
-    ENSURE(c->rcap, uint32_t, S0 + 1, xl.rcap);
+    ENSURE(c->pool, xl.pool_cap, xl.pool); ENSURE(c->rstart, S0 + 1, xl.rstart); ENSURE(c->rnleaf, S0 + 1, xl.rnleaf);
+    ENSURE(c->rcap, S0 + 1, xl.rcap);
     // incident-edge lists of the regions (d_inc_build): the initial lists take 2 E entries, a merge whose touched list outgrows a's segment takes a fresh one
     // (only the incident-list kernels have them: d_merge, the all-global fallback of the large-E scenes, scans the edge arrays.  What the loop can need is bounded: a
     // merge that leaves its segment takes at most nt + nt / 2 + 4 fresh entries, nt <= MC_TL_CAP, and there are at most S0 - 1 merges)
@@ -834,33 +846,33 @@ int seg_cluster_front(f3ds_ctx* c, const f3ds_params* prm, int kind) {
         uint64_t cap = 2ull * E + (uint64_t)g_sw.ilist_slack * E * c->ilist_mult + (g_sw.ilist_slack < 32u ? 16u : 1024u);
         if (cap > bound) cap = bound;
         xl.ilist_cap = cap > 0x7fffffffull ? 0x7fffffffu : (uint32_t)cap;
-        ENSURE(c->ilist, uint32_t, xl.ilist_cap, xl.ilist); ENSURE(c->istart, uint32_t, S0 + 1, xl.istart); ENSURE(c->ilen, uint32_t, S0 + 1, xl.ilen); ENSURE(c->icap, uint32_t, S0 + 1, xl.icap);
+        ENSURE(c->ilist, xl.ilist_cap, xl.ilist); ENSURE(c->istart, S0 + 1, xl.istart); ENSURE(c->ilen, S0 + 1, xl.ilen); ENSURE(c->icap, S0 + 1, xl.icap);
     }
-    if (use_lds) rec<d_inc_build>(c, 1u, 0u, E, S0, (const uint32_t*)m.ea, (const uint32_t*)m.eb, xl.istart, xl.ilen, xl.icap, xl.ilist);
+    if (use_lds) rec<d_inc_build>(c, 1u, 0u, E, S0, m.ea, m.eb, xl.istart, xl.ilen, xl.icap, xl.ilist);
     xl.stop_key = (prm->threshold != prm->threshold) ? 0u : n_weight_key(prm->threshold);
     c->merge_in_lds = use_lds; c->merge_kind = kind;
-    rec<d_region_reset>(c, grid_for(S0 + 1, 256), 0u, S0, (const uint32_t*)c->hcount.p, m.rhead, m.rtail, m.lnext, m.parent, m.markA, m.markB, xl.pool, xl.rstart, xl.rnleaf, xl.rcap, (const uint32_t*)c->loff.p);
+    rec<d_region_reset>(c, grid_for(S0 + 1, 256), 0u, S0, c->hcount.p, m.rhead, m.rtail, m.lnext, m.parent, m.markA, m.markB, xl.pool, xl.rstart, xl.rnleaf, xl.rcap, c->loff.p);
     m.mp.color_metric = prm->color_metric; m.mp.geom_metric = prm->geom_metric; m.mp.merging = prm->merging; m.mp.lambda = lambda; m.mp.bins = bins;
     uint64_t *sk0 = nullptr, *sk1 = nullptr; uint32_t *sv0 = nullptr, *sv1 = nullptr;
     if (prm->merging == F3DS_ADAPTIVE_LAMBDA) {
-        ENSURE(c->skeys0, uint64_t, (size_t)E * 2, sk0); ENSURE(c->skeys1, uint64_t, (size_t)E * 2, sk1);
-        ENSURE(c->svals0, uint32_t, (size_t)E * 2, sv0); ENSURE(c->svals1, uint32_t, (size_t)E * 2, sv1);
+        ENSURE(c->skeys0, (size_t)E * 2, sk0); ENSURE(c->skeys1, (size_t)E * 2, sk1);
+        ENSURE(c->svals0, (size_t)E * 2, sv0); ENSURE(c->svals1, (size_t)E * 2, sv1);
     }
-    rec<d_edge_deltas>(c, grid_for(E, 256), 0u, E, (const uint32_t*)m.ea, (const uint32_t*)m.eb, (const float*)m.rrec, prm->color_metric, prm->geom_metric, deltas, sk0, sv0);
+    rec<d_edge_deltas>(c, grid_for(E, 256), 0u, E, m.ea, m.eb, m.rrec, prm->color_metric, prm->geom_metric, deltas, sk0, sv0);
     if (prm->merging == F3DS_ADAPTIVE_LAMBDA) {
         uint64_t* ks; uint32_t* vs;
         int rc = radix_sort(c, sk0, sv0, sk1, sv1, E * 2u, 33, &ks, &vs);
         if (rc) return rc;
-        rec<d_lambda>(c, 1u, 0u, E, (const float*)deltas, (const uint32_t*)vs, c->d_dc);
+        rec<d_lambda>(c, 1u, 0u, E, deltas, vs, c->d_dc);
     } else if (prm->merging == F3DS_EQUALIZATION) {
         uint32_t* hist; float* cdf;
-        ENSURE(c->cdf_hist, uint32_t, (size_t)2 * (bins > 0 ? bins : 1), hist); ENSURE(c->cdf, float, (size_t)2 * (bins > 0 ? bins : 1), cdf);
+        ENSURE(c->cdf_hist, (size_t)2 * (bins > 0 ? bins : 1), hist); ENSURE(c->cdf, (size_t)2 * (bins > 0 ? bins : 1), cdf);
         rec_fill(c, hist, 0u, (size_t)2 * (bins > 0 ? bins : 1) * 4);
-        rec<d_cdf_hist>(c, grid_for((size_t)E * 2, 256), 0u, E, (const float*)deltas, bins, hist, c->d_dc);
-        rec<d_cdf_scan>(c, 1u, 0u, E, bins, (const uint32_t*)hist, cdf);
+        rec<d_cdf_hist>(c, grid_for((size_t)E * 2, 256), 0u, E, deltas, bins, hist, c->d_dc);
+        rec<d_cdf_scan>(c, 1u, 0u, E, bins, hist, cdf);
         m.mp.cdf_c = cdf; m.mp.cdf_g = cdf + bins;
     }
-    rec<d_edge_weights>(c, grid_for(E, 256), 0u, m, (const float*)deltas);
+    rec<d_edge_weights>(c, grid_for(E, 256), 0u, m, deltas);
     c->mdev = m; c->mlds = xl; c->host_lambda = lambda;
     return F3DS_OK;
 }
@@ -889,17 +901,17 @@ int seg_labels(f3ds_ctx* c) {
     const uint32_t S0 = c->S0, n = c->n;
     const MergeDev& m = c->mdev;
     uint32_t *root, *rincl, *d_labels;
-    ENSURE(c->root, uint32_t, S0 + 1, root); ENSURE(c->rincl, uint32_t, S0 + 1, rincl);
+    ENSURE(c->root, S0 + 1, root); ENSURE(c->rincl, S0 + 1, rincl);
     if (c->user_labels) d_labels = c->user_labels;      // a device output buffer is written in place
-    else ENSURE(c->labels, uint32_t, n, d_labels);
+    else ENSURE(c->labels, n, d_labels);
     if (c->relabel_lds) {
         // (every workgroup builds the table: a lone frame does not get more workgroups than it has 4096-point slices)
         const uint32_t gx = std::min(grid_for(n, 256), grid_wide(n, 4096));
-        rec<d_relabel>(c, gx, (S0 + 1u) * 4u, n, (const int*)c->pt_voxel.p, (const uint32_t*)c->owner0.p, S0, (const uint32_t*)m.parent, (const unsigned char*)m.ralive, root, rincl, d_labels, c->d_dc);
+        rec<d_relabel>(c, gx, (S0 + 1u) * 4u, n, c->pt_voxel.p, c->owner0.p, S0, m.parent, m.ralive, root, rincl, d_labels, c->d_dc);
     } else {
-        uint32_t* rank; ENSURE(c->rrank, uint32_t, S0 + 1, rank);
-        rec<d_region_ids>(c, 1u, 0u, S0, (const uint32_t*)m.parent, (const unsigned char*)m.ralive, rank, root, rincl, c->d_dc);
-        rec<d_point_labels>(c, grid_for(n, 256), 0u, n, (const int*)c->pt_voxel.p, (const uint32_t*)c->owner0.p, (const uint32_t*)rank, d_labels);
+        uint32_t* rank; ENSURE(c->rrank, S0 + 1, rank);
+        rec<d_region_ids>(c, 1u, 0u, S0, m.parent, m.ralive, rank, root, rincl, c->d_dc);
+        rec<d_point_labels>(c, grid_for(n, 256), 0u, n, c->pt_voxel.p, c->owner0.p, rank, d_labels);
     }
     return F3DS_OK;
 }
@@ -907,7 +919,7 @@ int seg_labels(f3ds_ctx* c) {
 // labels of a frame that has no voxels at all
 int finish_empty(f3ds_ctx* c, hipStream_t st, uint32_t* point_labels, int labels_on_device) {
     uint32_t* d_labels;
-    ENSURE(c->labels, uint32_t, c->n ? c->n : 1, d_labels);
+    ENSURE(c->labels, c->n ? c->n : 1, d_labels);
     if (c->n) {
         HIPCHECK(hipMemsetAsync(d_labels, 0xFF, (size_t)c->n * 4, st));
         if (point_labels) HIPCHECK(hipMemcpyAsync(point_labels, d_labels, (size_t)c->n * 4, labels_on_device ? hipMemcpyDefault : hipMemcpyDeviceToHost, st));
@@ -962,7 +974,7 @@ static uint32_t* pinned_device_alias(uint32_t* host) {
     memset(&at, 0, sizeof at);
     if (hipPointerGetAttributes(&at, host) != hipSuccess) { (void)hipGetLastError(); return nullptr; }      // (pageable memory: "invalid value", and the error must not stick)
     if (at.type != hipMemoryTypeHost || !at.devicePointer) return nullptr;
-    return (uint32_t*)at.devicePointer;
+    return static_cast<uint32_t*>(at.devicePointer);
 }
 
 // cluster stage for the live frames (also the whole of f3ds_recluster)
@@ -998,7 +1010,7 @@ int run_cluster(Batch& b, const f3ds_params* prm, uint32_t* const* labels_of, co
         if (dl) {      // queued on the copy stream only once the labels exist: that stream must never sit blocked behind unfinished compute
             for (int k = 1; k < 3; ++k) if (!b.owner->ev_copy[k]) HIPCHECK(hipEventCreateWithFlags(&b.owner->ev_copy[k], hipEventDisableTiming));
             HIPCHECK(hipEventRecord(b.owner->ev_copy[1], b.st));
-            { const double t0 = now_ms(); HIPCHECK(hipEventSynchronize(b.owner->ev_copy[1])); g_t_wait += now_ms() - t0; }
+            HIPCHECK(timed_sync(b.owner->ev_copy[1]));
         }
         for (size_t i = 0; i < b.fr.size(); ++i) {
             f3ds_ctx* c = b.fr[i];
@@ -1008,7 +1020,7 @@ int run_cluster(Batch& b, const f3ds_params* prm, uint32_t* const* labels_of, co
         }
         if (dl) HIPCHECK(hipEventRecord(b.owner->ev_copy[2], dl));
         if ((rc = flush_sync(b))) return rc;
-        if (dl) { const double t0 = now_ms(); HIPCHECK(hipEventSynchronize(b.owner->ev_copy[2])); g_t_wait += now_ms() - t0; }
+        if (dl) HIPCHECK(timed_sync(b.owner->ev_copy[2]));
     }
     {
         // a frame whose merge loop re-weights more edges than its event arrays hold (huge regions of tiny supervoxels)
@@ -1021,10 +1033,7 @@ int run_cluster(Batch& b, const f3ds_params* prm, uint32_t* const* labels_of, co
         }
         if (again) {
             if (g_sw.trace_err) fprintf(stderr, "f3ds: merge stage of %zu frames runs again with more history / leaf-pool room\n", b.fr.size());
-            for (f3ds_ctx* c : b.fr) {
-                c->h_dc->error = 0; c->h_dc->ev_overflow = 0;
-                HIPCHECK(hipMemsetAsync(&c->d_dc->error, 0, sizeof(int), b.st)); HIPCHECK(hipMemsetAsync(&c->d_dc->ev_overflow, 0, sizeof(int), b.st));
-            }
+            for (f3ds_ctx* c : b.fr) if ((rc = clear_counters(c, b.st, &DevCounters::error, &DevCounters::ev_overflow))) return rc;
             return run_cluster(b, prm, labels_of, index_of, labels_on_device, force_global);
         }
     }
@@ -1035,7 +1044,7 @@ int run_cluster(Batch& b, const f3ds_params* prm, uint32_t* const* labels_of, co
         for (f3ds_ctx* c : b.fr) if (c->h_dc->error == F3DS_ERR_UNSUPPORTED) again = true;
         if (again) {
             if (g_sw.trace_err) fprintf(stderr, "f3ds: merge stage of %zu frames runs again with the global-memory kernel\n", b.fr.size());
-            for (f3ds_ctx* c : b.fr) { c->h_dc->error = 0; HIPCHECK(hipMemsetAsync(&c->d_dc->error, 0, sizeof(int), b.st)); }
+            for (f3ds_ctx* c : b.fr) if ((rc = clear_counters(c, b.st, &DevCounters::error))) return rc;
             return run_cluster(b, prm, labels_of, index_of, labels_on_device, true);
         }
     }
@@ -1077,11 +1086,11 @@ int f3ds_create(int device, f3ds_ctx** out) {
         HIPCHECK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
         c->stream = c->own_stream;
         for (auto& e : c->ev) HIPCHECK(hipEventCreate(&e));
-        HIPCHECK(hipMalloc((void**)&c->d_dc, sizeof(DevCounters)));
-        HIPCHECK(hipHostMalloc((void**)&c->h_dc, sizeof(DevCounters), hipHostMallocDefault));
-        HIPCHECK(hipMalloc((void**)&c->d_grid, sizeof(GridInfo)));
-        HIPCHECK(hipHostMalloc((void**)&c->h_grid, sizeof(GridInfo), hipHostMallocDefault));
-        HIPCHECK(hipMalloc((void**)&c->d_sgrid, sizeof(SeedGrid)));
+        HIPCHECK(hipMalloc(&c->d_dc, sizeof(DevCounters)));
+        HIPCHECK(hipHostMalloc(&c->h_dc, sizeof(DevCounters), hipHostMallocDefault));
+        HIPCHECK(hipMalloc(&c->d_grid, sizeof(GridInfo)));
+        HIPCHECK(hipHostMalloc(&c->h_grid, sizeof(GridInfo), hipHostMallocDefault));
+        HIPCHECK(hipMalloc(&c->d_sgrid, sizeof(SeedGrid)));
         return F3DS_OK;
     }();
     if (rc) { c->stream = c->own_stream; f3ds_destroy(c); return rc; }      // a half-built context is released, not leaked
@@ -1095,9 +1104,7 @@ void f3ds_destroy(f3ds_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    Buf* bufs = &c->pts;
-    const size_t nb = (reinterpret_cast<char*>(&c->rincl) - reinterpret_cast<char*>(&c->pts)) / sizeof(Buf) + 1;
-    for (size_t i = 0; i < nb; ++i) if (bufs[i].p) (void)hipFree(bufs[i].p);
+    c->each_scratch([](auto& b) { if (b.p) (void)hipFree(b.p); return 0; });
     if (c->d_dc) (void)hipFree(c->d_dc);
     if (c->h_dc) (void)hipHostFree(c->h_dc);
     if (c->d_grid) (void)hipFree(c->d_grid);
@@ -1151,7 +1158,7 @@ int f3ds_segment_batch(f3ds_ctx** ctxs, int nctx, const void* const* points, con
     bool uploaded = false;
     for (int i = 0; i < nctx; ++i) {
         f3ds_ctx* c = ctxs[i];
-        c->cmds.clear(); c->blob.clear(); c->pend.clear(); c->ops.n = 0; c->ops_grid = 0;
+        reset_recording(c);
         c->have_frame = false; c->live = true; c->rc = 0; c->refined_itr = -1;
         c->user_mode = false; c->user_label.clear(); c->user_row.clear();
         { const int prc = pregrow_scratch(c); if (prc) return prc; }
@@ -1159,9 +1166,9 @@ int f3ds_segment_batch(f3ds_ctx** ctxs, int nctx, const void* const* points, con
         memset(&c->res, 0, sizeof c->res);
         c->res.n_points = c->n; c->res.sweeps = sweeps;
         c->fa = FrameArgs{prm->use_transform, prm->fold_negative_z, prm->leaf_order, prm->voxel_res, prm->seed_res, prm->w_color, prm->w_spatial, prm->w_normal};
-        if (points_on_device) c->d_pts = (const P16*)points[i];
+        if (points_on_device) c->d_pts = static_cast<const P16*>(points[i]);
         else {
-            P16* up; ENSURE(c->pts, P16, c->n ? c->n : 1, up);
+            P16* up; ENSURE(c->pts, c->n ? c->n : 1, up);
             if (c->n) { HIPCHECK(hipMemcpyAsync(up, points[i], (size_t)c->n * 16, hipMemcpyHostToDevice, up_stream ? up_stream : b.st)); uploaded = true; }
             c->d_pts = up;
         }
@@ -1208,7 +1215,7 @@ int f3ds_segment_batch(f3ds_ctx** ctxs, int nctx, const void* const* points, con
         const int tile_bits = bits_for((uint64_t)maxtiles - 1u);
         rc = for_frames(b, [&](f3ds_ctx* c) { return seg_vox_tiles(c, 3 * maxd, tile_bits); });
         if (rc == F3DS_ERR_UNSUPPORTED) {      // (a grid too deep / a frame too long for this path: nothing was flushed)
-            for (f3ds_ctx* c : b.fr) { c->cmds.clear(); c->blob.clear(); c->pend.clear(); c->ops.n = 0; c->ops_grid = 0; c->vox_hashed = false; }
+            for (f3ds_ctx* c : b.fr) { reset_recording(c); c->vox_hashed = false; }
             hashed = false;
         } else if (rc || (rc = flush_sync(b))) return rc;
         if (hashed && g_sw.trace_err) for (f3ds_ctx* c : b.fr) fprintf(stderr, "f3ds: tile path: most voxels in a tile %u, descriptors %u, leaves %u, lists sorted %u\n", c->h_dc->vox_max_tile, c->h_dc->seg_count, c->h_dc->n_voxels, c->h_dc->vox_disorder);
@@ -1219,9 +1226,8 @@ int f3ds_segment_batch(f3ds_ctx** ctxs, int nctx, const void* const* points, con
         if (!hashed) {
             if (g_sw.trace_err) fprintf(stderr, "f3ds: voxelisation of %zu frames runs again on the sort path (an unorganised cloud or dense voxels)\n", b.fr.size());
             for (f3ds_ctx* c : b.fr) {
-                c->h_dc->error = 0; c->h_dc->ev_overflow = 0; c->vox_hashed = false;
-                HIPCHECK(hipMemsetAsync(&c->d_dc->error, 0, sizeof(int), b.st)); HIPCHECK(hipMemsetAsync(&c->d_dc->ev_overflow, 0, sizeof(int), b.st));
-                HIPCHECK(hipMemsetAsync(&c->d_dc->n_voxels, 0, sizeof(uint32_t), b.st)); HIPCHECK(hipMemsetAsync(&c->d_dc->seg_count, 0, sizeof(uint32_t), b.st));
+                c->vox_hashed = false;
+                if ((rc = clear_counters(c, b.st, &DevCounters::error, &DevCounters::ev_overflow, &DevCounters::n_voxels, &DevCounters::seg_count))) return rc;
             }
         }
     }
@@ -1261,11 +1267,7 @@ int f3ds_segment_batch(f3ds_ctx** ctxs, int nctx, const void* const* points, con
         for (f3ds_ctx* c : b.fr) if (c->h_dc->ev_overflow == 3 && c->edge_mult < (1u << 14)) { c->edge_mult *= 4u; again = true; }
         if (!again) break;
         if (g_sw.trace_err) fprintf(stderr, "f3ds: adjacency pass of %zu frames runs again with more list room\n", b.fr.size());
-        for (f3ds_ctx* c : b.fr) {
-            c->h_dc->error = 0; c->h_dc->ev_overflow = 0;
-            HIPCHECK(hipMemsetAsync(&c->d_dc->error, 0, sizeof(int), b.st)); HIPCHECK(hipMemsetAsync(&c->d_dc->ev_overflow, 0, sizeof(int), b.st));
-            HIPCHECK(hipMemsetAsync(&c->d_dc->n_edges, 0, sizeof(uint32_t), b.st)); HIPCHECK(hipMemsetAsync(&c->d_dc->n_alive, 0, sizeof(uint32_t), b.st));
-        }
+        for (f3ds_ctx* c : b.fr) if ((rc = clear_counters(c, b.st, &DevCounters::error, &DevCounters::ev_overflow, &DevCounters::n_edges, &DevCounters::n_alive))) return rc;
         if ((rc = for_frames(b, seg_supervoxels)) || (rc = flush_sync(b))) return rc;
     }
     uint64_t maxkey = 1;
@@ -1304,9 +1306,8 @@ int f3ds_recluster(f3ds_ctx* c, const f3ds_params* prm, uint32_t* point_labels, 
     g_sw.read();
     HIPCHECK(hipSetDevice(c->device));
     Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); g_grid_cap = grid_cap_for_batch(1); g_batch_frames = 1;
-    c->cmds.clear(); c->blob.clear(); c->pend.clear(); c->ops.n = 0; c->ops_grid = 0;
-    c->h_dc->error = 0;
-    HIPCHECK(hipMemsetAsync(&c->d_dc->error, 0, sizeof(int), c->stream));
+    reset_recording(c);
+    { const int crc = clear_counters(c, c->stream, &DevCounters::error); if (crc) return crc; }
     stage_mark(b, 4);
     std::vector<int> idx{0}; uint32_t* lp[1] = {point_labels};
     int rc = run_cluster(b, prm, lp, idx, labels_on_device);
@@ -1372,7 +1373,7 @@ int f3ds_cluster_supervoxels(f3ds_ctx* c, const f3ds_supervoxel_set* sv, const u
     }
     const uint32_t E = (uint32_t)ea.size();
     // ---- frame state
-    c->cmds.clear(); c->blob.clear(); c->pend.clear(); c->ops.n = 0; c->ops_grid = 0;
+    reset_recording(c);
     c->have_frame = false; c->live = true; c->rc = 0; c->refined_itr = -1;
     { const int prc = pregrow_scratch(c); if (prc) return prc; }
     c->prm = *prm; c->n = Vt; c->V = c->C = 0; c->S0 = S; c->E = E; c->d_pts = nullptr;
@@ -1386,13 +1387,13 @@ int f3ds_cluster_supervoxels(f3ds_ctx* c, const f3ds_supervoxel_set* sv, const u
     }
     Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); g_grid_cap = grid_cap_for_batch(1); g_batch_frames = 1;
     uint32_t *d_src, *d_voff, *d_rgba, *loff, *hcount, *owner, *rcnt0, *ea0, *eb0; float *d_xyz, *d_cent, *d_nrm, *rows, *racc0, *rrec0, *hc; int *row_voxel, *pt_voxel; unsigned char* ralive0;
-    ENSURE(c->u_src, uint32_t, S + 1u, d_src); ENSURE(c->u_voff, uint32_t, S + 1u, d_voff); ENSURE(c->u_xyz, float, (size_t)Vt * 3, d_xyz); ENSURE(c->u_rgba, uint32_t, Vt, d_rgba);
-    ENSURE(c->u_cent, float, (size_t)S * 3, d_cent); ENSURE(c->u_nrm, float, (size_t)S * 3, d_nrm);
-    ENSURE(c->loff, uint32_t, S + 2u, loff); ENSURE(c->hcount, uint32_t, S + 1u, hcount); ENSURE(c->owner0, uint32_t, Vt, owner); ENSURE(c->pt_voxel, int, Vt, pt_voxel);
-    ENSURE(c->rows, float, ((size_t)Vt + S + 1) * 12, rows); ENSURE(c->row_voxel, int, (size_t)Vt + S + 1, row_voxel);
-    ENSURE(c->racc0, float, (size_t)(S + 1) * 12, racc0); ENSURE(c->rcnt0, uint32_t, S + 1u, rcnt0); ENSURE(c->rrec0, float, (size_t)(S + 1) * 16, rrec0);
-    ENSURE(c->ralive0, unsigned char, S + 1u, ralive0); ENSURE(c->hc, float, (size_t)(S + 1) * 12, hc);
-    ENSURE(c->ea0, uint32_t, E, ea0); ENSURE(c->eb0, uint32_t, E, eb0);
+    ENSURE(c->u_src, S + 1u, d_src); ENSURE(c->u_voff, S + 1u, d_voff); ENSURE(c->u_xyz, (size_t)Vt * 3, d_xyz); ENSURE(c->u_rgba, Vt, d_rgba);
+    ENSURE(c->u_cent, (size_t)S * 3, d_cent); ENSURE(c->u_nrm, (size_t)S * 3, d_nrm);
+    ENSURE(c->loff, S + 2u, loff); ENSURE(c->hcount, S + 1u, hcount); ENSURE(c->owner0, Vt, owner); ENSURE(c->pt_voxel, Vt, pt_voxel);
+    ENSURE(c->rows, ((size_t)Vt + S + 1) * 12, rows); ENSURE(c->row_voxel, (size_t)Vt + S + 1, row_voxel);
+    ENSURE(c->racc0, (size_t)(S + 1) * 12, racc0); ENSURE(c->rcnt0, S + 1u, rcnt0); ENSURE(c->rrec0, (size_t)(S + 1) * 16, rrec0);
+    ENSURE(c->ralive0, S + 1u, ralive0); ENSURE(c->hc, (size_t)(S + 1) * 12, hc);
+    ENSURE(c->ea0, E, ea0); ENSURE(c->eb0, E, eb0);
     std::vector<uint32_t> h_loff(S + 2u, 0u), h_cnt(S + 1u, 0u);
     for (uint32_t h = 1; h <= S; ++h) { h_loff[h] = sv->voxel_offset[row[h]]; h_cnt[h] = sv->voxel_offset[row[h] + 1] - sv->voxel_offset[row[h]]; }
     h_loff[S + 1] = Vt;      // (rows in use: f3ds_get_voxel_cloud)
@@ -1411,9 +1412,8 @@ int f3ds_cluster_supervoxels(f3ds_ctx* c, const f3ds_supervoxel_set* sv, const u
     rec_fill(c, ralive0, 0u, S + 1u);
     rec_fill(c, rcnt0, 0u, (size_t)(S + 1) * 4);
     rec_fill(c, racc0, 0u, 48); rec_fill(c, rrec0, 0u, 64); rec_fill(c, hc, 0u, 48);
-    rec<d_iota>(c, grid_for(Vt, 256), 0u, (uint32_t*)pt_voxel, Vt);
-    rec<d_sv_user_fill>(c, S, 0u, S, (const uint32_t*)d_src, (const uint32_t*)d_voff, (const float*)d_xyz, (const uint32_t*)d_rgba, (const float*)d_cent, (const float*)d_nrm, rows, row_voxel,
-                        owner, racc0, rcnt0, rrec0, ralive0, hc, c->d_dc);
+    rec<d_iota>(c, grid_for(Vt, 256), 0u, reinterpret_cast<uint32_t*>(pt_voxel), Vt);      // (the caller's voxels are their own "points": ordinal v >= 0 as int, written through the kernel's uint32 view)
+    rec<d_sv_user_fill>(c, S, 0u, S, d_src, d_voff, d_xyz, d_rgba, d_cent, d_nrm, rows, row_voxel, owner, racc0, rcnt0, rrec0, ralive0, hc, c->d_dc);
     int rc = flush(b);
     if (rc) return rc;
     uint32_t* lp[1] = {voxel_labels}; std::vector<int> idx{0};
@@ -1438,7 +1438,7 @@ int f3ds_cluster_supervoxels(f3ds_ctx* c, const f3ds_supervoxel_set* sv, const u
 // ------------------------------------------------------------------------------------------------
 namespace {
 template <class T>
-int fetch(f3ds_ctx* c, const Buf& b, size_t count, std::vector<T>& out) {
+int fetch(f3ds_ctx* c, const Scratch<T>& b, size_t count, std::vector<T>& out) {
     out.resize(count);
     if (count) HIPCHECK(hipMemcpy(out.data(), b.p, count * sizeof(T), hipMemcpyDeviceToHost));
     return F3DS_OK;
@@ -1581,23 +1581,22 @@ extern "C" int f3ds_refine_supervoxels(f3ds_ctx* c, int num_itr) {
     g_sw.read();
     HIPCHECK(hipSetDevice(c->device));
     Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); g_grid_cap = grid_cap_for_batch(1); g_batch_frames = 1;
-    c->cmds.clear(); c->blob.clear(); c->pend.clear(); c->ops.n = 0; c->ops_grid = 0;
+    reset_recording(c);
     c->refined_itr = -1;
     const uint32_t V = c->V, S0 = c->S0;
     float *r_vf, *r_hc; uint32_t *r_owner, *r_hcount, *L; int *r_gvox, *seed; unsigned char* r_gact;
-    ENSURE(c->r_vf, float, (size_t)V * 12, r_vf); ENSURE(c->r_owner, uint32_t, V, r_owner); ENSURE(c->r_hc, float, (size_t)(S0 + 1) * 12, r_hc);
-    ENSURE(c->r_hcount, uint32_t, S0 + 1, r_hcount); ENSURE(c->r_gvox, int, S0 + 1, r_gvox); ENSURE(c->r_gact, unsigned char, S0 + 1, r_gact);
-    ENSURE(c->r_seed, int, S0 + 1, seed); ENSURE(c->r_L, uint32_t, V, L);
+    ENSURE(c->r_vf, (size_t)V * 12, r_vf); ENSURE(c->r_owner, V, r_owner); ENSURE(c->r_hc, (size_t)(S0 + 1) * 12, r_hc);
+    ENSURE(c->r_hcount, S0 + 1, r_hcount); ENSURE(c->r_gvox, S0 + 1, r_gvox); ENSURE(c->r_gact, S0 + 1, r_gact);
+    ENSURE(c->r_seed, S0 + 1, seed); ENSURE(c->r_L, V, L);
     rec_copy(c, r_vf, c->vf.p, (size_t)V * 48); rec_copy(c, r_owner, c->owner0.p, (size_t)V * 4); rec_copy(c, r_hc, c->hc.p, (size_t)(S0 + 1) * 48);
     rec_copy(c, r_hcount, c->hcount.p, (size_t)(S0 + 1) * 4); rec_copy(c, r_gvox, c->ghost_vox.p, (size_t)(S0 + 1) * 4); rec_copy(c, r_gact, c->ghost_active.p, S0 + 1);
-    SweepBufs sb{&c->r_owner, &c->r_dist, &c->r_hc, &c->r_hcount, &c->r_hlo, &c->r_hhi, &c->r_gvox, &c->r_gact, &c->r_gdone, &c->r_ghead, &c->r_gnext,
-                 &c->r_tl, &c->r_tcnt, r_vf, seed, true};
+    SweepBufs sb{&c->r_owner, &c->r_dist, &c->r_hc, &c->r_hcount, &c->r_hlo, &c->r_hhi, &c->r_gvox, &c->r_gact, &c->r_gdone, &c->r_ghead, &c->r_gnext, &c->r_tl, &c->r_tcnt, r_vf, seed, true};
     int rc;
     for (int it = 0; it < num_itr; ++it) {
         rec_copy(c, L, r_owner, (size_t)V * 4);
-        rec<d_refine_ghost_L>(c, grid_for(S0, 256), 0u, S0, (const int*)r_gvox, (const unsigned char*)r_gact, L);
-        rec<d_refine_normals>(c, grid_for(V, 256), 0u, r_vf, (const int*)c->nbr.p, (const uint32_t*)r_owner, (const uint32_t*)L, V);
-        rec<d_reseed>(c, S0 ? S0 : 1u, 0u, (const float*)r_vf, V, S0, (const uint32_t*)r_hcount, (const float*)r_hc, seed);
+        rec<d_refine_ghost_L>(c, grid_for(S0, 256), 0u, S0, r_gvox, r_gact, L);
+        rec<d_refine_normals>(c, grid_for(V, 256), 0u, r_vf, c->nbr.p, r_owner, L, V);
+        rec<d_reseed>(c, S0 ? S0 : 1u, 0u, r_vf, V, S0, r_hcount, r_hc, seed);
         if ((rc = seg_sweeps_on(c, sb)) || (rc = flush_sync(b))) return rc;
         if (c->h_dc->error) return trace_err(c->h_dc->error, "refine", c);
     }
@@ -1627,7 +1626,7 @@ extern "C" int f3ds_get_refined_voxels(f3ds_ctx* c, uint32_t* sv_label, float* n
 }
 
 namespace {
-int supervoxels_of(f3ds_ctx* c, const Buf& hcount, const Buf& hcent, uint32_t* label, float* xyz, float* rgb, float* normal, uint32_t* n_voxels, size_t cap, size_t* n_out) {
+int supervoxels_of(f3ds_ctx* c, const Scratch<uint32_t>& hcount, const Scratch<float>& hcent, uint32_t* label, float* xyz, float* rgb, float* normal, uint32_t* n_voxels, size_t cap, size_t* n_out) {
     const uint32_t S0 = c->S0;
     std::vector<uint32_t> cnt; std::vector<float> hc;
     int rc;
@@ -1721,7 +1720,7 @@ extern "C" int f3ds_get_debug(f3ds_ctx* c, int what, void* dst, size_t cap_bytes
     HIPCHECK(hipStreamSynchronize(c->stream));
     const uint32_t V = c->V, S0 = c->S0, E = c->E, n = c->n;
     std::vector<uint8_t> buf;
-    auto put = [&](const void* p, size_t nb) { const uint8_t* b = (const uint8_t*)p; buf.insert(buf.end(), b, b + nb); };
+    auto put = [&](const void* src, size_t nb) { const uint8_t* b = static_cast<const uint8_t*>(src); buf.insert(buf.end(), b, b + nb); };
     int rc = F3DS_OK;
     std::vector<float> f; std::vector<uint32_t> u, u2, u3; std::vector<int> iv; std::vector<unsigned char> uc;
     if (what != F3DS_DBG_GRID && !c->have_frame) return F3DS_ERR_LOGIC;
@@ -1811,15 +1810,15 @@ namespace {
 int eval_truth(f3ds_ctx* c, const uint32_t* truth_point_labels) {
     const uint32_t n = c->n, V = c->V;
     uint32_t *lut, *tp, *tsum, *tcol, *tlab;
-    ENSURE(c->glut, uint32_t, 256, lut); ENSURE(c->truth_pts, uint32_t, n, tp); ENSURE(c->tsum, uint32_t, (size_t)V * 3, tsum);
-    ENSURE(c->tcol, uint32_t, V, tcol); ENSURE(c->tlab, uint32_t, V, tlab);
+    ENSURE(c->glut, 256, lut); ENSURE(c->truth_pts, n, tp); ENSURE(c->tsum, (size_t)V * 3, tsum);
+    ENSURE(c->tcol, V, tcol); ENSURE(c->tlab, V, tlab);
     HIPCHECK(hipMemcpyAsync(lut, f3ds_glasbey_256, 1024, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipMemcpyAsync(tp, truth_point_labels, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipMemsetAsync(tsum, 0, (size_t)V * 12, c->stream));
     Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); g_grid_cap = grid_cap_for_batch(1); g_batch_frames = 1;
-    c->cmds.clear(); c->blob.clear(); c->pend.clear(); c->ops.n = 0; c->ops_grid = 0;
-    rec<d_truth_accum>(c, grid_for(n, 256), 0u, n, (const int*)c->pt_voxel.p, (const uint32_t*)tp, (const uint32_t*)lut, tsum);
-    rec<d_truth_color>(c, grid_for(V, 256), 0u, V, (const uint32_t*)tsum, (const uint32_t*)c->vcount.p, tcol);
+    reset_recording(c);
+    rec<d_truth_accum>(c, grid_for(n, 256), 0u, n, c->pt_voxel.p, tp, lut, tsum);
+    rec<d_truth_color>(c, grid_for(V, 256), 0u, V, tsum, c->vcount.p, tcol);
     int rc = flush_sync(b);
     if (rc) return rc;
     std::vector<uint32_t> col;
@@ -1841,14 +1840,13 @@ int eval_scores(f3ds_ctx* c, const uint32_t* d_root, const uint32_t* d_incl, uin
     if (K == 0 || M == 0) return F3DS_ERR_ARG;                         // std::invalid_argument, testing.cpp:414,431
     if ((uint64_t)K * M > (1ull << 26)) return F3DS_ERR_UNSUPPORTED;
     uint32_t *tab, *ssz;
-    ENSURE(c->ctab, uint32_t, (size_t)K * M, tab); ENSURE(c->csize, uint32_t, K, ssz);
+    ENSURE(c->ctab, (size_t)K * M, tab); ENSURE(c->csize, K, ssz);
     HIPCHECK(hipMemsetAsync(tab, 0, (size_t)K * M * 4, c->stream));
     HIPCHECK(hipMemsetAsync(ssz, 0, (size_t)K * 4, c->stream));
     Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); g_grid_cap = grid_cap_for_batch(1); g_batch_frames = 1;
-    c->cmds.clear(); c->blob.clear(); c->pend.clear(); c->ops.n = 0; c->ops_grid = 0;
-    rec<d_contingency>(c, grid_for(V, 256), 0u, V, M, (const uint32_t*)c->owner0.p, d_root, d_incl, (const uint32_t*)c->tlab.p, tab, ssz);
-    rec<d_contingency_ghost>(c, grid_for(c->S0, 256), 0u, c->S0, M, (const int*)c->ghost_vox.p, (const unsigned char*)c->ghost_active.p,
-                             (const uint32_t*)c->owner0.p, d_root, d_incl, (const uint32_t*)c->tlab.p, tab, ssz);
+    reset_recording(c);
+    rec<d_contingency>(c, grid_for(V, 256), 0u, V, M, c->owner0.p, d_root, d_incl, c->tlab.p, tab, ssz);
+    rec<d_contingency_ghost>(c, grid_for(c->S0, 256), 0u, c->S0, M, c->ghost_vox.p, c->ghost_active.p, c->owner0.p, d_root, d_incl, c->tlab.p, tab, ssz);
     int rc = flush_sync(b);
     if (rc) return rc;
     std::vector<uint32_t> table, ssize;
@@ -1865,7 +1863,7 @@ extern "C" int f3ds_evaluate(f3ds_ctx* c, const uint32_t* truth_point_labels, f3
     HIPCHECK(hipStreamSynchronize(c->stream));
     int rc = eval_truth(c, truth_point_labels);
     if (rc) return rc;
-    return eval_scores(c, (const uint32_t*)c->root.p, (const uint32_t*)c->rincl.p, c->res.n_regions, out);
+    return eval_scores(c, c->root.p, c->rincl.p, c->res.n_regions, out);
 }
 
 extern "C" int f3ds_auto_threshold(f3ds_ctx* c, const f3ds_params* prm, const uint32_t* truth_point_labels, float start, float end, float step,
@@ -1888,7 +1886,7 @@ extern "C" int f3ds_auto_threshold(f3ds_ctx* c, const f3ds_params* prm, const ui
     if ((rc = fetch(c, c->merges, (size_t)nm * 3, log)) || (rc = fetch(c, c->hcount, S0 + 1, hcount))) return rc;
     if ((rc = eval_truth(c, truth_point_labels))) return rc;
     uint32_t *d_root, *d_incl;
-    ENSURE(c->eroot, uint32_t, S0 + 1, d_root); ENSURE(c->eincl, uint32_t, S0 + 1, d_incl);
+    ENSURE(c->eroot, S0 + 1, d_root); ENSURE(c->eincl, S0 + 1, d_incl);
     std::vector<uint32_t> parent(S0 + 1), root(S0 + 1), incl(S0 + 1);
     for (uint32_t h = 0; h <= S0; ++h) parent[h] = h;
     std::map<float, f3ds_performance> all;
@@ -1939,21 +1937,21 @@ int check_levels(const f3ds_ctx* c, const float* thr, int K) {
 int levels_record(f3ds_ctx* c, const float* d_thr, uint32_t K, bool lds_form, uint32_t* d_out, uint32_t* nreg) {
     const uint32_t S0 = c->S0, n = c->n, nm = c->res.n_merges, Kp = (K + 3u) & ~3u;
     uint32_t *into, *at, *pfx;
-    ENSURE(c->lv_into, uint32_t, S0 + 1, into); ENSURE(c->lv_at, uint32_t, S0 + 1, at); ENSURE(c->lv_pfx, uint32_t, (size_t)K * 2, pfx);      // (prefixes, then their order)
+    ENSURE(c->lv_into, S0 + 1, into); ENSURE(c->lv_at, S0 + 1, at); ENSURE(c->lv_pfx, (size_t)K * 2, pfx);      // (prefixes, then their order)
     const uint32_t* ord = pfx + K;
-    const uint32_t* merges = (const uint32_t*)c->merges.p;
+    const uint32_t* merges = c->merges.p;
     rec_fill(c, at, LV_NOT_ABSORBED, (size_t)(S0 + 1) * 4);
     rec<d_level_log>(c, grid_for(nm, 256), 0u, nm, S0, merges, into, at);
     rec<d_level_prefix>(c, 1u, 0u, nm, merges, K, d_thr, pfx, pfx + K);
-    const unsigned char* alive0 = (const unsigned char*)c->ralive0.p;
-    const int* pt_voxel = (const int*)c->pt_voxel.p; const uint32_t* owner = (const uint32_t*)c->owner0.p;
+    const unsigned char* alive0 = c->ralive0.p;
+    const int* pt_voxel = c->pt_voxel.p; const uint32_t* owner = c->owner0.p;
     if (lds_form) {
         const uint32_t gx = std::min(grid_for(n, 256), grid_wide(n, 4096));      // (every workgroup builds the tables: as d_relabel)
-        rec<d_level_labels>(c, gx, (S0 + 1u) * Kp * 4u, n, pt_voxel, owner, S0, K, Kp, alive0, (const uint32_t*)into, (const uint32_t*)at, (const uint32_t*)pfx, ord, d_out, nreg);
+        rec<d_level_labels>(c, gx, (S0 + 1u) * Kp * 4u, n, pt_voxel, owner, S0, K, Kp, alive0, into, at, pfx, ord, d_out, nreg);
     } else {
-        uint32_t* tab; ENSURE(c->lv_tab, uint32_t, (size_t)(S0 + 1) * Kp, tab);
-        rec<d_level_tables>(c, 1u, 0u, S0, K, Kp, alive0, (const uint32_t*)into, (const uint32_t*)at, (const uint32_t*)pfx, ord, tab, nreg);
-        rec<d_level_points>(c, grid_for(n, 256), 0u, n, K, Kp, pt_voxel, owner, (const uint32_t*)tab, d_out);
+        uint32_t* tab; ENSURE(c->lv_tab, (size_t)(S0 + 1) * Kp, tab);
+        rec<d_level_tables>(c, 1u, 0u, S0, K, Kp, alive0, into, at, pfx, ord, tab, nreg);
+        rec<d_level_points>(c, grid_for(n, 256), 0u, n, K, Kp, pt_voxel, owner, tab, d_out);
     }
     return F3DS_OK;
 }
@@ -1966,12 +1964,12 @@ int run_levels(f3ds_ctx** ctxs, int nctx, const float* thr, int K, uint32_t* con
     for (int i = 0; i < nctx; ++i) {
         f3ds_ctx* c = ctxs[i];
         if (c->stream != b.st) HIPCHECK(hipStreamSynchronize(c->stream));      // (the frame state is read on the owner's stream)
-        c->cmds.clear(); c->blob.clear(); c->pend.clear(); c->ops.n = 0; c->ops_grid = 0;
+        reset_recording(c);
         b.fr.push_back(c);
     }
     // the thresholds (shared by every frame) go up once, the region counts of all frames come back in one copy: both in the owner's scratch
     float* d_thr; uint32_t* d_nreg;
-    { int rc = ensure<float>(o, o->lv_thr, (size_t)K, &d_thr); if (rc) return rc; rc = ensure<uint32_t>(o, o->lv_nreg, (size_t)nctx * K, &d_nreg); if (rc) return rc; }
+    { int rc = ensure(o, o->lv_thr, (size_t)K, &d_thr); if (rc) return rc; rc = ensure(o, o->lv_nreg, (size_t)nctx * K, &d_nreg); if (rc) return rc; }
     HIPCHECK(hipMemcpyAsync(d_thr, thr, (size_t)K * 4, hipMemcpyHostToDevice, b.st));
     const uint32_t Kp = ((uint32_t)K + 3u) & ~3u;
     bool lds_form = !g_sw.levels_global;      // one form for the whole batch: its frames record identical command shapes
@@ -1980,7 +1978,7 @@ int run_levels(f3ds_ctx** ctxs, int nctx, const float* thr, int K, uint32_t* con
         f3ds_ctx* c = ctxs[i];
         uint32_t* d_out;
         if (labels_on_device) d_out = point_labels[i];
-        else ENSURE(c->lv_out, uint32_t, (size_t)c->n * K, d_out);
+        else ENSURE(c->lv_out, (size_t)c->n * K, d_out);
         const int rc = levels_record(c, d_thr, (uint32_t)K, lds_form, d_out, d_nreg + (size_t)i * K);
         if (rc) return rc;
     }

@@ -6,22 +6,6 @@
 
 namespace {
 
-thread_local std::string g_last_hip_error;
-
-#define HIPCHECK(expr)                                                                          \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) {                                                                 \
-            g_last_hip_error = std::string(#expr) + ": " + hipGetErrorString(e_);               \
-            return F3DS_ERR_HIP;                                                                \
-        }                                                                                       \
-    } while (0)
-
-struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-};
-
 struct P16 { float x, y, z; uint32_t rgba; };
 
 // small block of device scalars the host reads back at the few sync points
