@@ -1,6 +1,8 @@
 // f3ds_eval_levels.h -- the scoring rules of f3ds_evaluate over a SPARSE contingency table, as F3DS_HD code: the building block for
 // scoring many hierarchy levels (f3ds_labels_at_thresholds) without one dense K x M table per level.  No library
-// code calls it yet; tests/eval_levels_harness/ (tests/test_eval_levels_cpu.py) checks it against f3ds_scores_from_table.
+// code calls it yet; tests/eval_levels_harness/ (tests/test_eval_levels_cpu.py) checks it against f3ds_scores_from_table.  The only
+// device build of it so far is the test probe: tests/devprobe/devprobe.hip compiles it with hipcc for gfx950 and
+// tests/test_devprobe_gpu.py::test_evl_scores_on_the_device compares all seven scores with the g++ build, bit for bit.
 //
 // They are the rules of f3ds_scores_from_table (f3ds_eval.h, Testing::eval_performance, the reference's src/testing.cpp:88-136,
 // 239-406) restated for a table that holds only its non-zero entries:

@@ -3459,60 +3459,7 @@ __device__ inline uint32_t wave_incl_scan_dpp(uint32_t v) {
     const int row = lane_id() >> 4;
     return v + (row >= 1 ? t0 : 0u) + (row >= 2 ? t1 : 0u) + (row >= 3 ? t2 : 0u);
 }
-// n_plane_normal (f3ds_numerics.h) for a whole wave whose lane k < 9 holds raw sum k: the same operations on the same values, but the
-// 21 IEEE divisions (64 cycles each on one lane after the other) are taken side by side: lane k divides sum k by the count, lanes 0..5 the
-// covariance entries by the scale, lanes 0..2 the eigenvector and the final normal by their lengths.  count >= 3 (the caller keeps the
-// generic function for less).  cen = the centroid (sums 6..8 over the count: the same quotients).
-__device__ inline float wave_pick(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
-template <class MC>
-__device__ inline void plane_normal_wave(float acc, unsigned count, int lane, float cen[3], float out[4], MC mc) {
-    const float cnt = (float)count;
-    const float qa = acc / cnt;
-    float a[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) a[k] = wave_pick(qa, k);
-    cen[0] = a[6]; cen[1] = a[7]; cen[2] = a[8];
-    const float c00 = a[0] - a[6] * a[6], c01 = a[1] - a[6] * a[7], c02 = a[2] - a[6] * a[8];
-    const float c11 = a[3] - a[7] * a[7], c12 = a[4] - a[7] * a[8], c22 = a[5] - a[8] * a[8];
-    float scale = m_absf(c00);
-    float t;
-    t = m_absf(c01); if (t > scale) scale = t;
-    t = m_absf(c02); if (t > scale) scale = t;
-    t = m_absf(c11); if (t > scale) scale = t;
-    t = m_absf(c12); if (t > scale) scale = t;
-    t = m_absf(c22); if (t > scale) scale = t;
-    if (scale <= F3DS_FLT_MIN) scale = 1.0f;
-    const float cm = lane == 0 ? c00 : (lane == 1 ? c01 : (lane == 2 ? c02 : (lane == 3 ? c11 : (lane == 4 ? c12 : c22))));
-    const float qm = cm / scale;
-    float m00 = wave_pick(qm, 0), m01 = wave_pick(qm, 1), m02 = wave_pick(qm, 2), m11 = wave_pick(qm, 3), m12 = wave_pick(qm, 4), m22 = wave_pick(qm, 5);
-    float r[3];
-    n_roots(m00, m01, m02, m11, m12, m22, r, mc);
-    m00 -= r[0]; m11 -= r[0]; m22 -= r[0];
-    float v1[3], v2[3], v3[3];
-    n_cross(m00, m01, m02, m01, m11, m12, v1);      // row0 x row1
-    n_cross(m00, m01, m02, m02, m12, m22, v2);      // row0 x row2
-    n_cross(m01, m11, m12, m02, m12, m22, v3);      // row1 x row2
-    const float l1 = n_sum3(v1[0] * v1[0], v1[1] * v1[1], v1[2] * v1[2]);
-    const float l2 = n_sum3(v2[0] * v2[0], v2[1] * v2[1], v2[2] * v2[2]);
-    const float l3 = n_sum3(v3[0] * v3[0], v3[1] * v3[1], v3[2] * v3[2]);
-    float v[3], l;
-    if (l1 >= l2 && l1 >= l3) { v[0] = v1[0]; v[1] = v1[1]; v[2] = v1[2]; l = l1; }
-    else if (l2 >= l1 && l2 >= l3) { v[0] = v2[0]; v[1] = v2[1]; v[2] = v2[2]; l = l2; }
-    else { v[0] = v3[0]; v[1] = v3[1]; v[2] = v3[2]; l = l3; }
-    const float sl = n_sqrtf(l);
-    const float qn = (lane == 0 ? v[0] : (lane == 1 ? v[1] : v[2])) / sl;
-    float nx = wave_pick(qn, 0), ny = wave_pick(qn, 1), nz = wave_pick(qn, 2);
-    const float nw = -1.0f * ((nx * a[6] + ny * a[7]) + (nz * a[8] + 0.0f * 1.0f));
-    const float cos_theta = ((0.0f - cen[0]) * nx + (0.0f - cen[1]) * ny) + ((0.0f - cen[2]) * nz + 0.0f * nw);
-    if (cos_theta < 0.0f) { nx *= -1.0f; ny *= -1.0f; nz *= -1.0f; }
-    const float z = (nx * nx + ny * ny) + (nz * nz + 0.0f);
-    if (z > 0.0f) {
-        const float sz = n_sqrtf(z);
-        const float qz = (lane == 0 ? nx : (lane == 1 ? ny : nz)) / sz;
-        nx = wave_pick(qz, 0); ny = wave_pick(qz, 1); nz = wave_pick(qz, 2);
-    }
-    out[0] = nx; out[1] = ny; out[2] = nz; out[3] = 0.0f;
-}
+// (plane_normal_wave and wave_pick: f3ds_quad.h)
 // LDS reads of the ordered folds, issued and awaited by hand (see the fold loops of d_merge_cw_t)
 typedef float f2v __attribute__((ext_vector_type(2)));
 typedef float f4v __attribute__((ext_vector_type(4)));

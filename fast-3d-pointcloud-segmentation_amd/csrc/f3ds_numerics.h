@@ -268,9 +268,11 @@ F3DS_HD void n_rgb2lab(const float rgb[3], float lab[3]) {
     lab[2] = 200.0f * (fy - fz);
 }
 
-// lab_ciede00 (:190-294) with kL = kC = kH = 1: float inputs, double intermediates, float result
+// lab_ciede00 (:190-294) with kL = kC = kH = 1: float inputs, double intermediates, float result.
+// n_ciede00_sq is the radicand of the last line, still in double: the rounding to float hides a reordered or contracted sum in all but one of
+// ~10^9 evaluations, so tests/devprobe compares host and device (and the quad version, f3ds_quad.h) on this value as well as on the result.
 F3DS_HD double n_pow7(double x) { double x2 = x * x; double x4 = x2 * x2; return (x4 * x2) * x; }
-template <class K = m_lit> F3DS_HD float n_ciede00(const float lab1[3], const float lab2[3], K mc = K()) {
+template <class K = m_lit> F3DS_HD double n_ciede00_sq(const float lab1[3], const float lab2[3], K mc = K()) {
     const double PI = mc(MC_CIE_PI), TWO_PI = mc(MC_CIE_2PI);          // (2.0 * PI is exact: the same double as the table's)
     const double P25_7 = mc(MC_CIE_25_7);
     float L1 = lab1[0], a1 = lab1[1], b1 = lab1[2];
@@ -320,7 +322,10 @@ template <class K = m_lit> F3DS_HD float n_ciede00(const float lab1[3], const fl
     double kHSH = 1.0 * (1.0 + mc(MC_CIE_0015) * Cp * T);
     double RT = -m_sin(2.0 * dtheta, mc) * Rc;
     double tL = dL / kLSL, tC = dC / kLSC, tH = dH / kHSH;
-    return (float)n_sqrt(tL * tL + tC * tC + tH * tH + RT * tC * tH);
+    return tL * tL + tC * tC + tH * tH + RT * tC * tH;
+}
+template <class K = m_lit> F3DS_HD float n_ciede00(const float lab1[3], const float lab2[3], K mc = K()) {
+    return (float)n_sqrt(n_ciede00_sq(lab1, lab2, mc));
 }
 // rgb_eucl (:304-319): std::pow(float,int) squares in double, the result is stored to float
 F3DS_HD float n_rgb_eucl(const float a[3], const float b[3]) {

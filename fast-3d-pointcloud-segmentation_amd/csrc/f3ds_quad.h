@@ -1,5 +1,7 @@
 // f3ds_quad.h -- device-only pieces of the merge loop's re-weighting that the micro-benchmarks time on their own (tools/ubench/ubench_math.hip):
-// CIEDE2000 on the four lanes of a quad, the edge weight built on it, rgb -> Lab on three lanes.  Included by f3ds_kernels.inc inside its anonymous namespace.
+// CIEDE2000 on the four lanes of a quad, the edge weight built on it, rgb -> Lab on three lanes, and the plane normal of a wave whose lanes hold the nine
+// running sums (plane_normal_wave, with wave_pick).  Included by f3ds_kernels.inc inside its anonymous namespace, and by tests/devprobe/devprobe.hip, which
+// runs every function here beside its one-lane original (f3ds_numerics.h, f3ds_algo.h) and compares the bits with a g++ build of the originals.
 #ifndef F3DS_QUAD_H_
 #define F3DS_QUAD_H_
 // ------------------------------------------------------------------------------------------------
@@ -35,8 +37,9 @@ __device__ inline float quad_bcastf(float x) {
     constexpr int ctrl = K | (K << 2) | (K << 4) | (K << 6);
     return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), ctrl, 0xF, 0xF, true));
 }
+// (n_ciede00_quad_sq: the radicand in double, as n_ciede00_sq)
 template <class MC = m_lit>
-__device__ inline float n_ciede00_quad(const float lab1[3], const float lab2[3], int q, MC mc = MC()) {
+__device__ inline double n_ciede00_quad_sq(const float lab1[3], const float lab2[3], int q, MC mc = MC()) {
     const double PI = mc(MC_CIE_PI), TWO_PI = mc(MC_CIE_2PI);
     const double P25_7 = mc(MC_CIE_25_7);
     const float L1 = lab1[0], a1 = lab1[1], b1 = lab1[2];
@@ -88,7 +91,11 @@ __device__ inline float n_ciede00_quad(const float lab1[3], const float lab2[3],
     const double kHSH = 1.0 * (1.0 + mc(MC_CIE_0015) * Cp * T);
     const double RT = -quad_bcast<1>(sn) * Rc;
     const double tL = dL / kLSL, tC = dC / kLSC, tH = dH / kHSH;
-    return (float)n_sqrt(tL * tL + tC * tC + tH * tH + RT * tC * tH);
+    return tL * tL + tC * tC + tH * tH + RT * tC * tH;
+}
+template <class MC = m_lit>
+__device__ inline float n_ciede00_quad(const float lab1[3], const float lab2[3], int q, MC mc = MC()) {
+    return (float)n_sqrt(n_ciede00_quad_sq(lab1, lab2, q, mc));
 }
 // a_edge_weight with the quad version of the colour distance (LAB_CIEDE00 only)
 template <class MC = m_lit>
@@ -118,5 +125,59 @@ __device__ inline void lab_three_lanes(float mine, int lane, float lab[3], MC mc
     lab[0] = Y > 0.008856f ? 116.0f * fy - 16.0f : 903.3f * Y;
     lab[1] = 500.0f * (fx - fy);
     lab[2] = 200.0f * (fy - fz);
+}
+// n_plane_normal (f3ds_numerics.h) for a whole wave whose lane k < 9 holds raw sum k: the same operations on the same values, but the
+// 21 IEEE divisions (64 cycles each on one lane after the other) are taken side by side: lane k divides sum k by the count, lanes 0..5 the
+// covariance entries by the scale, lanes 0..2 the eigenvector and the final normal by their lengths.  count >= 3 (the caller keeps the
+// generic function for less).  cen = the centroid (sums 6..8 over the count: the same quotients).
+__device__ inline float wave_pick(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
+template <class MC>
+__device__ inline void plane_normal_wave(float acc, unsigned count, int lane, float cen[3], float out[4], MC mc) {
+    const float cnt = (float)count;
+    const float qa = acc / cnt;
+    float a[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) a[k] = wave_pick(qa, k);
+    cen[0] = a[6]; cen[1] = a[7]; cen[2] = a[8];
+    const float c00 = a[0] - a[6] * a[6], c01 = a[1] - a[6] * a[7], c02 = a[2] - a[6] * a[8];
+    const float c11 = a[3] - a[7] * a[7], c12 = a[4] - a[7] * a[8], c22 = a[5] - a[8] * a[8];
+    float scale = m_absf(c00);
+    float t;
+    t = m_absf(c01); if (t > scale) scale = t;
+    t = m_absf(c02); if (t > scale) scale = t;
+    t = m_absf(c11); if (t > scale) scale = t;
+    t = m_absf(c12); if (t > scale) scale = t;
+    t = m_absf(c22); if (t > scale) scale = t;
+    if (scale <= F3DS_FLT_MIN) scale = 1.0f;
+    const float cm = lane == 0 ? c00 : (lane == 1 ? c01 : (lane == 2 ? c02 : (lane == 3 ? c11 : (lane == 4 ? c12 : c22))));
+    const float qm = cm / scale;
+    float m00 = wave_pick(qm, 0), m01 = wave_pick(qm, 1), m02 = wave_pick(qm, 2), m11 = wave_pick(qm, 3), m12 = wave_pick(qm, 4), m22 = wave_pick(qm, 5);
+    float r[3];
+    n_roots(m00, m01, m02, m11, m12, m22, r, mc);
+    m00 -= r[0]; m11 -= r[0]; m22 -= r[0];
+    float v1[3], v2[3], v3[3];
+    n_cross(m00, m01, m02, m01, m11, m12, v1);      // row0 x row1
+    n_cross(m00, m01, m02, m02, m12, m22, v2);      // row0 x row2
+    n_cross(m01, m11, m12, m02, m12, m22, v3);      // row1 x row2
+    const float l1 = n_sum3(v1[0] * v1[0], v1[1] * v1[1], v1[2] * v1[2]);
+    const float l2 = n_sum3(v2[0] * v2[0], v2[1] * v2[1], v2[2] * v2[2]);
+    const float l3 = n_sum3(v3[0] * v3[0], v3[1] * v3[1], v3[2] * v3[2]);
+    float v[3], l;
+    if (l1 >= l2 && l1 >= l3) { v[0] = v1[0]; v[1] = v1[1]; v[2] = v1[2]; l = l1; }
+    else if (l2 >= l1 && l2 >= l3) { v[0] = v2[0]; v[1] = v2[1]; v[2] = v2[2]; l = l2; }
+    else { v[0] = v3[0]; v[1] = v3[1]; v[2] = v3[2]; l = l3; }
+    const float sl = n_sqrtf(l);
+    const float qn = (lane == 0 ? v[0] : (lane == 1 ? v[1] : v[2])) / sl;
+    float nx = wave_pick(qn, 0), ny = wave_pick(qn, 1), nz = wave_pick(qn, 2);
+    const float nw = -1.0f * ((nx * a[6] + ny * a[7]) + (nz * a[8] + 0.0f * 1.0f));
+    const float cos_theta = ((0.0f - cen[0]) * nx + (0.0f - cen[1]) * ny) + ((0.0f - cen[2]) * nz + 0.0f * nw);
+    if (cos_theta < 0.0f) { nx *= -1.0f; ny *= -1.0f; nz *= -1.0f; }
+    const float z = (nx * nx + ny * ny) + (nz * nz + 0.0f);
+    if (z > 0.0f) {
+        const float sz = n_sqrtf(z);
+        const float qz = (lane == 0 ? nx : (lane == 1 ? ny : nz)) / sz;
+        nx = wave_pick(qz, 0); ny = wave_pick(qz, 1); nz = wave_pick(qz, 2);
+    }
+    out[0] = nx; out[1] = ny; out[2] = nz; out[3] = 0.0f;
 }
 #endif  // F3DS_QUAD_H_
