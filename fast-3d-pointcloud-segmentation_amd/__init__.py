@@ -144,6 +144,11 @@ def load_library(path=None):
         lib.f3ds_labels_at_thresholds.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]; lib.f3ds_labels_at_thresholds.restype = ctypes.c_int
         lib.f3ds_labels_at_thresholds_batch.argtypes = [ctypes.POINTER(vp), ctypes.c_int, vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.c_int, vp]
         lib.f3ds_labels_at_thresholds_batch.restype = ctypes.c_int
+    if hasattr(lib, "f3ds_evaluate_levels"):      # (scores of hierarchy levels)
+        lib.f3ds_evaluate_levels.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp]; lib.f3ds_evaluate_levels.restype = ctypes.c_int
+        lib.f3ds_evaluate_levels_batch.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(vp), ctypes.c_int, vp, ctypes.c_int, vp, vp]
+        lib.f3ds_evaluate_levels_batch.restype = ctypes.c_int
+        lib.f3ds_best_level.argtypes = [vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]; lib.f3ds_best_level.restype = ctypes.c_int
         lib.f3ds_get_merge_tree.argtypes = [vp, vp, vp, vp, sz, ctypes.POINTER(sz)]; lib.f3ds_get_merge_tree.restype = ctypes.c_int
     lib.f3ds_get_region_voxels.argtypes = [vp, vp, vp, vp, sz, ctypes.POINTER(sz)]; lib.f3ds_get_region_voxels.restype = ctypes.c_int
     lib.f3ds_multi_create.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]; lib.f3ds_multi_create.restype = ctypes.c_int
@@ -389,6 +394,13 @@ class Context:
             ptr = labels.ctypes.data
         _check(self.lib, self.lib.f3ds_labels_at_thresholds(self.handle, t.ctypes.data, k, ptr, 1 if on_device else 0, nreg.ctypes.data))
         return labels, nreg[:k]
+
+    def evaluate_levels(self, truth, thresholds, on_device=False):
+        """f3ds_evaluate_levels: the scores of recluster(threshold=t_l) + evaluate(truth) for every threshold t_l <= T of the last
+        cluster run, on the device, from that run's merge log.  Returns (list of k Performance, (k,) uint32 region counts).
+        ``on_device``: ``truth`` is a device buffer of n uint32 labels (a torch tensor or a pointer)."""
+        scores, nreg = evaluate_levels_batch([self], [truth], thresholds, on_device)
+        return scores[0], nreg[0]
 
     def merge_tree(self):
         """f3ds_get_merge_tree: the merges of the last cluster run in the order performed, as (survivor, absorbed, weight) arrays of
@@ -785,6 +797,46 @@ def labels_at_thresholds_batch(ctxs, thresholds, out=None, on_device=False):
     nreg = np.zeros((max(m, 1), max(k, 1)), np.uint32)
     _check(lib, lib.f3ds_labels_at_thresholds_batch(handles, m, t.ctypes.data, k, lp, 1 if on_device else 0, nreg.ctypes.data))
     return labels, nreg[:m, :k]
+
+
+def evaluate_levels_batch(ctxs, truths, thresholds, on_device=False):
+    """f3ds_evaluate_levels_batch: Context.evaluate_levels for every context at once (one GPU, one dispatch per kernel for all frames
+    and levels).  ``truths[i]``: the n_i ground-truth labels of ctxs[i] (device buffers with ``on_device``).  Returns (list of lists of k
+    Performance, (len(ctxs), k) uint32 region counts)."""
+    lib = load_library()
+    t = np.ascontiguousarray(np.atleast_1d(np.asarray(thresholds, np.float32)).ravel())
+    k, m = len(t), len(ctxs)
+    if len(truths) != m:
+        raise ValueError("one ground-truth label array per context is required")
+    vp = ctypes.c_void_p
+    handles = (vp * m)(*[c.handle for c in ctxs])
+    if on_device:
+        keep = list(truths)
+        tp = (vp * m)(*[_device_ptr(x) for x in keep])
+    else:
+        keep = [np.ascontiguousarray(x, np.uint32) for x in truths]
+        for c, x in zip(ctxs, keep):
+            if c._n and len(x) != c._n:      # (a context that has not seen a frame yet is the library's to refuse: LogicError)
+                raise ValueError("one ground-truth label per input point is required")
+        tp = (vp * m)(*[vp(x.ctypes.data) for x in keep])
+    ps = (Performance * (max(m, 1) * max(k, 1)))()
+    nreg = np.zeros((max(m, 1), max(k, 1)), np.uint32)
+    _check(lib, lib.f3ds_evaluate_levels_batch(handles, m, tp, 1 if on_device else 0, t.ctypes.data, k, ps, nreg.ctypes.data))
+    return [[ps[i * k + l] for l in range(k)] for i in range(m)], nreg[:m, :k]
+
+
+def best_level(thresholds, scores):
+    """f3ds_best_level: Clustering::best_thresh over scored levels: the index of the best level by F-score (levels by ascending
+    threshold, the first strictly greater F-score wins), or -1 when no level has fscore > 0.  ``scores``: Performance records."""
+    lib = load_library()
+    t = np.ascontiguousarray(np.atleast_1d(np.asarray(thresholds, np.float32)).ravel())
+    k = len(t)
+    if len(scores) != k:
+        raise ValueError("one score record per threshold is required")
+    ps = (Performance * max(k, 1))(*scores)
+    best = ctypes.c_int(-2)
+    _check(lib, lib.f3ds_best_level(t.ctypes.data, ps, k, ctypes.byref(best)))
+    return best.value
 
 
 def segment(points, params=None, device=0):

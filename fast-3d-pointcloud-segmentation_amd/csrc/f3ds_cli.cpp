@@ -7,7 +7,8 @@
 // per-point uint32 region ids, --gpu <id>, --gpus <N> (label files only: the files are sharded over N GPUs, file i on GPU i mod N, one host thread per
 // GPU, labels gathered on GPU 0 over RCCL: f3ds_multi_*), --dump <dir> (what visualize() draws, as PCD files), --refine <n> (refineSupervoxels, :369-375), --stream <depth> (label files only: the files go through the frame
 // pipeline f3ds_stream_*, reading ahead of the GPU, no evaluation), --levels <t1,t2,...> (with -p and --labels: <file>.L<i> at each t_i <= -t, from the
-// one merge run: f3ds_labels_at_thresholds).  Without -t the threshold is chosen by the ground-truth sweep
+// one merge run: f3ds_labels_at_thresholds), --level-scores <file> (with --levels: one line per level -- threshold and the seven scores against the
+// `label` field -- from f3ds_evaluate_levels, and the best level by F-score: f3ds_best_level).  Without -t the threshold is chosen by the ground-truth sweep
 // (all_thresh 0.8..1 step 0.005 + best_thresh, :428-437) and the <-f name>_*.csv score files are written
 // (:471, manageAllPerformances); every file is scored against its `label` field (:462-463).
 #include <algorithm>
@@ -88,6 +89,7 @@ int main(int argc, char** argv) {
                " --stream <depth>               (with -t and --labels: files through the frame pipeline, <depth> in flight) \n\t"
                " --refine <iterations>          (refineSupervoxels as main() does with 3, :369-375; with -o also <out.pcd>.refined) \n\t"
                " --levels <t1,t2,...>           (with -p and --labels: also <file>.L<i>, the labels at threshold t_i <= -t (default: the largest), from one merge run) \n\t"
+               " --level-scores <file>          (with --levels: threshold, voi, precision, recall, fscore, wov, fpr, fnr of every level against the label field) \n\t"
                " --bench <frames>               (no input files: <frames> synthetic 1M-point RGB-D frames through the path, with --gpus N sharded and pipelined; prints Mpoints/s) \n",
                argv[0]);
         return 1;
@@ -117,6 +119,11 @@ int main(int argc, char** argv) {
         }
         for (const float t : levels)
             if (t_given && t > t_run) { fprintf(stderr, "--levels: threshold %g is above -t %g (levels come from the merge run to -t)\n", t, t_run); return 1; }
+    }
+    std::string level_scores;
+    if (find_switch(argc, argv, "--level-scores")) {
+        parse(argc, argv, "--level-scores", level_scores);
+        if (levels.empty() || level_scores.empty()) { fprintf(stderr, "--level-scores needs --levels <t1,t2,...> and a file name\n"); return 1; }
     }
     verbose = find_switch(argc, argv, "--V");
     const bool disable_transform = find_switch(argc, argv, "--NT");
@@ -415,6 +422,21 @@ int main(int argc, char** argv) {
                         FILE* g = fopen(name.c_str(), "wb");
                         if (!g || fwrite(lv.data() + (size_t)l * n, 4, n, g) != n) { fprintf(stderr, "writing %s failed\n", name.c_str()); if (g) fclose(g); f3ds_destroy(ctx); return 1; }
                         fclose(g);
+                    }
+                    if (!level_scores.empty()) {      // the levels scored on the device from the same merge run, and the best of them
+                        std::vector<f3ds_performance> ps((size_t)K);
+                        int best = -1;
+                        rc = f3ds_evaluate_levels(ctx, gt.data(), 0, levels.data(), K, ps.data(), nullptr);
+                        if (!rc) rc = f3ds_best_level(levels.data(), ps.data(), K, &best);
+                        if (rc) { fprintf(stderr, "f3ds_evaluate_levels: %s %s\n", f3ds_strerror(rc), f3ds_last_hip_error()); f3ds_destroy(ctx); return 1; }
+                        const std::string name = level_scores + suffix;
+                        FILE* g = fopen(name.c_str(), "w");
+                        if (!g) { fprintf(stderr, "writing %s failed\n", name.c_str()); f3ds_destroy(ctx); return 1; }
+                        for (int l = 0; l < K; ++l)
+                            fprintf(g, "%.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g\n", levels[l], ps[l].voi, ps[l].precision, ps[l].recall, ps[l].fscore, ps[l].wov, ps[l].fpr, ps[l].fnr);
+                        fclose(g);
+                        if (best >= 0) printf("Using best threshold: %f (F-score %f, voi %f)\n", levels[best], ps[best].fscore, ps[best].voi);
+                        else printf("Using best threshold: %f (F-score %f, voi %f)\n", 0.0f, 0.0f, 0.0f);
                     }
                 }
             }

@@ -15,6 +15,8 @@
 //   5 merge      d_inc_build, d_merge_il_t<4 or 8 waves, per-edge arrays in LDS or L2> (one persistent workgroup per frame), d_merge (global memory)
 //   6 labels     d_relabel (union-find relabel in LDS + per-point label write; d_region_ids + d_point_labels beyond 12 k supervoxels)
 //   levels       (f3ds_labels_at_thresholds, off the segment path) d_level_log, d_level_prefix, d_level_labels | d_level_tables + d_level_points (f3ds_levels.inc)
+//   level scores (f3ds_evaluate_levels, off the segment path) d_truth_*, d_level_log / prefix / tables, d_evl_base_keys, radix sort, d_evl_heads / scan / d_evl_reduce,
+//                d_evl_level_keys, radix sort + reduce, d_evl_col_keys, radix sort, d_evl_ht, d_evl_score (f3ds_eval_levels.inc)
 // Every frame RECORDS its kernel calls; flush() zips the records of a batch into one dispatch per kernel (grid.y = frame).
 //
 // Layout in HBM: points stay as the caller's 16-byte records (one global_load_dwordx4 per lane);
@@ -44,11 +46,13 @@
 #include "f3ds_eval.h"
 #include "f3ds_dev.h"
 #include "f3ds_levels.h"
+#include "f3ds_eval_levels.h"
 
 using namespace f3ds;
 
 #include "f3ds_kernels.inc"
 #include "f3ds_levels.inc"
+#include "f3ds_eval_levels.inc"
 
 // ================================================================================================
 // batched launch machinery
@@ -161,7 +165,10 @@ const int g_merge_shared_res = [] { const char* e = dev_getenv("F3DS_MERGE_SHARE
     /* stage 0, tile path: per (tile, entry) point count / list base / leaf ordinal; per point its (entry, rank in tile); per-leaf point lists */ X(uint32_t, hcnt) X(uint32_t, pslot) X(uint32_t, vlist) \
     /* f3ds_cluster_supervoxels: the caller's supervoxels as uploaded */ X(uint32_t, u_src) X(uint32_t, u_voff) X(float, u_xyz) X(uint32_t, u_rgba) X(float, u_cent) X(float, u_nrm) \
     X(float, deltas) X(uint64_t, skeys0) X(uint64_t, skeys1) X(uint32_t, svals0) X(uint32_t, svals1) X(uint32_t, cdf_hist) X(float, cdf) X(uint32_t, root) X(uint32_t, rincl) X(uint32_t, rrank) X(uint2, pool) X(uint32_t, rstart) X(uint32_t, rnleaf) X(uint32_t, rcap) X(uint32_t, tile_n1) X(uint32_t, tile_ord) X(uint32_t, tile_slots) X(uint32_t, ilist) X(uint32_t, istart) X(uint32_t, ilen) X(uint32_t, icap) \
-    /* hierarchy levels */ X(uint32_t, lv_into) X(uint32_t, lv_at) X(uint32_t, lv_pfx) X(float, lv_thr) X(uint32_t, lv_tab) X(uint32_t, lv_nreg) X(uint32_t, lv_out)
+    /* hierarchy levels */ X(uint32_t, lv_into) X(uint32_t, lv_at) X(uint32_t, lv_pfx) X(float, lv_thr) X(uint32_t, lv_tab) X(uint32_t, lv_nreg) X(uint32_t, lv_out) \
+    /* level scores (f3ds_eval_levels.inc): sort buffers, base table, reduced level entries, ghost list, per-level sizes / flags / terms, truth sizes and visiting order, matches, counts and results of a batch */ \
+    X(uint64_t, evl_k0) X(uint64_t, evl_k1) X(uint32_t, evl_v0) X(uint32_t, evl_v1) X(uint32_t, evl_flag) X(uint64_t, evl_bkey) X(uint32_t, evl_bcnt) X(uint64_t, evl_ukey) X(uint32_t, evl_ucnt) X(uint32_t, evl_glist) \
+    X(uint32_t, evl_ssize) X(unsigned char, evl_used) X(float, evl_hterm) X(float, evl_mterm) X(float, evl_tterm) X(uint32_t, evl_tsize) X(uint32_t, evl_order) X(uint32_t, evl_slot) X(uint32_t, evl_counts) X(uint32_t, evl_out)
 template <class T> struct Scratch { T* p = nullptr; size_t cap = 0; int slot = -1; };      // cap: bytes allocated; slot: position in F3DS_SCRATCH
 #define F3DS_SCRATCH_SLOT(T, name) S_##name,
 #define F3DS_SCRATCH_MEMBER(T, name) Scratch<T> name{nullptr, 0, S_##name};
@@ -2020,6 +2027,200 @@ extern "C" int f3ds_labels_at_thresholds_batch(f3ds_ctx** ctxs, int nctx, const 
     }
     for (int i = 0; i < nctx; ++i) { const int rc = check_levels(ctxs[i], thresholds, k); if (rc) return rc; }
     return run_levels(ctxs, nctx, thresholds, k, point_labels, labels_on_device, n_regions);
+}
+
+// ------------------------------------------------------------------------------------------------
+// scores of hierarchy levels (f3ds_eval_levels.h / .inc): f3ds_evaluate's seven scores for K thresholds of the last
+// cluster run, for every frame of a batch.  Reads the frame state and leaves it as it was: only the evaluation scratch (truth_pts ... tlab, which
+// every f3ds_evaluate fills anew), the lv_* and the evl_* scratch are written.  Three waits per batch whatever k and nctx are: the truth
+// colours (the first-appearance numbering is the host's, as in eval_truth), the base-table sizes, the results.
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct EvlTruth { std::vector<uint32_t> col, tsize, order; uint32_t M = 0, nvis = 0, Eb = 0, G = 0; };
+// sorted (key, value) pairs -> the distinct keys below `limit` with summed values and their count
+int evl_reduce_record(f3ds_ctx* c, const uint64_t* keys, const uint32_t* vals, uint32_t n, uint64_t limit, uint64_t* ukey, uint32_t* ucnt, uint32_t* total) {
+    uint32_t* flag = c->evl_flag.p;
+    rec_fill(c, ucnt, 0u, (size_t)n * 4);
+    rec<d_evl_heads>(c, grid_for(n, 256), 0u, keys, n, limit, flag);
+    if (const int rc = scan_u32(c, flag, flag, n)) return rc;
+    rec<d_evl_reduce>(c, grid_for(n, 256), 0u, keys, vals, n, limit, flag, ukey, ucnt, total);
+    return F3DS_OK;
+}
+int run_eval_levels(f3ds_ctx** ctxs, int nctx, const uint32_t* const* truth, int truth_on_device, const float* thr, int K_, f3ds_performance* scores, uint32_t* n_regions) {
+    g_sw.read();
+    f3ds_ctx* o = ctxs[0];
+    const uint32_t K = (uint32_t)K_, Kp = (K + 3u) & ~3u;
+    HIPCHECK(hipSetDevice(o->device));
+    Batch b; b.owner = o; b.st = o->stream; g_grid_cap = grid_cap_for_batch(nctx); g_batch_frames = nctx;
+    for (int i = 0; i < nctx; ++i) {
+        f3ds_ctx* c = ctxs[i];
+        if ((uint64_t)c->V + c->S0 >= (1u << 24)) return F3DS_ERR_UNSUPPORTED;      // (d_evl_score adds sizes as integers: exact in float below 2^24)
+        if (c->stream != b.st) HIPCHECK(hipStreamSynchronize(c->stream));
+        reset_recording(c);
+        b.fr.push_back(c);
+    }
+    float* d_thr; uint32_t *d_nreg, *d_counts, *d_out;
+    { int rc; if ((rc = ensure(o, o->lv_thr, (size_t)K, &d_thr)) || (rc = ensure(o, o->lv_nreg, (size_t)nctx * K, &d_nreg)) || (rc = ensure(o, o->evl_counts, (size_t)nctx * 4, &d_counts)) ||
+                  (rc = ensure(o, o->evl_out, (size_t)nctx * K * 8, &d_out))) return rc; }
+    HIPCHECK(hipMemcpyAsync(d_thr, thr, (size_t)K * 4, hipMemcpyHostToDevice, b.st));
+    HIPCHECK(hipMemsetAsync(d_counts, 0, (size_t)nctx * 16, b.st));
+    // 1. truth colours per voxel, the level tables (they do not depend on the truth) and the ghost list: one flush for all frames
+    std::vector<EvlTruth> tr((size_t)nctx);
+    for (int i = 0; i < nctx; ++i) {
+        f3ds_ctx* c = ctxs[i];
+        const uint32_t n = c->n, V = c->V, S0 = c->S0, nm = c->res.n_merges;
+        uint32_t *lut, *tp = nullptr, *tsum, *tcol, *into, *at, *pfx, *tab, *glist;
+        ENSURE(c->glut, 256, lut); ENSURE(c->tsum, (size_t)V * 3, tsum); ENSURE(c->tcol, V, tcol);
+        ENSURE(c->lv_into, S0 + 1, into); ENSURE(c->lv_at, S0 + 1, at); ENSURE(c->lv_pfx, (size_t)K * 2, pfx); ENSURE(c->lv_tab, (size_t)(S0 + 1) * Kp, tab); ENSURE(c->evl_glist, S0 + 1, glist);
+        HIPCHECK(hipMemcpyAsync(lut, f3ds_glasbey_256, 1024, hipMemcpyHostToDevice, b.st));
+        const uint32_t* d_truth = truth[i];
+        if (!truth_on_device) { ENSURE(c->truth_pts, n, tp); HIPCHECK(hipMemcpyAsync(tp, truth[i], (size_t)n * 4, hipMemcpyHostToDevice, b.st)); d_truth = tp; }
+        rec_fill(c, tsum, 0u, (size_t)V * 12);
+        rec_fill(c, at, LV_NOT_ABSORBED, (size_t)(S0 + 1) * 4);
+        rec<d_truth_accum>(c, grid_for(n, 256), 0u, n, c->pt_voxel.p, d_truth, lut, tsum);
+        rec<d_truth_color>(c, grid_for(V, 256), 0u, V, tsum, c->vcount.p, tcol);
+        rec<d_level_log>(c, grid_for(nm, 256), 0u, nm, S0, c->merges.p, into, at);
+        rec<d_level_prefix>(c, 1u, 0u, nm, c->merges.p, K, d_thr, pfx, pfx + K);
+        rec<d_level_tables>(c, 1u, 0u, S0, K, Kp, c->ralive0.p, into, at, pfx, pfx + K, tab, d_nreg + (size_t)i * K);
+        rec<d_evl_ghosts>(c, grid_for(S0, 256), 0u, S0, c->ghost_active.p, glist, d_counts + (size_t)i * 4 + 1);
+    }
+    int rc = flush(b);
+    if (rc) return rc;
+    for (int i = 0; i < nctx; ++i) { tr[i].col.resize(ctxs[i]->V); HIPCHECK(hipMemcpyAsync(tr[i].col.data(), ctxs[i]->tcol.p, (size_t)ctxs[i]->V * 4, hipMemcpyDeviceToHost, b.st)); }
+    HIPCHECK(timed_sync(b.st));
+    // 2. truth labels in first-appearance order (color2label, as eval_truth), their sizes, the visiting order (evl_visit_order); then the base table
+    uint32_t maxM = 1, maxS0 = 1;
+    for (int i = 0; i < nctx; ++i) {
+        EvlTruth& t = tr[i];
+        std::map<uint32_t, uint32_t> ids;
+        for (uint32_t& cv : t.col) {
+            auto it = ids.find(cv);
+            uint32_t l;
+            if (it == ids.end()) { l = (uint32_t)t.tsize.size(); ids.insert({cv, l}); t.tsize.push_back(0); } else l = it->second;
+            cv = l; t.tsize[l]++;
+        }
+        t.M = (uint32_t)t.tsize.size();
+        if (t.M == 0) return F3DS_ERR_ARG;      // (std::invalid_argument, testing.cpp:414,431, as eval_scores; a level has K >= 1 whenever the frame has a voxel)
+        t.order.resize((size_t)t.M * 3);      // order, rank, then the visited labels ascending
+        t.nvis = evl_visit_order_sorted(t.M, t.tsize.data(), t.order.data(), t.order.data() + t.M);
+        for (uint32_t k = 0; k < t.nvis; ++k) { t.order[t.nvis + k] = t.order[t.M + k]; }
+        for (uint32_t k = 0; k < t.nvis; ++k) t.order[2 * (size_t)t.nvis + t.order[t.nvis + k]] = t.order[k];
+        t.order.resize((size_t)t.nvis * 3);
+        maxM = std::max(maxM, t.M); maxS0 = std::max(maxS0, ctxs[i]->S0);
+    }
+    const int jb = bits_for(maxM - 1u), hb = bits_for((uint64_t)maxS0 + 1u), ib = bits_for(maxS0), lb = bits_for(K);
+    if (lb + ib + jb > 64) return F3DS_ERR_UNSUPPORTED;
+    for (int i = 0; i < nctx; ++i) {
+        f3ds_ctx* c = ctxs[i];
+        EvlTruth& t = tr[i];
+        const uint32_t V = c->V, S0 = c->S0;
+        uint64_t *k0, *k1, *bkey; uint32_t *v0, *v1, *flag, *bcnt, *tlab, *tsz, *ord, *hist, *tiles;
+        ENSURE(c->tlab, V, tlab); ENSURE(c->evl_tsize, t.M, tsz); ENSURE(c->evl_order, t.order.size(), ord);
+        ENSURE(c->evl_k0, V, k0); ENSURE(c->evl_k1, V, k1); ENSURE(c->evl_v0, V, v0); ENSURE(c->evl_v1, V, v1); ENSURE(c->evl_flag, V, flag); ENSURE(c->evl_bkey, V, bkey); ENSURE(c->evl_bcnt, V, bcnt);
+        ENSURE(c->hist, (size_t)RS_BINS * ((V + RS_TILE - 1) / RS_TILE + 1), hist); ENSURE(c->tiles, (V + SCAN_TILE - 1) / SCAN_TILE + 1, tiles);
+        HIPCHECK(hipMemcpyAsync(tlab, t.col.data(), (size_t)V * 4, hipMemcpyHostToDevice, b.st));
+        HIPCHECK(hipMemcpyAsync(tsz, t.tsize.data(), (size_t)t.M * 4, hipMemcpyHostToDevice, b.st));
+        HIPCHECK(hipMemcpyAsync(ord, t.order.data(), t.order.size() * 4, hipMemcpyHostToDevice, b.st));
+        rec<d_evl_base_keys>(c, grid_for(V, 256), 0u, V, S0, t.M, c->owner0.p, tlab, jb, k0, v0);
+        uint64_t* ks; uint32_t* vs;
+        if ((rc = radix_sort(c, k0, v0, k1, v1, V, hb + jb, &ks, &vs))) return rc;
+        if ((rc = evl_reduce_record(c, ks, vs, V, (uint64_t)(S0 + 1u) << jb, bkey, bcnt, d_counts + (size_t)i * 4))) return rc;
+    }
+    if ((rc = flush(b))) return rc;
+    std::vector<uint32_t> counts((size_t)nctx * 4);
+    HIPCHECK(hipMemcpyAsync(counts.data(), d_counts, counts.size() * 4, hipMemcpyDeviceToHost, b.st));
+    HIPCHECK(timed_sync(b.st));
+    // 3. every level's table, the matching and the scores
+    for (int i = 0; i < nctx; ++i) {
+        f3ds_ctx* c = ctxs[i];
+        EvlTruth& t = tr[i];
+        t.Eb = counts[(size_t)i * 4]; t.G = counts[(size_t)i * 4 + 1];
+        const uint32_t V = c->V, S0 = c->S0, ne = t.Eb + t.G;
+        const uint64_t n64 = (uint64_t)K * ne;
+        if (t.Eb > V || t.G > S0 || n64 == 0 || n64 >= (1ull << 31)) return n64 >= (1ull << 31) ? F3DS_ERR_UNSUPPORTED : F3DS_ERR_ARG;
+        const uint32_t n = (uint32_t)n64;
+        uint64_t *k0, *k1, *ukey; uint32_t *v0, *v1, *flag, *ucnt, *ssize, *slot, *hist, *tiles; unsigned char* used; float *hterm, *mterm, *tterm;
+        ENSURE(c->evl_k0, n, k0); ENSURE(c->evl_k1, n, k1); ENSURE(c->evl_v0, n, v0); ENSURE(c->evl_v1, n, v1); ENSURE(c->evl_flag, n, flag); ENSURE(c->evl_ukey, n, ukey); ENSURE(c->evl_ucnt, n, ucnt);
+        ENSURE(c->evl_ssize, (size_t)K * (S0 + 1), ssize); ENSURE(c->evl_used, (size_t)K * (S0 + 1), used); ENSURE(c->evl_hterm, (size_t)K * (S0 + 1), hterm); ENSURE(c->evl_mterm, n, mterm);
+        ENSURE(c->evl_tterm, (size_t)t.M + 1, tterm); ENSURE(c->evl_slot, (size_t)K * t.nvis * 4 + 1, slot);
+        ENSURE(c->hist, (size_t)RS_BINS * ((n + RS_TILE - 1) / RS_TILE + 1), hist); ENSURE(c->tiles, (n + SCAN_TILE - 1) / SCAN_TILE + 1, tiles);
+        uint32_t* d_total = d_counts + (size_t)i * 4 + 2;
+        const uint32_t* ord = c->evl_order.p;
+        rec_fill(c, ssize, 0u, (size_t)K * (S0 + 1) * 4);
+        rec_fill(c, used, 0u, (size_t)K * (S0 + 1));
+        rec<d_evl_level_keys>(c, grid_for(ne, 256), 0u, t.Eb, t.G, K, Kp, S0, t.M, V, c->evl_bkey.p, c->evl_bcnt.p, c->evl_glist.p, c->ghost_vox.p, c->owner0.p, c->tlab.p, c->lv_tab.p, ib, jb, k0, v0, ssize);
+        uint64_t* ks; uint32_t* vs;
+        if ((rc = radix_sort(c, k0, v0, k1, v1, n, lb + ib + jb, &ks, &vs))) return rc;
+        if ((rc = evl_reduce_record(c, ks, vs, n, (uint64_t)K << (ib + jb), ukey, ucnt, d_total))) return rc;
+        rec<d_evl_col_keys>(c, grid_for(n, 256), 0u, ukey, ucnt, d_total, ib, jb, k0, v0);
+        if ((rc = radix_sort(c, k0, v0, k1, v1, n, lb + jb, &ks, &vs, ib, d_total))) return rc;
+        rec<d_evl_ht>(c, 1u, 0u, t.M, c->evl_tsize.p, V, tterm, tterm + t.M);
+        rec<d_evl_score>(c, K, 0u, K, S0, V, d_nreg + (size_t)i * K, ssize, c->evl_tsize.p, ukey, ucnt, ks, vs, d_total, ib, jb, ord, ord + t.nvis, ord + 2 * (size_t)t.nvis, t.nvis,
+                         tterm + t.M, used, hterm, mterm, slot, d_out + (size_t)i * K * 8);
+    }
+    if ((rc = flush(b))) return rc;
+    std::vector<uint32_t> out((size_t)nctx * K * 8);
+    HIPCHECK(hipMemcpyAsync(out.data(), d_out, out.size() * 4, hipMemcpyDeviceToHost, b.st));
+    if (g_sw.host_prof) HIPCHECK(hipMemcpyAsync(counts.data(), d_counts, counts.size() * 4, hipMemcpyDeviceToHost, b.st));
+    HIPCHECK(timed_sync(b.st));
+    HIPCHECK(hipGetLastError());
+    if (g_sw.host_prof) {      // F3DS_HOST_PROF: the sizes the scratch follows, per frame (min / mean / max over the batch)
+        auto line = [&](const char* what, auto get) {
+            double lo = 1e300, hi = 0, sum = 0;
+            for (int i = 0; i < nctx; ++i) { const double v = get(i); lo = std::min(lo, v); hi = std::max(hi, v); sum += v; }
+            fprintf(stderr, " %s %.0f / %.0f / %.0f;", what, lo, sum / nctx, hi);
+        };
+        fprintf(stderr, "f3ds_evaluate_levels: %d frames x %u levels, global-memory tables:", nctx, K);
+        line("truth labels M", [&](int i) { return (double)tr[i].M; }); line("visited labels", [&](int i) { return (double)tr[i].nvis; });
+        line("base entries", [&](int i) { return (double)tr[i].Eb; }); line("live ghost leaves", [&](int i) { return (double)tr[i].G; });
+        line("entries per level (mean over the levels)", [&](int i) { return (double)counts[(size_t)i * 4 + 2] / K; });
+        fprintf(stderr, " key bits %d + %d + %d\n", lb, ib, jb);
+    }
+    for (size_t q = 0; q < (size_t)nctx * K; ++q) {
+        if (out[q * 8 + 7] == 0u) return F3DS_ERR_ARG;      // (a level without regions: std::invalid_argument, as eval_scores)
+        memcpy(&scores[q], &out[q * 8], sizeof(f3ds_performance));
+        if (n_regions) n_regions[q] = out[q * 8 + 7];
+    }
+    return F3DS_OK;
+}
+}  // namespace
+
+extern "C" int f3ds_evaluate_levels(f3ds_ctx* c, const uint32_t* truth_point_labels, int truth_on_device, const float* thresholds, int k, f3ds_performance* scores,
+                                    uint32_t* n_regions) {
+    const uint32_t* tp[1] = {truth_point_labels};
+    return f3ds_evaluate_levels_batch(&c, 1, tp, truth_on_device, thresholds, k, scores, n_regions);
+}
+
+extern "C" int f3ds_evaluate_levels_batch(f3ds_ctx** ctxs, int nctx, const uint32_t* const* truth_point_labels, int truth_on_device, const float* thresholds, int k,
+                                          f3ds_performance* scores, uint32_t* n_regions) {
+    if (!ctxs || nctx < 1 || !truth_point_labels || !thresholds || k < 1 || !scores) return F3DS_ERR_ARG;
+    for (int l = 0; l < k; ++l) if (thresholds[l] != thresholds[l]) return F3DS_ERR_ARG;
+    for (int i = 0; i < nctx; ++i) {
+        if (!ctxs[i] || !truth_point_labels[i] || ctxs[i]->device != ctxs[0]->device) return F3DS_ERR_ARG;
+        for (int j = 0; j < i; ++j) if (ctxs[j] == ctxs[i]) return F3DS_ERR_ARG;      // (one context holds one frame's scratch)
+    }
+    for (int i = 0; i < nctx; ++i) {
+        if (ctxs[i]->have_frame && (ctxs[i]->user_mode || ctxs[i]->V == 0)) return F3DS_ERR_LOGIC;      // (as f3ds_evaluate; no voxel: nothing to score)
+        const int rc = check_levels(ctxs[i], thresholds, k);
+        if (rc) return rc;
+    }
+    return run_eval_levels(ctxs, nctx, truth_point_labels, truth_on_device, thresholds, k, scores, n_regions);
+}
+
+extern "C" int f3ds_best_level(const float* thresholds, const f3ds_performance* scores, int k, int* best_index) {
+    if (!thresholds || !scores || !best_index || k < 1) return F3DS_ERR_ARG;
+    for (int l = 0; l < k; ++l) if (thresholds[l] != thresholds[l]) return F3DS_ERR_ARG;
+    std::vector<int> idx((size_t)k);
+    for (int l = 0; l < k; ++l) idx[l] = l;
+    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return thresholds[a] < thresholds[b]; });
+    int best = -1; float bf = 0.0f;
+    for (int q = 0; q < k; ++q) {
+        const int l = idx[q];
+        if (q > 0 && thresholds[idx[q - 1]] == thresholds[l]) continue;      // (std::map::insert keeps the first of equal thresholds)
+        if (scores[l].fscore > bf) { bf = scores[l].fscore; best = l; }       // best_thresh, clustering.cpp:759-774
+    }
+    *best_index = best;
+    return F3DS_OK;
 }
 
 extern "C" int f3ds_get_merge_tree(f3ds_ctx* c, uint32_t* survivor, uint32_t* absorbed, float* weight, size_t cap, size_t* n_out) {

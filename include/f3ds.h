@@ -312,6 +312,35 @@ int f3ds_labels_at_thresholds(f3ds_ctx* ctx, const float* thresholds, int k, uin
  * to ctxs[i] (k * n_i words); n_regions (nctx * k words, context-major, may be NULL).  Every threshold must be <= each context's T. */
 int f3ds_labels_at_thresholds_batch(f3ds_ctx** ctxs, int nctx, const float* thresholds, int k, uint32_t* const* point_labels,
                                     int labels_on_device, uint32_t* n_regions /* nctx * k, may be NULL */);
+/* ---- scores of hierarchy levels: f3ds_evaluate for K thresholds of the last cluster run, on the device, from ONE merge log ----
+ * Level l is the segmentation f3ds_labels_at_thresholds defines for t_l (the first logged merge i with !(w_i < t_l) stops the
+ * prefix; any order, repeats allowed).  scores[l] are the scores of f3ds_recluster(threshold = t_l) followed by
+ * f3ds_evaluate(truth): precision, recall, fscore, wov, fpr and fnr bit for bit; voi is computed with the library's own logf
+ * (f3ds::m_logf, the same bits on every compiler) where f3ds_evaluate takes libm's, and differs from it by at most 1e-5.
+ * n_regions[l] (may be NULL) is f3ds_labels_at_thresholds' region count.
+ * Truth handling is f3ds_evaluate's: label colours Glasbey[label & 255] averaged per voxel, one truth label per distinct voxel
+ * colour in first-appearance (leaf) order; N = the frame's voxels.  A ghost leaf adds to its segment's size always and to the
+ * intersection only if that voxel is not already in that segment at that level.  truth_on_device: the labels are device memory.
+ * No dense segment x label table is built at any level (csrc/f3ds_eval_levels.inc): scratch grows with the non-zero entries and
+ * there is no limit on regions x labels as in f3ds_evaluate.  The context's state does not change (regions, voxel cloud,
+ * adjacency, F3DS_DBG_* arrays and a later f3ds_evaluate, f3ds_recluster or f3ds_auto_threshold behave as if the call never
+ * happened); only scratch of its own is written.
+ * Errors, in this order: F3DS_ERR_ARG for a NULL pointer, k < 1, nctx < 1, a NaN threshold, contexts on different devices or a
+ * context named twice; F3DS_ERR_LOGIC before any cluster run, for a frame without voxels or after f3ds_cluster_supervoxels (as
+ * f3ds_evaluate); F3DS_ERR_OUT_OF_RANGE for t_l > T; F3DS_ERR_ARG for an infinite threshold.  F3DS_ERR_UNSUPPORTED for a frame of
+ * 2^24 or more voxels (sizes are added as integers that a float must hold exactly). */
+int f3ds_evaluate_levels(f3ds_ctx* ctx, const uint32_t* truth_point_labels, int truth_on_device, const float* thresholds, int k,
+                         f3ds_performance* scores /* k */, uint32_t* n_regions /* k, may be NULL */);
+/* the same for every context of a batch on one GPU: one dispatch per kernel for all frames and levels.  truth_point_labels[i]
+ * holds ctxs[i]'s n_i labels; scores: nctx * k, context-major; n_regions likewise, may be NULL */
+int f3ds_evaluate_levels_batch(f3ds_ctx** ctxs, int nctx, const uint32_t* const* truth_point_labels, int truth_on_device,
+                               const float* thresholds, int k, f3ds_performance* scores, uint32_t* n_regions);
+/* Clustering::best_thresh (src/clustering.cpp:759-774) over scored levels; host arithmetic only, no device needed.  The levels
+ * are visited by ascending threshold (of equal thresholds the first given counts: std::map::insert), the first whose fscore is
+ * strictly greater than the best so far -- starting from 0 -- is kept.  *best_index = -1 when no level has fscore > 0 (the
+ * reference then returns threshold 0 and zero scores).  F3DS_ERR_ARG for a NULL pointer, k < 1 or a NaN threshold. */
+int f3ds_best_level(const float* thresholds, const f3ds_performance* scores, int k, int* best_index);
+
 /* the dendrogram: the merges of the last cluster run in the order performed -- survivor[i] took absorbed[i] at weight[i] -- as
  * supervoxel labels (the label space of f3ds_get_supervoxels / F3DS_DBG_SV_REGION; the caller's keys after
  * f3ds_cluster_supervoxels).  Any output may be NULL; n_out receives the merge count (F3DS_ERR_CAPACITY if cap is smaller). */

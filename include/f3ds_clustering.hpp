@@ -246,6 +246,26 @@ public:
         if (!all.empty()) cluster(all.rbegin()->first);
         return all;
     }
+    // all_thresh on the hierarchy levels: ONE cluster run to the largest threshold of the sweep, then every threshold scored on the device from
+    // that run's merge log (f3ds_evaluate_levels).  The same keys (float t += step) and the same scores as all_thresh in precision, recall,
+    // fscore, wov, fpr and fnr, bit for bit; voi is computed with the library's own logf and may differ from all_thresh's in the last bits
+    // (at most 1e-5).  The state is left clustered at the last threshold of the sweep, as all_thresh leaves it.  best_thresh(map) gives what
+    // f3ds_best_level gives over the same levels.
+    std::map<float, performanceSet> all_thresh_levels(const uint32_t* truth_point_labels, float start_thresh, float end_thresh, float step_thresh) {
+        need_state("all_thresh_levels");
+        if (have_user_) throw std::logic_error("all_thresh_levels needs the frame's points (the ground truth is per input point): use the SupervoxelClustering state");
+        if (start_thresh < 0 || start_thresh > 1 || end_thresh < 0 || end_thresh > 1 || !(step_thresh > 0) || step_thresh > 1)
+            throw std::out_of_range("start_thresh, end_thresh and/or step_thresh outside of range [0, 1]");
+        if (start_thresh > end_thresh) std::swap(start_thresh, end_thresh);
+        std::vector<float> ts{start_thresh};
+        for (float t = start_thresh + step_thresh; t <= end_thresh; t += step_thresh) ts.push_back(t);
+        cluster(ts.back());
+        std::vector<performanceSet> ps(ts.size());
+        check(f3ds_evaluate_levels(ctx(), truth_point_labels, 0, ts.data(), (int)ts.size(), ps.data(), nullptr), "f3ds_evaluate_levels");
+        std::map<float, performanceSet> all;
+        for (size_t i = 0; i < ts.size(); ++i) all.insert({ts[i], ps[i]});
+        return all;
+    }
     static std::pair<float, performanceSet> best_thresh(const std::map<float, performanceSet>& all) {           // :759-774
         float bt = 0; performanceSet bp = performanceSet();
         for (const auto& kv : all) if (kv.second.fscore > bp.fscore) { bp = kv.second; bt = kv.first; }

@@ -1,0 +1,353 @@
+"""Scores of hierarchy levels on the MI355X (f3ds_evaluate_levels, csrc/f3ds_eval_levels.inc).  For every frame and level, with
+ref = recluster(t_l) then evaluate(truth) on the same context:
+  1. precision, recall, fscore, wov, fpr, fnr are bit-equal to ref, n_regions equals labels_at_thresholds';
+  2. all seven fields are bit-equal to the g++ build of the sparse routine with evl_m_logf (third block of evl_check in
+     tests/eval_levels_harness) on the dense table built from public outputs (recluster + voxel_cloud, ghost repeats removed per segment);
+  3. |voi - ref.voi| <= 1e-5 (ref takes libm's logf, which is not correctly rounded everywhere: no equality is asserted);
+  4. a batch call equals single calls in every byte; the order of the thresholds and repeats do not change a threshold's record.
+There is one table form (global memory), so no form comparison.  The "seen" branch of the ghost rule (a ghost leaf whose voxel is already in
+its segment at some level) occurs in no golden case: three seeded small clouds reach it (eval_levels_common.seen_cloud)."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from golden_cases import GOLDEN_CASES, case_points, case_params, synthetic_truth
+from levels_common import level_thresholds
+from eval_levels_common import FIELDS, NO_LABEL, SEEN_SEEDS, seen_cloud, bits, build_harness, dense_table, harness_scores, voxel_truth_labels
+
+pytestmark = pytest.mark.gpu
+
+CLI = os.path.join(ROOT, "fast-3d-pointcloud-segmentation_amd", "supervoxel_clustering")
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    return build_harness(tmp_path_factory.mktemp("eval_levels_gpu"))
+
+
+def _at(prm, t):
+    p = prm.copy()
+    p.threshold = float(t)
+    return p
+
+
+def _check_levels(P, ctx, harness, pts, prm, truth, ts, what, with_harness=True):
+    """contract 1 - 3 for the levels ts of the context's frame; returns (scores, n_regions, per-level notes)"""
+    scores, nreg = ctx.evaluate_levels(truth, ts)
+    _, want_nreg = ctx.labels_at_thresholds(ts)
+    assert np.array_equal(nreg, want_nreg), what
+    tl = voxel_truth_labels(ctx.debug("POINT_VOXEL"), ctx.debug("VOXEL_COUNT"), truth, P)
+    vx = ctx.debug("VOXEL_XYZ").reshape(-1, 3)
+    notes = []
+    for l, t in enumerate(ts):
+        ctx.recluster(_at(prm, t))
+        ref = ctx.evaluate(truth)
+        got = scores[l]
+        print("%s level %d t %.9g K %d: got %s ref voi %.9g" % (what, l, t, nreg[l], [getattr(got, f) for f in FIELDS], ref.voi))
+        assert nreg[l] == ctx.result.n_regions
+        assert bits(got)[1:] == bits(ref)[1:], "%s level %d (t = %r): %s vs %s" % (what, l, t, got.as_dict(), ref.as_dict())
+        assert abs(float(got.voi) - float(ref.voi)) <= 1e-5, "%s level %d: voi %r vs %r" % (what, l, got.voi, ref.voi)
+        if with_harness:
+            xyz, seg, _ = ctx.voxel_cloud()
+            table, ssize, tsize, repeats = dense_table(xyz, seg, vx, tl)
+            assert table.shape[0] == nreg[l]
+            dense, _, sparse_m = harness_scores(harness, table, ssize, tsize, len(vx))
+            assert bits(got) == sparse_m.view(np.uint32).tolist(), "%s level %d: %s vs the g++ build %s" % (what, l, got.as_dict(), sparse_m.tolist())
+            assert dense.view(np.uint32).tolist() == bits(ref), "%s level %d: the dense construction is not f3ds_evaluate's table" % (what, l)
+            notes.append(dict(unvisited=len(tsize) - len(set(tsize.tolist())), empty_columns=int((table.sum(0) == 0).sum()), repeats=repeats,
+                              cloud=len(seg), owned=int((ctx.debug("VOXEL_REGION") != NO_LABEL).sum())))
+    ctx.recluster(_at(prm, prm.threshold))
+    return scores, nreg, notes
+
+
+_no_merges = []
+_cases_run = []
+
+
+@pytest.mark.parametrize("name", sorted(GOLDEN_CASES))
+def test_golden_levels_equal_recluster_evaluate_and_the_host_build(P, gpu_ctx, harness, name):
+    pts, prm = case_points(P, name), case_params(P, name)
+    gpu_ctx.segment(pts, prm)
+    w = gpu_ctx.merge_tree()[2]
+    ts = level_thresholds(w, prm.threshold)
+    many = synthetic_truth(pts)
+    scores, nreg, notes = _check_levels(P, gpu_ctx, harness, pts, prm, many, ts, name + " synthetic truth")
+    _cases_run.append(name)
+    if name == "rgbd_160x120":      # every quirk of the matching occurs on a real frame
+        assert min(n["unvisited"] for n in notes) >= 1 and min(n["empty_columns"] for n in notes) >= 1, notes
+    if name == "fused_200k_nan_lambda":      # one live ghost leaf: a region more than owning supervoxels, one cloud entry more than owned voxels
+        assert all(n["cloud"] == n["owned"] + 1 for n in notes), notes
+    if len(w) == 0 or len(set(nreg.tolist())) == 1:
+        _no_merges.append(name)
+        print("NOTE: %s has no merges: all its levels are equal" % name)
+    else:
+        assert len(set(nreg.tolist())) >= 5, (name, nreg)
+        assert len({s.fscore for s in scores}) >= 5, (name, [s.fscore for s in scores])
+    zeros = np.zeros(len(pts), np.uint32)
+    gpu_ctx.segment(pts, prm)
+    _check_levels(P, gpu_ctx, harness, pts, prm, zeros, ts, name + " all-zero truth")
+
+
+@pytest.mark.parametrize("seed", SEEN_SEEDS)
+def test_seen_ghost_leaf(P, gpu_ctx, harness, seed):
+    pts, prm, truth = seen_cloud(P, seed)
+    gpu_ctx.segment(pts, prm)
+    ts = level_thresholds(gpu_ctx.merge_tree()[2], prm.threshold)
+    _, _, notes = _check_levels(P, gpu_ctx, harness, pts, prm, truth, ts, "seen-ghost seed %d" % seed)
+    assert max(n["repeats"] for n in notes) >= 1, notes              # a level where voxel_cloud() repeats a voxel inside a segment ...
+    assert min(n["repeats"] for n in notes) == 0, notes              # ... and one where the same ghost leaf still adds its entry
+
+
+def test_at_most_two_golden_cases_without_merges():
+    if len(_cases_run) < len(GOLDEN_CASES):
+        pytest.fail("run with the golden-case test above (it records the cases without merges)")
+    assert len(_no_merges) <= 2, _no_merges
+
+
+def test_threshold_order_and_repeats(P, gpu_ctx):
+    name = "rgbd_320x240_ghosts"
+    pts, prm = case_points(P, name), case_params(P, name)
+    truth = synthetic_truth(pts)
+    gpu_ctx.segment(pts, prm)
+    ts = np.array([0.0, 0.05, 0.1, 0.15, 0.2], np.float32)
+    base, nreg = gpu_ctx.evaluate_levels(truth, ts)
+    mixed = np.array([0.15, 0.0, 0.2, 0.15, 0.05, 0.0, 0.1], np.float32)
+    got, nreg2 = gpu_ctx.evaluate_levels(truth, mixed)
+    for l, t in enumerate(mixed):
+        k = ts.tolist().index(t)
+        assert bits(got[l]) == bits(base[k]) and nreg2[l] == nreg[k]
+    one, nreg1 = gpu_ctx.evaluate_levels(truth, [0.1])
+    assert bits(one[0]) == bits(base[2]) and nreg1[0] == nreg[2]
+
+
+def _batch_frames(P):
+    frames = []
+    for name in sorted(GOLDEN_CASES):
+        frames.append((case_points(P, name), case_params(P, name)))
+    frames.append((P.synth_frame(0, 1000, 1000, 1000, 30), P.launch_params()))        # the bench workload's 1M-point frame
+    frames.append((P.synth_frame(0, 21, 160, 120, 30), P.launch_params(voxel_res=0.02, seed_res=0.2)))
+    frames.append((P.synth_frame(1, 5, 200, 150, 0), P.launch_params(voxel_res=0.03, seed_res=0.3, use_transform=0)))
+    assert len(frames) == 16
+    return frames
+
+
+def test_batch_equals_single_calls(P):
+    import torch
+    frames = _batch_frames(P)
+    ts = np.array([0.2, 0.0, 0.05, 0.1, 0.15, 0.12, 0.18, 0.199], np.float32)          # (every golden run goes to T >= 0.2)
+    ctxs = [P.Context(0) for _ in frames]
+    try:
+        truths = []
+        for c, (pts, prm) in zip(ctxs, frames):
+            c.segment(pts, prm)
+            truths.append(synthetic_truth(pts))
+        single = [c.evaluate_levels(t, ts) for c, t in zip(ctxs, truths)]
+        scores, nreg = P.evaluate_levels_batch(ctxs, truths, ts)
+        for i, (sc, nr) in enumerate(single):
+            assert [bits(s) for s in scores[i]] == [bits(s) for s in sc], "frame %d" % i
+            assert np.array_equal(nreg[i], nr)
+        dev = [torch.from_numpy(t.view(np.int32)).to("cuda") for t in truths]
+        torch.cuda.synchronize()
+        scores_d, nreg_d = P.evaluate_levels_batch(ctxs, dev, ts, on_device=True)
+        for i in range(len(frames)):
+            assert [bits(s) for s in scores_d[i]] == [bits(s) for s in scores[i]], "device truth, frame %d" % i
+        assert np.array_equal(nreg_d, nreg)
+        sc1, _ = ctxs[3].evaluate_levels(dev[3], ts, on_device=True)
+        assert [bits(s) for s in sc1] == [bits(s) for s in scores[3]]
+        # the 1M-point frame at T is its segmentation: the scores of f3ds_evaluate
+        ref = ctxs[13].evaluate(truths[13])
+        assert bits(scores[13][0])[1:] == bits(ref)[1:] and abs(scores[13][0].voi - ref.voi) <= 1e-5
+    finally:
+        for c in ctxs:
+            c.close()
+
+
+def _state(ctx):
+    return dict(regions=ctx.regions(), cloud=ctx.voxel_cloud(), adj=ctx.region_adjacency(), vreg=ctx.debug("VOXEL_REGION"),
+                merges=ctx.debug("MERGES"), svreg=ctx.debug("SV_REGION"))
+
+
+def test_state_is_unchanged(P, gpu_ctx):
+    name = "rgbd_320x240_ghosts"
+    pts, prm = case_points(P, name), case_params(P, name)
+    truth = synthetic_truth(pts)
+    gpu_ctx.segment(pts, prm)
+    before = _state(gpu_ctx)
+    res = (gpu_ctx.result.n_regions, gpu_ctx.result.n_merges)
+    ev_before = gpu_ctx.evaluate(truth)
+    gpu_ctx.evaluate_levels(truth, [0.0, 0.05, 0.1, 0.2, 0.15])
+    after = _state(gpu_ctx)
+    assert (gpu_ctx.result.n_regions, gpu_ctx.result.n_merges) == res
+    for k in before:
+        a, b = before[k], after[k]
+        if isinstance(a, dict):
+            assert a.keys() == b.keys() and all(np.asarray(a[x]).tobytes() == np.asarray(b[x]).tobytes() for x in a), k
+        elif isinstance(a, tuple):
+            assert all(np.asarray(x).tobytes() == np.asarray(y).tobytes() for x, y in zip(a, b)), k
+        else:
+            assert np.asarray(a).tobytes() == np.asarray(b).tobytes(), k
+    assert bits(gpu_ctx.evaluate(truth)) == bits(ev_before)
+    later = gpu_ctx.recluster(_at(prm, 0.1))
+    fresh = P.Context(0)
+    try:
+        fresh.segment(pts, prm)
+        assert np.array_equal(later, fresh.recluster(_at(prm, 0.1)))
+        at_fresh = fresh.auto_threshold(prm, truth, 0.05, 0.2, 0.05)
+        gpu_ctx.recluster(prm)
+        gpu_ctx.evaluate_levels(truth, [0.1, 0.2])
+        at_here = gpu_ctx.auto_threshold(prm, truth, 0.05, 0.2, 0.05)
+        assert at_here[0] == at_fresh[0] and bits(at_here[1]) == bits(at_fresh[1]) and at_here[2] == at_fresh[2] and np.array_equal(at_here[3], at_fresh[3])
+    finally:
+        fresh.close()
+
+
+def test_auto_threshold_grid(P, gpu_ctx):
+    name = "rgbd_160x120"
+    pts, prm = case_points(P, name), case_params(P, name)
+    truth = synthetic_truth(pts)
+    gpu_ctx.segment(pts, prm)
+    bt, bp, table, _ = gpu_ctx.auto_threshold(prm, truth, 0.05, 0.6, 0.05)
+    ts = np.array(list(table), np.float32)
+    assert len(ts) >= 10 and [float(t) for t in ts] == list(table)
+    gpu_ctx.recluster(_at(prm, ts[-1]))
+    scores, _ = gpu_ctx.evaluate_levels(truth, ts)
+    for l, t in enumerate(table):
+        want = np.array([table[t][f] for f in FIELDS], np.float32).view(np.uint32).tolist()
+        assert bits(scores[l])[1:] == want[1:], "t = %r" % t
+        assert abs(scores[l].voi - table[t]["voi"]) <= 1e-5
+    best = P.best_level(ts, scores)
+    assert best >= 0 and float(ts[best]) == bt and bits(scores[best])[1:] == bits(bp)[1:]
+
+
+def test_frame_the_dense_path_refuses(P, gpu_ctx, harness):
+    pts, prm = P.synth_frame(0, 1000, 1000, 1000, 30), P.launch_params()
+    truth = ((np.arange(len(pts)) // 977) % 7).astype(np.uint32)
+    gpu_ctx.segment(pts, prm)
+    S = int(gpu_ctx.result.n_supervoxels)
+    tl = voxel_truth_labels(gpu_ctx.debug("POINT_VOXEL"), gpu_ctx.debug("VOXEL_COUNT"), truth, P)
+    M = int(tl.max()) + 1
+    assert (M, S) == (35068, 2813), "the generator changed: M %d, S %d" % (M, S)
+    assert S * M > 2 ** 26
+    gpu_ctx.recluster(_at(prm, 0.0))
+    assert gpu_ctx.result.n_regions == S
+    with pytest.raises(P.F3dsError) as e:
+        gpu_ctx.evaluate(truth)
+    assert e.value.code == -7                                   # F3DS_ERR_UNSUPPORTED: the dense table is refused
+    gpu_ctx.recluster(_at(prm, 0.2))
+    ts = np.array([0.0, 0.05, 0.1, 0.2], np.float32)
+    scores, nreg = gpu_ctx.evaluate_levels(truth, ts)
+    assert nreg[0] == S and nreg[3] == 26
+    vx = gpu_ctx.debug("VOXEL_XYZ").reshape(-1, 3)
+    checked_dense = checked_refused = 0
+    for l, t in enumerate(ts):
+        gpu_ctx.recluster(_at(prm, t))
+        K = int(gpu_ctx.result.n_regions)
+        assert K == nreg[l]
+        print("level %d t %.9g K %d: %s" % (l, t, K, scores[l].as_dict()))
+        if K * M <= 2 ** 26:
+            ref = gpu_ctx.evaluate(truth)
+            assert bits(scores[l])[1:] == bits(ref)[1:], "level %d: %s vs %s" % (l, scores[l].as_dict(), ref.as_dict())
+            assert abs(scores[l].voi - ref.voi) <= 1e-5
+            checked_dense += 1
+        else:
+            # the refused level: the g++ build of the sparse routine on the dense table (395 MB of host memory, once)
+            xyz, seg, _ = gpu_ctx.voxel_cloud()
+            table, ssize, tsize, _ = dense_table(xyz, seg, vx, tl)
+            assert table.shape == (K, M)
+            dense, _, sparse_m = harness_scores(harness, table, ssize, tsize, len(vx))
+            del table
+            assert bits(scores[l]) == sparse_m.view(np.uint32).tolist(), "level %d: %s vs the g++ build %s" % (l, scores[l].as_dict(), sparse_m.tolist())
+            assert dense[1:].view(np.uint32).tolist() == bits(scores[l])[1:] and abs(float(dense[0]) - scores[l].voi) <= 1e-5
+            checked_refused += 1
+    assert checked_dense >= 1 and checked_refused >= 1 and nreg[3] * M <= 2 ** 26
+    gpu_ctx.recluster(_at(prm, prm.threshold))
+
+
+def test_errors(P, gpu_ctx):
+    lib = P.load_library()
+    fresh = P.Context(0)
+    try:
+        pts, prm = case_points(P, "rgbd_160x120"), case_params(P, "rgbd_160x120")
+        truth = synthetic_truth(pts)
+        with pytest.raises(P.LogicError):
+            P.evaluate_levels_batch([fresh], [truth], [0.1])          # no cluster run yet
+        fresh.segment(pts, prm)
+        with pytest.raises(IndexError):
+            fresh.evaluate_levels(truth, [0.1, np.nextafter(np.float32(prm.threshold), np.float32(1))])
+        for bad in (float("nan"), float("-inf")):
+            with pytest.raises(P.F3dsError) as e:
+                fresh.evaluate_levels(truth, [0.1, bad])
+            assert e.value.code == -1
+        t = np.array([0.1], np.float32)
+        ps = (P.Performance * 1)()
+        tp = truth.ctypes.data
+        assert lib.f3ds_evaluate_levels(fresh.handle, tp, 0, t.ctypes.data, 0, ps, None) == -1
+        assert lib.f3ds_evaluate_levels(fresh.handle, None, 0, t.ctypes.data, 1, ps, None) == -1
+        assert lib.f3ds_evaluate_levels(fresh.handle, tp, 0, None, 1, ps, None) == -1
+        assert lib.f3ds_evaluate_levels(fresh.handle, tp, 0, t.ctypes.data, 1, None, None) == -1
+        assert lib.f3ds_evaluate_levels(fresh.handle, tp, 0, t.ctypes.data, 1, ps, None) == 0
+        with pytest.raises(P.F3dsError) as e:
+            P.evaluate_levels_batch([fresh, fresh], [truth, truth], [0.1])      # a context named twice
+        assert e.value.code == -1
+        with pytest.raises(ValueError):
+            fresh.evaluate_levels(truth[:-1], [0.1])
+        fresh.recluster(_at(prm, 0.05))               # a recluster is a cluster run: T is now 0.05
+        with pytest.raises(IndexError):
+            fresh.evaluate_levels(truth, [0.1])
+        fresh.evaluate_levels(truth, [0.05, 0.01])
+        empty = np.full((100, 4), np.nan, np.float32)
+        fresh.segment(empty, prm)                    # a frame without voxels
+        with pytest.raises(P.LogicError):
+            fresh.evaluate_levels(np.zeros(100, np.uint32), [0.1])
+    finally:
+        fresh.close()
+
+
+def test_user_mode_is_a_logic_error(P, oracle, gpu_ctx):
+    name = "rgbd_160x120"
+    pts, prm = case_points(P, name), case_params(P, name)
+    rc, _, _, h = oracle.segment(pts, prm)
+    assert rc == 0
+    sv, pairs = h.export_supervoxels()
+    user = P.Context(0)
+    try:
+        _, vlab = user.cluster_supervoxels(sv, pairs, prm)
+        lib = P.load_library()
+        t = np.array([0.1], np.float32)
+        truth = np.zeros(max(len(vlab), 1), np.uint32)
+        ps = (P.Performance * 1)()
+        assert lib.f3ds_evaluate_levels(user.handle, truth.ctypes.data, 0, t.ctypes.data, 1, ps, None) == -5
+    finally:
+        user.close()
+
+
+def test_cli_level_scores(P, gpu_ctx, tmp_path):
+    assert os.path.exists(CLI)
+    name = "rgbd_160x120"
+    pts = case_points(P, name)
+    truth = synthetic_truth(pts)
+    pcd = str(tmp_path / "frame.pcd")
+    ok = np.isfinite(pts[:, :3]).all(1)
+    P.write_pcd(pcd, pts[ok, :3], pts[ok, 3].copy().view(np.uint32), truth[ok])
+    levels = ["0.1", "0.15", "0.05", "0.2"]
+    out = tmp_path / "scores.txt"
+    base = [CLI, "-p", pcd, "--CVX", "--AL", "-t", "0.2", "--labels", str(tmp_path / "lv"), "--levels", ",".join(levels)]
+    r = subprocess.run(base + ["--level-scores", str(out)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    rpts, rlab = P.read_pcd(pcd, with_labels=True)
+    assert np.array_equal(rlab, truth[ok])
+    gpu_ctx.segment(rpts, P.launch_params())                     # the CLI's parameters for --CVX --AL -t 0.2
+    ts = np.array([float(x) for x in levels], np.float32)
+    scores, _ = gpu_ctx.evaluate_levels(rlab, ts)
+    want = ["%.9g %s" % (ts[l], " ".join("%.9g" % getattr(scores[l], f) for f in FIELDS)) for l in range(len(ts))]
+    assert out.read_text().splitlines() == want
+    for i in range(len(levels)):                                 # and they belong to the label files of the same run
+        assert os.path.exists(str(tmp_path / ("lv.L%d" % i)))
+    best = P.best_level(ts, scores)
+    assert best >= 0 and ("Using best threshold: %f (F-score %f, voi %f)" % (ts[best], scores[best].fscore, scores[best].voi)) in r.stdout, r.stdout
+    # --level-scores without --levels is an argument error, found before any device call
+    r = subprocess.run([CLI, "-p", pcd, "-t", "0.2", "--labels", str(tmp_path / "x"), "--level-scores", str(out)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 1 and "--level-scores needs --levels" in r.stderr
