@@ -3,10 +3,10 @@
 // Stage map (kernel functors d_<name> live in f3ds_kernels.inc; reference citations are in include/f3ds.h,
 // csrc/f3ds_numerics.h, csrc/f3ds_algo.h):
 //   0 voxelise   d_bbox -> d_grid, then one of two paths:
-//                tile path (batches): d_tile_keys -> radix sort of the tile descriptors -> d_desc_part / d_desc_offsets / d_desc_apply -> d_tile_place -> d_voxel_list_accum (-> d_vox_hash)
+//                tile path (batches): d_tile_keys -> radix sort of the tile descriptors -> d_desc_part / d_desc_offsets / d_desc_apply -> d_tile_place -> d_voxel_list_accum
 //                sort path (lone frames, refused frames): d_keys -> radix sort of the points -> d_seg_count / scan / d_seg_write -> d_voxel_gather_accum
 //                (F3DS_SPLIT_VOXEL_ACCUM, development: the sort path as d_heads / scan / d_segstart -> d_point_gather -> d_voxel_accum)
-//   1 neighbours d_neighbors (hash probe of the 27 cells), d_normals_t<384 | 256 threads> (two-ring ordered covariance, LDS tile)
+//   1 neighbours d_vox_table (leaf keys -> one table entry per 4x4x4 block of cells, after either path of stage 0), d_neighbors (the 27 cells through that table), d_normals_t<384 | 256 threads> (two-ring ordered covariance, LDS tile)
 //   2 seeds      d_chunkbox, d_seed_grow, d_seed_keys, radix sort, d_cell_hash, d_seed_nn, d_seed_filter
 //   3 sweeps     per sweep: d_sweep_begin, d_sweep_R_first (pre-pass | round 0), d_sweep_R_round x2 | d_sweep_R + d_sweep_R_tail, d_sweep_claim,
 //                d_centroid (both mark dirty tiles on the spot)  
@@ -579,32 +579,36 @@ int seg_vox_tiles(f3ds_ctx* c, int code_bits, int tile_bits) {      // (code_bit
     c->vox_hashed = true;
     return F3DS_OK;
 }
+// the voxel table of the neighbour search (f3ds_kernels.inc, vt_* / bt_*) from the leaf keys, then the search.  Grids of depth <= 12: an entry of two words per 4x4x4 block, at most V
+// of them, in the hkeys buffer; deeper grids: an entry per voxel, keys in hkeys and ordinals in hvals.  The kernels choose by the depth on the device, as the host does here.
+// wgs: workgroups that build the table -- one on the tile path (workgroup-scope atomics), several for a frame that has the chip to itself.
+int seg_neighbors(f3ds_ctx* c, uint32_t wgs) {
+    const uint32_t V = c->V;
+    const bool blocks = c->h_dc->depth <= N_BLOCK_DEPTH_MAX;
+    const uint32_t cap = blocks ? pow2_ge((size_t)V + 16) : pow2_ge((size_t)V * 2 + 16);
+    const size_t words = blocks ? (size_t)cap * 2 : cap;      // (8-byte words of hkeys)
+    uint32_t* hvals = nullptr; int *nbr, *nbrT; uint64_t* hkeys;
+    c->hmask = cap - 1;
+    ENSURE(c->nbr, (size_t)V * 27, nbr); ENSURE(c->nbrT, (size_t)V * 27, nbrT); ENSURE(c->hkeys, words, hkeys);
+    if (!blocks) ENSURE(c->hvals, cap, hvals);
+    rec_fill(c, hkeys, 0xFFFFFFFFu, words * 8);
+    rec<d_vox_table>(c, wgs, 0u, c->vkey.p, V, c->d_grid, hkeys, hvals, c->hmask);
+    rec<d_neighbors>(c, grid_wide((size_t)V * 27, 256), 0u, c->vkey.p, c->d_dc, c->d_grid, c->fa.leaf_order, hkeys, hvals, c->hmask, nbr, nbrT);
+    return F3DS_OK;
+}
 // stage 0c + 1 + 2a: voxel sums, neighbour tables, normals, seed grid growth
 int seg_voxels(f3ds_ctx* c) {
     const uint32_t V = c->V, n = c->n;
-    uint32_t *vkey, *vcount, *hvals; float *vf; int *nbr, *nbrT; uint64_t* hkeys;
-    if (c->vox_hashed) {      // the leaf sums exist already (seg_vox_tiles): the leaf keys go into the hash table, then the neighbour search
-        const uint32_t hc2 = pow2_ge((size_t)V * 2 + 16);
-        c->hmask = hc2 - 1;
-        ENSURE(c->nbr, (size_t)V * 27, nbr); ENSURE(c->nbrT, (size_t)V * 27, nbrT); ENSURE(c->hkeys, hc2, hkeys); ENSURE(c->hvals, hc2, hvals);
-        rec_fill(c, hkeys, 0xFFFFFFFFu, (size_t)hc2 * 8);
-        rec<d_vox_hash>(c, 1u, 0u, c->vkey.p, V, c->d_grid, hkeys, hvals, c->hmask);
-        rec<d_neighbors>(c, grid_wide((size_t)V * 27, 256), 0u, c->vkey.p, c->d_dc, c->d_grid, hkeys, hvals, c->hmask, nbr, nbrT);
-        return F3DS_OK;
-    }
-    const uint32_t hcap = pow2_ge((size_t)V * 2 + 16);
-    c->hmask = hcap - 1;
+    if (c->vox_hashed) return seg_neighbors(c, 1u);      // the leaf sums exist already (seg_vox_tiles)
+    uint32_t *vkey, *vcount; float *vf;
     ENSURE(c->vkey, (size_t)V * 3, vkey); ENSURE(c->vcount, V, vcount); ENSURE(c->vf, (size_t)V * 12, vf);
-    ENSURE(c->nbr, (size_t)V * 27, nbr); ENSURE(c->nbrT, (size_t)V * 27, nbrT); ENSURE(c->hkeys, hcap, hkeys); ENSURE(c->hvals, hcap, hvals);
-    rec_fill(c, hkeys, 0xFFFFFFFFu, (size_t)hcap * 8);
     if (g_sw.split_voxel_accum) {      // development: round 2's two kernels (a sorted copy of the frame in between)
         P16* spts; ENSURE(c->spts, n, spts);
         rec<d_point_gather>(c, grid_wide(n, 256), 0u, c->d_pts, c->vs, c->ks, c->idxbits < 0 ? 0 : c->idxbits, c->incl.p, n, c->d_dc, spts, c->pt_voxel.p);
-        rec<d_voxel_accum>(c, grid_wide(V, 256), 0u, spts, c->ks, c->idxbits < 0 ? 0 : c->idxbits, c->seg_start.p, c->d_dc, c->fa, c->d_grid, vkey, vcount, vf, hkeys, hvals, c->hmask);
+        rec<d_voxel_accum>(c, grid_wide(V, 256), 0u, spts, c->ks, c->idxbits < 0 ? 0 : c->idxbits, c->seg_start.p, c->d_dc, c->fa, c->d_grid, vkey, vcount, vf);
     } else
-        rec<d_voxel_gather_accum>(c, grid_wide(V, 256), 0u, c->d_pts, c->vs, c->ks, c->idxbits < 0 ? 0 : c->idxbits, c->seg_start.p, n, c->d_dc, c->fa, c->d_grid, vkey, vcount, vf, hkeys, hvals, c->hmask, c->pt_voxel.p);
-    rec<d_neighbors>(c, grid_wide((size_t)V * 27, 256), 0u, vkey, c->d_dc, c->d_grid, hkeys, hvals, c->hmask, nbr, nbrT);
-    return F3DS_OK;
+        rec<d_voxel_gather_accum>(c, grid_wide(V, 256), 0u, c->d_pts, c->vs, c->ks, c->idxbits < 0 ? 0 : c->idxbits, c->seg_start.p, n, c->d_dc, c->fa, c->d_grid, vkey, vcount, vf, c->pt_voxel.p);
+    return seg_neighbors(c, grid_for(V, 4096));
 }
 // stage 1b: voxel normals -- ONE launch per batch call, bracketed by its own pair of events (f3ds_result.ms_stage[7]: besides the merge
 // loop the only kernel of the path whose launch duration is measured live, bench.py's roofline picks the longer of the two)

@@ -339,35 +339,32 @@ __device__ inline P16 load_point(const P16* pts, size_t i) {
     return p;
 }
 
-// The voxel table of the neighbour search (cell key -> leaf ordinal), open addressing.  Grids of depth <= 10 (30 key bits: every BASELINE configuration) keep key and ordinal in ONE
-// 8-byte word -- a hit is one load, where the general layout (63-bit keys in hkeys, ordinals in hvals) makes it two dependent ones on two lines: d_neighbors issues 27 probes per
-// voxel and runs at the rate its address unit can touch lines (DESIGN.md 5).  Keys are unique (one insert per leaf): an insert never meets its own key.
-__device__ inline bool vt_compact(int depth) { return depth <= 10; }
-__device__ inline uint32_t vt_key30(unsigned x, unsigned y, unsigned z) { return (x << 20) | (y << 10) | z; }
-template <bool WG_SCOPE>
-__device__ inline void vt_insert(uint64_t* hkeys, uint32_t* hvals, uint32_t hmask, int depth, unsigned x, unsigned y, unsigned z, uint32_t v) {
-    const bool compact = vt_compact(depth);
-    const unsigned long long pk = compact ? (((unsigned long long)vt_key30(x, y, z) << 32) | v) : (unsigned long long)n_pack_key(x, y, z);
-    uint32_t h = (uint32_t)hash64(compact ? (uint64_t)vt_key30(x, y, z) : (uint64_t)pk) & hmask;
+// The voxel table of the neighbour search (cell key -> leaf ordinal), open addressing, built by d_vox_table after the host knows V and read by d_neighbors.  d_neighbors runs at the
+// rate its address unit can touch lines (DESIGN.md 5) and nearly all its lines were probes: 27 per voxel into a table with an entry per voxel.  Grids of depth <= 12 (every BASELINE
+// configuration) therefore keep an entry per 4x4x4 BLOCK of cells (f3ds_numerics.h, n_block_*): 16 bytes -- block key, ordinal of the block's first leaf, 64-bit mask of its EMPTY cells
+// (stored complemented so that the all-ones fill is an empty entry and a build is atomic ANDs) -- read with one load.  A voxel's 27 cells lie in at most 8 blocks and the lanes of a wave
+// ask for about ten blocks between them: lanes that want the same block read the same line, the rest is arithmetic.  A surface fills 10-16 cells of a block it crosses, so the table
+// has a tenth of the entries.  Deeper grids keep an entry per voxel: 63-bit keys in hkeys, ordinals in hvals, two dependent loads per hit.
+__device__ inline bool vt_blocks(int depth) { return depth <= N_BLOCK_DEPTH_MAX; }
+constexpr uint32_t BT_EMPTY = 0xFFFFFFFFu;
+struct __attribute__((aligned(16))) BtEntry { uint32_t key, base; unsigned long long vacant; };
+static_assert(sizeof(BtEntry) == 16, "one 16-byte load per probe");
+// The atomics of a table one workgroup builds are WORKGROUP-scope (resolved in the XCD's L2); several workgroups need agent scope (resolved beyond it: ~0.1 us of the chip per thousand).
+template <class T> __device__ inline bool vt_cas(T* p, T* expect, T v, bool agent) {
+    return agent ? __hip_atomic_compare_exchange_strong(p, expect, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                 : __hip_atomic_compare_exchange_strong(p, expect, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+// general layout: keys are unique (one insert per leaf)
+__device__ inline void vt_insert(uint64_t* hkeys, uint32_t* hvals, uint32_t hmask, bool agent, unsigned x, unsigned y, unsigned z, uint32_t v) {
+    const unsigned long long pk = (unsigned long long)n_pack_key(x, y, z);
+    uint32_t h = (uint32_t)hash64((uint64_t)pk) & hmask;
     for (;;) {
         unsigned long long expect = HASH_EMPTY;
-        const bool won = WG_SCOPE ? __hip_atomic_compare_exchange_strong((unsigned long long*)&hkeys[h], &expect, pk, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-                                  : __hip_atomic_compare_exchange_strong((unsigned long long*)&hkeys[h], &expect, pk, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (won || (!compact && expect == pk)) { if (!compact) hvals[h] = v; return; }
+        if (vt_cas((unsigned long long*)&hkeys[h], &expect, pk, agent) || expect == pk) { hvals[h] = v; return; }
         h = (h + 1u) & hmask;
     }
 }
-__device__ inline int vt_find(const uint64_t* hkeys, const uint32_t* hvals, uint32_t hmask, bool compact, unsigned x, unsigned y, unsigned z) {
-    if (compact) {
-        const uint32_t ck = vt_key30(x, y, z);
-        uint32_t h = (uint32_t)hash64((uint64_t)ck) & hmask;
-        for (;;) {
-            const uint64_t e = hkeys[h];
-            if ((uint32_t)(e >> 32) == ck) return (int)(uint32_t)e;
-            if (e == HASH_EMPTY) return -1;
-            h = (h + 1u) & hmask;
-        }
-    }
+__device__ inline int vt_find(const uint64_t* hkeys, const uint32_t* hvals, uint32_t hmask, unsigned x, unsigned y, unsigned z) {
     const uint64_t pk = n_pack_key(x, y, z);
     uint32_t h = (uint32_t)hash64(pk) & hmask;
     for (;;) {
@@ -375,6 +372,25 @@ __device__ inline int vt_find(const uint64_t* hkeys, const uint32_t* hvals, uint
         if (k == pk) return (int)hvals[h];
         if (k == HASH_EMPTY) return -1;
         h = (h + 1u) & hmask;
+    }
+}
+// block layout: the entry of block `bk`, claimed on the way if no lane has asked for it yet (the heads of a block's run of leaves and the lanes that continue a run across a wave border)
+__device__ inline BtEntry* bt_entry(BtEntry* tab, uint32_t tmask, bool agent, uint32_t bk) {
+    uint32_t h = (uint32_t)hash64((uint64_t)bk) & tmask;
+    for (;;) {
+        uint32_t expect = BT_EMPTY;
+        if (vt_cas(&tab[h].key, &expect, bk, agent) || expect == bk) return &tab[h];
+        h = (h + 1u) & tmask;
+    }
+}
+__device__ inline int bt_find(const BtEntry* tab, uint32_t tmask, int leaf_order, unsigned x, unsigned y, unsigned z) {
+    const uint32_t bk = n_block_key(x, y, z);
+    uint32_t h = (uint32_t)hash64((uint64_t)bk) & tmask;
+    for (;;) {
+        const uint4 e = reinterpret_cast<const uint4*>(tab)[h];      // one global_load_dwordx4
+        if (e.x == bk) return n_block_ordinal(e.y, ~(((uint64_t)e.w << 32) | (uint64_t)e.z), n_block_cell(x, y, z), leaf_order);
+        if (e.x == BT_EMPTY) return -1;
+        h = (h + 1u) & tmask;
     }
 }
 // bounding box of the transformed finite points + count of finite input points
@@ -548,12 +564,12 @@ struct d_point_gather {
         }
     }
 };
-// one lane per voxel: ordered sums over its points (input order), centroid, key, hash insert
+// one lane per voxel: ordered sums over its points (input order), centroid, key
 struct d_voxel_accum {
     static constexpr int BLOCK = 256;
     __device__ void operator()(const P16* spts, const uint64_t* keys, int keyshift, const uint32_t* seg_start,
                                                     const DevCounters* dc, FrameArgs fa, const GridInfo* gp, uint32_t* vkey, uint32_t* vcount,
-                                                    float* vf, uint64_t* hkeys, uint32_t* hvals, uint32_t hmask) const {
+                                                    float* vf) const {
         const uint32_t V = dc->n_voxels;
         const int depth = gp->depth;
         for (uint32_t v = BIX * blockDim.x + threadIdx.x; v < V; v += gridDim.x * blockDim.x) {
@@ -577,7 +593,6 @@ struct d_voxel_accum {
             unsigned k[3];
             n_demorton(code, depth, k);
             vkey[v * 3] = k[0]; vkey[v * 3 + 1] = k[1]; vkey[v * 3 + 2] = k[2];
-            vt_insert<false>(hkeys, hvals, hmask, depth, k[0], k[1], k[2], v);
         }
     }
 };
@@ -590,7 +605,7 @@ struct d_voxel_gather_accum {
     static constexpr int BLOCK = 256;
     __device__ void operator()(const P16* pts, const uint32_t* vals, const uint64_t* keys, int keyshift, const uint32_t* seg_start, uint32_t n,
                                const DevCounters* dc, FrameArgs fa, const GridInfo* gp, uint32_t* vkey, uint32_t* vcount,
-                               float* vf, uint64_t* hkeys, uint32_t* hvals, uint32_t hmask, int* pt_voxel) const {
+                               float* vf, int* pt_voxel) const {
         __shared__ __attribute__((aligned(16))) uint4 buf[VG_CHUNK];
         __shared__ uint32_t ibuf[VG_CHUNK], vbuf[VG_CHUNK];
         const uint32_t V = dc->n_voxels, nv = dc->n_valid;
@@ -644,7 +659,6 @@ struct d_voxel_gather_accum {
             unsigned k[3];
             n_demorton(code, depth, k);
             vkey[v * 3] = k[0]; vkey[v * 3 + 1] = k[1]; vkey[v * 3 + 2] = k[2];
-            vt_insert<false>(hkeys, hvals, hmask, depth, k[0], k[1], k[2], v);
         }
     }
 };
@@ -663,7 +677,7 @@ struct d_voxel_gather_accum {
 //                  where a descriptor's points go: chunk totals, one workgroup's prefix over the chunks, per-descriptor results
 //   d_tile_place   second pass over the per-point words: voxel of every point (pt_voxel) and the point's index into its leaf's list
 //   d_voxel_list_accum   per leaf: the points gathered through LDS and added in list order -- the additions of d_voxel_accum, bit for bit
-//   d_vox_hash     the leaf keys into the hash table of the neighbour search (after the host knows V)
+//   d_vox_table    the leaf keys into the voxel table of the neighbour search (after the host knows V; the sort path runs it too)
 // No global atomic on the way (an agent-scope atomic is resolved beyond the XCD's L2: ~0.1 us of the chip per thousand -- the first version of this path,
 // a global hash insert per run of points, spent 47 us per frame on them), 121-143 MB of HBM traffic per 1M-point frame where the sort path moves 185-200.
 // Inside a tile the 256-point steps are separated by barriers, so a leaf's list comes out ascending except when two runs of one voxel meet in one
@@ -948,22 +962,57 @@ struct d_tile_place {
         }
     }
 };
-// leaf keys -> hash table of the neighbour search (the sort path does this inside its accumulation kernel, with agent-scope atomics: 77 k of them per 1M-point
-// frame, ~6 us of the chip).  Here ONE workgroup builds a frame's table: its waves share a compute unit, so WORKGROUP-scope compare-and-swaps -- resolved in the
-// XCD's L2, not beyond it -- are all the coherence the build needs; the readers come in later kernels.
-struct d_vox_hash {
+// leaf keys -> voxel table of the neighbour search (vt_* / bt_* above), on both stage-0 paths: they leave vkey in leaf order.  Block layout: a lane per leaf; a leaf whose block key
+// differs from its predecessor's is the HEAD of its block's run and gives the entry its base ordinal; the cell bits of the run are ORed along the lanes of a wave (a suffix scan cut at
+// the heads, no LDS) and the first lane of every piece of a run -- the head, or lane 0 where a run continues across a wave border -- clears them in the entry's mask with one atomic AND.
+// So a frame of 77 k leaves costs ~7 k compare-and-swaps where an entry per voxel cost 77 k.  On the tile path ONE workgroup builds a frame's table: its waves share a compute unit, so
+// WORKGROUP-scope atomics -- resolved in the XCD's L2, not beyond it -- are all the coherence the build needs; the readers come in later kernels.  The sort path (a lone frame: nothing
+// else to fill the chip with) spreads the leaves over several workgroups, and its atomics are agent-scope then.
+struct d_vox_table {
     static constexpr bool LATENCY_KERNEL = true;
     static constexpr int BLOCK = 1024;
     __device__ void operator()(const uint32_t* vkey, uint32_t V, const GridInfo* gp, uint64_t* hkeys, uint32_t* hvals, uint32_t hmask) const {
-        if (BIX) return;
-        const int depth = gp->depth;
+        const bool blocks = vt_blocks(gp->depth);
+        const bool agent = gridDim.x > 1u;
+        BtEntry* const tab = reinterpret_cast<BtEntry*>(hkeys);
+        const uint32_t lane = (uint32_t)lane_id();
         constexpr uint32_t PF = 4;      // keys per thread requested together
-        for (uint32_t v0 = threadIdx.x; v0 < V; v0 += blockDim.x * PF) {
-            unsigned k[PF][3];
+        for (uint32_t s0 = BIX * (BLOCK * PF); s0 < V; s0 += gridDim.x * (BLOCK * PF)) {      // (uniform: every lane takes part in the shuffles)
+            unsigned k[PF][3]; uint32_t prev[PF];
     #pragma unroll
-            for (uint32_t j = 0; j < PF; ++j) { const uint32_t v = v0 + j * blockDim.x, vv = v < V ? v : 0u; k[j][0] = vkey[vv * 3]; k[j][1] = vkey[vv * 3 + 1]; k[j][2] = vkey[vv * 3 + 2]; }
+            for (uint32_t j = 0; j < PF; ++j) { const uint32_t v = s0 + j * BLOCK + threadIdx.x, vv = v < V ? v : 0u; k[j][0] = vkey[vv * 3]; k[j][1] = vkey[vv * 3 + 1]; k[j][2] = vkey[vv * 3 + 2]; }
+            if (!blocks) {
     #pragma unroll
-            for (uint32_t j = 0; j < PF; ++j) { const uint32_t v = v0 + j * blockDim.x; if (v < V) vt_insert<true>(hkeys, hvals, hmask, depth, k[j][0], k[j][1], k[j][2], v); }
+                for (uint32_t j = 0; j < PF; ++j) { const uint32_t v = s0 + j * BLOCK + threadIdx.x; if (v < V) vt_insert(hkeys, hvals, hmask, agent, k[j][0], k[j][1], k[j][2], v); }
+                continue;
+            }
+    #pragma unroll
+            for (uint32_t j = 0; j < PF; ++j) {      // lane 0 of a wave: the block of the leaf before the wave's first
+                const uint32_t v = s0 + j * BLOCK + threadIdx.x;
+                prev[j] = lane == 0u && v > 0u && v < V ? n_block_key(vkey[(v - 1u) * 3], vkey[(v - 1u) * 3 + 1], vkey[(v - 1u) * 3 + 2]) : BT_EMPTY;
+            }
+    #pragma unroll
+            for (uint32_t j = 0; j < PF; ++j) {
+                const uint32_t v = s0 + j * BLOCK + threadIdx.x;
+                const bool in = v < V;
+                const uint32_t bk = n_block_key(k[j][0], k[j][1], k[j][2]);
+                const uint32_t up = __shfl_up(bk, 1, 64);
+                const bool head = in && bk != (lane ? up : prev[j]);
+                const uint64_t cuts = __ballot(head || !in);            // lanes that start a piece (lane 0 always does)
+                const uint64_t ahead = (cuts >> 1) >> lane;             // bit d-1: lane + d starts a piece
+                unsigned long long m = in ? 1ull << n_block_cell(k[j][0], k[j][1], k[j][2]) : 0ull;
+    #pragma unroll
+                for (uint32_t d = 1; d < 64u; d <<= 1) {                // m: OR over the lanes from this one to the end of its piece
+                    const unsigned long long o = __shfl_down(m, d, 64);
+                    if (lane + d < 64u && !(ahead & ((1ull << d) - 1ull))) m |= o;
+                }
+                if (in && (head || lane == 0u)) {
+                    BtEntry* const e = bt_entry(tab, hmask, agent, bk);
+                    if (agent) __hip_atomic_fetch_and(&e->vacant, ~m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    else __hip_atomic_fetch_and(&e->vacant, ~m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (head) e->base = v;
+                }
+            }
         }
     }
 };
@@ -1041,12 +1090,14 @@ struct d_neighbors {
     // What a gather or scatter costs a compute unit is the number of distinct lines it touches (tools/ubench/ta_cost.hip: ~2.4 cycles per line from L2, a full
     // 256-byte run 8): the kernel ran at exactly that rate, and a third of its lines were the slot-major stores (27 consecutive lanes = 27 rows of nbrT).  A
     // workgroup now takes 64 consecutive voxels, keeps their 27 x 64 results in LDS and writes the slot-major rows as 256-byte runs.
-    __device__ void operator()(const uint32_t* vkey, const DevCounters* dc, const GridInfo* gp, const uint64_t* hkeys,
+    // The lines left were the probes, one per lane: they now go to the 4x4x4 block table (bt_find), where the ~2.4 voxels of a wave ask for about ten entries between them.
+    __device__ void operator()(const uint32_t* vkey, const DevCounters* dc, const GridInfo* gp, int leaf_order, const uint64_t* hkeys,
                                                   const uint32_t* hvals, uint32_t hmask, int* nbr, int* nbrT) const {
         __shared__ int tr[27][65];      // (65: consecutive slots of one voxel fall into different banks)
         const uint32_t V = dc->n_voxels;
         const unsigned max_key = gp->max_key;
-        const bool compact = vt_compact(gp->depth);
+        const bool blocks = vt_blocks(gp->depth);
+        const BtEntry* const tab = reinterpret_cast<const BtEntry*>(hkeys);
         for (uint32_t vb = BIX * 64u; vb < V; vb += gridDim.x * 64u) {
             const uint32_t nv = V - vb < 64u ? V - vb : 64u, np = nv * 27u;
             for (uint32_t tl = threadIdx.x; tl < np; tl += 256u) {
@@ -1058,7 +1109,7 @@ struct d_neighbors {
                     if (q < 0 || q > (long long)max_key) ok = false;
                     k[a] = (unsigned)q;
                 }
-                const int u = ok ? vt_find(hkeys, hvals, hmask, compact, k[0], k[1], k[2]) : -1;
+                const int u = !ok ? -1 : blocks ? bt_find(tab, hmask, leaf_order, k[0], k[1], k[2]) : vt_find(hkeys, hvals, hmask, k[0], k[1], k[2]);
                 nbr[(size_t)vb * 27u + tl] = u;              // row-major: a voxel's 27 slots together (normals, adjacency)
                 tr[s][vl] = u;
             }

@@ -131,6 +131,18 @@ F3DS_HD void n_demorton(uint64_t c, int depth, unsigned key[3]) {
 F3DS_HD uint64_t n_pack_key(unsigned x, unsigned y, unsigned z) {
     return ((uint64_t)x << 42) | ((uint64_t)y << 21) | (uint64_t)z;
 }
+// 4x4x4 blocks of cells (the voxel table of the neighbour search).  Leaves are in Morton order (leaf_order 0) or in the order of the complemented codes (1: descending), so
+// the occupied cells of one block are consecutive leaf ordinals sorted by the low six code bits: (ordinal of the block's first leaf, 64-bit occupancy mask) gives every ordinal.
+// The key packs ten bits per axis: grids of depth <= N_BLOCK_DEPTH_MAX; 0xFFFFFFFF is never a key.
+#define N_BLOCK_DEPTH_MAX 12
+F3DS_HD uint32_t n_block_key(unsigned x, unsigned y, unsigned z) { return ((x >> 2) << 20) | ((y >> 2) << 10) | (z >> 2); }
+F3DS_HD unsigned n_block_cell(unsigned x, unsigned y, unsigned z) { return (unsigned)n_morton(x & 3u, y & 3u, z & 3u, 2); }      // the bit order of the leaf sort
+// ordinal of cell `cell` (0..63) of a block whose first leaf (in leaf order) has ordinal `base`; -1 when the cell is empty
+F3DS_HD int n_block_ordinal(uint32_t base, uint64_t mask, unsigned cell, int leaf_order) {
+    if (!((mask >> cell) & 1ull)) return -1;
+    const uint64_t before = leaf_order == 1 ? ((mask >> cell) >> 1) : (mask & ((1ull << cell) - 1ull));      // (no shift by 64 at cell 63 / 0)
+    return (int)(base + (uint32_t)__builtin_popcountll(before));
+}
 
 // -------------------------------------------------------------------------------------------
 // plane normal from the nine running sums (computeMeanAndCovarianceMatrix,
