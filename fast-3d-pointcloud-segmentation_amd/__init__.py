@@ -37,6 +37,8 @@ MANUAL_LAMBDA, ADAPTIVE_LAMBDA, EQUALIZATION = 0, 1, 2
 DBG = dict(GRID=0, VOXEL_KEYS=1, VOXEL_COUNT=2, VOXEL_XYZ=3, VOXEL_RGB=4, VOXEL_NORMAL=5, VOXEL_NEIGHBORS=6,
            POINT_VOXEL=7, SEED_ORIG=8, SEED_KEPT=9, VOXEL_SVLABEL=10, VOXEL_DIST=11, SV_LABELS=12, SV_CENTROID=13,
            EDGES=14, EDGE_DELTAS=15, EDGE_WEIGHTS=16, MERGES=17, VOXEL_REGION=18, SV_REGION=19)
+# ... and the selectors of diagnostics (a few words about the last call, not an array of the frame): Context.merge_layout() etc.
+DBG_INFO = dict(MERGE_LAYOUT=20, TILE_LIST_LEN=21, SWEEP_STATS=22, STAGE0_PATH=23, LAUNCH_SHAPE=24)
 DBG_DTYPE = dict(GRID=np.float64, VOXEL_KEYS=np.uint32, VOXEL_COUNT=np.uint32, VOXEL_XYZ=np.float32, VOXEL_RGB=np.float32,
                  VOXEL_NORMAL=np.float32, VOXEL_NEIGHBORS=np.int32, POINT_VOXEL=np.int32, SEED_ORIG=np.int32, SEED_KEPT=np.int32,
                  VOXEL_SVLABEL=np.uint32, VOXEL_DIST=np.float32, SV_LABELS=np.uint32, SV_CENTROID=np.float32, EDGES=np.uint32,
@@ -546,6 +548,13 @@ class Context:
         nb = ctypes.c_size_t(); buf = np.zeros(1, np.uint32)
         _check(self.lib, self.lib.f3ds_get_debug(self.handle, 23, buf.ctypes.data, 4, ctypes.byref(nb)))
         return "tiles" if buf[0] else "sort"
+
+    def launch_shape(self):
+        """(workgroups per frame a streaming kernel got at most, ... a gathering kernel got at most, frames of the call) of the last call that ran
+        kernels for this context (F3DS_DBG_LAUNCH_SHAPE).  (2048, 2048, 1) for a lone frame unless the development switch F3DS_GRID_CAP narrows the launches."""
+        nb = ctypes.c_size_t(); buf = np.zeros(3, np.uint32)
+        _check(self.lib, self.lib.f3ds_get_debug(self.handle, DBG_INFO["LAUNCH_SHAPE"], buf.ctypes.data, 12, ctypes.byref(nb)))
+        return tuple(int(x) for x in buf)
 
     def sweep_stats(self):
         """(full, incremental, fallback, skipped) sweeps of the last run of label-propagation sweeps (F3DS_DBG_SWEEP_STATS)."""

@@ -124,11 +124,11 @@ struct Cmd { LaunchFn fn; uint32_t gx, lds, bytes, off; };
 const int g_inc_shift = [] { const char* e = dev_getenv("F3DS_INC_SHIFT"); return e ? atoi(e) : 6; }();
 
 // Development / test switches (none is needed in production and none changes results).  The environment is read ONCE per entry
-// call of the library (f3ds_segment_batch, f3ds_recluster, f3ds_refine_supervoxels) into this per-thread struct -- not per frame on the hot path,
+// call of the library (f3ds_segment_batch, f3ds_recluster, f3ds_refine_supervoxels, f3ds_evaluate, ...) into this per-thread struct -- not per frame on the hot path,
 // where hundreds of getenv() scans per call would also race with a setenv from another thread.  Tests still see per-call values.
 struct Switches {
     bool direct_labels = false, copy_stream = true, copy_duplex = false, split_voxel_accum = false, sweep_tiles = true, merge_spec = true, force_global_merge = false, no_stream_pool = false, sort_pairs = false, host_prof = false, trace_err = false, vox_hash = true, vox_tiles_forced = false, levels_global = false;
-    int normals_threads = 0, merge_nw = 0, merge_keys = -1; uint32_t tile_holes = 0, ilist_slack = 32, r_rounds = F3DS_R_ROUNDS; long relabel_lds_cap = -1;
+    int normals_threads = 0, merge_nw = 0, merge_keys = -1; uint32_t tile_holes = 0, ilist_slack = 32, r_rounds = F3DS_R_ROUNDS, grid_cap = 0; long relabel_lds_cap = -1;
     void read() {
         auto on = [](const char* n) { return dev_getenv(n) != nullptr; };
         auto num = [](const char* n, long dflt) { const char* e = dev_getenv(n); return e ? atol(e) : dflt; };
@@ -144,6 +144,7 @@ struct Switches {
         levels_global = num("F3DS_LEVELS_GLOBAL", 0) != 0;      // (tests: the hierarchy levels take the global-table form on small frames too)
         { const long v = num("F3DS_R_ROUNDS_RUN", F3DS_R_ROUNDS); r_rounds = v >= 1 && v <= F3DS_R_ROUNDS ? (uint32_t)v : (uint32_t)F3DS_R_ROUNDS; }
         { const long v = num("F3DS_ILIST_SLACK", 32); ilist_slack = v >= 1 && v <= 32 ? (uint32_t)v : 32u; }      // tests: a short incident-list pool (the merge stage then reruns with a larger one)
+        { const long v = num("F3DS_GRID_CAP", 0); grid_cap = v >= 1 && v <= 2048 ? (uint32_t)v : 0u; }      // tests: 1 ... 2048 workgroups per frame, exactly, for grid_for() and grid_wide(): the grid-stride loops make several trips on small frames (0: unset)
     }
 };
 thread_local Switches g_sw;
@@ -228,6 +229,7 @@ struct f3ds_ctx {
     // device scratch (grow-only): one typed member per entry of F3DS_SCRATCH; each_scratch(f) calls f on every one of them until one returns non-zero
     F3DS_SCRATCH(F3DS_SCRATCH_MEMBER)
     template <class F> int each_scratch(F&& f) { F3DS_SCRATCH(F3DS_SCRATCH_VISIT) return 0; }
+    uint32_t launch_shape[3] = {0, 0, 0};      // cap of grid_for(), cap of grid_wide(), frames of the last entry call that recorded kernels for this context (F3DS_DBG_LAUNCH_SHAPE)
     std::vector<uint32_t> tsize;       // voxels per truth label (evaluation)
     float cluster_T = 0.0f;            // threshold of the last cluster run: f3ds_labels_at_thresholds serves levels t <= cluster_T from its merge log
     // f3ds_cluster_supervoxels: the state is caller-supplied supervoxels (no points, no voxel grid).  user_label[h] = the caller's label of internal
@@ -317,6 +319,7 @@ int pregrow_scratch(f3ds_ctx* c) {
 // 300 thin ones (per-workgroup prologue: argument pack, counters, stamps), see DESIGN.md 4b.  The hash-probing /
 // gathering kernels want every wave they can get and keep the old cap (grid_wide).  Set per batch call (one host thread).
 thread_local size_t g_grid_cap = 2048;
+thread_local size_t g_wide_cap = 2048;    // cap of grid_wide(): 2048 unless F3DS_GRID_CAP narrows every launch
 thread_local int g_batch_frames = 1;      // frames of the batch call this thread is running
 // batch calls inside f3ds_segment_batch right now, per device: a call whose merge dispatch shares the chip with other calls takes the 4-wave merge kernel (choose_merge_kind)
 std::atomic<int> g_batch_calls[16];
@@ -327,9 +330,17 @@ size_t grid_cap_for_batch(int frames) {
     size_t cap = target / (size_t)(frames > 0 ? frames : 1);
     return cap < 8 ? 8 : (cap > 2048 ? 2048 : cap);
 }
+// Start of every entry call that records kernels, after g_sw.read(): the launch widths of this call, noted in its frames (F3DS_DBG_LAUNCH_SHAPE).
+// F3DS_GRID_CAP (development) replaces both caps by the given one; unset, grid_for() gets the batch's share and grid_wide() 2048 as ever.
+inline void set_launch_shape(f3ds_ctx* const* frames, int nframes) {
+    g_grid_cap = g_sw.grid_cap ? (size_t)g_sw.grid_cap : grid_cap_for_batch(nframes);
+    g_wide_cap = g_sw.grid_cap ? (size_t)g_sw.grid_cap : 2048;
+    g_batch_frames = nframes;
+    for (int i = 0; i < nframes; ++i) { frames[i]->launch_shape[0] = (uint32_t)g_grid_cap; frames[i]->launch_shape[1] = (uint32_t)g_wide_cap; frames[i]->launch_shape[2] = (uint32_t)nframes; }
+}
 inline uint32_t grid_wide(size_t work, int block) {
     size_t g = (work + block - 1) / block;
-    return (uint32_t)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
+    return (uint32_t)(g < 1 ? 1 : (g > g_wide_cap ? g_wide_cap : g));
 }
 inline uint32_t grid_for(size_t work, int block) {
     size_t g = (work + block - 1) / block;
@@ -1160,7 +1171,7 @@ int f3ds_segment_batch(f3ds_ctx** ctxs, int nctx, const void* const* points, con
     b.owner = ctxs[0]; b.st = ctxs[0]->stream;
     BatchStreamLease lease;
     if (nctx > 1 && ctxs[0]->stream == ctxs[0]->own_stream && !g_sw.no_stream_pool) { hipStream_t ps = lease.acquire(ctxs[0]->device); if (ps) b.st = ps; }
-    g_grid_cap = grid_cap_for_batch(nctx); g_batch_frames = nctx;
+    set_launch_shape(ctxs, nctx);
     std::vector<int> index_of;
     const int max_depth = (int)(1.8f * prm->seed_res / prm->voxel_res);      // [PCL-recall] SupervoxelClustering::extract
     const uint32_t sweeps = max_depth > 1 ? (uint32_t)(max_depth - 1) : 0u;
@@ -1316,7 +1327,7 @@ int f3ds_recluster(f3ds_ctx* c, const f3ds_params* prm, uint32_t* point_labels, 
     const auto t0 = std::chrono::steady_clock::now();
     g_sw.read();
     HIPCHECK(hipSetDevice(c->device));
-    Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); g_grid_cap = grid_cap_for_batch(1); g_batch_frames = 1;
+    Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); set_launch_shape(&c, 1);
     reset_recording(c);
     { const int crc = clear_counters(c, c->stream, &DevCounters::error); if (crc) return crc; }
     stage_mark(b, 4);
@@ -1396,7 +1407,7 @@ int f3ds_cluster_supervoxels(f3ds_ctx* c, const f3ds_supervoxel_set* sv, const u
         if (result) *result = c->res;
         return F3DS_OK;
     }
-    Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); g_grid_cap = grid_cap_for_batch(1); g_batch_frames = 1;
+    Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); set_launch_shape(&c, 1);
     uint32_t *d_src, *d_voff, *d_rgba, *loff, *hcount, *owner, *rcnt0, *ea0, *eb0; float *d_xyz, *d_cent, *d_nrm, *rows, *racc0, *rrec0, *hc; int *row_voxel, *pt_voxel; unsigned char* ralive0;
     ENSURE(c->u_src, S + 1u, d_src); ENSURE(c->u_voff, S + 1u, d_voff); ENSURE(c->u_xyz, (size_t)Vt * 3, d_xyz); ENSURE(c->u_rgba, Vt, d_rgba);
     ENSURE(c->u_cent, (size_t)S * 3, d_cent); ENSURE(c->u_nrm, (size_t)S * 3, d_nrm);
@@ -1591,7 +1602,7 @@ extern "C" int f3ds_refine_supervoxels(f3ds_ctx* c, int num_itr) {
     if (!c->have_frame || c->user_mode) return F3DS_ERR_LOGIC;
     g_sw.read();
     HIPCHECK(hipSetDevice(c->device));
-    Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); g_grid_cap = grid_cap_for_batch(1); g_batch_frames = 1;
+    Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); set_launch_shape(&c, 1);
     reset_recording(c);
     c->refined_itr = -1;
     const uint32_t V = c->V, S0 = c->S0;
@@ -1734,10 +1745,11 @@ extern "C" int f3ds_get_debug(f3ds_ctx* c, int what, void* dst, size_t cap_bytes
     auto put = [&](const void* src, size_t nb) { const uint8_t* b = static_cast<const uint8_t*>(src); buf.insert(buf.end(), b, b + nb); };
     int rc = F3DS_OK;
     std::vector<float> f; std::vector<uint32_t> u, u2, u3; std::vector<int> iv; std::vector<unsigned char> uc;
-    if (what != F3DS_DBG_GRID && !c->have_frame) return F3DS_ERR_LOGIC;
+    if (what != F3DS_DBG_GRID && what != F3DS_DBG_LAUNCH_SHAPE && !c->have_frame) return F3DS_ERR_LOGIC;      // (the launch shape describes the call: an empty frame of a batch has one too)
     switch (what) {
         case F3DS_DBG_GRID: { HIPCHECK(hipMemcpy(c->h_grid, c->d_grid, sizeof(GridInfo), hipMemcpyDeviceToHost)); double g[5] = {c->h_grid->min[0], c->h_grid->min[1], c->h_grid->min[2], c->h_grid->res, (double)c->h_grid->depth}; put(g, sizeof g); break; }
         case F3DS_DBG_TILE_LIST_LEN: if ((rc = fetch(c, c->tile_n1, (size_t)(V + NT_TILE - 1) / NT_TILE, u))) return rc; put(u.data(), u.size() * 4); break;
+        case F3DS_DBG_LAUNCH_SHAPE: put(c->launch_shape, 12); break;
         case F3DS_DBG_STAGE0_PATH: { const uint32_t w = c->vox_hashed ? 1u : 0u; put(&w, 4); break; }
         case F3DS_DBG_SWEEP_STATS: {
             DevCounters dcs;
@@ -1826,7 +1838,7 @@ int eval_truth(f3ds_ctx* c, const uint32_t* truth_point_labels) {
     HIPCHECK(hipMemcpyAsync(lut, f3ds_glasbey_256, 1024, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipMemcpyAsync(tp, truth_point_labels, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipMemsetAsync(tsum, 0, (size_t)V * 12, c->stream));
-    Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); g_grid_cap = grid_cap_for_batch(1); g_batch_frames = 1;
+    Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); set_launch_shape(&c, 1);
     reset_recording(c);
     rec<d_truth_accum>(c, grid_for(n, 256), 0u, n, c->pt_voxel.p, tp, lut, tsum);
     rec<d_truth_color>(c, grid_for(V, 256), 0u, V, tsum, c->vcount.p, tcol);
@@ -1854,7 +1866,7 @@ int eval_scores(f3ds_ctx* c, const uint32_t* d_root, const uint32_t* d_incl, uin
     ENSURE(c->ctab, (size_t)K * M, tab); ENSURE(c->csize, K, ssz);
     HIPCHECK(hipMemsetAsync(tab, 0, (size_t)K * M * 4, c->stream));
     HIPCHECK(hipMemsetAsync(ssz, 0, (size_t)K * 4, c->stream));
-    Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); g_grid_cap = grid_cap_for_batch(1); g_batch_frames = 1;
+    Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); set_launch_shape(&c, 1);
     reset_recording(c);
     rec<d_contingency>(c, grid_for(V, 256), 0u, V, M, c->owner0.p, d_root, d_incl, c->tlab.p, tab, ssz);
     rec<d_contingency_ghost>(c, grid_for(c->S0, 256), 0u, c->S0, M, c->ghost_vox.p, c->ghost_active.p, c->owner0.p, d_root, d_incl, c->tlab.p, tab, ssz);
@@ -1870,6 +1882,7 @@ int eval_scores(f3ds_ctx* c, const uint32_t* d_root, const uint32_t* d_incl, uin
 extern "C" int f3ds_evaluate(f3ds_ctx* c, const uint32_t* truth_point_labels, f3ds_performance* out) {
     if (!c || !truth_point_labels || !out) return F3DS_ERR_ARG;
     if (!c->have_frame || c->user_mode) return F3DS_ERR_LOGIC;
+    g_sw.read();      // (eval_truth / eval_scores size their launches by the switches; f3ds_auto_threshold reads them in f3ds_recluster)
     HIPCHECK(hipSetDevice(c->device));
     HIPCHECK(hipStreamSynchronize(c->stream));
     int rc = eval_truth(c, truth_point_labels);
@@ -1971,7 +1984,7 @@ int run_levels(f3ds_ctx** ctxs, int nctx, const float* thr, int K, uint32_t* con
     g_sw.read();
     f3ds_ctx* o = ctxs[0];
     HIPCHECK(hipSetDevice(o->device));
-    Batch b; b.owner = o; b.st = o->stream; g_grid_cap = grid_cap_for_batch(nctx); g_batch_frames = nctx;
+    Batch b; b.owner = o; b.st = o->stream; set_launch_shape(ctxs, nctx);
     for (int i = 0; i < nctx; ++i) {
         f3ds_ctx* c = ctxs[i];
         if (c->stream != b.st) HIPCHECK(hipStreamSynchronize(c->stream));      // (the frame state is read on the owner's stream)
@@ -2055,7 +2068,7 @@ int run_eval_levels(f3ds_ctx** ctxs, int nctx, const uint32_t* const* truth, int
     f3ds_ctx* o = ctxs[0];
     const uint32_t K = (uint32_t)K_, Kp = (K + 3u) & ~3u;
     HIPCHECK(hipSetDevice(o->device));
-    Batch b; b.owner = o; b.st = o->stream; g_grid_cap = grid_cap_for_batch(nctx); g_batch_frames = nctx;
+    Batch b; b.owner = o; b.st = o->stream; set_launch_shape(ctxs, nctx);
     for (int i = 0; i < nctx; ++i) {
         f3ds_ctx* c = ctxs[i];
         if ((uint64_t)c->V + c->S0 >= (1u << 24)) return F3DS_ERR_UNSUPPORTED;      // (d_evl_score adds sizes as integers: exact in float below 2^24)

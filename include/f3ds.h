@@ -193,6 +193,10 @@ enum {
     F3DS_DBG_STAGE0_PATH = 23,    /* 1 u32: how the last frame was voxelised -- 1 = the tile path (the points stay where they are, only per-tile voxel
                                      descriptors are sorted: frames of a batch), 0 = the sort path (every point's key through a radix sort: lone frames,
                                      unorganised clouds, very dense voxels).  Diagnostics and tests: the two paths give the same bits              */
+    F3DS_DBG_LAUNCH_SHAPE = 24,   /* 3 u32: the launch widths of the last call that ran kernels for this context -- workgroups per frame that a
+                                     streaming kernel gets at most (its share of the batch's budget), that a gathering kernel gets at most (2048), and
+                                     the frames of that call.  Diagnostics and tests: the development switch F3DS_GRID_CAP sets both widths, and
+                                     results do not depend on them                                                                                   */
     F3DS_DBG_MERGE_LAYOUT = 20    /* 2 u32: which merge kernel the last cluster stage ran -- waves per frame (4, 8; 0 = d_merge,
                                      everything in global memory) and where it kept the per-edge arrays (2 = order keys + endpoints in
                                      LDS, 0 = in global memory).  Diagnostics (bench.py names the kernel it timed): results do not depend on it */

@@ -22,6 +22,20 @@ def test_every_declared_symbol_is_exported(P):
     assert lib.f3ds_version_string().decode().startswith("f3ds 1.2.0 src:")
 
 
+def test_debug_selectors_match_the_header(P):
+    """Every F3DS_DBG_* of include/f3ds.h has its own number and is in one of the package's two tables under that number: DBG (arrays of the frame, with a dtype)
+    or DBG_INFO (a few words about the last call); F3DS_DBG_LAUNCH_SHAPE is the newest of the latter."""
+    hdr = open(os.path.join(ROOT, "include", "f3ds.h")).read()
+    ids = {n: int(v) for n, v in re.findall(r"\bF3DS_DBG_([A-Z0-9_]+)\s*=\s*(\d+)", hdr)}
+    assert len(ids) == 25 and sorted(ids.values()) == list(range(25)), sorted(ids.items(), key=lambda kv: kv[1])
+    assert {**P.DBG, **P.DBG_INFO} == ids and not set(P.DBG) & set(P.DBG_INFO)
+    assert set(P.DBG_DTYPE) == set(P.DBG)
+    assert ids["LAUNCH_SHAPE"] == 24 and ids["STAGE0_PATH"] == 23
+    assert callable(P.Context.launch_shape)
+    lib = P.load_library()
+    assert lib.f3ds_get_debug(None, ids["LAUNCH_SHAPE"], None, 0, None) == P.ERR_ARG      # no context: an argument error, no crash
+
+
 def test_merge_kernel_lds_layout(P):
     """The LDS carve-up of d_merge_il_t (host arithmetic shared with the kernel): what fits a compute unit, and how many voxel rows the speculative second merge
     of an epoch gets -- 128 with four waves; 1024, 512, 256 or 128 with eight, whichever the layout has room for (BASELINE config 4's supervoxels of ~190 voxels need > 128)."""

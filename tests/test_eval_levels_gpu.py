@@ -67,28 +67,39 @@ _no_merges = []
 _cases_run = []
 
 
-@pytest.mark.parametrize("name", sorted(GOLDEN_CASES))
-def test_golden_levels_equal_recluster_evaluate_and_the_host_build(P, gpu_ctx, harness, name):
+def check_golden_level_scores(P, gpu_ctx, harness, name, after_call=None):
+    """contract 1 - 3 on a golden case with the synthetic truth and with an all-zero truth; returns (merge weights, region counts of the levels).
+    after_call(ctx): called after the device calls of each truth (tests/test_narrow_launch_gpu.py asserts the launch shape there)."""
     pts, prm = case_points(P, name), case_params(P, name)
     gpu_ctx.segment(pts, prm)
     w = gpu_ctx.merge_tree()[2]
     ts = level_thresholds(w, prm.threshold)
     many = synthetic_truth(pts)
     scores, nreg, notes = _check_levels(P, gpu_ctx, harness, pts, prm, many, ts, name + " synthetic truth")
-    _cases_run.append(name)
+    if after_call:
+        after_call(gpu_ctx)
     if name == "rgbd_160x120":      # every quirk of the matching occurs on a real frame
         assert min(n["unvisited"] for n in notes) >= 1 and min(n["empty_columns"] for n in notes) >= 1, notes
     if name == "fused_200k_nan_lambda":      # one live ghost leaf: a region more than owning supervoxels, one cloud entry more than owned voxels
         assert all(n["cloud"] == n["owned"] + 1 for n in notes), notes
-    if len(w) == 0 or len(set(nreg.tolist())) == 1:
-        _no_merges.append(name)
-        print("NOTE: %s has no merges: all its levels are equal" % name)
-    else:
+    if not (len(w) == 0 or len(set(nreg.tolist())) == 1):
         assert len(set(nreg.tolist())) >= 5, (name, nreg)
         assert len({s.fscore for s in scores}) >= 5, (name, [s.fscore for s in scores])
     zeros = np.zeros(len(pts), np.uint32)
     gpu_ctx.segment(pts, prm)
     _check_levels(P, gpu_ctx, harness, pts, prm, zeros, ts, name + " all-zero truth")
+    if after_call:
+        after_call(gpu_ctx)
+    return w, nreg
+
+
+@pytest.mark.parametrize("name", sorted(GOLDEN_CASES))
+def test_golden_levels_equal_recluster_evaluate_and_the_host_build(P, gpu_ctx, harness, name):
+    w, nreg = check_golden_level_scores(P, gpu_ctx, harness, name)
+    _cases_run.append(name)
+    if len(w) == 0 or len(set(nreg.tolist())) == 1:
+        _no_merges.append(name)
+        print("NOTE: %s has no merges: all its levels are equal" % name)
 
 
 @pytest.mark.parametrize("seed", SEEN_SEEDS)

@@ -957,21 +957,24 @@ def test_relabel_as_two_kernels_matches_too(P, oracle, monkeypatch, cap):
 @pytest.mark.gpu
 def test_development_switches_are_ignored_without_f3ds_dev(P, oracle, monkeypatch):
     """VERDICT r5 item 6 on the device: with F3DS_DEV unset a stray F3DS_MERGE_NW / F3DS_MERGE_KEYS / F3DS_FORCE_GLOBAL_MERGE in the environment does not change
-    which merge kernel a lone frame runs (F3DS_DBG_MERGE_LAYOUT); with the gate open the same variables do."""
+    which merge kernel a lone frame runs (F3DS_DBG_MERGE_LAYOUT), and a stray F3DS_GRID_CAP not how wide its kernels are launched (F3DS_DBG_LAUNCH_SHAPE); with the gate open
+    the same variables do."""
     prm = P.launch_params(voxel_res=0.012, seed_res=0.1)
     pts = P.synth_frame(0, 4100, 200, 150, 30)
     want = oracle.segment(pts, prm)[1]
     ctx = P.Context(0)
     monkeypatch.delenv("F3DS_DEV", raising=False)
-    monkeypatch.setenv("F3DS_MERGE_NW", "4"); monkeypatch.setenv("F3DS_MERGE_KEYS", "global")
+    monkeypatch.setenv("F3DS_MERGE_NW", "4"); monkeypatch.setenv("F3DS_MERGE_KEYS", "global"); monkeypatch.setenv("F3DS_GRID_CAP", "3")
     assert np.array_equal(ctx.segment(pts, prm), want)
     assert ctx.merge_layout() == (8, 2)
+    assert ctx.launch_shape() == (2048, 2048, 1)         # F3DS_GRID_CAP (F3DS_DBG_LAUNCH_SHAPE): the launches keep their width
     monkeypatch.setenv("F3DS_FORCE_GLOBAL_MERGE", "1")
     assert np.array_equal(ctx.segment(pts, prm), want)
     assert ctx.merge_layout() == (8, 2)
     monkeypatch.setenv("F3DS_DEV", "1")
     assert np.array_equal(ctx.segment(pts, prm), want)
     assert ctx.merge_layout() == (0, 0)                  # d_merge
+    assert ctx.launch_shape() == (3, 3, 1)
     monkeypatch.delenv("F3DS_FORCE_GLOBAL_MERGE")
     assert np.array_equal(ctx.segment(pts, prm), want)
     assert ctx.merge_layout() == (4, 0)

@@ -36,8 +36,9 @@ def _levels_and_reclusters(ctx, pts, prm, ts):
 _distinct = {}
 
 
-@pytest.mark.parametrize("name", sorted(GOLDEN_CASES))
-def test_golden_levels_equal_recluster_and_oracle(P, oracle, gpu_ctx, monkeypatch, name):
+def check_golden_levels(P, oracle, gpu_ctx, monkeypatch, name, after_segment=None):
+    """Every level of a golden case equals recluster and the oracle's cluster(t), in every table form; returns the region counts of the levels.
+    after_segment(ctx): called after every device call group (tests/test_narrow_launch_gpu.py asserts the launch shape there)."""
     pts, prm = case_points(P, name), case_params(P, name)
     rc, _, ores, h = oracle.segment(pts, prm)
     assert rc == 0
@@ -47,6 +48,8 @@ def test_golden_levels_equal_recluster_and_oracle(P, oracle, gpu_ctx, monkeypatc
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         got, nreg, want = _levels_and_reclusters(gpu_ctx, pts, prm, ts)
+        if after_segment:
+            after_segment(gpu_ctx)
         assert got.shape == (len(ts), len(pts))
         for l, (lab, nr, _) in enumerate(want):
             assert np.array_equal(got[l], lab), "%s %s: level %d (t = %r) differs from recluster" % (name, env, l, ts[l])
@@ -60,7 +63,13 @@ def test_golden_levels_equal_recluster_and_oracle(P, oracle, gpu_ctx, monkeypatc
             assert got.tobytes() == first[0].tobytes() and np.array_equal(nreg, first[1]), "%s: the table forms disagree (%s)" % (name, env)
         for k in env:
             monkeypatch.delenv(k)
-    _distinct[name] = len(set(first[1].tolist()))
+    return first[1]
+
+
+@pytest.mark.parametrize("name", sorted(GOLDEN_CASES))
+def test_golden_levels_equal_recluster_and_oracle(P, oracle, gpu_ctx, monkeypatch, name):
+    nreg = check_golden_levels(P, oracle, gpu_ctx, monkeypatch, name)
+    _distinct[name] = len(set(nreg.tolist()))
 
 
 def test_most_golden_cases_have_three_region_counts():
