@@ -32,6 +32,8 @@ NO_LABEL = 0xFFFFFFFF
 LAB_CIEDE00, RGB_EUCL = 0, 1
 NORMALS_DIFF, CONVEX_NORMALS_DIFF = 0, 1
 MANUAL_LAMBDA, ADAPTIVE_LAMBDA, EQUALIZATION = 0, 1, 2
+DEPTH_U16, DEPTH_F32 = 0, 1
+COLOR_RGB8, COLOR_RGBA8, COLOR_PACKED = 0, 1, 2
 
 # debug selectors (include/f3ds.h)
 DBG = dict(GRID=0, VOXEL_KEYS=1, VOXEL_COUNT=2, VOXEL_XYZ=3, VOXEL_RGB=4, VOXEL_NORMAL=5, VOXEL_NEIGHBORS=6,
@@ -81,6 +83,19 @@ class Result(ctypes.Structure):
         return d
 
 
+class RgbdFormat(ctypes.Structure):
+    """f3ds_rgbd_format (include/f3ds.h): size, element types and pinhole intrinsics of a depth + colour image pair.  Pitches are bytes per
+    image row, 0 = tightly packed; the wrappers that take numpy images fill them in from the arrays' row strides."""
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("depth_type", ctypes.c_int32), ("depth_scale", ctypes.c_float),
+                ("color_format", ctypes.c_int32), ("depth_pitch", ctypes.c_uint32), ("color_pitch", ctypes.c_uint32),
+                ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float)]
+
+    def copy(self):
+        f = RgbdFormat()
+        ctypes.memmove(ctypes.byref(f), ctypes.byref(self), ctypes.sizeof(RgbdFormat))
+        return f
+
+
 class SupervoxelSet(ctypes.Structure):
     """f3ds_supervoxel_set (include/f3ds.h): the supervoxel_clusters map of the reference as plain arrays."""
     _fields_ = [("n_supervoxels", ctypes.c_uint32), ("label", ctypes.c_void_p), ("voxel_offset", ctypes.c_void_p), ("voxel_xyz", ctypes.c_void_p),
@@ -124,6 +139,16 @@ def load_library(path=None):
     lib.f3ds_segment_batch.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.c_int, ctypes.POINTER(Params),
                                        ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(Result)]
     lib.f3ds_segment_batch.restype = ctypes.c_int
+    if hasattr(lib, "f3ds_segment_rgbd"):      # (RGB-D frames; F3DS_LIB may point at an older build during A/B runs)
+        fp = ctypes.POINTER(RgbdFormat)
+        lib.f3ds_deproject.argtypes = [fp, vp, vp, vp]; lib.f3ds_deproject.restype = ctypes.c_int
+        lib.f3ds_segment_rgbd.argtypes = [vp, fp, vp, vp, ctypes.c_int, ctypes.POINTER(Params), vp, ctypes.c_int, ctypes.POINTER(Result)]
+        lib.f3ds_segment_rgbd.restype = ctypes.c_int
+        lib.f3ds_segment_rgbd_batch.argtypes = [ctypes.POINTER(vp), ctypes.c_int, fp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(Params),
+                                                ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(Result)]
+        lib.f3ds_segment_rgbd_batch.restype = ctypes.c_int
+        lib.f3ds_get_points.argtypes = [vp, vp, sz, ctypes.c_int, ctypes.POINTER(sz)]; lib.f3ds_get_points.restype = ctypes.c_int
+        lib.f3ds_stream_submit_rgbd.argtypes = [vp, fp, vp, vp, ctypes.POINTER(Params), ctypes.c_uint64]; lib.f3ds_stream_submit_rgbd.restype = ctypes.c_int
     lib.f3ds_recluster.argtypes = [vp, ctypes.POINTER(Params), vp, ctypes.c_int, ctypes.POINTER(Result)]
     lib.f3ds_recluster.restype = ctypes.c_int
     lib.f3ds_evaluate.argtypes = [vp, vp, ctypes.POINTER(Performance)]; lib.f3ds_evaluate.restype = ctypes.c_int
@@ -321,6 +346,48 @@ def label_color(label):
     return load_library().f3ds_label_color(label)
 
 
+# ---- RGB-D frames ---------------------------------------------------------------------------------
+_DEPTH_DTYPE = {DEPTH_U16: np.uint16, DEPTH_F32: np.float32}
+
+
+def _rgbd_images(fmt, depth, color):
+    """(format with the pitches of these arrays, depth array, colour array): the images as the library reads them.  Rows may be strided (a
+    view of a wider image): the row stride becomes the pitch; an array whose pixels are not contiguous within a row is copied."""
+    w, h = int(fmt.width), int(fmt.height)
+    if fmt.depth_type not in _DEPTH_DTYPE or fmt.color_format not in (COLOR_RGB8, COLOR_RGBA8, COLOR_PACKED):
+        raise F3dsError(ERR_ARG, "unknown depth type or colour format")
+    d = np.asarray(depth, _DEPTH_DTYPE[fmt.depth_type])
+    if fmt.color_format == COLOR_PACKED:
+        c = np.asarray(color, np.uint32)
+        cshape, cinner = (h, w), (c.itemsize,)
+    else:
+        ch = 3 if fmt.color_format == COLOR_RGB8 else 4
+        c = np.asarray(color, np.uint8)
+        cshape, cinner = (h, w, ch), (ch, 1)
+    if d.shape != (h, w) or c.shape != cshape:
+        raise ValueError("depth must be (height, width) and colour %r, got %r and %r" % (cshape, d.shape, c.shape))
+    if h > 1 and w > 0 and (d.strides[1] != d.itemsize or d.strides[0] < w * d.itemsize):
+        d = np.ascontiguousarray(d)
+    if h > 1 and w > 0 and (tuple(c.strides[1:]) != cinner or c.strides[0] < w * cinner[0]):
+        c = np.ascontiguousarray(c)
+    if h <= 1 or w == 0:
+        d, c = np.ascontiguousarray(d), np.ascontiguousarray(c)
+    f = fmt.copy()
+    f.depth_pitch = 0 if d.flags.c_contiguous else d.strides[0]
+    f.color_pitch = 0 if c.flags.c_contiguous else c.strides[0]
+    return f, d, c
+
+
+def deproject(fmt, depth, color):
+    """f3ds_deproject: the (N, 4) float32 records (x, y, z, rgba bits; N = width * height, pixel (u, v) at row v * width + u) that
+    Context.segment_rgbd builds on the device, bit for bit.  Host arithmetic only."""
+    lib = load_library()
+    f, d, c = _rgbd_images(fmt, depth, color)
+    pts = np.empty((int(fmt.width) * int(fmt.height), 4), np.float32)
+    _check(lib, lib.f3ds_deproject(ctypes.byref(f), d.ctypes.data, c.ctypes.data, pts.ctypes.data))
+    return pts
+
+
 # ---- device context ------------------------------------------------------------------------------
 class Context:
     """One (device, stream) pair with its grow-only scratch.  Not thread-safe; one per GPU/stream."""
@@ -369,6 +436,38 @@ class Context:
                                                ctypes.byref(self.result)))
         self._n = len(pts)
         return labels
+
+    def segment_rgbd(self, depth, color, fmt, params, labels_out=None, on_device=False):
+        """f3ds_segment_rgbd: segment() on the records deproject(fmt, depth, color) gives, built on the device from the two images.
+        depth: (height, width) uint16 / float32, color: (height, width, 3 | 4) uint8 or (height, width) uint32 as ``fmt`` says (rows may be
+        strided), or device pointers (ints, the pitches of ``fmt`` apply) with ``on_device=True``; labels as in segment()."""
+        n = int(fmt.width) * int(fmt.height)
+        if on_device:
+            out_ptr = ctypes.c_void_p(int(labels_out)) if labels_out is not None else None
+            _check(self.lib, self.lib.f3ds_segment_rgbd(self.handle, ctypes.byref(fmt), ctypes.c_void_p(int(depth)), ctypes.c_void_p(int(color)), 1, ctypes.byref(params),
+                                                        out_ptr, 1, ctypes.byref(self.result)))
+            self._n = n
+            return None
+        f, d, c = _rgbd_images(fmt, depth, color)
+        if labels_out is None:
+            labels = np.empty(n, np.uint32)
+        else:
+            labels = labels_out
+            if not (isinstance(labels, np.ndarray) and labels.dtype == np.uint32 and labels.flags.c_contiguous and labels.size == n):
+                raise ValueError("labels_out must be a contiguous uint32 array with one entry per pixel")
+        _check(self.lib, self.lib.f3ds_segment_rgbd(self.handle, ctypes.byref(f), d.ctypes.data, c.ctypes.data, 0, ctypes.byref(params), labels.ctypes.data, 0,
+                                                    ctypes.byref(self.result)))
+        self._n = n
+        return labels
+
+    def points(self):
+        """f3ds_get_points: the (N, 4) float32 records the last segment call ran on, when the context holds them (segment_rgbd, or segment
+        with host points); LogicError when they were the caller's device buffer or nothing has run."""
+        n = ctypes.c_size_t()
+        _check(self.lib, self.lib.f3ds_get_points(self.handle, None, 0, 0, ctypes.byref(n)))
+        pts = np.empty((n.value, 4), np.float32)
+        _check(self.lib, self.lib.f3ds_get_points(self.handle, pts.ctypes.data, n.value, 0, ctypes.byref(n)))
+        return pts
 
     def recluster(self, params):
         labels = np.empty(int(self.result.n_points) or self._n, np.uint32)      # f3ds_recluster writes one label per point of the frame
@@ -627,6 +726,16 @@ class FrameStream:
         _check(self.lib, rc)
         return True
 
+    def submit_rgbd(self, depth, color, fmt, params, tag=0):
+        """Queue an RGB-D frame (host images as Context.segment_rgbd takes them); its width * height labels come out of next() / peek() in
+        submission order, among those of submit()."""
+        f, d, c = _rgbd_images(fmt, depth, color)
+        rc = self.lib.f3ds_stream_submit_rgbd(self.handle, ctypes.byref(f), d.ctypes.data, c.ctypes.data, ctypes.byref(params), tag)
+        if rc == ERR_BUSY:
+            return False
+        _check(self.lib, rc)
+        return True
+
     def next(self, wait=True):
         n = ctypes.c_size_t(); tag = ctypes.c_uint64(); res = Result()
         probe = np.empty(1, np.uint32)
@@ -772,6 +881,36 @@ def segment_batch(ctxs, points, params, labels_out=None, n=None, on_device=False
         for c, a in zip(ctxs, arrs):
             c._n = len(a)
     for c, r in zip(ctxs, results):
+        ctypes.memmove(ctypes.byref(c.result), ctypes.byref(r), ctypes.sizeof(Result))
+    return out
+
+
+def segment_rgbd_batch(ctxs, depths, colors, fmt, params, labels_out=None, on_device=False, raw_host=False):
+    """f3ds_segment_rgbd_batch: Context.segment_rgbd for len(ctxs) frames of ONE format at once (one context per frame, all on one GPU).
+    Host mode: depths / colors = lists of arrays with the same row strides, returns a list of label arrays.  on_device / raw_host: lists of
+    device / host pointers (ints) and ``labels_out`` likewise; the pitches of ``fmt`` apply."""
+    lib = load_library()
+    k = len(ctxs)
+    vp = ctypes.c_void_p
+    handles = (vp * k)(*[c.handle for c in ctxs])
+    results = (Result * k)()
+    n = int(fmt.width) * int(fmt.height)
+    if on_device or raw_host:
+        where = 1 if on_device else 0
+        dp = (vp * k)(*[vp(int(p)) for p in depths]); cp = (vp * k)(*[vp(int(p)) for p in colors]); lp = (vp * k)(*[vp(int(p)) for p in labels_out])
+        _check(lib, lib.f3ds_segment_rgbd_batch(handles, k, ctypes.byref(fmt), dp, cp, where, ctypes.byref(params), lp, where, results))
+        out = None
+    else:
+        imgs = [_rgbd_images(fmt, d, c) for d, c in zip(depths, colors)]
+        f = imgs[0][0]
+        for g, d, c in imgs[1:]:
+            if (g.depth_pitch, g.color_pitch) != (f.depth_pitch, f.color_pitch):
+                raise ValueError("the images of a batch must share their row strides (one f3ds_rgbd_format for the batch)")
+        out = [np.empty(n, np.uint32) for _ in imgs]
+        dp = (vp * k)(*[vp(d.ctypes.data) for _, d, _c in imgs]); cp = (vp * k)(*[vp(c.ctypes.data) for _, _d, c in imgs]); lp = (vp * k)(*[vp(o.ctypes.data) for o in out])
+        _check(lib, lib.f3ds_segment_rgbd_batch(handles, k, ctypes.byref(f), dp, cp, 0, ctypes.byref(params), lp, 0, results))
+    for c, r in zip(ctxs, results):
+        c._n = n
         ctypes.memmove(ctypes.byref(c.result), ctypes.byref(r), ctypes.sizeof(Result))
     return out
 

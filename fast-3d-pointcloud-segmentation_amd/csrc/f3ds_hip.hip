@@ -47,6 +47,7 @@
 #include "f3ds_dev.h"
 #include "f3ds_levels.h"
 #include "f3ds_eval_levels.h"
+#include "f3ds_rgbd.h"
 
 using namespace f3ds;
 
@@ -155,7 +156,7 @@ const int g_merge_shared_res = [] { const char* e = dev_getenv("F3DS_MERGE_SHARE
 // Device scratch of a context: typed, grow-only buffers (ensure(), below).  F3DS_SCRATCH is THE list of them: it declares the members of f3ds_ctx, numbers their slots in
 // the device-wide high-water table, and is what pregrow_scratch() and f3ds_destroy() walk.  A new buffer is one X(element type, name) here and nothing else.
 #define F3DS_SCRATCH(X) \
-    X(P16, pts) X(P16, spts) X(uint64_t, keys0) X(uint64_t, keys1) X(uint32_t, vals0) X(uint32_t, vals1) X(uint32_t, flags) X(uint32_t, incl) X(uint32_t, tiles) X(uint32_t, hist) X(uint32_t, seg_start) X(int, pt_voxel) X(uint32_t, labels) \
+    X(P16, pts) /* rgbd frames: the two images as uploaded */ X(unsigned char, img_depth) X(unsigned char, img_color) X(P16, spts) X(uint64_t, keys0) X(uint64_t, keys1) X(uint32_t, vals0) X(uint32_t, vals1) X(uint32_t, flags) X(uint32_t, incl) X(uint32_t, tiles) X(uint32_t, hist) X(uint32_t, seg_start) X(int, pt_voxel) X(uint32_t, labels) \
     X(uint32_t, vkey) X(uint32_t, vcount) X(float, vf) X(int, nbr) X(int, nbrT) X(uint64_t, hkeys) X(uint32_t, hvals) X(float, boxes) X(uint32_t, ckey) X(uint32_t, cell_start) X(uint64_t, chk) X(uint32_t, chv) X(uint32_t, chvals) X(int, seed_orig) X(uint32_t, keep) X(int, seed_kept) \
     X(uint32_t, owner0) X(uint32_t, ownR) X(float, dist0) X(unsigned char, R) X(float, hc) X(uint32_t, hcount) X(uint32_t, hlo) X(uint32_t, hhi) X(int, ghost_vox) X(unsigned char, ghost_active) X(unsigned char, ghost_done) X(uint32_t, ghost_head) X(uint32_t, ghost_next) \
     X(uint32_t, loff) X(float, rows) X(int, row_voxel) X(float, racc0) X(uint32_t, rcnt0) X(float, rrec0) X(unsigned char, ralive0) X(uint64_t, ehk) X(uint64_t, ekeys0) X(uint64_t, ekeys1) X(uint32_t, evals0) X(uint32_t, evals1) X(uint32_t, ea0) X(uint32_t, eb0) \
@@ -1157,11 +1158,14 @@ int f3ds_segment(f3ds_ctx* c, const void* points, size_t n_, int points_on_devic
 // lockstep on the first context's stream: per stage every frame records its kernel calls, flush()
 // turns them into batched dispatches (grid.y = frame), and the few host decisions (octree depth,
 // voxel / seed / edge counts) are taken for all frames at one synchronisation point per stage.
-int f3ds_segment_batch(f3ds_ctx** ctxs, int nctx, const void* const* points, const size_t* counts, int points_on_device, const f3ds_params* prm,
-                       uint32_t* const* point_labels, int labels_on_device, f3ds_result* results) {
-    if (!ctxs || nctx <= 0 || !points || !counts || !prm) return F3DS_ERR_ARG;
-    if (!(prm->voxel_res > 0) || !(prm->seed_res > 0)) return F3DS_ERR_ARG;
-    for (int i = 0; i < nctx; ++i) if (!ctxs[i] || (!points[i] && counts[i]) || counts[i] > 0x7fffffffull || ctxs[i]->device != ctxs[0]->device) return F3DS_ERR_ARG;
+}  // extern "C"
+namespace {
+// `source(c, i, copy, uploaded)` is where frame i's points come from: it sets c->n and c->d_pts, queues what it uploads on `copy` (the device's copy stream, or the
+// call's own) and says so in `uploaded`, and may record kernels that build the records (they run first: stage 0 is recorded after them).  `sources_on_device`: nothing is uploaded.
+template <class Source>
+int segment_batch_from(f3ds_ctx** ctxs, int nctx, Source&& source, int sources_on_device, const f3ds_params* prm, uint32_t* const* point_labels, int labels_on_device,
+                              f3ds_result* results) {
+    const int points_on_device = sources_on_device;
     const auto t0 = std::chrono::steady_clock::now();
     g_t_wait = 0; g_t_launch = 0;
     g_sw.read();
@@ -1184,16 +1188,11 @@ int f3ds_segment_batch(f3ds_ctx** ctxs, int nctx, const void* const* points, con
         c->have_frame = false; c->live = true; c->rc = 0; c->refined_itr = -1;
         c->user_mode = false; c->user_label.clear(); c->user_row.clear();
         { const int prc = pregrow_scratch(c); if (prc) return prc; }
-        c->prm = *prm; c->n = (uint32_t)counts[i]; c->V = c->C = c->S0 = c->E = 0;
+        c->prm = *prm; c->V = c->C = c->S0 = c->E = 0;
+        c->fa = FrameArgs{prm->use_transform, prm->fold_negative_z, prm->leaf_order, prm->voxel_res, prm->seed_res, prm->w_color, prm->w_spatial, prm->w_normal};
+        { const int src_rc = source(c, i, up_stream ? up_stream : b.st, uploaded); if (src_rc) return src_rc; }
         memset(&c->res, 0, sizeof c->res);
         c->res.n_points = c->n; c->res.sweeps = sweeps;
-        c->fa = FrameArgs{prm->use_transform, prm->fold_negative_z, prm->leaf_order, prm->voxel_res, prm->seed_res, prm->w_color, prm->w_spatial, prm->w_normal};
-        if (points_on_device) c->d_pts = static_cast<const P16*>(points[i]);
-        else {
-            P16* up; ENSURE(c->pts, c->n ? c->n : 1, up);
-            if (c->n) { HIPCHECK(hipMemcpyAsync(up, points[i], (size_t)c->n * 16, hipMemcpyHostToDevice, up_stream ? up_stream : b.st)); uploaded = true; }
-            c->d_pts = up;
-        }
         b.fr.push_back(c); index_of.push_back(i);
     }
     if (up_stream && uploaded) {      // the call's kernels wait for its uploads, which went through the device's copy stream
@@ -1318,6 +1317,72 @@ int f3ds_segment_batch(f3ds_ctx** ctxs, int nctx, const void* const* points, con
         c->res.ms_total = ms;
         if (results) results[i] = c->res;
     }
+    return F3DS_OK;
+}
+
+}  // namespace
+extern "C" {
+
+int f3ds_segment_batch(f3ds_ctx** ctxs, int nctx, const void* const* points, const size_t* counts, int points_on_device, const f3ds_params* prm,
+                       uint32_t* const* point_labels, int labels_on_device, f3ds_result* results) {
+    if (!ctxs || nctx <= 0 || !points || !counts || !prm) return F3DS_ERR_ARG;
+    if (!(prm->voxel_res > 0) || !(prm->seed_res > 0)) return F3DS_ERR_ARG;
+    for (int i = 0; i < nctx; ++i) if (!ctxs[i] || (!points[i] && counts[i]) || counts[i] > 0x7fffffffull || ctxs[i]->device != ctxs[0]->device) return F3DS_ERR_ARG;
+    auto source = [&](f3ds_ctx* c, int i, hipStream_t copy, bool& uploaded) -> int {
+        c->n = (uint32_t)counts[i];
+        if (points_on_device) c->d_pts = static_cast<const P16*>(points[i]);
+        else {
+            P16* up; ENSURE(c->pts, c->n ? c->n : 1, up);
+            if (c->n) { HIPCHECK(hipMemcpyAsync(up, points[i], (size_t)c->n * 16, hipMemcpyHostToDevice, copy)); uploaded = true; }
+            c->d_pts = up;
+        }
+        return F3DS_OK;
+    };
+    return segment_batch_from(ctxs, nctx, source, points_on_device, prm, point_labels, labels_on_device, results);
+}
+
+// RGB-D frames: the images are uploaded (5 to 8 bytes per pixel where the records take 16) or read where they are, and one d_deproject per frame writes the records into
+// c->pts, in the same dispatch sequence as the bounding box that reads them.  From there on the call is f3ds_segment_batch on host points.
+int f3ds_segment_rgbd_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format* fmt, const void* const* depth, const void* const* color, int images_on_device,
+                            const f3ds_params* prm, uint32_t* const* point_labels, int labels_on_device, f3ds_result* results) {
+    if (!ctxs || nctx <= 0 || !fmt || !depth || !color || !prm) return F3DS_ERR_ARG;
+    if (!(prm->voxel_res > 0) || !(prm->seed_res > 0)) return F3DS_ERR_ARG;
+    f3ds::RgbdLayout lay;
+    if (const int rc = f3ds::rgbd_layout(fmt, &lay)) return rc;
+    for (int i = 0; i < nctx; ++i) if (!ctxs[i] || !depth[i] || !color[i] || ctxs[i]->device != ctxs[0]->device) return F3DS_ERR_ARG;
+    const RgbdArgs args{fmt->width, (uint32_t)lay.n, lay.depth_pitch, lay.color_pitch, fmt->depth_type == F3DS_DEPTH_F32 ? 1 : 0, fmt->color_format, fmt->depth_scale, fmt->fx, fmt->fy, fmt->cx, fmt->cy};
+    auto source = [&](f3ds_ctx* c, int i, hipStream_t copy, bool& uploaded) -> int {
+        c->n = (uint32_t)lay.n;
+        P16* records; ENSURE(c->pts, c->n, records);
+        const unsigned char* d_depth = static_cast<const unsigned char*>(depth[i]);
+        const unsigned char* d_color = static_cast<const unsigned char*>(color[i]);
+        if (!images_on_device) {
+            unsigned char *ud, *uc; ENSURE(c->img_depth, lay.depth_bytes, ud); ENSURE(c->img_color, lay.color_bytes, uc);
+            HIPCHECK(hipMemcpyAsync(ud, depth[i], lay.depth_bytes, hipMemcpyHostToDevice, copy));
+            HIPCHECK(hipMemcpyAsync(uc, color[i], lay.color_bytes, hipMemcpyHostToDevice, copy));
+            uploaded = true; d_depth = ud; d_color = uc;
+        }
+        rec<d_deproject>(c, grid_for(c->n, 256), 0u, d_depth, d_color, args, records);
+        c->d_pts = records;
+        return F3DS_OK;
+    };
+    return segment_batch_from(ctxs, nctx, source, images_on_device, prm, point_labels, labels_on_device, results);
+}
+int f3ds_segment_rgbd(f3ds_ctx* c, const f3ds_rgbd_format* fmt, const void* depth, const void* color, int images_on_device, const f3ds_params* prm, uint32_t* point_labels,
+                      int labels_on_device, f3ds_result* result) {
+    const void* dp[1] = {depth}; const void* cp[1] = {color}; uint32_t* lp[1] = {point_labels};
+    return f3ds_segment_rgbd_batch(&c, 1, fmt, dp, cp, images_on_device, prm, lp, labels_on_device, result);
+}
+
+// the records of the last segment call when they sit in the context's own buffer (uploaded host points, or built by d_deproject)
+int f3ds_get_points(f3ds_ctx* c, void* points16, size_t cap, int dst_on_device, size_t* n_out) {
+    if (!c || (!points16 && !n_out)) return F3DS_ERR_ARG;
+    if (!c->d_pts || c->d_pts != c->pts.p) return F3DS_ERR_LOGIC;
+    if (n_out) *n_out = c->n;
+    if (!points16) return F3DS_OK;
+    if (cap < c->n) return F3DS_ERR_CAPACITY;
+    HIPCHECK(hipSetDevice(c->device));
+    if (c->n) HIPCHECK(hipMemcpy(points16, c->pts.p, (size_t)c->n * 16, dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
     return F3DS_OK;
 }
 

@@ -15,6 +15,8 @@
 #include "f3ds_build_stamp.h"
 #include "f3ds_math.h"
 #include "f3ds_dev.h"
+#include "f3ds_numerics.h"
+#include "f3ds_rgbd.h"
 
 extern "C" {
 
@@ -73,6 +75,36 @@ const char* f3ds_strerror(int code) {
 }
 
 uint32_t f3ds_label_color(uint32_t label) { return f3ds_glasbey_256[label % 256u]; }
+
+// The records of an RGB-D frame on the host: the arithmetic of d_deproject (csrc/f3ds_kernels.inc), which calls the same functions of f3ds_numerics.h.
+// Pixels are read with memcpy: an image row may start anywhere its pitch puts it.
+int f3ds_deproject(const f3ds_rgbd_format* fmt, const void* depth, const void* color, void* points16) {
+    f3ds::RgbdLayout l;
+    if (!fmt || !depth || !color || !points16) return F3DS_ERR_ARG;
+    if (const int rc = f3ds::rgbd_layout(fmt, &l)) return rc;
+    const unsigned char* dimg = static_cast<const unsigned char*>(depth);
+    const unsigned char* cimg = static_cast<const unsigned char*>(color);
+    unsigned char* out = static_cast<unsigned char*>(points16);
+    for (uint32_t v = 0; v < fmt->height; ++v) {
+        const unsigned char* drow = dimg + (size_t)v * l.depth_pitch;
+        const unsigned char* crow = cimg + (size_t)v * l.color_pitch;
+        for (uint32_t u = 0; u < fmt->width; ++u) {
+            float z = 0.0f; bool valid;
+            if (fmt->depth_type == F3DS_DEPTH_F32) { float d; memcpy(&d, drow + 4u * (size_t)u, 4); valid = f3ds::n_depth_to_z(d, fmt->depth_scale, z); }
+            else { uint16_t d; memcpy(&d, drow + 2u * (size_t)u, 2); valid = f3ds::n_depth_to_z(d, fmt->depth_scale, z); }
+            const unsigned char* p = crow + (size_t)l.color_elem * u;
+            uint32_t rgba;
+            if (fmt->color_format == F3DS_COLOR_RGB8) rgba = f3ds::n_color_word(p[0], p[1], p[2], 255u);
+            else if (fmt->color_format == F3DS_COLOR_RGBA8) rgba = f3ds::n_color_word(p[0], p[1], p[2], p[3]);
+            else memcpy(&rgba, p, 4);
+            float rec[3];
+            f3ds::n_deproject(u, v, valid, z, fmt->fx, fmt->fy, fmt->cx, fmt->cy, rec[0], rec[1], rec[2]);
+            unsigned char* o = out + 16u * ((size_t)v * fmt->width + u);
+            memcpy(o, rec, 12); memcpy(o + 12, &rgba, 4);
+        }
+    }
+    return F3DS_OK;
+}
 
 }  // extern "C"
 

@@ -393,6 +393,59 @@ __device__ inline int bt_find(const BtEntry* tab, uint32_t tmask, int leaf_order
         h = (h + 1u) & tmask;
     }
 }
+// RGB-D frames (f3ds_segment_rgbd): the XYZRGBA records of a depth image + a colour image, pixel (u, v) -> record v * width + u.  One pixel per lane and trip,
+// consecutive lanes on consecutive pixels: a wave reads 128 or 256 contiguous bytes of depth and 192 or 256 of colour (less where a row ends inside it) and writes
+// 1 KiB of records, one 16-byte store per lane.  Rows are addressed through their pitches and nothing but byte alignment is assumed of a colour row (the loads are
+// unaligned ones: RGB8 rows, and rows of any format behind an odd pitch); depth elements are aligned to their size.  The two formats are template parameters so that the
+// loop holds no branch between its loads: both are in flight before the first is waited for.  The arithmetic is n_depth_to_z / n_deproject (f3ds_numerics.h), which
+// f3ds_deproject runs on the host.
+struct RgbdArgs {
+    uint32_t width, n;                 // n = width * height
+    uint32_t depth_pitch, color_pitch; // bytes per row (never 0 here: the host resolves "tightly packed")
+    int depth_f32, color_format;       // depth elements are f32 (else u16); F3DS_COLOR_*
+    float depth_scale, fx, fy, cx, cy;
+};
+template <class T> __device__ inline T load_unaligned(const unsigned char* p) { T t; __builtin_memcpy(&t, p, sizeof(T)); return t; }
+template <bool DEPTH_F32, int COLOR>
+__device__ inline void deproject_loop(const unsigned char* depth, const unsigned char* color, const RgbdArgs& a, P16* out) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const uint32_t sv = stride / a.width, su = stride - sv * a.width;      // a trip moves every lane this many rows and columns on
+    uint32_t i = BIX * blockDim.x + threadIdx.x;
+    uint32_t v = i / a.width, u = i - v * a.width;
+    for (; i < a.n; i += stride) {
+        const unsigned char* drow = depth + (size_t)v * a.depth_pitch;
+        const unsigned char* crow = color + (size_t)v * a.color_pitch;
+        float z = 0.0f;
+        bool valid;
+        if constexpr (DEPTH_F32) valid = n_depth_to_z(reinterpret_cast<const float*>(drow)[u], a.depth_scale, z);
+        else valid = n_depth_to_z(reinterpret_cast<const uint16_t*>(drow)[u], a.depth_scale, z);
+        uint32_t rgba;
+        if constexpr (COLOR == 0) { const unsigned char* p = crow + 3u * (size_t)u; rgba = n_color_word(p[0], p[1], p[2], 255u); }
+        else {
+            const uint32_t w = load_unaligned<uint32_t>(crow + 4u * (size_t)u);      // bytes r, g, b, a in memory = a << 24 | b << 16 | g << 8 | r as a little-endian word
+            rgba = COLOR == 1 ? n_color_word(w & 255u, (w >> 8) & 255u, (w >> 16) & 255u, w >> 24) : w;
+        }
+        float x, y, zo;
+        n_deproject(u, v, valid, z, a.fx, a.fy, a.cx, a.cy, x, y, zo);
+        reinterpret_cast<uint4*>(out)[i] = make_uint4(__float_as_uint(x), __float_as_uint(y), __float_as_uint(zo), rgba);      // one global_store_dwordx4
+        u += su; v += sv;
+        if (u >= a.width) { u -= a.width; ++v; }
+    }
+}
+struct d_deproject {
+    static constexpr int BLOCK = 256;
+    __device__ void operator()(const unsigned char* depth, const unsigned char* color, RgbdArgs a, P16* out) const {
+        if (a.depth_f32) {
+            if (a.color_format == 0) deproject_loop<true, 0>(depth, color, a, out);
+            else if (a.color_format == 1) deproject_loop<true, 1>(depth, color, a, out);
+            else deproject_loop<true, 2>(depth, color, a, out);
+        } else {
+            if (a.color_format == 0) deproject_loop<false, 0>(depth, color, a, out);
+            else if (a.color_format == 1) deproject_loop<false, 1>(depth, color, a, out);
+            else deproject_loop<false, 2>(depth, color, a, out);
+        }
+    }
+};
 // bounding box of the transformed finite points + count of finite input points
 struct d_bbox {
     static constexpr int BLOCK = 256;

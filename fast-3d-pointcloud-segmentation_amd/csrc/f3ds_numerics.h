@@ -42,6 +42,33 @@ F3DS_HD void n_transform(float& x, float& y, float& z, int use_transform) {
     if (use_transform) { x = x / z; y = y / z; z = m_logf(z); }
 }
 
+// -------------------------------------------------------------------------------------------
+// RGB-D deprojection (include/f3ds.h, f3ds_rgbd_format): a depth image, a colour image and pinhole
+// intrinsics become the XYZRGBA records of the path.  Every operation is one rounded f32 operation,
+// in this order, on the host (f3ds_deproject) and on the device (d_deproject) alike.
+// -------------------------------------------------------------------------------------------
+// u16 depth: 0 is "no measurement"; otherwise metres = (float)d * depth_scale
+F3DS_HD bool n_depth_to_z(uint16_t d, float depth_scale, float& z) {
+    if (d == 0) return false;
+    z = (float)d * depth_scale;
+    return true;
+}
+// f32 depth: NaN, zero, negatives and infinities are "no measurement"
+F3DS_HD bool n_depth_to_z(float d, float depth_scale, float& z) {
+    if (!(d > 0.0f) || !m_isfinitef(d)) return false;
+    z = d * depth_scale;
+    return true;
+}
+// pixel (u, v) at depth z; an invalid pixel is a quiet NaN in x, y and z (a non-finite point belongs to no voxel)
+F3DS_HD void n_deproject(uint32_t u, uint32_t v, bool valid, float z, float fx, float fy, float cx, float cy, float& x, float& y, float& zo) {
+    if (!valid) { x = y = zo = n_nanf(); return; }
+    x = (((float)u - cx) * z) / fx;
+    y = (((float)v - cy) * z) / fy;
+    zo = z;
+}
+// colour word a<<24 | r<<16 | g<<8 | b from the bytes of a pixel in memory order r, g, b (, a)
+F3DS_HD uint32_t n_color_word(uint32_t r, uint32_t g, uint32_t b, uint32_t a) { return (a << 24) | (r << 16) | (g << 8) | b; }
+
 // cube side is a power of two voxels, centred on the data
 F3DS_HD void n_key_bit_size(GridInfo& g) {
     const double eps = (double)F3DS_FLT_EPS;

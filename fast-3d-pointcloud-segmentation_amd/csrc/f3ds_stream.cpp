@@ -1,5 +1,6 @@
 // Frame pipeline over the public entry points (include/f3ds.h, "frame pipeline"): a ring of slots, each with a
-// context and pinned staging, and a few host threads that turn whatever is queued into f3ds_segment_batch calls.
+// context and pinned staging, and a few host threads that turn whatever is queued into f3ds_segment_batch calls
+// (f3ds_segment_rgbd_batch for frames that came in as depth + colour images).
 // Row N4 of SURVEY.md section 8: the reference itself processes one frame per main() iteration
 // (src/supervoxel_clustering.cpp:303-469) and points at a ROS node for streams (README.md:72).
 #include <hip/hip_runtime_api.h>
@@ -14,6 +15,7 @@
 
 #include "../../include/f3ds.h"
 #include "f3ds_dev.h"
+#include "f3ds_rgbd.h"
 
 namespace {
 enum { FREE = 0, QUEUED, RUNNING, DONE };
@@ -21,6 +23,9 @@ struct Slot {
     f3ds_ctx* ctx = nullptr;
     void* h_pts = nullptr; size_t pts_cap = 0;          // pinned, grow-only
     uint32_t* h_lab = nullptr; size_t lab_cap = 0;
+    void* h_depth = nullptr; size_t depth_cap = 0;      // rgbd frames: the two images, rows packed tightly
+    void* h_color = nullptr; size_t color_cap = 0;
+    bool rgbd = false; f3ds_rgbd_format fmt = {};           // (fmt: pitches 0, as staged)
     size_t n = 0; f3ds_params prm; uint64_t tag = 0; f3ds_result res; int rc = 0; int state = FREE;
 };
 }  // namespace
@@ -50,7 +55,7 @@ int pinned_grow(void** p, size_t* cap, size_t bytes) {
 
 void worker(f3ds_stream* s) {
     (void)hipSetDevice(s->device);
-    std::vector<f3ds_ctx*> ctxs; std::vector<const void*> pts; std::vector<size_t> cnt; std::vector<uint32_t*> lab; std::vector<f3ds_result> res;
+    std::vector<f3ds_ctx*> ctxs; std::vector<const void*> pts, col; std::vector<size_t> cnt; std::vector<uint32_t*> lab; std::vector<f3ds_result> res;
     std::unique_lock<std::mutex> lk(s->m);
     for (;;) {
         s->cv_work.wait(lk, [&] { return s->stop || s->started < s->submitted; });
@@ -67,25 +72,29 @@ void worker(f3ds_stream* s) {
         }
         if (s->stop) return;
         if (!take) continue;
-        // the run of queued frames from the oldest one on, as long as their parameters agree
+        // the run of queued frames from the oldest one on, as long as they are of one kind (points / rgbd images of one format) and their parameters agree
         const uint64_t first = s->started;
         const f3ds_params prm = s->slots[first % s->depth].prm;
+        const bool rgbd = s->slots[first % s->depth].rgbd;
+        const f3ds_rgbd_format fmt = s->slots[first % s->depth].fmt;
+        auto joins = [&](const Slot& sl) { return sl.rgbd == rgbd && !memcmp(&sl.prm, &prm, sizeof prm) && (!rgbd || !memcmp(&sl.fmt, &fmt, sizeof fmt)); };
         uint64_t end = first;
-        while (end < s->submitted && end - first < (uint64_t)s->max_batch && !memcmp(&s->slots[end % s->depth].prm, &prm, sizeof prm)) ++end;
-        ctxs.clear(); pts.clear(); cnt.clear(); lab.clear();
+        while (end < s->submitted && end - first < (uint64_t)s->max_batch && joins(s->slots[end % s->depth])) ++end;
+        ctxs.clear(); pts.clear(); col.clear(); cnt.clear(); lab.clear();
         for (uint64_t f = first; f < end; ++f) {
             Slot& sl = s->slots[f % s->depth];
             sl.state = RUNNING;
-            ctxs.push_back(sl.ctx); pts.push_back(sl.h_pts); cnt.push_back(sl.n); lab.push_back(sl.h_lab);
+            ctxs.push_back(sl.ctx); pts.push_back(rgbd ? sl.h_depth : sl.h_pts); col.push_back(sl.h_color); cnt.push_back(sl.n); lab.push_back(sl.h_lab);
         }
         s->started = end;
         ++s->running;
         lk.unlock();
         res.assign(ctxs.size(), f3ds_result{});
-        int rc = f3ds_segment_batch(ctxs.data(), (int)ctxs.size(), pts.data(), cnt.data(), 0, &prm, lab.data(), 0, res.data());
+        int rc = rgbd ? f3ds_segment_rgbd_batch(ctxs.data(), (int)ctxs.size(), &fmt, pts.data(), col.data(), 0, &prm, lab.data(), 0, res.data())
+                      : f3ds_segment_batch(ctxs.data(), (int)ctxs.size(), pts.data(), cnt.data(), 0, &prm, lab.data(), 0, res.data());
         if (rc != F3DS_OK && ctxs.size() > 1) {          // which frame was it?  one by one, so that the others still get their labels
             for (size_t i = 0; i < ctxs.size(); ++i) {
-                int r1 = f3ds_segment(ctxs[i], pts[i], cnt[i], 0, &prm, lab[i], 0, &res[i]);
+                int r1 = rgbd ? f3ds_segment_rgbd(ctxs[i], &fmt, pts[i], col[i], 0, &prm, lab[i], 0, &res[i]) : f3ds_segment(ctxs[i], pts[i], cnt[i], 0, &prm, lab[i], 0, &res[i]);
                 Slot& sl = s->slots[(first + i) % s->depth];
                 sl.rc = r1;
             }
@@ -132,6 +141,8 @@ void f3ds_stream_destroy(f3ds_stream* s) {
         if (sl.ctx) f3ds_destroy(sl.ctx);
         if (sl.h_pts) (void)hipHostFree(sl.h_pts);
         if (sl.h_lab) (void)hipHostFree(sl.h_lab);
+        if (sl.h_depth) (void)hipHostFree(sl.h_depth);
+        if (sl.h_color) (void)hipHostFree(sl.h_color);
     }
 
     delete s;
@@ -158,7 +169,31 @@ int f3ds_stream_submit(f3ds_stream* s, const void* points, size_t n, const f3ds_
     Slot& sl = s->slots[s->submitted % s->depth];          // only this (producer) thread advances `submitted`
     if ((rc = pinned_grow((void**)&sl.h_lab, &sl.lab_cap, (n ? n : 1) * 4))) return rc;
     if (n && points != buf) memcpy(buf, points, n * 16);
-    sl.n = n; sl.prm = *params; sl.tag = tag; sl.rc = 0;
+    sl.n = n; sl.prm = *params; sl.tag = tag; sl.rc = 0; sl.rgbd = false;
+    { std::lock_guard<std::mutex> lk(s->m); sl.state = QUEUED; ++s->submitted; }
+    s->cv_work.notify_one();
+    return F3DS_OK;
+}
+
+int f3ds_stream_submit_rgbd(f3ds_stream* s, const f3ds_rgbd_format* fmt, const void* depth, const void* color, const f3ds_params* params, uint64_t tag) {
+    if (!s || !fmt || !depth || !color || !params) return F3DS_ERR_ARG;
+    if (!(params->voxel_res > 0) || !(params->seed_res > 0)) return F3DS_ERR_ARG;
+    f3ds::RgbdLayout l;
+    int rc = f3ds::rgbd_layout(fmt, &l);
+    if (rc) return rc;
+    Slot* slp;
+    { std::lock_guard<std::mutex> lk(s->m); if (s->submitted - s->taken >= (uint64_t)s->depth) return F3DS_ERR_BUSY; slp = &s->slots[s->submitted % s->depth]; }
+    Slot& sl = *slp;                                       // the slot is FREE: no worker looks at it; only this (producer) thread advances `submitted`
+    (void)hipSetDevice(s->device);
+    const size_t drow = (size_t)fmt->width * l.depth_elem, crow = (size_t)fmt->width * l.color_elem;
+    if ((rc = pinned_grow(&sl.h_depth, &sl.depth_cap, drow * fmt->height)) || (rc = pinned_grow(&sl.h_color, &sl.color_cap, crow * fmt->height)) ||
+        (rc = pinned_grow((void**)&sl.h_lab, &sl.lab_cap, l.n * 4))) return rc;
+    for (uint32_t v = 0; v < fmt->height; ++v) {           // rows leave their pitch behind
+        memcpy(static_cast<unsigned char*>(sl.h_depth) + v * drow, static_cast<const unsigned char*>(depth) + (size_t)v * l.depth_pitch, drow);
+        memcpy(static_cast<unsigned char*>(sl.h_color) + v * crow, static_cast<const unsigned char*>(color) + (size_t)v * l.color_pitch, crow);
+    }
+    sl.fmt = *fmt; sl.fmt.depth_pitch = 0; sl.fmt.color_pitch = 0;
+    sl.n = l.n; sl.prm = *params; sl.tag = tag; sl.rc = 0; sl.rgbd = true;
     { std::lock_guard<std::mutex> lk(s->m); sl.state = QUEUED; ++s->submitted; }
     s->cv_work.notify_one();
     return F3DS_OK;

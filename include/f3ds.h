@@ -149,6 +149,47 @@ int f3ds_segment_batch(f3ds_ctx** ctxs, int nctx, const void* const* points, con
                        int points_on_device, const f3ds_params* params, uint32_t* const* point_labels,
                        int labels_on_device, f3ds_result* results);
 
+/* ---- RGB-D frames: a depth image, a colour image and pinhole intrinsics in, the records built on the device ----
+ * Pixel (u, v) becomes point v * width + u.  u16 depth d: invalid iff d == 0, else z = (float)d * depth_scale; f32 depth d:
+ * invalid iff !(d > 0) or d is infinite (NaN, zero and negatives included), else z = d * depth_scale.  A valid pixel gets
+ * x = (((float)u - cx) * z) / fx, y = (((float)v - cy) * z) / fy and z as is, every operation one rounded f32 operation; an
+ * invalid one gets quiet NaN in x, y and z (such a point belongs to no voxel and is labelled F3DS_NO_LABEL).  The colour word
+ * is a<<24 | r<<16 | g<<8 | b: F3DS_COLOR_RGB8 = 3 bytes r, g, b per pixel, alpha 255; F3DS_COLOR_RGBA8 = 4 bytes r, g, b, a;
+ * F3DS_COLOR_PACKED = a u32 per pixel that is the word itself.  Rows are addressed through the pitches; nothing but the
+ * element's own alignment is assumed of them (RGB8 rows with an odd pitch are fine). */
+enum { F3DS_DEPTH_U16 = 0, F3DS_DEPTH_F32 = 1 };
+enum { F3DS_COLOR_RGB8 = 0, F3DS_COLOR_RGBA8 = 1, F3DS_COLOR_PACKED = 2 };
+typedef struct f3ds_rgbd_format {
+    uint32_t width, height;
+    int32_t depth_type;           /* F3DS_DEPTH_*                                            */
+    float depth_scale;            /* metres per depth unit, e.g. 0.001f                      */
+    int32_t color_format;         /* F3DS_COLOR_*                                            */
+    uint32_t depth_pitch, color_pitch;   /* bytes per image row; 0 = tightly packed          */
+    float fx, fy, cx, cy;
+} f3ds_rgbd_format;
+
+/* host arithmetic only, no device needed: the width * height records the device path builds, bit for bit.  F3DS_ERR_ARG for a NULL
+ * pointer, width or height 0, width * height > 0x7fffffff, an unknown enum value, fx / fy / depth_scale not finite, fx or fy
+ * equal to 0, depth_scale <= 0, cx or cy not finite, a non-zero pitch smaller than a row, or a depth pitch that is no multiple
+ * of the depth element's size (the rgbd entry points below refuse the same). */
+int f3ds_deproject(const f3ds_rgbd_format* fmt, const void* depth, const void* color, void* points16);
+
+/* f3ds_segment / f3ds_segment_batch on the records of f3ds_deproject, which are built on the device (d_deproject): the same
+ * labels, f3ds_result counts and F3DS_DBG_* arrays, and afterwards the context answers every call it answers after
+ * f3ds_segment (truth labels are one per pixel).  Host images go through the device's copy stream like host points, at 5 to 8
+ * bytes per pixel where the records take 16; images_on_device: they are read where they are.  One format for the whole batch.
+ * A frame whose pixels are all invalid returns F3DS_OK with all labels F3DS_NO_LABEL. */
+int f3ds_segment_rgbd(f3ds_ctx* ctx, const f3ds_rgbd_format* fmt, const void* depth, const void* color, int images_on_device,
+                      const f3ds_params* params, uint32_t* point_labels, int labels_on_device, f3ds_result* result);
+int f3ds_segment_rgbd_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format* fmt, const void* const* depth, const void* const* color,
+                            int images_on_device, const f3ds_params* params, uint32_t* const* point_labels, int labels_on_device,
+                            f3ds_result* results);
+
+/* the XYZRGBA records the context's last segment call ran on, when the context owns them (an rgbd call, or a call with host
+ * points); F3DS_ERR_LOGIC when they were the caller's device buffer or nothing has run.  points16 == NULL: count only.
+ * F3DS_ERR_CAPACITY when cap (in records) is smaller than the count. */
+int f3ds_get_points(f3ds_ctx* ctx, void* points16, size_t cap, int dst_on_device, size_t* n_out);
+
 /* Clustering::cluster(threshold) again on the supervoxels of the last f3ds_segment call, with
  * possibly different metric / merging settings (src/clustering.cpp:670-679).  Only the merge
  * fields of `params` are read. */
@@ -381,6 +422,12 @@ int f3ds_stream_buffer(f3ds_stream* s, size_t n, void** points16);
 /* queue a frame (host memory; copied unless it is the pointer f3ds_stream_buffer gave).  Never blocks:
  * F3DS_ERR_BUSY when depth frames are in flight -- take one with f3ds_stream_next first. */
 int f3ds_stream_submit(f3ds_stream* s, const void* points, size_t n, const f3ds_params* params, uint64_t tag);
+/* queue an RGB-D frame (host images, f3ds_rgbd_format above; both are copied into the slot's pinned staging, rows packed tightly).
+ * Its width * height labels come out through f3ds_stream_next / f3ds_stream_peek like those of any frame, and point and rgbd
+ * submissions may be mixed on one stream: consecutive frames share a batch call when they are of one kind and have equal
+ * formats and parameters.  Results are those of f3ds_segment_rgbd.  Never blocks (F3DS_ERR_BUSY as above). */
+int f3ds_stream_submit_rgbd(f3ds_stream* s, const f3ds_rgbd_format* fmt, const void* depth, const void* color,
+                            const f3ds_params* params, uint64_t tag);
 /* oldest frame not taken yet: its labels (n_out of them) into point_labels, its tag and result.  wait != 0 blocks
  * until it is done, else F3DS_ERR_BUSY while it is running; F3DS_ERR_EMPTY when nothing is in flight;
  * F3DS_ERR_CAPACITY (frame stays) when cap < its point count; n_out and tag are set in all three cases but EMPTY.
