@@ -96,6 +96,20 @@ class RgbdFormat(ctypes.Structure):
         return f
 
 
+class TrackParams(ctypes.Structure):
+    """f3ds_track_params (include/f3ds.h): when a region takes over a previous id."""
+    _fields_ = [("min_votes", ctypes.c_uint32), ("min_permille", ctypes.c_uint32), ("depth_tol", ctypes.c_float)]
+
+
+class TrackResult(ctypes.Structure):
+    """f3ds_track_result (include/f3ds.h): the counts of one tracker update."""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("n_regions", "n_nonempty", "n_matched", "n_new", "n_retired", "n_entries", "next_id", "first_frame")] + \
+               [("n_labelled", ctypes.c_uint64), ("n_votes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class SupervoxelSet(ctypes.Structure):
     """f3ds_supervoxel_set (include/f3ds.h): the supervoxel_clusters map of the reference as plain arrays."""
     _fields_ = [("n_supervoxels", ctypes.c_uint32), ("label", ctypes.c_void_p), ("voxel_offset", ctypes.c_void_p), ("voxel_xyz", ctypes.c_void_p),
@@ -149,6 +163,18 @@ def load_library(path=None):
         lib.f3ds_segment_rgbd_batch.restype = ctypes.c_int
         lib.f3ds_get_points.argtypes = [vp, vp, sz, ctypes.c_int, ctypes.POINTER(sz)]; lib.f3ds_get_points.restype = ctypes.c_int
         lib.f3ds_stream_submit_rgbd.argtypes = [vp, fp, vp, vp, ctypes.POINTER(Params), ctypes.c_uint64]; lib.f3ds_stream_submit_rgbd.restype = ctypes.c_int
+    if hasattr(lib, "f3ds_tracker_update"):
+        tpp, trp = ctypes.POINTER(TrackParams), ctypes.POINTER(TrackResult)
+        lib.f3ds_default_track_params.argtypes = [tpp]; lib.f3ds_default_track_params.restype = None
+        lib.f3ds_tracker_create.argtypes = [ctypes.c_int, tpp, ctypes.POINTER(vp)]; lib.f3ds_tracker_create.restype = ctypes.c_int
+        lib.f3ds_tracker_destroy.argtypes = [vp]; lib.f3ds_tracker_destroy.restype = None
+        lib.f3ds_tracker_set_stream.argtypes = [vp, vp]; lib.f3ds_tracker_set_stream.restype = ctypes.c_int
+        lib.f3ds_tracker_reset.argtypes = [vp]; lib.f3ds_tracker_reset.restype = ctypes.c_int
+        lib.f3ds_tracker_update.argtypes = [vp, ctypes.POINTER(RgbdFormat), vp, vp, ctypes.c_uint32, ctypes.c_int, vp, vp, ctypes.c_int, trp]
+        lib.f3ds_tracker_update.restype = ctypes.c_int
+        lib.f3ds_tracker_get_ids.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]; lib.f3ds_tracker_get_ids.restype = ctypes.c_int
+        lib.f3ds_track_reproject.argtypes = [ctypes.POINTER(RgbdFormat), vp, vp, sz, vp, vp]; lib.f3ds_track_reproject.restype = ctypes.c_int
+        lib.f3ds_track_assign.argtypes = [tpp, vp, ctypes.c_uint32, vp, sz, vp, ctypes.c_uint32, u32p, vp, trp]; lib.f3ds_track_assign.restype = ctypes.c_int
     lib.f3ds_recluster.argtypes = [vp, ctypes.POINTER(Params), vp, ctypes.c_int, ctypes.POINTER(Result)]
     lib.f3ds_recluster.restype = ctypes.c_int
     lib.f3ds_evaluate.argtypes = [vp, vp, ctypes.POINTER(Performance)]; lib.f3ds_evaluate.restype = ctypes.c_int
@@ -386,6 +412,132 @@ def deproject(fmt, depth, color):
     pts = np.empty((int(fmt.width) * int(fmt.height), 4), np.float32)
     _check(lib, lib.f3ds_deproject(ctypes.byref(f), d.ctypes.data, c.ctypes.data, pts.ctypes.data))
     return pts
+
+
+# ---- label tracker -----------------------------------------------------------------------------------
+def default_track_params(**kw):
+    p = TrackParams()
+    load_library().f3ds_default_track_params(ctypes.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _pose12(pose):
+    """None, or the 12 floats of a row-major 3 x 4 pose (a 4 x 4 matrix gives its first three rows)"""
+    if pose is None:
+        return None
+    m = np.asarray(pose, np.float32)
+    if m.shape == (4, 4):
+        m = m[:3]
+    if m.size != 12:
+        raise ValueError("a pose is 12 floats (row-major 3 x 4) or a 4 x 4 matrix")
+    return np.ascontiguousarray(m, np.float32).reshape(12)
+
+
+def track_reproject(fmt, points, pose=None):
+    """f3ds_track_reproject: (pixel index in the previous frame or -1 (int32), depth there (float32)) of every (N, 4) float32 record under `pose`
+    (p_prev = R p_cur + t; None = identity).  Host arithmetic only: what Tracker.update does per labelled pixel on the device."""
+    lib = load_library()
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+    m = _pose12(pose)
+    pixel, zp = np.empty(len(pts), np.int32), np.empty(len(pts), np.float32)
+    _check(lib, lib.f3ds_track_reproject(ctypes.byref(fmt), None if m is None else m.ctypes.data, pts.ctypes.data, len(pts), pixel.ctypes.data, zp.ctypes.data))
+    return pixel, zp
+
+
+def track_assign(size, entries, prev_id, next_id, params=None):
+    """f3ds_track_assign: (id of every region (uint32, NO_LABEL for an empty one), next_id afterwards, TrackResult) from the regions' sizes, the vote
+    entries ((n, 3) uint32 rows: region, previous slot, votes) and the previous slots' ids.  Host arithmetic only."""
+    lib = load_library()
+    size = np.ascontiguousarray(size, np.uint32).reshape(-1)
+    entries = np.ascontiguousarray(entries, np.uint32).reshape(-1, 3)
+    prev_id = np.ascontiguousarray(prev_id, np.uint32).reshape(-1)
+    ids = np.full(len(size), NO_LABEL, np.uint32)
+    nxt, res = ctypes.c_uint32(int(next_id)), TrackResult()
+    _check(lib, lib.f3ds_track_assign(ctypes.byref(params) if params is not None else None, size.ctypes.data, len(size), entries.ctypes.data, len(entries),
+                                      prev_id.ctypes.data, len(prev_id), ctypes.byref(nxt), ids.ctypes.data, ctypes.byref(res)))
+    return ids, int(nxt.value), res
+
+
+class Tracker:
+    """f3ds_tracker (include/f3ds.h): persistent ids for the regions of consecutive RGB-D frames.  Not thread-safe; one per camera."""
+
+    def __init__(self, device=0, params=None):
+        self.lib = load_library()
+        h = ctypes.c_void_p()
+        _check(self.lib, self.lib.f3ds_tracker_create(device, ctypes.byref(params) if params is not None else None, ctypes.byref(h)))
+        self.handle = h
+        self.device = device
+        self.result = TrackResult()
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.f3ds_tracker_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def set_stream(self, hip_stream_ptr):
+        _check(self.lib, self.lib.f3ds_tracker_set_stream(self.handle, ctypes.c_void_p(hip_stream_ptr)))
+
+    def reset(self):
+        """Forget the previous frame (the next update matches nothing); ids given out so far are not given out again."""
+        _check(self.lib, self.lib.f3ds_tracker_reset(self.handle))
+
+    def update(self, depth, labels, n_regions, fmt, pose=None, ids_out=None, on_device=False):
+        """f3ds_tracker_update: the track id of every pixel.  depth: (height, width) uint16 / float32 as ``fmt`` says (rows may be strided), labels: one
+        uint32 per pixel as segment_rgbd wrote them, n_regions: ``Context.result.n_regions`` of that call; or device pointers (ints, the depth pitch
+        of ``fmt`` applies) with ``on_device=True``, ``ids_out`` then a device pointer too.  pose: 12 floats (row-major 3 x 4) or a 4 x 4 matrix that
+        takes this frame's camera coordinates to the previous frame's; None = the camera has not moved.  ``self.result`` holds the counts."""
+        n = int(fmt.width) * int(fmt.height)
+        m = _pose12(pose)
+        mp = None if m is None else m.ctypes.data
+        if on_device:
+            _check(self.lib, self.lib.f3ds_tracker_update(self.handle, ctypes.byref(fmt), ctypes.c_void_p(int(depth)), ctypes.c_void_p(int(labels)), int(n_regions), 1, mp,
+                                                          ctypes.c_void_p(int(ids_out)), 1, ctypes.byref(self.result)))
+            return None
+        if fmt.depth_type not in _DEPTH_DTYPE:
+            raise F3dsError(ERR_ARG, "unknown depth type")
+        d = np.asarray(depth, _DEPTH_DTYPE[fmt.depth_type])
+        if d.shape != (int(fmt.height), int(fmt.width)):
+            raise ValueError("depth must be (height, width), got %r" % (d.shape,))
+        if d.shape[0] <= 1 or d.strides[1] != d.itemsize or d.strides[0] < d.shape[1] * d.itemsize:
+            d = np.ascontiguousarray(d)
+        f = fmt.copy()
+        f.depth_pitch = 0 if d.flags.c_contiguous else d.strides[0]
+        lab = np.ascontiguousarray(labels, np.uint32).reshape(-1)
+        if lab.size != n:
+            raise ValueError("labels must hold one entry per pixel")
+        if ids_out is None:
+            ids = np.empty(n, np.uint32)
+        else:
+            ids = ids_out
+            if not (isinstance(ids, np.ndarray) and ids.dtype == np.uint32 and ids.flags.c_contiguous and ids.size == n):
+                raise ValueError("ids_out must be a contiguous uint32 array with one entry per pixel")
+        _check(self.lib, self.lib.f3ds_tracker_update(self.handle, ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), 0, mp, ids.ctypes.data, 0,
+                                                      ctypes.byref(self.result)))
+        return ids
+
+    def ids(self):
+        """f3ds_tracker_get_ids: the track id of every region of the last update (NO_LABEL for a region without a labelled pixel); LogicError before any."""
+        n = ctypes.c_size_t()
+        _check(self.lib, self.lib.f3ds_tracker_get_ids(self.handle, None, 0, ctypes.byref(n)))
+        out = np.empty(n.value, np.uint32)
+        _check(self.lib, self.lib.f3ds_tracker_get_ids(self.handle, out.ctypes.data, n.value, ctypes.byref(n)))
+        return out
 
 
 # ---- device context ------------------------------------------------------------------------------

@@ -48,12 +48,14 @@
 #include "f3ds_levels.h"
 #include "f3ds_eval_levels.h"
 #include "f3ds_rgbd.h"
+#include "f3ds_track.h"
 
 using namespace f3ds;
 
 #include "f3ds_kernels.inc"
 #include "f3ds_levels.inc"
 #include "f3ds_eval_levels.inc"
+#include "f3ds_track.inc"
 
 // ================================================================================================
 // batched launch machinery
@@ -170,7 +172,9 @@ const int g_merge_shared_res = [] { const char* e = dev_getenv("F3DS_MERGE_SHARE
     /* hierarchy levels */ X(uint32_t, lv_into) X(uint32_t, lv_at) X(uint32_t, lv_pfx) X(float, lv_thr) X(uint32_t, lv_tab) X(uint32_t, lv_nreg) X(uint32_t, lv_out) \
     /* level scores (f3ds_eval_levels.inc): sort buffers, base table, reduced level entries, ghost list, per-level sizes / flags / terms, truth sizes and visiting order, matches, counts and results of a batch */ \
     X(uint64_t, evl_k0) X(uint64_t, evl_k1) X(uint32_t, evl_v0) X(uint32_t, evl_v1) X(uint32_t, evl_flag) X(uint64_t, evl_bkey) X(uint32_t, evl_bcnt) X(uint64_t, evl_ukey) X(uint32_t, evl_ucnt) X(uint32_t, evl_glist) \
-    X(uint32_t, evl_ssize) X(unsigned char, evl_used) X(float, evl_hterm) X(float, evl_mterm) X(float, evl_tterm) X(uint32_t, evl_tsize) X(uint32_t, evl_order) X(uint32_t, evl_slot) X(uint32_t, evl_counts) X(uint32_t, evl_out)
+    X(uint32_t, evl_ssize) X(unsigned char, evl_used) X(float, evl_hterm) X(float, evl_mterm) X(float, evl_tterm) X(uint32_t, evl_tsize) X(uint32_t, evl_order) X(uint32_t, evl_slot) X(uint32_t, evl_counts) X(uint32_t, evl_out) \
+    /* label tracker (f3ds_track.inc; the sort and the reduction use the evl_ buffers of the tracker's private context): labels as uploaded, the ends of the entries' runs, the packed entries, id[], the ids of a host caller */ \
+    X(uint32_t, trk_lab) X(uint32_t, trk_end) X(uint32_t, trk_out) X(uint32_t, trk_id) X(uint32_t, trk_tid)
 template <class T> struct Scratch { T* p = nullptr; size_t cap = 0; int slot = -1; };      // cap: bytes allocated; slot: position in F3DS_SCRATCH
 #define F3DS_SCRATCH_SLOT(T, name) S_##name,
 #define F3DS_SCRATCH_MEMBER(T, name) Scratch<T> name{nullptr, 0, S_##name};
@@ -2322,5 +2326,205 @@ extern "C" int f3ds_get_merge_tree(f3ds_ctx* c, uint32_t* survivor, uint32_t* ab
         if (absorbed) absorbed[i] = label_out(c, u[i * 3 + 1]);
         if (weight) memcpy(&weight[i], &u[i * 3 + 2], 4);
     }
+    return F3DS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// label tracker (f3ds_track.h / .inc): persistent ids for the regions of consecutive RGB-D frames.  The tracker owns a
+// private context for its stream, scratch and copy-stream plumbing, and two state buffers (slot and depth per pixel of the previous frame) that
+// it swaps: an update reads one and writes the other.  Per update: d_track_keys, the stage-0 radix sort on the keys alone, d_evl_heads / scan,
+// d_track_runs, d_track_pack; ONE download (entries, their count, the bad-label flag) and the update's only wait before the output; the
+// assignment on the host (f3ds_track_assign: the entries number thousands, not pixels); one upload of id[]; d_track_apply.
+// ------------------------------------------------------------------------------------------------
+struct f3ds_tracker {
+    f3ds_ctx* c = nullptr;
+    f3ds_track_params prm;
+    uint32_t* slot[2] = {nullptr, nullptr}; float* z[2] = {nullptr, nullptr}; size_t state_n = 0;      // pixels a state buffer holds
+    int cur = 0;                            // slot[cur] / z[cur]: the previous frame
+    bool have_prev = false, have_fmt = false, have_ids = false;
+    f3ds_rgbd_format fmt;                   // remembered with the state: width, height and intrinsics must not change under it
+    std::vector<uint32_t> prev_id, ids;     // prev_id[slot]: persistent id of the previous frame's regions; ids: id[] of the last update
+    uint32_t next_id = 0;
+    uint32_t* h_out = nullptr; size_t out_cap = 0;      // pinned: TRK_HEAD words + out_cap (i, j, c) triples
+    uint32_t* h_id = nullptr; size_t id_cap = 0;        // pinned: id[] on its way up
+};
+
+namespace {
+constexpr size_t TRK_FIRST_CAP = 1024;      // entries the first download has room for; a frame with more is packed again with room for twice its count
+int trk_pinned(uint32_t** p, size_t* cap, size_t want) {
+    if (*cap >= want && *p) return F3DS_OK;
+    if (*p) { HIPCHECK(hipHostFree(*p)); *p = nullptr; *cap = 0; }
+    HIPCHECK(hipHostMalloc(p, (want ? want : 1) * sizeof(uint32_t), hipHostMallocDefault));
+    *cap = want;
+    return F3DS_OK;
+}
+int trk_state(f3ds_tracker* t, size_t n) {
+    if (t->state_n == n && t->slot[0]) return F3DS_OK;      // (a remembered format fixes n: only a tracker without a previous frame gets here)
+    for (int k = 0; k < 2; ++k) {
+        if (t->slot[k]) HIPCHECK(hipFree(t->slot[k]));
+        if (t->z[k]) HIPCHECK(hipFree(t->z[k]));
+        t->slot[k] = nullptr; t->z[k] = nullptr;
+    }
+    t->state_n = 0;
+    for (int k = 0; k < 2; ++k) { HIPCHECK(hipMalloc(&t->slot[k], n * 4)); HIPCHECK(hipMalloc(&t->z[k], n * 4)); }
+    t->state_n = n;
+    return F3DS_OK;
+}
+}  // namespace
+
+extern "C" int f3ds_tracker_create(int device, const f3ds_track_params* params, f3ds_tracker** out) {
+    if (!out) return F3DS_ERR_ARG;
+    *out = nullptr;
+    f3ds_track_params prm;
+    if (params) prm = *params; else f3ds_default_track_params(&prm);
+    if (!tk_params_ok(prm.min_permille, prm.depth_tol)) return F3DS_ERR_ARG;
+    f3ds_ctx* c = nullptr;
+    if (const int rc = f3ds_create(device, &c)) return rc;
+    f3ds_tracker* t = new f3ds_tracker;
+    t->c = c; t->prm = prm;
+    memset(&t->fmt, 0, sizeof t->fmt);
+    *out = t;
+    return F3DS_OK;
+}
+
+extern "C" void f3ds_tracker_destroy(f3ds_tracker* t) {
+    if (!t) return;
+    (void)hipSetDevice(t->c->device);
+    if (t->c->stream) (void)hipStreamSynchronize(t->c->stream);
+    for (int k = 0; k < 2; ++k) { if (t->slot[k]) (void)hipFree(t->slot[k]); if (t->z[k]) (void)hipFree(t->z[k]); }
+    if (t->h_out) (void)hipHostFree(t->h_out);
+    if (t->h_id) (void)hipHostFree(t->h_id);
+    f3ds_destroy(t->c);
+    delete t;
+}
+
+extern "C" int f3ds_tracker_set_stream(f3ds_tracker* t, void* hip_stream) {
+    if (!t) return F3DS_ERR_ARG;
+    return f3ds_set_stream(t->c, hip_stream);
+}
+
+extern "C" int f3ds_tracker_reset(f3ds_tracker* t) {
+    if (!t) return F3DS_ERR_ARG;
+    t->have_prev = false; t->have_fmt = false; t->prev_id.clear();
+    return F3DS_OK;
+}
+
+extern "C" int f3ds_tracker_get_ids(f3ds_tracker* t, uint32_t* id_of_region, size_t cap, size_t* n_out) {
+    if (!t || (!id_of_region && !n_out)) return F3DS_ERR_ARG;
+    if (!t->have_ids) return F3DS_ERR_LOGIC;
+    if (n_out) *n_out = t->ids.size();
+    if (!id_of_region) return F3DS_OK;
+    if (cap < t->ids.size()) return F3DS_ERR_CAPACITY;
+    if (!t->ids.empty()) memcpy(id_of_region, t->ids.data(), t->ids.size() * 4);
+    return F3DS_OK;
+}
+
+extern "C" int f3ds_tracker_update(f3ds_tracker* t, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, int inputs_on_device,
+                                   const float* pose12, uint32_t* track_ids, int ids_on_device, f3ds_track_result* result) {
+    if (!t || !fmt_ || !depth || !labels || !track_ids) return F3DS_ERR_ARG;
+    f3ds_rgbd_format fmt = *fmt_;
+    fmt.color_format = F3DS_COLOR_RGB8; fmt.color_pitch = 0;      // (no colour image is passed: the two colour fields are not looked at)
+    f3ds::RgbdLayout lay;
+    if (const int rc = f3ds::rgbd_layout(&fmt, &lay)) return rc;
+    if (pose12) for (int k = 0; k < 12; ++k) if (!m_isfinitef(pose12[k])) return F3DS_ERR_ARG;
+    if (t->have_fmt && (fmt.width != t->fmt.width || fmt.height != t->fmt.height || fmt.fx != t->fmt.fx || fmt.fy != t->fmt.fy || fmt.cx != t->fmt.cx || fmt.cy != t->fmt.cy))
+        return F3DS_ERR_ARG;      // (the state is an image of the remembered camera: the caller resets first)
+    if (n_regions > TK_MAX_REGIONS) return F3DS_ERR_UNSUPPORTED;
+    f3ds_ctx* c = t->c;
+    g_sw.read();
+    HIPCHECK(hipSetDevice(c->device));
+    Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c);
+    { f3ds_ctx* one[1] = {c}; set_launch_shape(one, 1); }
+    reset_recording(c);
+    const uint32_t n = (uint32_t)lay.n, Kc = n_regions, Kp = t->have_prev ? (uint32_t)t->prev_id.size() : 0u;
+    const int jb = tk_bits(Kp), sort_bits = tk_bits(Kc) + jb;
+    if (const int rc = trk_state(t, n)) return rc;
+    if (!t->h_out) { if (const int rc = trk_pinned(&t->h_out, &t->out_cap, TRK_HEAD + 3 * TRK_FIRST_CAP)) return rc; }
+    size_t cap = (t->out_cap - TRK_HEAD) / 3;
+    // every buffer of the update before anything is recorded
+    uint64_t *k0, *k1, *ukey; uint32_t *flag, *ustart, *uend, *out, *d_id, *cnt, *hist, *tiles, *tid = nullptr, *ul = nullptr; unsigned char* ud = nullptr;
+    ENSURE(c->evl_k0, n, k0); ENSURE(c->evl_k1, n, k1); ENSURE(c->evl_flag, n, flag); ENSURE(c->evl_ukey, n, ukey); ENSURE(c->evl_ucnt, n, ustart); ENSURE(c->trk_end, n, uend);
+    ENSURE(c->trk_out, TRK_HEAD + 3 * cap, out); ENSURE(c->trk_id, Kc ? Kc : 1u, d_id); ENSURE(c->evl_counts, 4, cnt);
+    ENSURE(c->hist, (size_t)RS_BINS * ((n + RS_TILE - 1) / RS_TILE + 1), hist); ENSURE(c->tiles, (n + SCAN_TILE - 1) / SCAN_TILE + 1, tiles);
+    if (!ids_on_device) ENSURE(c->trk_tid, n, tid);
+    const unsigned char* d_depth = static_cast<const unsigned char*>(depth);
+    const uint32_t* d_lab = labels;
+    if (!inputs_on_device) {      // host images go through the device's copy stream, like those of f3ds_segment_rgbd
+        ENSURE(c->img_depth, lay.depth_bytes, ud); ENSURE(c->trk_lab, n, ul);
+        hipStream_t up = g_sw.copy_stream ? copy_stream_of(c->device) : nullptr;
+        HIPCHECK(hipMemcpyAsync(ud, depth, lay.depth_bytes, hipMemcpyHostToDevice, up ? up : b.st));
+        HIPCHECK(hipMemcpyAsync(ul, labels, (size_t)n * 4, hipMemcpyHostToDevice, up ? up : b.st));
+        if (up) {
+            if (!c->ev_copy[0]) HIPCHECK(hipEventCreateWithFlags(&c->ev_copy[0], hipEventDisableTiming));
+            HIPCHECK(hipEventRecord(c->ev_copy[0], up));
+            HIPCHECK(hipStreamWaitEvent(b.st, c->ev_copy[0], 0));
+        }
+        d_depth = ud; d_lab = ul;
+    }
+    TrackArgs a;
+    memset(&a, 0, sizeof a);
+    a.width = fmt.width; a.height = fmt.height; a.n = n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
+    a.has_pose = pose12 ? 1 : 0; a.has_prev = t->have_prev ? 1 : 0; a.Kc = Kc; a.Kp = Kp; a.jb = jb;
+    a.depth_scale = fmt.depth_scale; a.fx = fmt.fx; a.fy = fmt.fy; a.cx = fmt.cx; a.cy = fmt.cy; a.depth_tol = t->prm.depth_tol;
+    if (pose12) memcpy(a.pose, pose12, sizeof a.pose);
+    const int nxt = t->cur ^ 1;
+    int rc;
+    HIPCHECK(hipMemsetAsync(cnt, 0, 16, b.st));      // [0] entries, [1] the bad-label flag
+    rec<d_track_keys>(c, grid_for(n, 256), 0u, d_depth, d_lab, t->have_prev ? t->slot[t->cur] : nullptr, t->have_prev ? t->z[t->cur] : nullptr, a, k0, t->slot[nxt], t->z[nxt], cnt + 1);
+    uint64_t* ks;
+    if ((rc = radix_sort(c, k0, nullptr, k1, nullptr, n, sort_bits, &ks, nullptr))) return rc;
+    rec<d_evl_heads>(c, grid_for(n, 256), 0u, ks, n, tk_hole(Kc, jb), flag);
+    if ((rc = scan_u32(c, flag, flag, n))) return rc;
+    rec<d_track_runs>(c, grid_for(n, 256), 0u, ks, n, tk_hole(Kc, jb), flag, ukey, ustart, uend, cnt);
+    rec<d_track_pack>(c, grid_for(cap, 256), 0u, ukey, ustart, uend, cnt, cnt + 1, jb, (uint32_t)cap, out);
+    if ((rc = flush(b))) return rc;
+    HIPCHECK(hipMemcpyAsync(t->h_out, out, (TRK_HEAD + 3 * cap) * 4, hipMemcpyDeviceToHost, b.st));
+    HIPCHECK(timed_sync(b.st));
+    HIPCHECK(hipGetLastError());
+    if (t->h_out[1]) return F3DS_ERR_ARG;      // a label >= n_regions: the state buffers are not swapped, nothing of the tracker has changed
+    const uint32_t total = t->h_out[0];
+    if (total > n) return F3DS_ERR_LOGIC;
+    if (total > cap) {      // (rare: more distinct (region, slot) pairs than the download had room for)
+        cap = (size_t)total * 2;
+        if ((rc = trk_pinned(&t->h_out, &t->out_cap, TRK_HEAD + 3 * cap))) return rc;
+        ENSURE(c->trk_out, TRK_HEAD + 3 * cap, out);
+        rec<d_track_pack>(c, grid_for(cap, 256), 0u, ukey, ustart, uend, cnt, cnt + 1, jb, (uint32_t)cap, out);
+        if ((rc = flush(b))) return rc;
+        HIPCHECK(hipMemcpyAsync(t->h_out, out, (TRK_HEAD + 3 * (size_t)total) * 4, hipMemcpyDeviceToHost, b.st));
+        HIPCHECK(timed_sync(b.st));
+    }
+    // size[i] = the sum of region i's row, the no-vote column (j == Kp) included; the votes go to the assignment
+    std::vector<uint32_t> size(Kc, 0u), votes, ids(Kc, F3DS_NO_LABEL);
+    votes.reserve((size_t)total * 3);
+    for (uint32_t e = 0; e < total; ++e) {
+        const uint32_t* en = t->h_out + TRK_HEAD + (size_t)e * 3;
+        if (en[0] >= Kc || en[1] > Kp) return F3DS_ERR_LOGIC;
+        size[en[0]] += en[2];
+        if (en[1] < Kp) votes.insert(votes.end(), en, en + 3);
+    }
+    uint32_t next = t->next_id;
+    f3ds_track_result r;
+    if ((rc = f3ds_track_assign(&t->prm, size.data(), Kc, votes.data(), votes.size() / 3, t->prev_id.data(), Kp, &next, ids.data(), &r))) return rc;
+    r.first_frame = t->have_prev ? 0u : 1u;
+    if ((rc = trk_pinned(&t->h_id, &t->id_cap, Kc))) return rc;
+    if (Kc) { memcpy(t->h_id, ids.data(), (size_t)Kc * 4); HIPCHECK(hipMemcpyAsync(d_id, t->h_id, (size_t)Kc * 4, hipMemcpyHostToDevice, b.st)); }
+    rec<d_track_apply>(c, grid_for(n, 256), 0u, d_lab, n, d_id, Kc, ids_on_device ? track_ids : tid);
+    if ((rc = flush(b))) return rc;
+    if (!ids_on_device) {
+        hipStream_t dl = g_sw.copy_stream ? copy_stream_of(c->device, g_sw.copy_duplex ? 1 : 0) : nullptr;
+        if (dl) {      // queued on the copy stream only once the ids exist (as the labels of f3ds_segment_batch)
+            for (int k = 1; k < 3; ++k) if (!c->ev_copy[k]) HIPCHECK(hipEventCreateWithFlags(&c->ev_copy[k], hipEventDisableTiming));
+            HIPCHECK(hipEventRecord(c->ev_copy[1], b.st));
+            HIPCHECK(timed_sync(c->ev_copy[1]));
+        }
+        HIPCHECK(hipMemcpyAsync(track_ids, tid, (size_t)n * 4, hipMemcpyDeviceToHost, dl ? dl : b.st));
+        if (dl) { HIPCHECK(hipEventRecord(c->ev_copy[2], dl)); HIPCHECK(timed_sync(c->ev_copy[2])); }
+    }
+    HIPCHECK(timed_sync(b.st));
+    HIPCHECK(hipGetLastError());
+    // the update stands: the buffer just written is the previous frame from now on
+    t->cur = nxt; t->have_prev = true; t->have_fmt = true; t->fmt = fmt;
+    t->prev_id = ids; t->ids.swap(ids); t->have_ids = true; t->next_id = next;
+    if (result) *result = r;
     return F3DS_OK;
 }

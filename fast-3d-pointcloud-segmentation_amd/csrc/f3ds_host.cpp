@@ -17,6 +17,7 @@
 #include "f3ds_dev.h"
 #include "f3ds_numerics.h"
 #include "f3ds_rgbd.h"
+#include "f3ds_track.h"
 
 extern "C" {
 
@@ -102,6 +103,74 @@ int f3ds_deproject(const f3ds_rgbd_format* fmt, const void* depth, const void* c
             unsigned char* o = out + 16u * ((size_t)v * fmt->width + u);
             memcpy(o, rec, 12); memcpy(o + 12, &rgba, 4);
         }
+    }
+    return F3DS_OK;
+}
+
+// ---- label tracker: the two host halves of f3ds_tracker_update (the rules are in f3ds_track.h, which d_track_keys calls too) ----
+void f3ds_default_track_params(f3ds_track_params* p) {
+    if (!p) return;
+    p->min_votes = 16u;
+    p->min_permille = 300u;
+    p->depth_tol = 0.05f;
+}
+
+// steps 2 and 3 of an update for n records: where each lands in the previous image (-1: nowhere) and its depth there
+int f3ds_track_reproject(const f3ds_rgbd_format* fmt, const float* pose12, const void* points16, size_t n, int32_t* pixel, float* zp) {
+    if (!fmt || !points16 || !pixel || !zp) return F3DS_ERR_ARG;
+    f3ds_rgbd_format f = *fmt;
+    f.color_format = F3DS_COLOR_RGB8; f.color_pitch = 0;      // (no colour image is passed)
+    if (const int rc = f3ds::rgbd_layout(&f, nullptr)) return rc;
+    if (pose12) for (int k = 0; k < 12; ++k) if (!f3ds::m_isfinitef(pose12[k])) return F3DS_ERR_ARG;
+    const unsigned char* in = static_cast<const unsigned char*>(points16);
+    for (size_t i = 0; i < n; ++i) {
+        float p[3];
+        memcpy(p, in + 16u * i, 12);
+        float xp, yp, z;
+        f3ds::tk_transform(pose12, p[0], p[1], p[2], xp, yp, z);
+        pixel[i] = f3ds::tk_project(xp, yp, z, f.fx, f.fy, f.cx, f.cy, f.width, f.height);
+        zp[i] = z;
+    }
+    return F3DS_OK;
+}
+
+// step 5 of an update.  entries: n_entries rows (region i, previous slot j, votes c), every (i, j) at most once, in any order.
+int f3ds_track_assign(const f3ds_track_params* params, const uint32_t* size, uint32_t n_regions, const uint32_t* entries, size_t n_entries, const uint32_t* prev_id,
+                      uint32_t n_prev, uint32_t* next_id, uint32_t* id_of_region, f3ds_track_result* result) {
+    f3ds_track_params prm;
+    if (params) prm = *params; else f3ds_default_track_params(&prm);
+    if (!next_id || (n_regions && (!size || !id_of_region)) || (n_entries && !entries) || (n_prev && !prev_id)) return F3DS_ERR_ARG;
+    if (!f3ds::tk_params_ok(prm.min_permille, prm.depth_tol)) return F3DS_ERR_ARG;
+    if (n_regions > f3ds::TK_MAX_REGIONS || n_prev > f3ds::TK_MAX_REGIONS || n_entries > 0xFFFFFFFFull) return F3DS_ERR_UNSUPPORTED;
+    struct Entry { uint32_t c, i, j; };
+    std::vector<Entry> el;
+    uint64_t n_votes = 0, n_labelled = 0;
+    for (size_t e = 0; e < n_entries; ++e) {
+        const uint32_t i = entries[e * 3], j = entries[e * 3 + 1], c = entries[e * 3 + 2];
+        if (i >= n_regions || j >= n_prev || prev_id[j] == F3DS_NO_LABEL || c > size[i]) return F3DS_ERR_ARG;
+        n_votes += c;
+        if (f3ds::tk_eligible(c, size[i], prm.min_votes, prm.min_permille)) el.push_back(Entry{c, i, j});
+    }
+    std::sort(el.begin(), el.end(), [](const Entry& a, const Entry& b) { return a.c != b.c ? a.c > b.c : (a.i != b.i ? a.i < b.i : a.j < b.j); });
+    std::vector<uint32_t> id(n_regions, F3DS_NO_LABEL);
+    std::vector<unsigned char> claimed(n_prev, 0);
+    uint32_t n_matched = 0, n_new = 0, n_nonempty = 0, n_retired = 0;
+    for (const Entry& en : el)
+        if (id[en.i] == F3DS_NO_LABEL && !claimed[en.j]) { id[en.i] = prev_id[en.j]; claimed[en.j] = 1; ++n_matched; }
+    for (uint32_t i = 0; i < n_regions; ++i) {
+        n_labelled += size[i];
+        if (size[i]) { ++n_nonempty; if (id[i] == F3DS_NO_LABEL) ++n_new; }
+    }
+    if ((uint64_t)*next_id + n_new >= 0xFFFFFFFFull) return F3DS_ERR_UNSUPPORTED;      // (ids are never reused, and 0xFFFFFFFF is F3DS_NO_LABEL)
+    uint32_t next = *next_id;
+    for (uint32_t i = 0; i < n_regions; ++i) if (size[i] && id[i] == F3DS_NO_LABEL) id[i] = next++;
+    for (uint32_t j = 0; j < n_prev; ++j) if (prev_id[j] != F3DS_NO_LABEL && !claimed[j]) ++n_retired;
+    *next_id = next;
+    if (n_regions) memcpy(id_of_region, id.data(), (size_t)n_regions * 4);
+    if (result) {
+        memset(result, 0, sizeof *result);
+        result->n_regions = n_regions; result->n_nonempty = n_nonempty; result->n_matched = n_matched; result->n_new = n_new; result->n_retired = n_retired;
+        result->n_entries = (uint32_t)n_entries; result->next_id = next; result->first_frame = 0u; result->n_labelled = n_labelled; result->n_votes = n_votes;
     }
     return F3DS_OK;
 }

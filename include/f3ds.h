@@ -190,6 +190,71 @@ int f3ds_segment_rgbd_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format* f
  * F3DS_ERR_CAPACITY when cap (in records) is smaller than the count. */
 int f3ds_get_points(f3ds_ctx* ctx, void* points16, size_t cap, int dst_on_device, size_t* n_out);
 
+/* ---- label tracker: persistent ids for the regions of consecutive RGB-D frames ----------------------------------------------
+ * A frame's region ids are ranks (0..K-1) and relate to nothing in the next frame.  A tracker turns each frame's labels into TRACK IDS that
+ * follow surfaces: it holds the previous frame on the device -- per pixel a slot (that frame's region label, or F3DS_NO_LABEL) and an f32 depth
+ * (NaN = invalid) --, the previous format, a host table prev_id[slot] and next_id (0 at creation).  One update, bit for bit (csrc/f3ds_track.h):
+ *  1. point     pixel p = v * width + u gets (x, y, z) by the rule of f3ds_deproject; it is VALID iff its depth is, LABELLED iff valid and label[p] != F3DS_NO_LABEL.
+ *  2. transform with a pose (12 floats, row-major 3 x 4, p_prev = R p_cur + t): xp = ((r00*x + r01*y) + r02*z) + t0, likewise yp, zp, every operation one
+ *               rounded f32 operation, none fused; a NULL pose is the identity and does no arithmetic.
+ *  3. project   uf = (xp * fx) / zp + cx, vf = (yp * fy) / zp + cy, us = uf + 0.5f, vs = vf + 0.5f.  The point lands on pixel (floor(us), floor(vs)) of the
+ *               previous frame iff zp > 0, zp is finite, 0 <= us < (float)width and 0 <= vs < (float)height (comparisons with NaN fail).
+ *  4. vote      a labelled pixel of region i that lands on q votes for j = slot[q] iff j != F3DS_NO_LABEL and fabsf(zp - z_prev[q]) <= depth_tol * zp; otherwise
+ *               it is a no-vote.  size[i] = the labelled pixels of region i (votes and no-votes), count[i][j] = its votes for j.  On the first update, or
+ *               after a reset, every labelled pixel is a no-vote.
+ *  5. assign    (integers only) entry (i, j, c = count[i][j]) is eligible iff c >= max(min_votes, 1) and (uint64)c * 1000 >= (uint64)min_permille * size[i].
+ *               Eligible entries are visited by c descending, then i ascending, then j ascending; one is taken iff region i has no id yet and slot j has not been
+ *               claimed: id[i] = prev_id[j].  Then the regions with size[i] > 0 and no id get next_id++ in ascending i; regions with size[i] == 0 get
+ *               F3DS_NO_LABEL and use no id.  Ids are never reused; a next_id that would reach 0xFFFFFFFF is F3DS_ERR_UNSUPPORTED.
+ *  6. output    track_ids[p] = F3DS_NO_LABEL if label[p] == F3DS_NO_LABEL, else id[label[p]] (also where the depth is invalid).  New state: slot[p] = label[p]
+ *               if labelled, else F3DS_NO_LABEL; z_prev[p] = z if valid, else NaN; prev_id = id; the format is remembered.
+ * So ids follow surfaces and not label numbers; of the parts of a split region the one with more votes keeps the id; a merged region takes the id with
+ * more votes and the other id retires.
+ * The colour fields of the format are not looked at.  labels: one u32 per pixel, < n_regions or F3DS_NO_LABEL (what f3ds_segment_rgbd wrote and
+ * f3ds_result.n_regions counts).  inputs_on_device: depth and labels are device memory, read where they are; host ones go through the device's copy stream.
+ * ids_on_device likewise for track_ids.  Synchronous.  The work per pixel is on the device (csrc/f3ds_track.inc); the host sees the distinct (i, j) pairs only.
+ * Errors: F3DS_ERR_ARG for a NULL pointer, what f3ds_deproject refuses of a format, a non-finite pose entry, depth_tol negative or not finite,
+ * min_permille > 1000, a format whose width, height or intrinsics differ from the remembered one (reset first) and a label >= n_regions other than
+ * F3DS_NO_LABEL (found on the device; the tracker is then unchanged); F3DS_ERR_UNSUPPORTED for n_regions > 0x00FFFFFF; F3DS_ERR_NO_DEVICE as f3ds_create;
+ * F3DS_ERR_LOGIC from f3ds_tracker_get_ids before any update.  A frame without a valid pixel, or n_regions == 0, is F3DS_OK with all ids F3DS_NO_LABEL, and
+ * leaves a state the next frame matches nothing in.  Threading as for a context: one tracker per host thread. */
+typedef struct f3ds_track_params {
+    uint32_t min_votes;           /* default 16                                              */
+    uint32_t min_permille;        /* default 300: votes per thousand labelled pixels of the region */
+    float depth_tol;              /* default 0.05f, relative to zp                           */
+} f3ds_track_params;
+typedef struct f3ds_track_result {
+    uint32_t n_regions;           /* as given                                                */
+    uint32_t n_nonempty;          /* regions with a labelled pixel                           */
+    uint32_t n_matched;           /* ... that took a previous id                             */
+    uint32_t n_new;               /* ... that got a new one                                  */
+    uint32_t n_retired;           /* previous slots that had an id and were not claimed      */
+    uint32_t n_entries;           /* distinct (i, j) pairs with votes                        */
+    uint32_t next_id;             /* after the update                                        */
+    uint32_t first_frame;         /* 1: there was no previous frame (first update, or after a reset); f3ds_track_assign writes 0 */
+    uint64_t n_labelled, n_votes; /* labelled pixels; those of them that voted               */
+} f3ds_track_result;
+typedef struct f3ds_tracker f3ds_tracker;
+void f3ds_default_track_params(f3ds_track_params* p);
+/* a tracker on `device` with a stream of its own; params == NULL: the defaults */
+int f3ds_tracker_create(int device, const f3ds_track_params* params, f3ds_tracker** out);
+void f3ds_tracker_destroy(f3ds_tracker* t);
+int f3ds_tracker_set_stream(f3ds_tracker* t, void* hip_stream);
+/* forget the previous frame and the format; next_id is kept */
+int f3ds_tracker_reset(f3ds_tracker* t);
+int f3ds_tracker_update(f3ds_tracker* t, const f3ds_rgbd_format* fmt, const void* depth, const uint32_t* labels, uint32_t n_regions, int inputs_on_device,
+                        const float* pose12 /* NULL = identity */, uint32_t* track_ids, int ids_on_device, f3ds_track_result* result /* may be NULL */);
+/* id[] of the last update that returned F3DS_OK: n_regions entries.  id_of_region == NULL: count only; F3DS_ERR_CAPACITY when cap is smaller than the count */
+int f3ds_tracker_get_ids(f3ds_tracker* t, uint32_t* id_of_region, size_t cap, size_t* n_out);
+/* host arithmetic only, no device needed: steps 2 and 3 for n records {float x, y, z; uint32 rgba} -- pixel[k] = the previous frame's pixel index record k lands
+ * on, or -1; zp[k] = its depth there (written for every record) */
+int f3ds_track_reproject(const f3ds_rgbd_format* fmt, const float* pose12, const void* points16, size_t n, int32_t* pixel, float* zp);
+/* host arithmetic only, no device needed: step 5.  size: n_regions; entries: n_entries rows (i, j, c), every (i, j) at most once, any order; prev_id: n_prev;
+ * *next_id in and out; id_of_region: n_regions out; result may be NULL, params == NULL: the defaults.  F3DS_ERR_ARG also for an entry with i >= n_regions,
+ * j >= n_prev, prev_id[j] == F3DS_NO_LABEL or c > size[i].  On an error nothing is written. */
+int f3ds_track_assign(const f3ds_track_params* params, const uint32_t* size, uint32_t n_regions, const uint32_t* entries, size_t n_entries,
+                      const uint32_t* prev_id, uint32_t n_prev, uint32_t* next_id, uint32_t* id_of_region, f3ds_track_result* result);
+
 /* Clustering::cluster(threshold) again on the supervoxels of the last f3ds_segment call, with
  * possibly different metric / merging settings (src/clustering.cpp:670-679).  Only the merge
  * fields of `params` are read. */
