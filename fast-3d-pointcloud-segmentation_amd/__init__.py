@@ -299,6 +299,44 @@ def _check(lib, rc):
     raise F3dsError(rc, text)
 
 
+def _two_call(lib, fn, lead, outs, tail=()):
+    """The two-call protocol of the C getters, ``fn(*lead, outputs..., cap, *tail, &n)``: once with null outputs for the count n, then with one fresh
+    array per ``(dtype, trailing shape)`` of ``outs``, n entries each.  Returns the list of arrays."""
+    n = ctypes.c_size_t()
+    _check(lib, fn(*lead, *[None] * len(outs), 0, *tail, ctypes.byref(n)))
+    arrays = [np.zeros((n.value,) + tuple(shape), dtype) for dtype, shape in outs]
+    _check(lib, fn(*lead, *[a.ctypes.data for a in arrays], n.value, *tail, ctypes.byref(n)))
+    return arrays
+
+
+_U32, _F32, _XYZ, _PAIR = (np.uint32, ()), (np.float32, ()), (np.float32, (3,)), (np.uint32, (2,))      # output kinds of _two_call
+
+
+def _label_buffer(buf, n, what, name="labels_out"):
+    """The host array a call writes one uint32 per ``what`` into: a fresh one, or the caller's own after a check."""
+    if buf is None:
+        return np.empty(n, np.uint32)
+    if not (isinstance(buf, np.ndarray) and buf.dtype == np.uint32 and buf.flags.c_contiguous and buf.size == n):
+        raise ValueError("%s must be a contiguous uint32 array with one entry per %s" % (name, what))
+    return buf
+
+
+class _Handle:
+    """close() / __del__ of an object that owns a C handle; ``_destroy`` names the library function that releases it."""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "handle", None):
+            getattr(self.lib, self._destroy)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def pack_supervoxels(segm):
     """{label: dict(voxels_xyz (n,3) f32, voxels_rgba (n,) u32, centroid (3,), normal (3,))} -- the shape of the reference's
     ``std::map<uint32_t, pcl::Supervoxel::Ptr>`` -- -> dict of the arrays f3ds_supervoxel_set points at (rows in the dict's own order)."""
@@ -462,8 +500,10 @@ def track_assign(size, entries, prev_id, next_id, params=None):
     return ids, int(nxt.value), res
 
 
-class Tracker:
+class Tracker(_Handle):
     """f3ds_tracker (include/f3ds.h): persistent ids for the regions of consecutive RGB-D frames.  Not thread-safe; one per camera."""
+
+    _destroy = "f3ds_tracker_destroy"
 
     def __init__(self, device=0, params=None):
         self.lib = load_library()
@@ -472,17 +512,6 @@ class Tracker:
         self.handle = h
         self.device = device
         self.result = TrackResult()
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.f3ds_tracker_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __enter__(self):
         return self
@@ -521,28 +550,21 @@ class Tracker:
         lab = np.ascontiguousarray(labels, np.uint32).reshape(-1)
         if lab.size != n:
             raise ValueError("labels must hold one entry per pixel")
-        if ids_out is None:
-            ids = np.empty(n, np.uint32)
-        else:
-            ids = ids_out
-            if not (isinstance(ids, np.ndarray) and ids.dtype == np.uint32 and ids.flags.c_contiguous and ids.size == n):
-                raise ValueError("ids_out must be a contiguous uint32 array with one entry per pixel")
+        ids = _label_buffer(ids_out, n, "pixel", "ids_out")
         _check(self.lib, self.lib.f3ds_tracker_update(self.handle, ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), 0, mp, ids.ctypes.data, 0,
                                                       ctypes.byref(self.result)))
         return ids
 
     def ids(self):
         """f3ds_tracker_get_ids: the track id of every region of the last update (NO_LABEL for a region without a labelled pixel); LogicError before any."""
-        n = ctypes.c_size_t()
-        _check(self.lib, self.lib.f3ds_tracker_get_ids(self.handle, None, 0, ctypes.byref(n)))
-        out = np.empty(n.value, np.uint32)
-        _check(self.lib, self.lib.f3ds_tracker_get_ids(self.handle, out.ctypes.data, n.value, ctypes.byref(n)))
-        return out
+        return _two_call(self.lib, self.lib.f3ds_tracker_get_ids, [self.handle], [_U32])[0]
 
 
 # ---- device context ------------------------------------------------------------------------------
-class Context:
+class Context(_Handle):
     """One (device, stream) pair with its grow-only scratch.  Not thread-safe; one per GPU/stream."""
+
+    _destroy = "f3ds_destroy"
 
     def __init__(self, device=0):
         self.lib = load_library()
@@ -553,16 +575,9 @@ class Context:
         self.result = Result()
         self._n = 0
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.f3ds_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _get(self, what, outs, *lead, tail=()):
+        """the arrays of f3ds_get_<what> (see _two_call)"""
+        return _two_call(self.lib, getattr(self.lib, "f3ds_get_" + what), [self.handle, *lead], outs, tail)
 
     def set_stream(self, hip_stream_ptr):
         _check(self.lib, self.lib.f3ds_set_stream(self.handle, ctypes.c_void_p(hip_stream_ptr)))
@@ -578,12 +593,7 @@ class Context:
             self._n = count
             return None
         pts = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
-        if labels_out is None:
-            labels = np.empty(len(pts), np.uint32)
-        else:       # the caller's own buffer (reused from call to call: a fresh 80 MB array for a 20M-point scene is 20 000 page faults inside the download)
-            labels = labels_out
-            if not (isinstance(labels, np.ndarray) and labels.dtype == np.uint32 and labels.flags.c_contiguous and labels.size == len(pts)):
-                raise ValueError("labels_out must be a contiguous uint32 array with one entry per point")
+        labels = _label_buffer(labels_out, len(pts), "point")      # (the caller's own buffer, reused from call to call: a fresh 80 MB array for a 20M-point scene is 20 000 page faults inside the download)
         _check(self.lib, self.lib.f3ds_segment(self.handle, pts.ctypes.data, len(pts), 0, ctypes.byref(params), labels.ctypes.data, 0,
                                                ctypes.byref(self.result)))
         self._n = len(pts)
@@ -601,12 +611,7 @@ class Context:
             self._n = n
             return None
         f, d, c = _rgbd_images(fmt, depth, color)
-        if labels_out is None:
-            labels = np.empty(n, np.uint32)
-        else:
-            labels = labels_out
-            if not (isinstance(labels, np.ndarray) and labels.dtype == np.uint32 and labels.flags.c_contiguous and labels.size == n):
-                raise ValueError("labels_out must be a contiguous uint32 array with one entry per pixel")
+        labels = _label_buffer(labels_out, n, "pixel")
         _check(self.lib, self.lib.f3ds_segment_rgbd(self.handle, ctypes.byref(f), d.ctypes.data, c.ctypes.data, 0, ctypes.byref(params), labels.ctypes.data, 0,
                                                     ctypes.byref(self.result)))
         self._n = n
@@ -615,11 +620,7 @@ class Context:
     def points(self):
         """f3ds_get_points: the (N, 4) float32 records the last segment call ran on, when the context holds them (segment_rgbd, or segment
         with host points); LogicError when they were the caller's device buffer or nothing has run."""
-        n = ctypes.c_size_t()
-        _check(self.lib, self.lib.f3ds_get_points(self.handle, None, 0, 0, ctypes.byref(n)))
-        pts = np.empty((n.value, 4), np.float32)
-        _check(self.lib, self.lib.f3ds_get_points(self.handle, pts.ctypes.data, n.value, 0, ctypes.byref(n)))
-        return pts
+        return self._get("points", [(np.float32, (4,))], tail=[0])[0]
 
     def recluster(self, params):
         labels = np.empty(int(self.result.n_points) or self._n, np.uint32)      # f3ds_recluster writes one label per point of the frame
@@ -658,11 +659,7 @@ class Context:
     def merge_tree(self):
         """f3ds_get_merge_tree: the merges of the last cluster run in the order performed, as (survivor, absorbed, weight) arrays of
         supervoxel labels (the caller's keys after cluster_supervoxels) and float32 weights."""
-        n = ctypes.c_size_t()
-        _check(self.lib, self.lib.f3ds_get_merge_tree(self.handle, None, None, None, 0, ctypes.byref(n)))
-        a = np.zeros(n.value, np.uint32); b = np.zeros(n.value, np.uint32); w = np.zeros(n.value, np.float32)
-        _check(self.lib, self.lib.f3ds_get_merge_tree(self.handle, a.ctypes.data, b.ctypes.data, w.ctypes.data, n.value, ctypes.byref(n)))
-        return a, b, w
+        return tuple(self._get("merge_tree", [_U32, _U32, _F32]))
 
     def evaluate(self, truth_point_labels):
         """Scores of the current segmentation against per-point ground-truth labels (Testing::eval_performance)."""
@@ -689,54 +686,26 @@ class Context:
 
     def voxel_centroid_cloud(self):
         """getVoxelCentroidCloud / getLabeledVoxelCloud: (xyz, rgba, supervoxel label) per voxel in leaf order."""
-        n = ctypes.c_size_t()
-        _check(self.lib, self.lib.f3ds_get_voxel_centroid_cloud(self.handle, None, None, None, 0, ctypes.byref(n)))
-        xyz = np.zeros((n.value, 3), np.float32); rgba = np.zeros(n.value, np.uint32); lab = np.zeros(n.value, np.uint32)
-        _check(self.lib, self.lib.f3ds_get_voxel_centroid_cloud(self.handle, xyz.ctypes.data, rgba.ctypes.data, lab.ctypes.data, n.value, ctypes.byref(n)))
-        return xyz, rgba, lab
+        return tuple(self._get("voxel_centroid_cloud", [_XYZ, _U32, _U32]))
 
     def supervoxels(self):
         """The supervoxel_clusters map: dict of arrays label, xyz, rgb, normal, n_voxels (ascending label)."""
-        n = ctypes.c_size_t()
-        _check(self.lib, self.lib.f3ds_get_supervoxels(self.handle, None, None, None, None, None, 0, ctypes.byref(n)))
-        k = n.value
-        out = dict(label=np.zeros(k, np.uint32), xyz=np.zeros((k, 3), np.float32), rgb=np.zeros((k, 3), np.float32), normal=np.zeros((k, 3), np.float32),
-                   n_voxels=np.zeros(k, np.uint32))
-        _check(self.lib, self.lib.f3ds_get_supervoxels(self.handle, out["label"].ctypes.data, out["xyz"].ctypes.data, out["rgb"].ctypes.data, out["normal"].ctypes.data,
-                                                       out["n_voxels"].ctypes.data, k, ctypes.byref(n)))
-        return out
+        return dict(zip(("label", "xyz", "rgb", "normal", "n_voxels"), self._get("supervoxels", [_U32, _XYZ, _XYZ, _XYZ, _U32])))
 
     def refine_supervoxels(self, num_itr):
         """refineSupervoxels(num_itr): dict with per-voxel ``voxel_label`` / ``voxel_normal`` (leaf order) and the refined
         supervoxel map ``label, xyz, rgb, normal, n_voxels``.  The frame's own supervoxels and clustering are untouched."""
         _check(self.lib, self.lib.f3ds_refine_supervoxels(self.handle, int(num_itr)))
-        n = ctypes.c_size_t()
-        _check(self.lib, self.lib.f3ds_get_refined_voxels(self.handle, None, None, 0, ctypes.byref(n)))
-        vl = np.zeros(n.value, np.uint32); vn = np.zeros((n.value, 3), np.float32)
-        _check(self.lib, self.lib.f3ds_get_refined_voxels(self.handle, vl.ctypes.data, vn.ctypes.data, n.value, ctypes.byref(n)))
-        _check(self.lib, self.lib.f3ds_get_refined_supervoxels(self.handle, None, None, None, None, None, 0, ctypes.byref(n)))
-        k = n.value
-        out = dict(voxel_label=vl, voxel_normal=vn, label=np.zeros(k, np.uint32), xyz=np.zeros((k, 3), np.float32), rgb=np.zeros((k, 3), np.float32),
-                   normal=np.zeros((k, 3), np.float32), n_voxels=np.zeros(k, np.uint32))
-        _check(self.lib, self.lib.f3ds_get_refined_supervoxels(self.handle, out["label"].ctypes.data, out["xyz"].ctypes.data, out["rgb"].ctypes.data,
-                                                               out["normal"].ctypes.data, out["n_voxels"].ctypes.data, k, ctypes.byref(n)))
-        return out
+        return dict(zip(("voxel_label", "voxel_normal", "label", "xyz", "rgb", "normal", "n_voxels"),
+                        self._get("refined_voxels", [_U32, _XYZ]) + self._get("refined_supervoxels", [_U32, _XYZ, _XYZ, _XYZ, _U32])))
 
     def supervoxel_adjacency(self):
         """getSupervoxelAdjacency after clear_adjacency: (E, 2) array of label pairs a < b, sorted."""
-        n = ctypes.c_size_t()
-        _check(self.lib, self.lib.f3ds_get_supervoxel_adjacency(self.handle, None, 0, ctypes.byref(n)))
-        pairs = np.zeros((n.value, 2), np.uint32)
-        _check(self.lib, self.lib.f3ds_get_supervoxel_adjacency(self.handle, pairs.ctypes.data, n.value, ctypes.byref(n)))
-        return pairs
+        return self._get("supervoxel_adjacency", [_PAIR])[0]
 
     def region_adjacency(self):
         """get_currentstate().second after cluster(): (K, 2) array of surviving supervoxel labels a < b, sorted."""
-        n = ctypes.c_size_t()
-        _check(self.lib, self.lib.f3ds_get_region_adjacency(self.handle, None, 0, ctypes.byref(n)))
-        pairs = np.zeros((n.value, 2), np.uint32)
-        _check(self.lib, self.lib.f3ds_get_region_adjacency(self.handle, pairs.ctypes.data, n.value, ctypes.byref(n)))
-        return pairs
+        return self._get("region_adjacency", [_PAIR])[0]
 
     def cluster_supervoxels(self, sv, adjacency_pairs, params):
         """f3ds_cluster_supervoxels: Clustering::set_initialstate(segm, adj) + cluster(threshold) on caller-supplied supervoxels.
@@ -764,29 +733,14 @@ class Context:
 
     def regions(self):
         """get_currentstate().first: dict of arrays label, n_voxels, xyz (centroid_), normal (normal_), rgb (mean_color) per merged region, ascending key."""
-        n = ctypes.c_size_t()
-        _check(self.lib, self.lib.f3ds_get_regions(self.handle, None, None, None, None, None, 0, ctypes.byref(n)))
-        k = n.value
-        out = dict(label=np.zeros(k, np.uint32), n_voxels=np.zeros(k, np.uint32), xyz=np.zeros((k, 3), np.float32), normal=np.zeros((k, 3), np.float32),
-                   rgb=np.zeros((k, 3), np.float32))
-        _check(self.lib, self.lib.f3ds_get_regions(self.handle, out["label"].ctypes.data, out["n_voxels"].ctypes.data, out["xyz"].ctypes.data, out["normal"].ctypes.data,
-                                                   out["rgb"].ctypes.data, k, ctypes.byref(n)))
-        return out
+        return dict(zip(("label", "n_voxels", "xyz", "normal", "rgb"), self._get("regions", [_U32, _U32, _XYZ, _XYZ, _XYZ])))
 
     def region_voxels(self):
         """The regions' voxels_ clouds concatenated in the order of regions(): (xyz, rgba, voxel index)."""
-        n = ctypes.c_size_t()
-        _check(self.lib, self.lib.f3ds_get_region_voxels(self.handle, None, None, None, 0, ctypes.byref(n)))
-        xyz = np.zeros((n.value, 3), np.float32); rgba = np.zeros(n.value, np.uint32); idx = np.zeros(n.value, np.uint32)
-        _check(self.lib, self.lib.f3ds_get_region_voxels(self.handle, xyz.ctypes.data, rgba.ctypes.data, idx.ctypes.data, n.value, ctypes.byref(n)))
-        return xyz, rgba, idx
+        return tuple(self._get("region_voxels", [_XYZ, _U32, _U32]))
 
     def voxel_cloud(self):
-        n = ctypes.c_size_t()
-        _check(self.lib, self.lib.f3ds_get_voxel_cloud(self.handle, None, None, None, 0, ctypes.byref(n)))
-        xyz = np.zeros((n.value, 3), np.float32); lab = np.zeros(n.value, np.uint32); rgba = np.zeros(n.value, np.uint32)
-        _check(self.lib, self.lib.f3ds_get_voxel_cloud(self.handle, xyz.ctypes.data, lab.ctypes.data, rgba.ctypes.data, n.value, ctypes.byref(n)))
-        return xyz, lab, rgba
+        return tuple(self._get("voxel_cloud", [_XYZ, _U32, _U32]))
 
     def merge_layout(self):
         """(waves per frame, per-edge arrays in LDS) of the merge kernel the last cluster stage ran; (0, 0) = d_merge (F3DS_DBG_MERGE_LAYOUT)."""
@@ -815,24 +769,18 @@ class Context:
 
     def tile_list_lengths(self):
         """Length of every 128-voxel tile's one-ring list; 0xFFFFFFFF = the tile overflowed the LDS tables (F3DS_DBG_TILE_LIST_LEN)."""
-        nb = ctypes.c_size_t()
-        _check(self.lib, self.lib.f3ds_get_debug(self.handle, 21, None, 0, ctypes.byref(nb)))
-        buf = np.zeros(nb.value // 4, np.uint32)
-        _check(self.lib, self.lib.f3ds_get_debug(self.handle, 21, buf.ctypes.data, nb.value, ctypes.byref(nb)))
-        return buf
+        return self._get("debug", [(np.uint8, ())], DBG_INFO["TILE_LIST_LEN"])[0].view(np.uint32)
 
     def debug(self, name):
-        nb = ctypes.c_size_t()
-        _check(self.lib, self.lib.f3ds_get_debug(self.handle, DBG[name], None, 0, ctypes.byref(nb)))
-        buf = np.zeros(nb.value, np.uint8)
-        _check(self.lib, self.lib.f3ds_get_debug(self.handle, DBG[name], buf.ctypes.data, nb.value, ctypes.byref(nb)))
-        return buf.view(DBG_DTYPE[name])
+        return self._get("debug", [(np.uint8, ())], DBG[name])[0].view(DBG_DTYPE[name])
 
 
-class FrameStream:
+class FrameStream(_Handle):
     """Frame pipeline (f3ds_stream_*): frames in from host memory, per-point labels out in submission order, up to
     ``depth`` frames in flight on ``groups`` host threads.  ``submit`` returns False instead of blocking when the
     pipeline is full; ``next`` returns (tag, labels, Result) of the oldest frame, None when nothing is in flight."""
+
+    _destroy = "f3ds_stream_destroy"
 
     def __init__(self, device=0, depth=8, groups=0):
         self.lib = load_library()
@@ -840,17 +788,6 @@ class FrameStream:
         _check(self.lib, self.lib.f3ds_stream_create(device, depth, groups, ctypes.byref(h)))
         self.handle = h
         self.depth = depth
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.f3ds_stream_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __enter__(self):
         return self
@@ -928,10 +865,12 @@ class FrameStream:
             yield self.next()
 
 
-class MultiGpu:
+class MultiGpu(_Handle):
     """f3ds_multi_*: a batch of independent frames sharded over the GPUs of one node from ONE process (frame i on
     devices[i mod G], one host thread per GPU inside the library), per-point labels gathered on devices[0] over RCCL and
     returned as host arrays.  The torch.distributed form of the same partitioning (one process per GPU) is batch.py."""
+
+    _destroy = "f3ds_multi_destroy"
 
     def __init__(self, devices=None, n_devices=None, max_frames_per_device=8):
         self.lib = load_library()
@@ -944,17 +883,6 @@ class MultiGpu:
         if rc:
             raise F3dsError(rc, self.lib.f3ds_strerror(rc).decode() + " " + self.lib.f3ds_multi_last_error().decode())
         self.handle = h
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.f3ds_multi_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def devices(self):
         return self.lib.f3ds_multi_devices(self.handle)

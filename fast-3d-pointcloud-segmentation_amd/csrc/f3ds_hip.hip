@@ -399,6 +399,25 @@ struct Batch {
     hipStream_t st = nullptr;
     f3ds_ctx* owner = nullptr;     // holds the argument arena and the stage events
 };
+// An entry point that records kernels starts from one of these two (after g_sw.read() and hipSetDevice): the batch on its owner's stream, the launch
+// widths of the call, and nothing left recorded in its frames.  One context ...
+inline Batch batch_of(f3ds_ctx* c) {
+    Batch b; b.owner = c; b.st = c->stream;
+    set_launch_shape(&c, 1); reset_recording(c);
+    b.fr.push_back(c);
+    return b;
+}
+// ... or ctxs[0..nctx) on the first one's stream: a context with another stream is waited for first (the frame state is read on the owner's stream)
+int batch_of(f3ds_ctx** ctxs, int nctx, Batch& b) {
+    b.owner = ctxs[0]; b.st = ctxs[0]->stream;
+    set_launch_shape(ctxs, nctx);
+    for (int i = 0; i < nctx; ++i) {
+        if (ctxs[i]->stream != b.st) HIPCHECK(hipStreamSynchronize(ctxs[i]->stream));
+        reset_recording(ctxs[i]);
+        b.fr.push_back(ctxs[i]);
+    }
+    return F3DS_OK;
+}
 
 thread_local double g_t_wait = 0, g_t_launch = 0;
 // F3DS_TRACE_ERR=1: say which stage refused a frame (development aid)
@@ -994,6 +1013,58 @@ int for_frames(Batch& b, F&& fn) {
     return F3DS_OK;
 }
 void stage_mark(Batch& b, int i) { (void)hipEventRecord(b.owner->ev[i], b.st); }
+// device time of stages first ... last - 1 of a call whose stream has been waited for (HIP events on that stream): ms_stage[k] = from mark k to mark k + 1
+void stage_times(const f3ds_ctx* owner, int first, int last, float* ms_stage) {
+    for (int k = first; k < last; ++k) { float ms = 0; if (hipEventElapsedTime(&ms, owner->ev[k], owner->ev[k + 1]) == hipSuccess) ms_stage[k] = ms; }
+}
+
+// The call's kernels wait for its uploads, which went through the device's copy stream `up` (the events of a call's copies are its owner's, made on first use)
+int await_uploads(Batch& b, hipStream_t up) {
+    hipEvent_t& ev = b.owner->ev_copy[0];
+    if (!ev) HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(ev, up));
+    HIPCHECK(hipStreamWaitEvent(b.st, ev, 0));
+    return F3DS_OK;
+}
+// Host outputs leave through the device's download stream, and are queued there only once they exist: that stream must never sit blocked behind unfinished
+// compute.  download_begin() waits for what the call's stream holds so far and gives the stream to copy on (nullptr with F3DS_COPY_STREAM=0: the call's own);
+// download_queued() marks the end of the copies on that stream and download_wait() waits for the mark: work that need not wait for the copies goes between the two.
+int download_begin(Batch& b, hipStream_t* dl) {
+    *dl = g_sw.copy_stream ? copy_stream_of(b.owner->device, g_sw.copy_duplex ? 1 : 0) : nullptr;
+    if (!*dl) return F3DS_OK;
+    for (int k = 1; k < 3; ++k) if (!b.owner->ev_copy[k]) HIPCHECK(hipEventCreateWithFlags(&b.owner->ev_copy[k], hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(b.owner->ev_copy[1], b.st));
+    HIPCHECK(timed_sync(b.owner->ev_copy[1]));
+    return F3DS_OK;
+}
+int download_queued(Batch& b, hipStream_t dl) { if (dl) HIPCHECK(hipEventRecord(b.owner->ev_copy[2], dl)); return F3DS_OK; }
+int download_wait(Batch& b, hipStream_t dl) { if (dl) HIPCHECK(timed_sync(b.owner->ev_copy[2])); return F3DS_OK; }
+// Start of every accessor: ARG for no context, LOGIC for a context that does not hold what the call needs -- both before any HIP call --, then the
+// context's device and everything queued on its stream.
+enum FrameNeed { NEED_NOTHING = 0, NEED_FRAME = 1, NEED_VOXEL_GRID = 2 /* not caller-supplied supervoxels */, NEED_REFINED = 4 };
+int on_frame(f3ds_ctx* c, int need = NEED_FRAME) {
+    if (!c) return F3DS_ERR_ARG;
+    if (((need & NEED_FRAME) && !c->have_frame) || ((need & NEED_VOXEL_GRID) && c->user_mode) || ((need & NEED_REFINED) && c->refined_itr < 0)) return F3DS_ERR_LOGIC;
+    HIPCHECK(hipSetDevice(c->device));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    return F3DS_OK;
+}
+// Output of an accessor that learns its entry count by walking the state: every entry is counted, those there is room() for are written, and
+// finish() reports the count -- with F3DS_ERR_CAPACITY when an array was asked for (any) that did not hold them all: its first `cap` entries stand.
+struct Capped {
+    size_t cap; bool any; size_t k = 0;
+    bool room() const { return k < cap; }
+    void next() { ++k; }
+    int finish(size_t* n_out) const { if (n_out) *n_out = k; return (k > cap && any) ? F3DS_ERR_CAPACITY : F3DS_OK; }
+};
+// ... and of one that knows its count n beforehand, all or nothing: n is reported; true = the caller's arrays take all n entries, go on and write
+// them; false = *rc is the accessor's result (F3DS_OK without any array, F3DS_ERR_CAPACITY with too short a one: nothing is written)
+inline bool all_fit(size_t n, size_t cap, bool any, size_t* n_out, int* rc) {
+    if (n_out) *n_out = n;
+    *rc = (any && cap < n) ? F3DS_ERR_CAPACITY : F3DS_OK;
+    return any && cap >= n;
+}
+inline void put3(float* dst, size_t k, const float* src) { if (dst) { dst[3 * k] = src[0]; dst[3 * k + 1] = src[1]; dst[3 * k + 2] = src[2]; } }
 
 // device address of a pinned host buffer (nullptr for pageable memory, which the device cannot reach)
 static uint32_t* pinned_device_alias(uint32_t* host) {
@@ -1033,21 +1104,15 @@ int run_cluster(Batch& b, const f3ds_params* prm, uint32_t* const* labels_of, co
     {
         bool want = false;
         for (size_t i = 0; i < b.fr.size(); ++i) if (labels_of && labels_of[index_of[i]] && !b.fr[i]->user_labels && b.fr[i]->n) want = true;
-        hipStream_t dl = (want && !labels_on_device && g_sw.copy_stream) ? copy_stream_of(b.fr[0]->device, g_sw.copy_duplex ? 1 : 0) : nullptr;
-        if (dl) {      // queued on the copy stream only once the labels exist: that stream must never sit blocked behind unfinished compute
-            for (int k = 1; k < 3; ++k) if (!b.owner->ev_copy[k]) HIPCHECK(hipEventCreateWithFlags(&b.owner->ev_copy[k], hipEventDisableTiming));
-            HIPCHECK(hipEventRecord(b.owner->ev_copy[1], b.st));
-            HIPCHECK(timed_sync(b.owner->ev_copy[1]));
-        }
+        hipStream_t dl = nullptr;
+        if (want && !labels_on_device && (rc = download_begin(b, &dl))) return rc;
         for (size_t i = 0; i < b.fr.size(); ++i) {
             f3ds_ctx* c = b.fr[i];
             uint32_t* out = labels_of ? labels_of[index_of[i]] : nullptr;
             if (out && !c->user_labels && c->n) HIPCHECK(hipMemcpyAsync(out, c->labels.p, (size_t)c->n * 4, hipMemcpyDeviceToHost, dl ? dl : b.st));
             c->user_labels = nullptr;
         }
-        if (dl) HIPCHECK(hipEventRecord(b.owner->ev_copy[2], dl));
-        if ((rc = flush_sync(b))) return rc;
-        if (dl) HIPCHECK(timed_sync(b.owner->ev_copy[2]));
+        if ((rc = download_queued(b, dl)) || (rc = flush_sync(b)) || (rc = download_wait(b, dl))) return rc;      // (the frames' counters come to the host while the labels travel)
     }
     {
         // a frame whose merge loop re-weights more edges than its event arrays hold (huge regions of tiny supervoxels)
@@ -1199,11 +1264,7 @@ int segment_batch_from(f3ds_ctx** ctxs, int nctx, Source&& source, int sources_o
         c->res.n_points = c->n; c->res.sweeps = sweeps;
         b.fr.push_back(c); index_of.push_back(i);
     }
-    if (up_stream && uploaded) {      // the call's kernels wait for its uploads, which went through the device's copy stream
-        if (!b.owner->ev_copy[0]) HIPCHECK(hipEventCreateWithFlags(&b.owner->ev_copy[0], hipEventDisableTiming));
-        HIPCHECK(hipEventRecord(b.owner->ev_copy[0], up_stream));
-        HIPCHECK(hipStreamWaitEvent(b.st, b.owner->ev_copy[0], 0));
-    }
+    if (up_stream && uploaded) { const int urc = await_uploads(b, up_stream); if (urc) return urc; }
     auto drop_dead = [&](auto&& dead) -> int {      // frames without voxels leave the batch with all labels = F3DS_NO_LABEL
         std::vector<f3ds_ctx*> keep; std::vector<int> keep_idx;
         for (size_t i = 0; i < b.fr.size(); ++i) {
@@ -1308,8 +1369,7 @@ int segment_batch_from(f3ds_ctx** ctxs, int nctx, Source&& source, int sources_o
     if ((rc = run_cluster(b, prm, point_labels, index_of, labels_on_device))) return rc;
     HIPCHECK(hipStreamSynchronize(b.st));
     float stage[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // device time of each stage of the whole batch (HIP events on the batch's stream)
-    for (int k = 0; k < 7; ++k) { float ms = 0; if (hipEventElapsedTime(&ms, b.owner->ev[k], b.owner->ev[k + 1]) == hipSuccess) stage[k] = ms; }
+    stage_times(b.owner, 0, 7, stage);      // (of the whole batch)
     // the d_normals launch (inside stage 1): a HIP event pair around that one dispatch on the call's stream (the time it waits at the head of its queue
     // for a compute unit with room for its first workgroup + its execution)
     if (!b.fr.empty()) { float ms = 0; if (hipEventElapsedTime(&ms, b.owner->ev[9], b.owner->ev[10]) == hipSuccess) stage[7] = ms; }
@@ -1382,9 +1442,8 @@ int f3ds_segment_rgbd(f3ds_ctx* c, const f3ds_rgbd_format* fmt, const void* dept
 int f3ds_get_points(f3ds_ctx* c, void* points16, size_t cap, int dst_on_device, size_t* n_out) {
     if (!c || (!points16 && !n_out)) return F3DS_ERR_ARG;
     if (!c->d_pts || c->d_pts != c->pts.p) return F3DS_ERR_LOGIC;
-    if (n_out) *n_out = c->n;
-    if (!points16) return F3DS_OK;
-    if (cap < c->n) return F3DS_ERR_CAPACITY;
+    int rc;
+    if (!all_fit(c->n, cap, points16 != nullptr, n_out, &rc)) return rc;
     HIPCHECK(hipSetDevice(c->device));
     if (c->n) HIPCHECK(hipMemcpy(points16, c->pts.p, (size_t)c->n * 16, dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
     return F3DS_OK;
@@ -1396,15 +1455,14 @@ int f3ds_recluster(f3ds_ctx* c, const f3ds_params* prm, uint32_t* point_labels, 
     const auto t0 = std::chrono::steady_clock::now();
     g_sw.read();
     HIPCHECK(hipSetDevice(c->device));
-    Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); set_launch_shape(&c, 1);
-    reset_recording(c);
+    Batch b = batch_of(c);
     { const int crc = clear_counters(c, c->stream, &DevCounters::error); if (crc) return crc; }
     stage_mark(b, 4);
     std::vector<int> idx{0}; uint32_t* lp[1] = {point_labels};
     int rc = run_cluster(b, prm, lp, idx, labels_on_device);
     if (rc) return rc;
     HIPCHECK(hipStreamSynchronize(b.st));
-    for (int k = 4; k < 7; ++k) { float ms = 0; if (hipEventElapsedTime(&ms, c->ev[k], c->ev[k + 1]) == hipSuccess) c->res.ms_stage[k] = ms; }
+    stage_times(c, 4, 7, c->res.ms_stage);
     c->res.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (result) *result = c->res;
     return F3DS_OK;
@@ -1476,7 +1534,7 @@ int f3ds_cluster_supervoxels(f3ds_ctx* c, const f3ds_supervoxel_set* sv, const u
         if (result) *result = c->res;
         return F3DS_OK;
     }
-    Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); set_launch_shape(&c, 1);
+    Batch b = batch_of(c);      // (clears the recording once more: nothing was recorded since)
     uint32_t *d_src, *d_voff, *d_rgba, *loff, *hcount, *owner, *rcnt0, *ea0, *eb0; float *d_xyz, *d_cent, *d_nrm, *rows, *racc0, *rrec0, *hc; int *row_voxel, *pt_voxel; unsigned char* ralive0;
     ENSURE(c->u_src, S + 1u, d_src); ENSURE(c->u_voff, S + 1u, d_voff); ENSURE(c->u_xyz, (size_t)Vt * 3, d_xyz); ENSURE(c->u_rgba, Vt, d_rgba);
     ENSURE(c->u_cent, (size_t)S * 3, d_cent); ENSURE(c->u_nrm, (size_t)S * 3, d_nrm);
@@ -1510,7 +1568,7 @@ int f3ds_cluster_supervoxels(f3ds_ctx* c, const f3ds_supervoxel_set* sv, const u
     uint32_t* lp[1] = {voxel_labels}; std::vector<int> idx{0};
     if ((rc = run_cluster(b, prm, lp, idx, 0))) return rc;
     HIPCHECK(hipStreamSynchronize(b.st));
-    for (int k = 4; k < 7; ++k) { float ms = 0; if (hipEventElapsedTime(&ms, c->ev[k], c->ev[k + 1]) == hipSuccess) c->res.ms_stage[k] = ms; }
+    stage_times(c, 4, 7, c->res.ms_stage);
     if (region_of_sv) {
         std::vector<uint32_t> root(S + 1u);
         HIPCHECK(hipMemcpy(root.data(), c->root.p, (size_t)(S + 1) * 4, hipMemcpyDeviceToHost));
@@ -1559,102 +1617,82 @@ inline size_t rows_in_use(const f3ds_ctx* c, const std::vector<uint32_t>& loff) 
 
 // get_currentstate().first: the merged regions in ascending key (include/f3ds.h)
 extern "C" int f3ds_get_regions(f3ds_ctx* c, uint32_t* label, uint32_t* n_voxels, float* centroid_xyz, float* normal, float* mean_rgb, size_t cap, size_t* n_out) {
-    if (!c) return F3DS_ERR_ARG;
-    if (!c->have_frame) return F3DS_ERR_LOGIC;
-    HIPCHECK(hipSetDevice(c->device));
-    HIPCHECK(hipStreamSynchronize(c->stream));
+    if (const int frc = on_frame(c)) return frc;
     const uint32_t S0 = c->S0;
     std::vector<unsigned char> ralive; std::vector<uint32_t> rcnt; std::vector<float> rrec;
     int rc;
     if ((rc = fetch(c, c->ralive, S0 + 1, ralive)) || (rc = fetch(c, c->rcnt, S0 + 1, rcnt)) || (rc = fetch(c, c->rrec, (size_t)(S0 + 1) * 16, rrec))) return rc;
-    size_t k = 0;
+    Capped out{cap, label || n_voxels || centroid_xyz || normal || mean_rgb};
     for (uint32_t h = 1; h <= S0; ++h) {
         if (!ralive[h]) continue;
-        if (k < cap) {
+        if (out.room()) {
             const float* r = &rrec[(size_t)h * 16];
-            if (label) label[k] = label_out(c, h);
-            if (n_voxels) n_voxels[k] = rcnt[h];
-            if (centroid_xyz) { centroid_xyz[3 * k] = r[0]; centroid_xyz[3 * k + 1] = r[1]; centroid_xyz[3 * k + 2] = r[2]; }
-            if (normal) { normal[3 * k] = r[3]; normal[3 * k + 1] = r[4]; normal[3 * k + 2] = r[5]; }
-            if (mean_rgb) { mean_rgb[3 * k] = r[6]; mean_rgb[3 * k + 1] = r[7]; mean_rgb[3 * k + 2] = r[8]; }
+            if (label) label[out.k] = label_out(c, h);
+            if (n_voxels) n_voxels[out.k] = rcnt[h];
+            put3(centroid_xyz, out.k, r); put3(normal, out.k, r + 3); put3(mean_rgb, out.k, r + 6);
         }
-        k++;
+        out.next();
     }
-    if (n_out) *n_out = k;
-    return (k > cap && (label || n_voxels || centroid_xyz || normal || mean_rgb)) ? F3DS_ERR_CAPACITY : F3DS_OK;
+    return out.finish(n_out);
 }
 
 extern "C" int f3ds_get_region_voxels(f3ds_ctx* c, float* xyz, uint32_t* rgba, uint32_t* voxel_index, size_t cap, size_t* n_out) {
-    if (!c) return F3DS_ERR_ARG;
-    if (!c->have_frame) return F3DS_ERR_LOGIC;
-    HIPCHECK(hipSetDevice(c->device));
-    HIPCHECK(hipStreamSynchronize(c->stream));
+    if (const int frc = on_frame(c)) return frc;
     std::vector<unsigned char> ralive; std::vector<std::vector<uint2>> leaves; std::vector<float> rows; std::vector<int> rv; std::vector<uint32_t> loff;
     int rc;
     if ((rc = region_leaves(c, ralive, leaves)) || (rc = fetch(c, c->loff, c->S0 + 2, loff))) return rc;
     const size_t nrows = rows_in_use(c, loff);
     if ((rc = fetch(c, c->rows, nrows * 12, rows)) || (rc = fetch(c, c->row_voxel, nrows, rv))) return rc;
-    size_t k = 0;
+    Capped out{cap, xyz || rgba || voxel_index};
     for (uint32_t h = 1; h <= c->S0; ++h)
         for (const uint2& leaf : leaves[h])
             for (uint32_t j = 0; j < leaf.y; ++j) {
-                if (k < cap) {
+                if (out.room()) {
                     const float* r = &rows[(size_t)(leaf.x + j) * 12];
-                    if (xyz) { xyz[3 * k] = r[6]; xyz[3 * k + 1] = r[7]; xyz[3 * k + 2] = r[8]; }
-                    if (rgba) rgba[k] = (uint32_t)r[9] << 16 | (uint32_t)r[10] << 8 | (uint32_t)r[11];
-                    if (voxel_index) voxel_index[k] = (uint32_t)rv[leaf.x + j];
+                    put3(xyz, out.k, r + 6);
+                    if (rgba) rgba[out.k] = (uint32_t)r[9] << 16 | (uint32_t)r[10] << 8 | (uint32_t)r[11];
+                    if (voxel_index) voxel_index[out.k] = (uint32_t)rv[leaf.x + j];
                 }
-                k++;
+                out.next();
             }
-    if (n_out) *n_out = k;
-    return (k > cap && (xyz || rgba || voxel_index)) ? F3DS_ERR_CAPACITY : F3DS_OK;
+    return out.finish(n_out);
 }
 
 extern "C" int f3ds_get_voxel_cloud(f3ds_ctx* c, float* xyz, uint32_t* label, uint32_t* rgba, size_t cap, size_t* n_out) {
-    if (!c) return F3DS_ERR_ARG;
-    if (!c->have_frame) return F3DS_ERR_LOGIC;
-    HIPCHECK(hipSetDevice(c->device));
-    HIPCHECK(hipStreamSynchronize(c->stream));
+    if (const int frc = on_frame(c)) return frc;
     const uint32_t S0 = c->S0;
     std::vector<unsigned char> ralive; std::vector<std::vector<uint2>> all_leaves; std::vector<uint32_t> loff; std::vector<float> rows;
     int rc;
     if ((rc = region_leaves(c, ralive, all_leaves)) || (rc = fetch(c, c->loff, S0 + 2, loff))) return rc;
     if ((rc = fetch(c, c->rows, rows_in_use(c, loff) * 12, rows))) return rc;
-    size_t k = 0; uint32_t cur = 0;
+    Capped out{cap, xyz || label || rgba}; uint32_t cur = 0;
     for (uint32_t h = 1; h <= S0; ++h) {
         if (!ralive[h]) continue;
         const std::vector<uint2>& leaves = all_leaves[h];      // the region's leaves (first payload row, rows) in voxels_ concatenation order
         for (const uint2& leaf : leaves)
             for (uint32_t j = 0; j < leaf.y; ++j) {
-                if (k < cap) {
-                    const float* r = &rows[(size_t)(leaf.x + j) * 12];
-                    if (xyz) { xyz[3 * k] = r[6]; xyz[3 * k + 1] = r[7]; xyz[3 * k + 2] = r[8]; }
-                    if (label) label[k] = cur;
-                    if (rgba) rgba[k] = f3ds_glasbey_256[cur % 256u];
+                if (out.room()) {
+                    put3(xyz, out.k, &rows[(size_t)(leaf.x + j) * 12 + 6]);
+                    if (label) label[out.k] = cur;
+                    if (rgba) rgba[out.k] = f3ds_glasbey_256[cur % 256u];
                 }
-                k++;
+                out.next();
             }
         cur++;
     }
-    if (n_out) *n_out = k;
-    return (k > cap && (xyz || label || rgba)) ? F3DS_ERR_CAPACITY : F3DS_OK;
+    return out.finish(n_out);
 }
 
 extern "C" int f3ds_get_voxel_centroid_cloud(f3ds_ctx* c, float* xyz, uint32_t* rgba, uint32_t* sv_label, size_t cap, size_t* n_out) {
-    if (!c) return F3DS_ERR_ARG;
-    if (!c->have_frame || c->user_mode) return F3DS_ERR_LOGIC;      // (caller-supplied supervoxels have no voxel grid)
-    HIPCHECK(hipSetDevice(c->device));
-    HIPCHECK(hipStreamSynchronize(c->stream));
+    if (const int frc = on_frame(c, NEED_FRAME | NEED_VOXEL_GRID)) return frc;
     const uint32_t V = c->V;
-    if (n_out) *n_out = V;
-    if (!xyz && !rgba && !sv_label) return F3DS_OK;
-    if (cap < V) return F3DS_ERR_CAPACITY;
-    std::vector<float> f; std::vector<uint32_t> o;
     int rc;
+    if (!all_fit(V, cap, xyz || rgba || sv_label, n_out, &rc)) return rc;
+    std::vector<float> f; std::vector<uint32_t> o;
     if ((rc = fetch(c, c->vf, (size_t)V * 12, f)) || (rc = fetch(c, c->owner0, V, o))) return rc;
     for (uint32_t v = 0; v < V; ++v) {
         const float* r = &f[(size_t)v * 12];
-        if (xyz) { xyz[3 * v] = r[0]; xyz[3 * v + 1] = r[1]; xyz[3 * v + 2] = r[2]; }
+        put3(xyz, v, r);
         if (rgba) rgba[v] = ((uint32_t)r[3] & 255u) << 16 | ((uint32_t)r[4] & 255u) << 8 | ((uint32_t)r[5] & 255u);
         if (sv_label) sv_label[v] = o[v];
     }
@@ -1671,8 +1709,7 @@ extern "C" int f3ds_refine_supervoxels(f3ds_ctx* c, int num_itr) {
     if (!c->have_frame || c->user_mode) return F3DS_ERR_LOGIC;
     g_sw.read();
     HIPCHECK(hipSetDevice(c->device));
-    Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); set_launch_shape(&c, 1);
-    reset_recording(c);
+    Batch b = batch_of(c);
     c->refined_itr = -1;
     const uint32_t V = c->V, S0 = c->S0;
     float *r_vf, *r_hc; uint32_t *r_owner, *r_hcount, *L; int *r_gvox, *seed; unsigned char* r_gact;
@@ -1698,20 +1735,15 @@ extern "C" int f3ds_refine_supervoxels(f3ds_ctx* c, int num_itr) {
 
 // the refined state: per voxel (leaf order) its supervoxel label (0 = none) and normal
 extern "C" int f3ds_get_refined_voxels(f3ds_ctx* c, uint32_t* sv_label, float* normal, size_t cap, size_t* n_out) {
-    if (!c) return F3DS_ERR_ARG;
-    if (!c->have_frame || c->refined_itr < 0) return F3DS_ERR_LOGIC;
-    HIPCHECK(hipSetDevice(c->device));
-    HIPCHECK(hipStreamSynchronize(c->stream));
+    if (const int frc = on_frame(c, NEED_FRAME | NEED_REFINED)) return frc;
     const uint32_t V = c->V;
-    if (n_out) *n_out = V;
-    if (!sv_label && !normal) return F3DS_OK;
-    if (cap < V) return F3DS_ERR_CAPACITY;
-    std::vector<float> f; std::vector<uint32_t> o;
     int rc;
+    if (!all_fit(V, cap, sv_label || normal, n_out, &rc)) return rc;
+    std::vector<float> f; std::vector<uint32_t> o;
     if ((rc = fetch(c, c->r_vf, (size_t)V * 12, f)) || (rc = fetch(c, c->r_owner, V, o))) return rc;
     for (uint32_t v = 0; v < V; ++v) {
         if (sv_label) sv_label[v] = o[v];
-        if (normal) { normal[3 * v] = f[(size_t)v * 12 + 6]; normal[3 * v + 1] = f[(size_t)v * 12 + 7]; normal[3 * v + 2] = f[(size_t)v * 12 + 8]; }
+        put3(normal, v, &f[(size_t)v * 12 + 6]);
     }
     return F3DS_OK;
 }
@@ -1722,52 +1754,38 @@ int supervoxels_of(f3ds_ctx* c, const Scratch<uint32_t>& hcount, const Scratch<f
     std::vector<uint32_t> cnt; std::vector<float> hc;
     int rc;
     if ((rc = fetch(c, hcount, S0 + 1, cnt)) || (rc = fetch(c, hcent, (size_t)(S0 + 1) * 12, hc))) return rc;
-    size_t k = 0;
+    Capped out{cap, label || xyz || rgb || normal || n_voxels};
     for (uint32_t h = 1; h <= S0; ++h) {
         if (!cnt[h]) continue;
-        if (k < cap) {
+        if (out.room()) {
             const float* r = &hc[(size_t)h * 12];
-            if (label) label[k] = label_out(c, h);
-            if (xyz) { xyz[3 * k] = r[0]; xyz[3 * k + 1] = r[1]; xyz[3 * k + 2] = r[2]; }
-            if (rgb) { rgb[3 * k] = r[3]; rgb[3 * k + 1] = r[4]; rgb[3 * k + 2] = r[5]; }
-            if (normal) { normal[3 * k] = r[6]; normal[3 * k + 1] = r[7]; normal[3 * k + 2] = r[8]; }
-            if (n_voxels) n_voxels[k] = cnt[h];
+            if (label) label[out.k] = label_out(c, h);
+            put3(xyz, out.k, r); put3(rgb, out.k, r + 3); put3(normal, out.k, r + 6);
+            if (n_voxels) n_voxels[out.k] = cnt[h];
         }
-        k++;
+        out.next();
     }
-    if (n_out) *n_out = k;
-    return (k > cap && (label || xyz || rgb || normal || n_voxels)) ? F3DS_ERR_CAPACITY : F3DS_OK;
+    return out.finish(n_out);
 }
 }  // namespace
 
 // the refined supervoxel map (refined_supervoxel_clusters): same layout as f3ds_get_supervoxels
 extern "C" int f3ds_get_refined_supervoxels(f3ds_ctx* c, uint32_t* label, float* xyz, float* rgb, float* normal, uint32_t* n_voxels, size_t cap, size_t* n_out) {
-    if (!c) return F3DS_ERR_ARG;
-    if (!c->have_frame || c->refined_itr < 0) return F3DS_ERR_LOGIC;
-    HIPCHECK(hipSetDevice(c->device));
-    HIPCHECK(hipStreamSynchronize(c->stream));
+    if (const int frc = on_frame(c, NEED_FRAME | NEED_REFINED)) return frc;
     return supervoxels_of(c, c->r_hcount, c->r_hc, label, xyz, rgb, normal, n_voxels, cap, n_out);
 }
 
 extern "C" int f3ds_get_supervoxels(f3ds_ctx* c, uint32_t* label, float* xyz, float* rgb, float* normal, uint32_t* n_voxels, size_t cap, size_t* n_out) {
-    if (!c) return F3DS_ERR_ARG;
-    if (!c->have_frame) return F3DS_ERR_LOGIC;
-    HIPCHECK(hipSetDevice(c->device));
-    HIPCHECK(hipStreamSynchronize(c->stream));
+    if (const int frc = on_frame(c)) return frc;
     return supervoxels_of(c, c->hcount, c->hc, label, xyz, rgb, normal, n_voxels, cap, n_out);
 }
 
 extern "C" int f3ds_get_supervoxel_adjacency(f3ds_ctx* c, uint32_t* pairs, size_t cap_pairs, size_t* n_out) {
-    if (!c) return F3DS_ERR_ARG;
-    if (!c->have_frame) return F3DS_ERR_LOGIC;
-    HIPCHECK(hipSetDevice(c->device));
-    HIPCHECK(hipStreamSynchronize(c->stream));
+    if (const int frc = on_frame(c)) return frc;
     const uint32_t E = c->E;
-    if (n_out) *n_out = E;
-    if (!pairs) return F3DS_OK;
-    if (cap_pairs < E) return F3DS_ERR_CAPACITY;
-    std::vector<uint32_t> a, b;
     int rc;
+    if (!all_fit(E, cap_pairs, pairs != nullptr, n_out, &rc)) return rc;
+    std::vector<uint32_t> a, b;
     if ((rc = fetch(c, c->ea0, E, a)) || (rc = fetch(c, c->eb0, E, b))) return rc;
     for (uint32_t e = 0; e < E; ++e) { pairs[2 * e] = label_out(c, a[e]); pairs[2 * e + 1] = label_out(c, b[e]); }
     return F3DS_OK;
@@ -1777,10 +1795,7 @@ extern "C" int f3ds_get_supervoxel_adjacency(f3ds_ctx* c, uint32_t* pairs, size_
 // surviving supervoxel labels, sorted (src/supervoxel_clustering.cpp:444,465: what visualize() draws as the graph).  Every
 // initial adjacency maps to the labels its two supervoxels ended in; merge() keeps one edge per pair (contains(), clustering.cpp:408-436).
 extern "C" int f3ds_get_region_adjacency(f3ds_ctx* c, uint32_t* pairs, size_t cap_pairs, size_t* n_out) {
-    if (!c) return F3DS_ERR_ARG;
-    if (!c->have_frame) return F3DS_ERR_LOGIC;
-    HIPCHECK(hipSetDevice(c->device));
-    HIPCHECK(hipStreamSynchronize(c->stream));
+    if (const int frc = on_frame(c)) return frc;
     std::vector<uint32_t> a, b, root;
     int rc;
     if ((rc = fetch(c, c->ea0, c->E, a)) || (rc = fetch(c, c->eb0, c->E, b)) || (rc = fetch(c, c->root, c->S0 + 1, root))) return rc;
@@ -1791,9 +1806,7 @@ extern "C" int f3ds_get_region_adjacency(f3ds_ctx* c, uint32_t* pairs, size_t ca
     }
     std::sort(keys.begin(), keys.end());
     keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-    if (n_out) *n_out = keys.size();
-    if (!pairs) return F3DS_OK;
-    if (cap_pairs < keys.size()) return F3DS_ERR_CAPACITY;
+    if (!all_fit(keys.size(), cap_pairs, pairs != nullptr, n_out, &rc)) return rc;
     for (size_t k = 0; k < keys.size(); ++k) { pairs[2 * k] = label_out(c, (uint32_t)(keys[k] >> 32)); pairs[2 * k + 1] = label_out(c, (uint32_t)keys[k]); }
     return F3DS_OK;
 }
@@ -1806,9 +1819,7 @@ extern "C" int f3ds_merge_layout_info(uint32_t n_edges, int waves, int keys_in_l
     return F3DS_OK;
 }
 extern "C" int f3ds_get_debug(f3ds_ctx* c, int what, void* dst, size_t cap_bytes, size_t* bytes_out) {
-    if (!c) return F3DS_ERR_ARG;
-    HIPCHECK(hipSetDevice(c->device));
-    HIPCHECK(hipStreamSynchronize(c->stream));
+    if (const int frc = on_frame(c, NEED_NOTHING)) return frc;
     const uint32_t V = c->V, S0 = c->S0, E = c->E, n = c->n;
     std::vector<uint8_t> buf;
     auto put = [&](const void* src, size_t nb) { const uint8_t* b = static_cast<const uint8_t*>(src); buf.insert(buf.end(), b, b + nb); };
@@ -1884,11 +1895,8 @@ extern "C" int f3ds_get_debug(f3ds_ctx* c, int what, void* dst, size_t cap_bytes
             break;
         default: return F3DS_ERR_ARG;
     }
-    if (bytes_out) *bytes_out = buf.size();
-    if (dst) {
-        if (buf.size() > cap_bytes) return F3DS_ERR_CAPACITY;
-        if (!buf.empty()) memcpy(dst, buf.data(), buf.size());
-    }
+    if (!all_fit(buf.size(), cap_bytes, dst != nullptr, bytes_out, &rc)) return rc;
+    if (!buf.empty()) memcpy(dst, buf.data(), buf.size());
     return F3DS_OK;
 }
 
@@ -1897,8 +1905,19 @@ extern "C" int f3ds_get_debug(f3ds_ctx* c, int what, void* dst, size_t cap_bytes
 // / best_thresh clustering.cpp:691-774, Testing src/testing.cpp).  Not on the per-frame hot path.
 // ------------------------------------------------------------------------------------------------
 namespace {
+// color2label (clustering.cpp:823-846): the distinct colours of col[] are numbered in order of first appearance; col[] becomes the labels, tsize[l] the voxels of label l
+void number_truth_colours(std::vector<uint32_t>& col, std::vector<uint32_t>& tsize) {
+    std::map<uint32_t, uint32_t> ids;
+    tsize.clear();
+    for (uint32_t& cv : col) {
+        const auto it = ids.find(cv);
+        uint32_t l;
+        if (it == ids.end()) { l = (uint32_t)tsize.size(); ids.insert({cv, l}); tsize.push_back(0); } else l = it->second;
+        cv = l; tsize[l]++;
+    }
+}
 // truth label of every voxel: label colours averaged per voxel on the GPU, distinct colours numbered
-// in first-appearance (leaf) order on the host (color2label, clustering.cpp:823-846)
+// in first-appearance (leaf) order on the host
 int eval_truth(f3ds_ctx* c, const uint32_t* truth_point_labels) {
     const uint32_t n = c->n, V = c->V;
     uint32_t *lut, *tp, *tsum, *tcol, *tlab;
@@ -1907,22 +1926,14 @@ int eval_truth(f3ds_ctx* c, const uint32_t* truth_point_labels) {
     HIPCHECK(hipMemcpyAsync(lut, f3ds_glasbey_256, 1024, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipMemcpyAsync(tp, truth_point_labels, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipMemsetAsync(tsum, 0, (size_t)V * 12, c->stream));
-    Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); set_launch_shape(&c, 1);
-    reset_recording(c);
+    Batch b = batch_of(c);
     rec<d_truth_accum>(c, grid_for(n, 256), 0u, n, c->pt_voxel.p, tp, lut, tsum);
     rec<d_truth_color>(c, grid_for(V, 256), 0u, V, tsum, c->vcount.p, tcol);
     int rc = flush_sync(b);
     if (rc) return rc;
     std::vector<uint32_t> col;
     if ((rc = fetch(c, c->tcol, V, col))) return rc;
-    std::map<uint32_t, uint32_t> ids;
-    c->tsize.clear();
-    for (uint32_t v = 0; v < V; ++v) {
-        auto it = ids.find(col[v]);
-        uint32_t l;
-        if (it == ids.end()) { l = (uint32_t)c->tsize.size(); ids.insert({col[v], l}); c->tsize.push_back(0); } else l = it->second;
-        col[v] = l; c->tsize[l]++;
-    }
+    number_truth_colours(col, c->tsize);
     HIPCHECK(hipMemcpy(tlab, col.data(), (size_t)V * 4, hipMemcpyHostToDevice));
     return F3DS_OK;
 }
@@ -1935,8 +1946,7 @@ int eval_scores(f3ds_ctx* c, const uint32_t* d_root, const uint32_t* d_incl, uin
     ENSURE(c->ctab, (size_t)K * M, tab); ENSURE(c->csize, K, ssz);
     HIPCHECK(hipMemsetAsync(tab, 0, (size_t)K * M * 4, c->stream));
     HIPCHECK(hipMemsetAsync(ssz, 0, (size_t)K * 4, c->stream));
-    Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c); set_launch_shape(&c, 1);
-    reset_recording(c);
+    Batch b = batch_of(c);
     rec<d_contingency>(c, grid_for(V, 256), 0u, V, M, c->owner0.p, d_root, d_incl, c->tlab.p, tab, ssz);
     rec<d_contingency_ghost>(c, grid_for(c->S0, 256), 0u, c->S0, M, c->ghost_vox.p, c->ghost_active.p, c->owner0.p, d_root, d_incl, c->tlab.p, tab, ssz);
     int rc = flush_sync(b);
@@ -1949,12 +1959,11 @@ int eval_scores(f3ds_ctx* c, const uint32_t* d_root, const uint32_t* d_incl, uin
 }  // namespace
 
 extern "C" int f3ds_evaluate(f3ds_ctx* c, const uint32_t* truth_point_labels, f3ds_performance* out) {
-    if (!c || !truth_point_labels || !out) return F3DS_ERR_ARG;
-    if (!c->have_frame || c->user_mode) return F3DS_ERR_LOGIC;
+    if (!truth_point_labels || !out) return F3DS_ERR_ARG;
+    int rc = on_frame(c, NEED_FRAME | NEED_VOXEL_GRID);
+    if (rc) return rc;
     g_sw.read();      // (eval_truth / eval_scores size their launches by the switches; f3ds_auto_threshold reads them in f3ds_recluster)
-    HIPCHECK(hipSetDevice(c->device));
-    HIPCHECK(hipStreamSynchronize(c->stream));
-    int rc = eval_truth(c, truth_point_labels);
+    rc = eval_truth(c, truth_point_labels);
     if (rc) return rc;
     return eval_scores(c, c->root.p, c->rincl.p, c->res.n_regions, out);
 }
@@ -2021,6 +2030,15 @@ extern "C" int f3ds_auto_threshold(f3ds_ctx* c, const f3ds_params* prm, const ui
 // the frame state and leaves it as it was: only the lv_* scratch is written.
 // ------------------------------------------------------------------------------------------------
 namespace {
+// a batch call's contexts: all there, on one device, no context twice (one context holds one frame's scratch)
+bool distinct_contexts_on_one_device(f3ds_ctx* const* ctxs, int nctx) {
+    for (int i = 0; i < nctx; ++i) {
+        if (!ctxs[i] || ctxs[i]->device != ctxs[0]->device) return false;
+        for (int j = 0; j < i; ++j) if (ctxs[j] == ctxs[i]) return false;
+    }
+    return true;
+}
+bool any_nan(const float* thr, int K) { for (int l = 0; l < K; ++l) if (thr[l] != thr[l]) return true; return false; }
 int check_levels(const f3ds_ctx* c, const float* thr, int K) {
     if (!c->have_frame) return F3DS_ERR_LOGIC;
     for (int l = 0; l < K; ++l) if (thr[l] > c->cluster_T) return F3DS_ERR_OUT_OF_RANGE;
@@ -2053,13 +2071,8 @@ int run_levels(f3ds_ctx** ctxs, int nctx, const float* thr, int K, uint32_t* con
     g_sw.read();
     f3ds_ctx* o = ctxs[0];
     HIPCHECK(hipSetDevice(o->device));
-    Batch b; b.owner = o; b.st = o->stream; set_launch_shape(ctxs, nctx);
-    for (int i = 0; i < nctx; ++i) {
-        f3ds_ctx* c = ctxs[i];
-        if (c->stream != b.st) HIPCHECK(hipStreamSynchronize(c->stream));      // (the frame state is read on the owner's stream)
-        reset_recording(c);
-        b.fr.push_back(c);
-    }
+    Batch b;
+    if (const int brc = batch_of(ctxs, nctx, b)) return brc;
     // the thresholds (shared by every frame) go up once, the region counts of all frames come back in one copy: both in the owner's scratch
     float* d_thr; uint32_t* d_nreg;
     { int rc = ensure(o, o->lv_thr, (size_t)K, &d_thr); if (rc) return rc; rc = ensure(o, o->lv_nreg, (size_t)nctx * K, &d_nreg); if (rc) return rc; }
@@ -2081,15 +2094,11 @@ int run_levels(f3ds_ctx** ctxs, int nctx, const float* thr, int K, uint32_t* con
     HIPCHECK(hipMemcpyAsync(nreg.data(), d_nreg, nreg.size() * 4, hipMemcpyDeviceToHost, b.st));
     if (!labels_on_device) {
         // host outputs as run_cluster copies labels: through the device's copy stream once the labels exist (async into pinned memory), done before the call returns
-        hipStream_t dl = g_sw.copy_stream ? copy_stream_of(o->device, g_sw.copy_duplex ? 1 : 0) : nullptr;
-        if (dl) {
-            for (int k = 1; k < 3; ++k) if (!o->ev_copy[k]) HIPCHECK(hipEventCreateWithFlags(&o->ev_copy[k], hipEventDisableTiming));
-            HIPCHECK(hipEventRecord(o->ev_copy[1], b.st));
-            HIPCHECK(hipEventSynchronize(o->ev_copy[1]));
-        }
+        hipStream_t dl;
+        if ((rc = download_begin(b, &dl))) return rc;
         for (int i = 0; i < nctx; ++i)
             if (ctxs[i]->n) HIPCHECK(hipMemcpyAsync(point_labels[i], ctxs[i]->lv_out.p, (size_t)ctxs[i]->n * K * 4, hipMemcpyDeviceToHost, dl ? dl : b.st));
-        if (dl) { HIPCHECK(hipEventRecord(o->ev_copy[2], dl)); HIPCHECK(hipEventSynchronize(o->ev_copy[2])); }
+        if ((rc = download_queued(b, dl)) || (rc = download_wait(b, dl))) return rc;
     }
     HIPCHECK(hipStreamSynchronize(b.st));
     HIPCHECK(hipGetLastError());
@@ -2106,11 +2115,8 @@ extern "C" int f3ds_labels_at_thresholds(f3ds_ctx* c, const float* thresholds, i
 extern "C" int f3ds_labels_at_thresholds_batch(f3ds_ctx** ctxs, int nctx, const float* thresholds, int k, uint32_t* const* point_labels, int labels_on_device,
                                                uint32_t* n_regions) {
     if (!ctxs || nctx < 1 || !thresholds || k < 1 || !point_labels) return F3DS_ERR_ARG;
-    for (int l = 0; l < k; ++l) if (thresholds[l] != thresholds[l]) return F3DS_ERR_ARG;
-    for (int i = 0; i < nctx; ++i) {
-        if (!ctxs[i] || !point_labels[i] || ctxs[i]->device != ctxs[0]->device) return F3DS_ERR_ARG;
-        for (int j = 0; j < i; ++j) if (ctxs[j] == ctxs[i]) return F3DS_ERR_ARG;      // (one context holds one frame's scratch)
-    }
+    if (any_nan(thresholds, k) || !distinct_contexts_on_one_device(ctxs, nctx)) return F3DS_ERR_ARG;
+    for (int i = 0; i < nctx; ++i) if (!point_labels[i]) return F3DS_ERR_ARG;
     for (int i = 0; i < nctx; ++i) { const int rc = check_levels(ctxs[i], thresholds, k); if (rc) return rc; }
     return run_levels(ctxs, nctx, thresholds, k, point_labels, labels_on_device, n_regions);
 }
@@ -2137,14 +2143,9 @@ int run_eval_levels(f3ds_ctx** ctxs, int nctx, const uint32_t* const* truth, int
     f3ds_ctx* o = ctxs[0];
     const uint32_t K = (uint32_t)K_, Kp = (K + 3u) & ~3u;
     HIPCHECK(hipSetDevice(o->device));
-    Batch b; b.owner = o; b.st = o->stream; set_launch_shape(ctxs, nctx);
-    for (int i = 0; i < nctx; ++i) {
-        f3ds_ctx* c = ctxs[i];
-        if ((uint64_t)c->V + c->S0 >= (1u << 24)) return F3DS_ERR_UNSUPPORTED;      // (d_evl_score adds sizes as integers: exact in float below 2^24)
-        if (c->stream != b.st) HIPCHECK(hipStreamSynchronize(c->stream));
-        reset_recording(c);
-        b.fr.push_back(c);
-    }
+    for (int i = 0; i < nctx; ++i) if ((uint64_t)ctxs[i]->V + ctxs[i]->S0 >= (1u << 24)) return F3DS_ERR_UNSUPPORTED;      // (d_evl_score adds sizes as integers: exact in float below 2^24)
+    Batch b;
+    if (const int brc = batch_of(ctxs, nctx, b)) return brc;
     float* d_thr; uint32_t *d_nreg, *d_counts, *d_out;
     { int rc; if ((rc = ensure(o, o->lv_thr, (size_t)K, &d_thr)) || (rc = ensure(o, o->lv_nreg, (size_t)nctx * K, &d_nreg)) || (rc = ensure(o, o->evl_counts, (size_t)nctx * 4, &d_counts)) ||
                   (rc = ensure(o, o->evl_out, (size_t)nctx * K * 8, &d_out))) return rc; }
@@ -2178,13 +2179,7 @@ int run_eval_levels(f3ds_ctx** ctxs, int nctx, const uint32_t* const* truth, int
     uint32_t maxM = 1, maxS0 = 1;
     for (int i = 0; i < nctx; ++i) {
         EvlTruth& t = tr[i];
-        std::map<uint32_t, uint32_t> ids;
-        for (uint32_t& cv : t.col) {
-            auto it = ids.find(cv);
-            uint32_t l;
-            if (it == ids.end()) { l = (uint32_t)t.tsize.size(); ids.insert({cv, l}); t.tsize.push_back(0); } else l = it->second;
-            cv = l; t.tsize[l]++;
-        }
+        number_truth_colours(t.col, t.tsize);
         t.M = (uint32_t)t.tsize.size();
         if (t.M == 0) return F3DS_ERR_ARG;      // (std::invalid_argument, testing.cpp:414,431, as eval_scores; a level has K >= 1 whenever the frame has a voxel)
         t.order.resize((size_t)t.M * 3);      // order, rank, then the visited labels ascending
@@ -2280,11 +2275,8 @@ extern "C" int f3ds_evaluate_levels(f3ds_ctx* c, const uint32_t* truth_point_lab
 extern "C" int f3ds_evaluate_levels_batch(f3ds_ctx** ctxs, int nctx, const uint32_t* const* truth_point_labels, int truth_on_device, const float* thresholds, int k,
                                           f3ds_performance* scores, uint32_t* n_regions) {
     if (!ctxs || nctx < 1 || !truth_point_labels || !thresholds || k < 1 || !scores) return F3DS_ERR_ARG;
-    for (int l = 0; l < k; ++l) if (thresholds[l] != thresholds[l]) return F3DS_ERR_ARG;
-    for (int i = 0; i < nctx; ++i) {
-        if (!ctxs[i] || !truth_point_labels[i] || ctxs[i]->device != ctxs[0]->device) return F3DS_ERR_ARG;
-        for (int j = 0; j < i; ++j) if (ctxs[j] == ctxs[i]) return F3DS_ERR_ARG;      // (one context holds one frame's scratch)
-    }
+    if (any_nan(thresholds, k) || !distinct_contexts_on_one_device(ctxs, nctx)) return F3DS_ERR_ARG;
+    for (int i = 0; i < nctx; ++i) if (!truth_point_labels[i]) return F3DS_ERR_ARG;
     for (int i = 0; i < nctx; ++i) {
         if (ctxs[i]->have_frame && (ctxs[i]->user_mode || ctxs[i]->V == 0)) return F3DS_ERR_LOGIC;      // (as f3ds_evaluate; no voxel: nothing to score)
         const int rc = check_levels(ctxs[i], thresholds, k);
@@ -2294,8 +2286,7 @@ extern "C" int f3ds_evaluate_levels_batch(f3ds_ctx** ctxs, int nctx, const uint3
 }
 
 extern "C" int f3ds_best_level(const float* thresholds, const f3ds_performance* scores, int k, int* best_index) {
-    if (!thresholds || !scores || !best_index || k < 1) return F3DS_ERR_ARG;
-    for (int l = 0; l < k; ++l) if (thresholds[l] != thresholds[l]) return F3DS_ERR_ARG;
+    if (!thresholds || !scores || !best_index || k < 1 || any_nan(thresholds, k)) return F3DS_ERR_ARG;
     std::vector<int> idx((size_t)k);
     for (int l = 0; l < k; ++l) idx[l] = l;
     std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return thresholds[a] < thresholds[b]; });
@@ -2310,17 +2301,12 @@ extern "C" int f3ds_best_level(const float* thresholds, const f3ds_performance* 
 }
 
 extern "C" int f3ds_get_merge_tree(f3ds_ctx* c, uint32_t* survivor, uint32_t* absorbed, float* weight, size_t cap, size_t* n_out) {
-    if (!c) return F3DS_ERR_ARG;
-    if (!c->have_frame) return F3DS_ERR_LOGIC;
-    HIPCHECK(hipSetDevice(c->device));
-    HIPCHECK(hipStreamSynchronize(c->stream));
+    if (const int frc = on_frame(c)) return frc;
     const size_t nm = c->res.n_merges;
-    if (n_out) *n_out = nm;
-    if (!survivor && !absorbed && !weight) return F3DS_OK;
-    if (cap < nm) return F3DS_ERR_CAPACITY;
+    int rc;
+    if (!all_fit(nm, cap, survivor || absorbed || weight, n_out, &rc)) return rc;
     std::vector<uint32_t> u;
-    const int rc = fetch(c, c->merges, nm * 3, u);
-    if (rc) return rc;
+    if ((rc = fetch(c, c->merges, nm * 3, u))) return rc;
     for (size_t i = 0; i < nm; ++i) {
         if (survivor) survivor[i] = label_out(c, u[i * 3]);
         if (absorbed) absorbed[i] = label_out(c, u[i * 3 + 1]);
@@ -2412,9 +2398,8 @@ extern "C" int f3ds_tracker_reset(f3ds_tracker* t) {
 extern "C" int f3ds_tracker_get_ids(f3ds_tracker* t, uint32_t* id_of_region, size_t cap, size_t* n_out) {
     if (!t || (!id_of_region && !n_out)) return F3DS_ERR_ARG;
     if (!t->have_ids) return F3DS_ERR_LOGIC;
-    if (n_out) *n_out = t->ids.size();
-    if (!id_of_region) return F3DS_OK;
-    if (cap < t->ids.size()) return F3DS_ERR_CAPACITY;
+    int rc;
+    if (!all_fit(t->ids.size(), cap, id_of_region != nullptr, n_out, &rc)) return rc;
     if (!t->ids.empty()) memcpy(id_of_region, t->ids.data(), t->ids.size() * 4);
     return F3DS_OK;
 }
@@ -2433,9 +2418,7 @@ extern "C" int f3ds_tracker_update(f3ds_tracker* t, const f3ds_rgbd_format* fmt_
     f3ds_ctx* c = t->c;
     g_sw.read();
     HIPCHECK(hipSetDevice(c->device));
-    Batch b; b.owner = c; b.st = c->stream; b.fr.push_back(c);
-    { f3ds_ctx* one[1] = {c}; set_launch_shape(one, 1); }
-    reset_recording(c);
+    Batch b = batch_of(c);
     const uint32_t n = (uint32_t)lay.n, Kc = n_regions, Kp = t->have_prev ? (uint32_t)t->prev_id.size() : 0u;
     const int jb = tk_bits(Kp), sort_bits = tk_bits(Kc) + jb;
     if (const int rc = trk_state(t, n)) return rc;
@@ -2454,11 +2437,7 @@ extern "C" int f3ds_tracker_update(f3ds_tracker* t, const f3ds_rgbd_format* fmt_
         hipStream_t up = g_sw.copy_stream ? copy_stream_of(c->device) : nullptr;
         HIPCHECK(hipMemcpyAsync(ud, depth, lay.depth_bytes, hipMemcpyHostToDevice, up ? up : b.st));
         HIPCHECK(hipMemcpyAsync(ul, labels, (size_t)n * 4, hipMemcpyHostToDevice, up ? up : b.st));
-        if (up) {
-            if (!c->ev_copy[0]) HIPCHECK(hipEventCreateWithFlags(&c->ev_copy[0], hipEventDisableTiming));
-            HIPCHECK(hipEventRecord(c->ev_copy[0], up));
-            HIPCHECK(hipStreamWaitEvent(b.st, c->ev_copy[0], 0));
-        }
+        if (up) { if (const int urc = await_uploads(b, up)) return urc; }
         d_depth = ud; d_lab = ul;
     }
     TrackArgs a;
@@ -2511,14 +2490,10 @@ extern "C" int f3ds_tracker_update(f3ds_tracker* t, const f3ds_rgbd_format* fmt_
     rec<d_track_apply>(c, grid_for(n, 256), 0u, d_lab, n, d_id, Kc, ids_on_device ? track_ids : tid);
     if ((rc = flush(b))) return rc;
     if (!ids_on_device) {
-        hipStream_t dl = g_sw.copy_stream ? copy_stream_of(c->device, g_sw.copy_duplex ? 1 : 0) : nullptr;
-        if (dl) {      // queued on the copy stream only once the ids exist (as the labels of f3ds_segment_batch)
-            for (int k = 1; k < 3; ++k) if (!c->ev_copy[k]) HIPCHECK(hipEventCreateWithFlags(&c->ev_copy[k], hipEventDisableTiming));
-            HIPCHECK(hipEventRecord(c->ev_copy[1], b.st));
-            HIPCHECK(timed_sync(c->ev_copy[1]));
-        }
+        hipStream_t dl;      // (queued on the copy stream only once the ids exist, as the labels of f3ds_segment_batch)
+        if ((rc = download_begin(b, &dl))) return rc;
         HIPCHECK(hipMemcpyAsync(track_ids, tid, (size_t)n * 4, hipMemcpyDeviceToHost, dl ? dl : b.st));
-        if (dl) { HIPCHECK(hipEventRecord(c->ev_copy[2], dl)); HIPCHECK(timed_sync(c->ev_copy[2])); }
+        if ((rc = download_queued(b, dl)) || (rc = download_wait(b, dl))) return rc;
     }
     HIPCHECK(timed_sync(b.st));
     HIPCHECK(hipGetLastError());
