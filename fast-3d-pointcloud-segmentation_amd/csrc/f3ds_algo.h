@@ -180,6 +180,47 @@ F3DS_HD float a_helper_dist_row(const SweepView& s, uint32_t g, const float vrow
 // read as "unknown" without clearing the array (it is zeroed before sweep 0, 63, 126, ...)
 F3DS_HD unsigned char a_sweep_tag(unsigned sweep) { return (unsigned char)((sweep % 63u) + 1u); }
 F3DS_HD bool a_sweep_needs_clear(unsigned sweep) { return sweep % 63u == 0u; }
+// ---- Sweep control: the five words that steer sweep t, decided once per sweep by a_sweep_begin and read by every other sweep kernel -- and by the
+// CPU emulation of the sweeps (tests/emul) -- through the predicates below.  A word holds t + 1 while its statement is true of sweep t; no clearing between sweeps.
+struct SweepCtl {
+    uint32_t* n_changed;      // voxels whose (owner, distance) changed in the current sweep (bumped by the claim pass)
+    uint32_t* sweep_full;     // sweep t evaluates every voxel (no dirty-tile skipping)
+    uint32_t* sweep_pre;      // sweep t was full from its start: its R pre-pass ran
+    uint32_t* sweep_marks;    // sweep t records which tiles the next sweep has to look at
+    uint32_t* sweep_idle;     // sweep t is known to change nothing
+};
+// a sweep that changes more than thr voxels makes the next one full: V >> inc_shift (inc_shift < 0: every sweep is full; >= 32: every sweep that may skip tiles does)
+F3DS_HD uint32_t a_sweep_thr(uint32_t V, int inc_shift) { return inc_shift >= 32 ? 0xFFFFFFFFu : (inc_shift < 0 ? 0u : V >> inc_shift); }
+F3DS_HD bool a_sweep_is_full(const SweepCtl& c, uint32_t t) { return *c.sweep_full == t + 1u; }
+F3DS_HD bool a_sweep_full_from_start(const SweepCtl& c, uint32_t t) { return *c.sweep_pre == t + 1u; }
+F3DS_HD bool a_sweep_is_idle(const SweepCtl& c, uint32_t t) { return *c.sweep_idle == t + 1u; }
+F3DS_HD bool a_sweep_marks(const SweepCtl& c, uint32_t t) { return *c.sweep_marks == t + 1u; }      // the claim pass marks around every voxel it changes (E1)
+// ... and, once the claim pass has counted its changes, whether the centroid pass marks around the leaves of the helpers it recomputes (E2): only when the next
+// sweep will be allowed to skip tiles (a_sweep_begin: n_changed <= thr and this sweep marking)
+F3DS_HD bool a_sweep_marks_after_claim(const SweepCtl& c, uint32_t t, uint32_t thr) { return *c.n_changed <= thr && a_sweep_marks(c, t); }
+// the last R round of an incremental sweep still changed a word: the chain walker redoes this sweep's R (no pre-pass has run: a_sweep_full_from_start stays false)
+F3DS_HD void a_sweep_turn_full(const SweepCtl& c, uint32_t t) { *c.sweep_full = t + 1u; }
+// the slot of F3DS_DBG_SWEEP_STATS sweep t counts in: an idle sweep when a_sweep_begin says so, any other once its R phase is over (a_sweep_kind)
+enum { F3DS_SWEEP_FULL = 0, F3DS_SWEEP_INCREMENTAL = 1, F3DS_SWEEP_FALLBACK = 2, F3DS_SWEEP_IDLE = 3 };
+F3DS_HD int a_sweep_kind(const SweepCtl& c, uint32_t t) {
+    return !a_sweep_is_full(c, t) ? F3DS_SWEEP_INCREMENTAL : (a_sweep_full_from_start(c, t) ? F3DS_SWEEP_FULL : F3DS_SWEEP_FALLBACK);
+}
+// Start of sweep t (n_ghosts: helpers that still hold a ghost leaf): may this sweep skip clean tiles, does it mark for the next one.  Returns false when the sweep
+// is idle -- nothing else is decided for it then.
+// Marking costs 27 stores per changed voxel, so it only starts once the changes have thinned out; a sweep can skip tiles only if the sweep before it was marking.
+F3DS_HD bool a_sweep_begin(const SweepCtl& c, uint32_t t, uint32_t n_ghosts, uint32_t thr) {
+    if (t == 0u) { *c.sweep_marks = 0u; *c.sweep_idle = 0u; }          // a run of sweeps starts (again: refineSupervoxels)
+    const uint32_t prev = *c.n_changed;
+    // A sweep that changed no voxel's (owner, distance) left every helper's leaf set, hence every centroid, as it found them (sweeps >= 1 recompute a centroid only
+    // when the leaf set changed): the next sweep sees the inputs this one saw and changes nothing either, and so on to the last sweep -- expandSupervoxels'
+    // remaining iterations are no-ops (late sweeps of a 1M-point frame change 50, 10, 0, 0 ... voxels) and their kernels return at once.  (Not while a ghost
+    // leaf is active: its helper's books still move.  Sweep 0 recomputes every centroid, so the argument starts with sweep 1's count.)
+    if (t >= 2u && prev == 0u && n_ghosts == 0u) { *c.sweep_idle = t + 1u; *c.n_changed = 0u; return false; }
+    if (n_ghosts != 0u || t == 0u || prev > thr || *c.sweep_marks != t) { *c.sweep_full = t + 1u; *c.sweep_pre = t + 1u; }
+    if (t != 0u && (thr >= 0x40000000u || prev <= 4u * thr)) *c.sweep_marks = t + 1u;
+    *c.n_changed = 0u;
+    return true;
+}
 // R(w) for an owned voxel w, memoised in `memo` (one byte per voxel).  Concurrent callers may race
 // on memo entries: every writer stores the same value, and a stale "unknown" only costs a
 // recomputation.  *overflow is set when the dependency chain is deeper than the explicit stack.

@@ -49,6 +49,8 @@ struct DevCounters {
 };
 
 static_assert(offsetof(DevCounters, rq) == 128, "rq[] on a 128-byte line of its own");
+// the sweep-control words as the shared protocol takes them (f3ds_algo.h: a_sweep_begin and its predicates)
+__device__ inline SweepCtl sweep_ctl(DevCounters* dc) { return SweepCtl{&dc->n_changed, &dc->sweep_full, &dc->sweep_pre, &dc->sweep_marks, &dc->sweep_idle}; }
 constexpr uint64_t HASH_EMPTY = 0xFFFFFFFFFFFFFFFFull;
 
 __host__ __device__ inline uint64_t hash64(uint64_t x) {
@@ -2088,6 +2090,11 @@ struct SweepFrame {
     uint32_t* tmask;                // V: per listed voxel the neighbour slots that carry a thief (a_thief_mask_words), written by the pre-pass of a full sweep
     uint32_t T, thr;                // tiles; a sweep that changes more than thr voxels makes the next one full
     const uint32_t *tile_n1, *tile_ord, *tile_slots;      // one-ring tables of the 128-voxel tiles (written by d_normals): list length, list of ordinals, 27 list positions per voxel
+    // the stamp arrays sweep t reads (R round 0 / claim pass) and the ones it marks for sweep t + 1 (ternaries, not an index: see tR0 above)
+    __device__ uint32_t* tR_this(uint32_t t) const { return (t & 1u) ? tR1 : tR0; }
+    __device__ uint32_t* tC_this(uint32_t t) const { return (t & 1u) ? tC1 : tC0; }
+    __device__ uint32_t* tR_next(uint32_t t) const { return (t & 1u) ? tR0 : tR1; }
+    __device__ uint32_t* tC_next(uint32_t t) const { return (t & 1u) ? tC0 : tC1; }
 };
 template <bool ROWS = false>      // ROWS: the lanes hold scattered voxels (a helper's leaves): neighbours from the row-major table
 __device__ inline void mark_tiles(const SweepView& s, int v, uint32_t* a, uint32_t* b, uint32_t stamp) {
@@ -2119,18 +2126,8 @@ struct d_sweep_begin {
         __syncthreads();
         if (threadIdx.x == 0) {
             f.dc->n_ghosts = s_n;
-            // marking costs 27 stores per changed voxel, so it only starts once the changes have thinned out;
-            // a sweep can skip tiles only if the sweep before it was marking
-            if (t == 0u) { f.dc->sweep_marks = 0u; f.dc->sweep_idle = 0u; f.dc->sweep_stats[0] = f.dc->sweep_stats[1] = f.dc->sweep_stats[2] = f.dc->sweep_stats[3] = 0u; }          // a run of sweeps starts (again: refineSupervoxels)
-            const uint32_t prev = f.dc->n_changed;
-            // A sweep that changed no voxel's (owner, distance) left every helper's leaf set, hence every centroid, as it found them (sweeps >= 1 recompute a centroid only
-            // when the leaf set changed): the next sweep sees the inputs this one saw and changes nothing either, and so on to the last sweep -- expandSupervoxels'
-            // remaining iterations are no-ops (late sweeps of a 1M-point frame change 50, 10, 0, 0 ... voxels) and their kernels return at once.  (Not while a ghost
-            // leaf is active: its helper's books still move.  Sweep 0 recomputes every centroid, so the argument starts with sweep 1's count.)
-            if (t >= 2u && prev == 0u && s_n == 0u) { f.dc->sweep_idle = t + 1u; f.dc->n_changed = 0u; f.dc->sweep_stats[3]++; return; }
-            if (s_n != 0u || t == 0u || prev > f.thr || f.dc->sweep_marks != t) { f.dc->sweep_full = t + 1u; f.dc->sweep_pre = t + 1u; }
-            if (t != 0u && (f.thr >= 0x40000000u || prev <= 4u * f.thr)) f.dc->sweep_marks = t + 1u;
-            f.dc->n_changed = 0u;
+            if (t == 0u) f.dc->sweep_stats[0] = f.dc->sweep_stats[1] = f.dc->sweep_stats[2] = f.dc->sweep_stats[3] = 0u;          // a run of sweeps starts (again: refineSupervoxels)
+            if (!a_sweep_begin(sweep_ctl(f.dc), t, s_n, f.thr)) { f.dc->sweep_stats[F3DS_SWEEP_IDLE]++; return; }
             for (int p = 0; p <= F3DS_R_PASSES; ++p) f.dc->rq[p] = 0u;
         }
     }
@@ -2244,7 +2241,7 @@ __device__ inline uint64_t marked_pairs(const uint32_t* stamps, uint32_t stamp, 
 struct d_sweep_R_pre {
     static constexpr int BLOCK = 256;
     __device__ void operator()(SweepFrame f, unsigned char tag, uint32_t t) const {
-        if (f.dc->sweep_full != t + 1u) return;
+        if (!a_sweep_is_full(sweep_ctl(f.dc), t)) return;
         __shared__ uint32_t nown[2][NT_RING1 + 1], ngh[2][NT_RING1 + 1];
         const SweepView s = f.sv;
         const bool ghosts = *s.n_ghosts != 0u;
@@ -2288,11 +2285,11 @@ struct d_sweep_R_pre {
 struct d_sweep_R {
     static constexpr int BLOCK = 256;
     __device__ void operator()(SweepFrame f, unsigned char tag, uint32_t t, uint32_t pass) const {
-        if (f.dc->sweep_full != t + 1u) return;
+        if (!a_sweep_is_full(sweep_ctl(f.dc), t)) return;
         const SweepView s = f.sv;
         const uint32_t* src = (pass & 1u) ? f.wl2 : f.wl;
         uint32_t* dst = (pass & 1u) ? f.wl : f.wl2;
-        if (f.dc->sweep_pre != t + 1u) {
+        if (!a_sweep_full_from_start(sweep_ctl(f.dc), t)) {
             // The sweep started incremental and its last R round still changed ownR (d_sweep_R_round): no pre-pass has run, the work list is empty and ownR is
             // somewhere between the sweep-start state and the fixed point.  Pass 0 then derives R for EVERY voxel with the memoised walker (nothing carries this
             // sweep's tag yet, so every entry reads "unknown"; no ghost leaf is active in an incremental sweep); chains deeper than its stack go to the next pass
@@ -2329,12 +2326,13 @@ struct d_sweep_R_tail {
                                             // chip this (normally idle) launch then waits ~1 ms for one, 16 times per batch
     __device__ void operator()(SweepFrame f, unsigned char tag, uint32_t t) const {
         // (the one place that sees how the sweep's R phase went, once per sweep and frame: by now the rounds have either converged or turned the sweep full)
-        if (f.dc->sweep_idle == t + 1u) return;
-        if (threadIdx.x == 0) f.dc->sweep_stats[f.dc->sweep_full != t + 1u ? 1 : (f.dc->sweep_pre == t + 1u ? 0 : 2)]++;
-        if (f.dc->sweep_full != t + 1u) return;
+        const SweepCtl ctl = sweep_ctl(f.dc);
+        if (a_sweep_is_idle(ctl, t)) return;
+        if (threadIdx.x == 0) f.dc->sweep_stats[a_sweep_kind(ctl, t)]++;
+        if (!a_sweep_is_full(ctl, t)) return;
         __shared__ uint32_t s_n, s_next;
         const SweepView s = f.sv;
-        const bool masks = f.dc->sweep_pre == t + 1u;      // (the list comes from the pre-pass: every entry has its thief mask; else from the fallback pass of d_sweep_R)
+        const bool masks = a_sweep_full_from_start(ctl, t);      // (the list comes from the pre-pass: every entry has its thief mask; else from the fallback pass of d_sweep_R)
         uint32_t q = F3DS_R_PASSES;
         if (threadIdx.x == 0) { s_n = f.dc->rq[F3DS_R_PASSES]; s_next = 0; }
         __syncthreads();
@@ -2364,13 +2362,14 @@ struct d_sweep_R_round {
     static constexpr int BLOCK = 256;
     static constexpr int WAVES_PER_SIMD = 6;      // (80 VGPRs, 8 bytes of scratch; occupancy 7: slower, 5 -- the compiler's own choice -- too: profiles/r4_ab_bench.txt 24)
     __device__ void operator()(SweepFrame f, uint32_t t, uint32_t r, uint32_t nrounds) const {      // nrounds: rounds recorded for this sweep (F3DS_R_ROUNDS; fewer under F3DS_R_ROUNDS_RUN, a test switch)
-        if (f.dc->sweep_full == t + 1u || f.dc->sweep_idle == t + 1u) return;
+        const SweepCtl ctl = sweep_ctl(f.dc);
+        if (a_sweep_is_full(ctl, t) || a_sweep_is_idle(ctl, t)) return;
         __shared__ uint32_t nown[2][NT_RING1 + 1];
         const SweepView s = f.sv;
         const uint32_t stamp = t + 1u;
-        const uint32_t* cur = r == 0u ? ((t & 1u) ? f.tR1 : f.tR0) : f.tRr + (size_t)(r - 1u) * f.T;
+        const uint32_t* cur = r == 0u ? f.tR_this(t) : f.tRr + (size_t)(r - 1u) * f.T;
         const bool last = r + 1u == nrounds;
-        uint32_t* tc = (t & 1u) ? f.tC1 : f.tC0;
+        uint32_t* tc = f.tC_this(t);
         uint32_t* nxt = last ? tc : f.tRr + (size_t)r * f.T;
         SweepTile st{nown, nown, (int)(threadIdx.x >> 7), (int)(threadIdx.x & 127u)};
         __shared__ uint32_t s_marked[2];
@@ -2396,7 +2395,7 @@ struct d_sweep_R_round {
             if (nw != f.ownR[v]) {
                 f.ownR[v] = nw;
                 mark_tiles(s, v, nxt, tc, stamp);
-                if (last) f.dc->sweep_full = stamp;      // not converged: the chain walker redoes this sweep's R
+                if (last) a_sweep_turn_full(ctl, t);      // not converged: the chain walker redoes this sweep's R
             }
         }
     }
@@ -2420,12 +2419,13 @@ struct d_sweep_claim {
     // with other calls in flight the bench does not move: profiles/r4_ab_bench.txt 24)
     __device__ void operator()(SweepFrame f, uint32_t t) const {
         __shared__ uint32_t nr[2][NT_RING1 + 1], ngh[2][NT_RING1 + 1];
-        if (f.dc->sweep_idle == t + 1u) return;
+        const SweepCtl ctl = sweep_ctl(f.dc);
+        if (a_sweep_is_idle(ctl, t)) return;
         const SweepView s = f.sv;
-        const bool full = f.dc->sweep_full == t + 1u;
-        const bool marks = f.dc->sweep_marks == t + 1u;
+        const bool full = a_sweep_is_full(ctl, t);
+        const bool marks = a_sweep_marks(ctl, t);
         const bool ghosts = *s.n_ghosts != 0u;
-        const uint32_t* cur = (t & 1u) ? f.tC1 : f.tC0;
+        const uint32_t* cur = f.tC_this(t);
         uint32_t changed = 0;
         SweepTile st{nr, ngh, (int)(threadIdx.x >> 7), (int)(threadIdx.x & 127u)};
         __shared__ uint32_t s_marked[2];
@@ -2463,7 +2463,7 @@ struct d_sweep_claim {
                 }
                 // E1 of the dirty-tile scheme on the spot (a kernel of its own, d_claim_mark, until round 4: a dispatch costs a call ~100 us of latency with other
                 // calls' kernels on the chip, 15 times per call): the tiles around a voxel that changed look again in the next sweep
-                if (marks) mark_tiles(s, v, (t & 1u) ? f.tR0 : f.tR1, (t & 1u) ? f.tC0 : f.tC1, t + 2u);
+                if (marks) mark_tiles(s, v, f.tR_next(t), f.tC_next(t), t + 2u);
                 changed++;
             }
             // A helper's books (ordinal window, dirty stamp, tile list) once per helper and WAVE, not once per voxel: the 64 voxels of a wave are one tile of the
@@ -2485,7 +2485,7 @@ struct d_sweep_claim {
         }
     #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) changed += __shfl_xor(changed, d, 64);
-        if (lane_id() == 0 && changed) atomicAdd(&f.dc->n_changed, changed);
+        if (lane_id() == 0 && changed) atomicAdd(ctl.n_changed, changed);
     }
 };
 // Sorted distinct tiles that can hold leaves of a helper (its list plus the tile of its ghost leaf), into
@@ -2633,7 +2633,7 @@ struct d_centroid {
         uint32_t (*const q_leaf)[QL + 32] = reinterpret_cast<uint32_t (*)[QL + 32]>(&tiles[threadIdx.x >> 6][0][0] + 4 * 16);
         float (*const q_fin)[12] = reinterpret_cast<float (*)[12]>(&tiles[threadIdx.x >> 6][0][0] + 4 * 16 + 4 * (QL + 32));
         const int wv = (int)(threadIdx.x >> 6);
-        if (f.dc->sweep_idle == t + 1u) return;
+        if (a_sweep_is_idle(sweep_ctl(f.dc), t)) return;
         // Which helpers have anything to do is asked for 64 of them at once, one per lane (late sweeps: a handful of ~1 500 do; asked helper by
         // helper, every "no" cost the wave a trip to L2); those that do are taken four at a time.  The 64 are the 16 groups of four consecutive helpers
         // the wave would own if the groups were dealt round-robin over all waves of the frame's launch: a full sweep (every helper has work) is spread
@@ -2643,7 +2643,7 @@ struct d_centroid {
         // takes is the chain of dependent loads behind one helper -- the 27 + 54 accesses of mark_tiles per leaf on top of the sums --, and a row walks it four
         // times slower than a wave (measured per launch of 192 frames, sweeps 9..15: 70-210 us a wave per helper, 160-280 us four per wave).
         // (and so do frames of big supervoxels -- 48 voxels and more on average, BASELINE config 4 has 190: most helpers would overflow a row's 64 leaves)
-        const bool by_wave = (f.dc->n_changed <= f.thr && f.dc->sweep_marks == t + 1u) || (uint32_t)f.sv.V > 48u * f.S0;
+        const bool by_wave = a_sweep_marks_after_claim(sweep_ctl(f.dc), t, f.thr) || (uint32_t)f.sv.V > 48u * f.S0;
         if (by_wave) {
             // (neighbouring labels are neighbours in space and change together: the four helpers of a group go to the four waves of a workgroup, side by side)
             const uint32_t bix = BIX, stp = gridDim.x;
@@ -2777,8 +2777,8 @@ struct d_centroid {
         uint32_t count = 0, kept = 0, nbuf = 0;
         // E2 of the dirty-tile scheme on the spot (d_centroid_mark until round 4): the leaves of a helper whose centroid is recomputed tell the tiles around them
         // to look again in the next sweep -- only when that sweep is allowed to skip tiles
-        const bool do_mark = f.dc->n_changed <= f.thr && f.dc->sweep_marks == t + 1u;
-        uint32_t* const mR = (t & 1u) ? f.tR0 : f.tR1; uint32_t* const mC = (t & 1u) ? f.tC0 : f.tC1;
+        const bool do_mark = a_sweep_marks_after_claim(sweep_ctl(f.dc), t, f.thr);
+        uint32_t* const mR = f.tR_next(t); uint32_t* const mC = f.tC_next(t);
         auto flush = [&]() {      // the listed leaves' rows, all requested at once, then added in list order
             if (nbuf == 0u) return;
             wave_lds_sync();

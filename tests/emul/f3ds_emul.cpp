@@ -57,6 +57,7 @@ struct f3ds_emul {
     // merge state kept for the voxel-cloud accessor
     std::vector<uint32_t> rhead, lnext;
     std::vector<uint8_t> ralive;
+    uint32_t sweep_stats[4] = {0u, 0u, 0u, 0u};      // the last run of sweeps, as the device counts them (F3DS_DBG_SWEEP_STATS): full from their start / incremental / fallback / idle
     f3ds_result res;
 };
 
@@ -239,39 +240,59 @@ int stage_sweeps(f3ds_emul& E, const std::vector<int>& seeds, bool reseed) {
     }
     int max_depth = (int)(1.8f * prm.seed_res / prm.voxel_res);
     E.res.sweeps = max_depth > 1 ? (uint32_t)(max_depth - 1) : 0u;
-    std::vector<unsigned char> R(V), done(S0 + 1);
-    std::vector<uint32_t> ghost_head(V, 0u), ghost_next(S0 + 1, 0u), ownR(V, 0u);
+    std::vector<unsigned char> R(V), Rchk(V), done(S0 + 1);      // R: the walkers' memo, as on the device; Rchk: the memo of the cross-check of a mask sweep
+    std::vector<uint32_t> ghost_head(V, 0u), ghost_next(S0 + 1, 0u), ownR(V, 0u), tmask(V, 0u);
     std::vector<int> nbrT((size_t)V * 27);
     for (int v = 0; v < V; ++v) for (int k = 0; k < 27; ++k) nbrT[(size_t)k * V + v] = E.nbr[(size_t)v * 27 + k];
-    // dirty-tile bookkeeping, the same events and stamps as the device kernels (f3ds_kernels.inc, SweepFrame)
+    // Sweep control and dirty-tile bookkeeping: the protocol of the device kernels (a_sweep_begin and its predicates in f3ds_algo.h; the same events and stamps as
+    // f3ds_kernels.inc, SweepFrame).  F3DS_EMUL_INC_SHIFT is the device's F3DS_INC_SHIFT; F3DS_EMUL_R_ROUNDS (1 .. F3DS_R_ROUNDS) its F3DS_R_ROUNDS_RUN: fewer
+    // rounds, so that tests reach the sweeps that turn full because their last round still changed a word.
     const char* env = getenv("F3DS_EMUL_INC_SHIFT");
     const int shift = env ? atoi(env) : 6;
     const uint32_t T = (uint32_t)(V + 63) / 64u;
-    const uint32_t thr = shift >= 32 ? 0xFFFFFFFFu : (shift < 0 ? 0u : (uint32_t)V >> shift);
-    const int ROUNDS = F3DS_R_ROUNDS;
+    const uint32_t thr = a_sweep_thr((uint32_t)V, shift);
+    env = getenv("F3DS_EMUL_R_ROUNDS");
+    const int ROUNDS = env && atoi(env) >= 1 && atoi(env) <= F3DS_R_ROUNDS ? atoi(env) : F3DS_R_ROUNDS;
     std::vector<uint32_t> tR[2] = {std::vector<uint32_t>(T, 0u), std::vector<uint32_t>(T, 0u)}, tC[2] = {std::vector<uint32_t>(T, 0u), std::vector<uint32_t>(T, 0u)};
     std::vector<std::vector<uint32_t>> tRr(ROUNDS, std::vector<uint32_t>(T, 0u));
     std::vector<uint32_t> hD(S0 + 1, 0u);
-    uint32_t n_changed = 0, sweep_full = 0, sweep_marks = 0;
-    long stat_inc_sweeps = 0, stat_fallbacks = 0, stat_r_evals = 0, stat_c_evals = 0, stat_h_evals = 0;
+    uint32_t n_changed = 0, sweep_full = 0, sweep_pre = 0, sweep_marks = 0, sweep_idle = 0;
+    const SweepCtl ctl{&n_changed, &sweep_full, &sweep_pre, &sweep_marks, &sweep_idle};
+    for (uint32_t& n : E.sweep_stats) n = 0u;
+    long stat_r_evals = 0, stat_c_evals = 0, stat_h_evals = 0;
     auto mark = [&](int v, std::vector<uint32_t>& a, std::vector<uint32_t>& b, uint32_t stamp) {
         for (int k = 0; k < 27; ++k) { int u = nbrT[(size_t)k * V + v]; if (u >= 0) { a[u >> 6] = stamp; b[u >> 6] = stamp; } }
     };
+    // like d_sweep_R and d_sweep_R_tail: voxels whose chain is deeper than the walker's stack are retried in later passes over the memo (the device: F3DS_R_PASSES
+    // grid passes, then one workgroup until done).  eval(v, &overflow) = R(v); out[v] = owner | R bit
+    auto walk = [&](std::vector<int> todo, std::vector<uint32_t>& out, auto&& eval) {
+        std::vector<int> again;
+        while (!todo.empty()) {
+            again.clear();
+            for (int v : todo) {
+                int overflow = 0;
+                const bool r = eval(v, &overflow);
+                if (overflow) again.push_back(v); else out[v] = E.owner[v] | (r ? F3DS_OWNR_RTRUE : 0u);
+            }
+            if (again.size() == todo.size()) return false;      // no progress: cannot happen
+            todo.swap(again);
+        }
+        return true;
+    };
     for (uint32_t t = 0; t < E.res.sweeps; ++t) {
+        if (a_sweep_needs_clear(t)) std::fill(R.begin(), R.end(), (unsigned char)0);
         for (int h = 1; h <= S0; ++h) if (E.ghost_vox[h] >= 0) ghost_head[E.ghost_vox[h]] = 0u;
         for (int h = 1; h <= S0; ++h) if (E.ghost_active[h]) { ghost_next[h] = ghost_head[E.ghost_vox[h]]; ghost_head[E.ghost_vox[h]] = (uint32_t)h; }
         uint32_t n_ghosts = 0;
         for (int h = 1; h <= S0; ++h) n_ghosts += E.ghost_active[h];
-        if (n_ghosts != 0u || t == 0u || n_changed > thr || sweep_marks != t) sweep_full = t + 1u;
-        if (t != 0u && (thr >= 0x40000000u || n_changed <= 4u * thr)) sweep_marks = t + 1u;
-        n_changed = 0;
+        if (!a_sweep_begin(ctl, t, n_ghosts, thr)) { E.sweep_stats[F3DS_SWEEP_IDLE]++; continue; }
         SweepView s{V, nbrT.data(), E.vf.data(), E.owner.data(), E.dist.data(), E.hc.data(), ghost_head.data(), ghost_next.data(), &n_ghosts,
                     prm.seed_res, prm.w_normal, prm.w_color, prm.w_spatial};
         const uint32_t stamp = t + 1u;
+        const unsigned char tag = a_sweep_tag(t);
         // incremental R rounds (Jacobi: every round reads the ownR of the round before, the least favourable interleaving)
-        if (shift >= 0 && sweep_full != stamp) {
-            stat_inc_sweeps++;
-            for (int r = 0; r < ROUNDS && sweep_full != stamp; ++r) {
+        if (shift >= 0 && !a_sweep_is_full(ctl, t)) {
+            for (int r = 0; r < ROUNDS && !a_sweep_is_full(ctl, t); ++r) {
                 const std::vector<uint32_t>& cur = r == 0 ? tR[t & 1u] : tRr[r - 1];
                 const bool last = r + 1 == ROUNDS;
                 std::vector<uint32_t> snap = ownR;
@@ -282,57 +303,42 @@ int stage_sweeps(f3ds_emul& E, const std::vector<int>& seeds, bool reseed) {
                     const uint32_t nw = E.owner[v] | (a_eval_R_step(s, snap.data(), v) ? F3DS_OWNR_RTRUE : 0u);
                     if (nw != snap[v]) writes.push_back({v, nw});
                 }
-                if (getenv("F3DS_EMUL_SWEEP_STATS")) fprintf(stderr, "   sweep %u round %d: %zu words changed\n", t, r, writes.size());
                 for (auto& w : writes) {
                     ownR[w.first] = w.second;
                     mark(w.first, last ? tC[t & 1u] : tRr[r], tC[t & 1u], stamp);
-                    if (last) sweep_full = stamp;
+                    if (last) a_sweep_turn_full(ctl, t);
                 }
             }
-            if (sweep_full == stamp) stat_fallbacks++;
         }
-        if (sweep_full == stamp && getenv("F3DS_EMUL_JACOBI_STATS")) {
-            // experiment: Jacobi rounds of a_eval_R_step from the previous sweep's R bits, all tiles dirty in round 0
-            std::vector<uint32_t> jr = ownR;
-            for (int v = 0; v < V; ++v) jr[v] = E.owner[v] | (t == 0 ? F3DS_OWNR_RTRUE : (jr[v] & F3DS_OWNR_RTRUE));
-            std::vector<unsigned char> dirty(T, 1), nd(T, 0);
-            for (int r = 0; r < 64; ++r) {
-                std::vector<uint32_t> snap = jr; long ev = 0, flips = 0;
-                std::fill(nd.begin(), nd.end(), 0);
-                for (int v = 0; v < V; ++v) {
-                    if (!dirty[v >> 6]) continue;
-                    ev++;
-                    const uint32_t nw = E.owner[v] | (a_eval_R_step(s, snap.data(), v) ? F3DS_OWNR_RTRUE : 0u);
-                    if (nw != snap[v]) { jr[v] = nw; flips++; for (int k = 0; k < 27; ++k) { int u = nbrT[(size_t)k * V + v]; if (u >= 0) nd[u >> 6] = 1; } }
+        E.sweep_stats[a_sweep_kind(ctl, t)]++;
+        if (a_sweep_is_full(ctl, t)) {
+            std::vector<int> owned, todo;
+            for (int v = 0; v < V; ++v) { if (E.owner[v]) owned.push_back(v); else ownR[v] = 0u; }
+            stat_r_evals += (long)owned.size();
+            if (a_sweep_full_from_start(ctl, t)) {
+                // d_sweep_R_pre: the voxels no lower helper can reach keep their owner for sure (also entered in the memo); the others leave the mask of the
+                // neighbour slots that carry a thief -- while ghost leaves are active with the ghost flag, which sends every owned voxel to the walker -- and
+                // d_sweep_R derives their R from the masks
+                for (int v : owned) {
+                    const uint32_t mask = a_thief_mask(s, v) | (n_ghosts ? F3DS_TMASK_GHOST : 0u);
+                    if (mask == 0u) { ownR[v] = E.owner[v] | F3DS_OWNR_RTRUE; R[v] = (unsigned char)((tag << 2) | F3DS_R_TRUE); }
+                    else { tmask[v] = mask; todo.push_back(v); }
                 }
-                fprintf(stderr, "   sweep %u jacobi round %d: evals %ld flips %ld\n", t, r, ev, flips);
-                if (!flips) break;
-                dirty.swap(nd);
-            }
-        }
-        if (sweep_full == stamp) {
-            int overflow = 0;
-            const unsigned char tag = a_sweep_tag(t);
-            std::fill(R.begin(), R.end(), (unsigned char)0);
-            // like d_sweep_R: voxels whose chain is deeper than the walker's stack are retried in later passes over the memo
-            std::vector<int> todo, again;
-            for (int v = 0; v < V; ++v) { if (E.owner[v]) todo.push_back(v); else ownR[v] = 0u; }
-            for (int pass = 0; !todo.empty(); ++pass) {      // (the device: F3DS_R_PASSES grid passes, then one workgroup until done)
-                const size_t before = todo.size();
-                again.clear();
-                for (int v : todo) {
-                    overflow = 0;
-                    const bool r = a_eval_R(s, v, R.data(), tag, &overflow);
-                    if (overflow) again.push_back(v); else ownR[v] = E.owner[v] | (r ? F3DS_OWNR_RTRUE : 0u);
-                }
-                todo.swap(again);
-                if (todo.size() == before) return F3DS_ERR_UNSUPPORTED;      // no progress: cannot happen
+                if (!walk(todo, ownR, [&](int v, int* overflow) { return a_eval_R_mask(s, v, R.data(), tag, tmask.data(), overflow); })) return F3DS_ERR_UNSUPPORTED;
+                // cross-check: R from the defining equation (a_eval_R, a memo of its own) says the same of every voxel
+                std::vector<uint32_t> chk = ownR;
+                std::fill(Rchk.begin(), Rchk.end(), (unsigned char)0);
+                if (!walk(owned, chk, [&](int v, int* overflow) { return a_eval_R(s, v, Rchk.data(), tag, overflow); })) return F3DS_ERR_UNSUPPORTED;
+                if (chk != ownR) return F3DS_ERR_LOGIC;
+            } else {
+                // the fallback of d_sweep_R: no pre-pass has run; R of every owned voxel from the memoised walker (no ghost leaf is active in an incremental sweep)
+                if (!walk(owned, ownR, [&](int v, int* overflow) { return a_eval_R(s, v, R.data(), tag, overflow, false); })) return F3DS_ERR_UNSUPPORTED;
             }
         }
         // claim, in place
         std::fill(done.begin(), done.end(), 0);
         {
-            const bool full = sweep_full == stamp;
+            const bool full = a_sweep_is_full(ctl, t), marks = a_sweep_marks(ctl, t);
             std::vector<std::pair<int, std::pair<uint32_t, float>>> writes;
             for (int v = 0; v < V; ++v) {
                 if (!full && tC[t & 1u][v >> 6] != stamp) continue;
@@ -346,17 +352,12 @@ int stage_sweeps(f3ds_emul& E, const std::vector<int>& seeds, bool reseed) {
                 const int v = w.first; const uint32_t o0 = E.owner[v], o = w.second.first;
                 E.owner[v] = o; E.dist[v] = w.second.second;
                 if (o != o0) { if (o) hD[o] = stamp; if (o0) hD[o0] = stamp; }
-                if (sweep_marks == stamp) mark(v, tR[(t + 1u) & 1u], tC[(t + 1u) & 1u], t + 2u);
+                if (marks) mark(v, tR[(t + 1u) & 1u], tC[(t + 1u) & 1u], t + 2u);
                 n_changed++;
             }
         }
-        if (getenv("F3DS_EMUL_SWEEP_STATS")) {
-            static long pr = 0, pc = 0;
-            fprintf(stderr, "sweep %u: changed %u ghosts %u full %d  R evals %ld claim evals %ld\n", t, n_changed, n_ghosts, sweep_full == stamp, stat_r_evals - pr, stat_c_evals - pc);
-            pr = stat_r_evals; pc = stat_c_evals;
-        }
         // updateCentroid of the helpers whose leaf set changed
-        const bool marks = n_changed <= thr && sweep_marks == stamp;
+        const bool marks = a_sweep_marks_after_claim(ctl, t, thr);
         std::map<int, std::vector<int>> gmap;
         for (int h = 1; h <= S0; ++h) if (E.ghost_active[h] && !done[h]) gmap[E.ghost_vox[h]].push_back(h);
         std::vector<unsigned char> proc(S0 + 1, 0);
@@ -385,8 +386,9 @@ int stage_sweeps(f3ds_emul& E, const std::vector<int>& seeds, bool reseed) {
         }
     }
     if (getenv("F3DS_EMUL_SWEEP_STATS"))
-        fprintf(stderr, "incremental sweeps %ld of %u, fallbacks %ld, R evals %ld, claim evals %ld, centroid evals %ld (full would be %ld / %ld / %ld)\n", stat_inc_sweeps,
-                E.res.sweeps, stat_fallbacks, stat_r_evals, stat_c_evals, stat_h_evals, (long)V * E.res.sweeps, (long)V * E.res.sweeps, (long)S0 * E.res.sweeps);
+        fprintf(stderr, "%u sweeps: %u full from their start, %u incremental, %u fallbacks, %u idle; R evals %ld, claim evals %ld, centroid evals %ld (evaluating everything: %ld / %ld / %ld)\n",
+                E.res.sweeps, E.sweep_stats[F3DS_SWEEP_FULL], E.sweep_stats[F3DS_SWEEP_INCREMENTAL], E.sweep_stats[F3DS_SWEEP_FALLBACK], E.sweep_stats[F3DS_SWEEP_IDLE],
+                stat_r_evals, stat_c_evals, stat_h_evals, (long)V * E.res.sweeps, (long)V * E.res.sweeps, (long)S0 * E.res.sweeps);
     return 0;
 }
 
@@ -646,6 +648,7 @@ int f3ds_emul_get(f3ds_emul* E, int what, void* dst, size_t cap, size_t* bytes_o
         case F3DS_DBG_MERGES: put(E->merges.data(), E->merges.size() * 4); break;
         case F3DS_DBG_VOXEL_REGION: put(E->voxel_region.data(), E->voxel_region.size() * 4); break;
         case F3DS_DBG_SV_REGION: put(E->sv_region.data(), E->sv_region.size() * 4); break;
+        case F3DS_DBG_SWEEP_STATS: put(E->sweep_stats, sizeof E->sweep_stats); break;
         default: return F3DS_ERR_ARG;
     }
     if (bytes_out) *bytes_out = buf.size();
@@ -729,6 +732,13 @@ int f3ds_emul_refine(f3ds_emul* Ep, int num_itr, uint32_t* voxel_sv_label, float
     E.vf = vf0; E.dist = dist0; E.hc = hc0; E.owner = owner0; E.hcount = hcount0; E.ghost_vox = gv0; E.ghost_active = ga0; E.res = res0;
     return k > cap_sv && (sv_label || sv_feat || sv_count) ? F3DS_ERR_CAPACITY : F3DS_OK;
 }
+
+// the sweep-control protocol of the device kernels (a_sweep_begin, a_sweep_thr in csrc/f3ds_algo.h) for tests/test_sweep_control_cpu.py.  words: n_changed, sweep_full,
+// sweep_pre, sweep_marks, sweep_idle, updated in place; returns 0 for an idle sweep
+int f3ds_emul_sweep_begin(uint32_t* words, uint32_t t, uint32_t n_ghosts, uint32_t thr) {
+    return a_sweep_begin(SweepCtl{&words[0], &words[1], &words[2], &words[3], &words[4]}, t, n_ghosts, thr) ? 1 : 0;
+}
+uint32_t f3ds_emul_sweep_thr(uint32_t V, int inc_shift) { return a_sweep_thr(V, inc_shift); }
 
 // numerics probes for tests/test_numerics.py (device arithmetic evaluated on the host)
 float f3ds_emul_ciede00(const float* l1, const float* l2) { return n_ciede00(l1, l2); }
