@@ -110,6 +110,26 @@ class TrackResult(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class RegionRow(ctypes.Structure):
+    """f3ds_region_row (include/f3ds.h): one region of a label image over an RGB-D frame, 72 bytes."""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("n_pixels", "first_pixel", "u_min", "v_min", "u_max", "v_max")] + \
+               [(k, ctypes.c_float * 3) for k in ("lo", "hi", "centroid", "mean_rgb")]
+
+
+class RegionTableResult(ctypes.Structure):
+    """f3ds_region_table_result (include/f3ds.h): the counts of one region table."""
+    _fields_ = [("n_regions", ctypes.c_uint32), ("n_nonempty", ctypes.c_uint32), ("n_labelled", ctypes.c_uint64), ("n_clamped", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+# the same 72 bytes as a numpy structured dtype: what region_table_host and Context.region_table return their rows in
+REGION_ROW_DTYPE = np.dtype([(k, np.uint32) for k in ("n_pixels", "first_pixel", "u_min", "v_min", "u_max", "v_max")] +
+                            [(k, np.float32, (3,)) for k in ("lo", "hi", "centroid", "mean_rgb")])
+assert REGION_ROW_DTYPE.itemsize == ctypes.sizeof(RegionRow) == 72
+
+
 class SupervoxelSet(ctypes.Structure):
     """f3ds_supervoxel_set (include/f3ds.h): the supervoxel_clusters map of the reference as plain arrays."""
     _fields_ = [("n_supervoxels", ctypes.c_uint32), ("label", ctypes.c_void_p), ("voxel_offset", ctypes.c_void_p), ("voxel_xyz", ctypes.c_void_p),
@@ -175,6 +195,11 @@ def load_library(path=None):
         lib.f3ds_tracker_get_ids.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]; lib.f3ds_tracker_get_ids.restype = ctypes.c_int
         lib.f3ds_track_reproject.argtypes = [ctypes.POINTER(RgbdFormat), vp, vp, sz, vp, vp]; lib.f3ds_track_reproject.restype = ctypes.c_int
         lib.f3ds_track_assign.argtypes = [tpp, vp, ctypes.c_uint32, vp, sz, vp, ctypes.c_uint32, u32p, vp, trp]; lib.f3ds_track_assign.restype = ctypes.c_int
+    if hasattr(lib, "f3ds_region_table"):
+        rtp = ctypes.POINTER(RegionTableResult)
+        lib.f3ds_region_table_host.argtypes = [ctypes.POINTER(RgbdFormat), vp, vp, vp, ctypes.c_uint32, vp, rtp]; lib.f3ds_region_table_host.restype = ctypes.c_int
+        lib.f3ds_region_table.argtypes = [vp, ctypes.POINTER(RgbdFormat), vp, vp, vp, ctypes.c_uint32, ctypes.c_int, vp, ctypes.c_int, rtp]
+        lib.f3ds_region_table.restype = ctypes.c_int
     lib.f3ds_recluster.argtypes = [vp, ctypes.POINTER(Params), vp, ctypes.c_int, ctypes.POINTER(Result)]
     lib.f3ds_recluster.restype = ctypes.c_int
     lib.f3ds_evaluate.argtypes = [vp, vp, ctypes.POINTER(Performance)]; lib.f3ds_evaluate.restype = ctypes.c_int
@@ -560,6 +585,47 @@ class Tracker(_Handle):
         return _two_call(self.lib, self.lib.f3ds_tracker_get_ids, [self.handle], [_U32])[0]
 
 
+# ---- region table --------------------------------------------------------------------------------------
+def _region_inputs(fmt, depth, labels, color):
+    """(format with the pitches of these arrays, depth array, colour array or None, labels) of the host forms of the region table"""
+    n = int(fmt.width) * int(fmt.height)
+    if color is not None:
+        f, d, c = _rgbd_images(fmt, depth, color)
+    else:
+        if fmt.depth_type not in _DEPTH_DTYPE:
+            raise F3dsError(ERR_ARG, "unknown depth type")
+        d = np.asarray(depth, _DEPTH_DTYPE[fmt.depth_type])
+        if d.shape != (int(fmt.height), int(fmt.width)):
+            raise ValueError("depth must be (height, width), got %r" % (d.shape,))
+        if d.shape[0] <= 1 or d.strides[1] != d.itemsize or d.strides[0] < d.shape[1] * d.itemsize:
+            d = np.ascontiguousarray(d)
+        f, c = fmt.copy(), None
+        f.depth_pitch = 0 if d.flags.c_contiguous else d.strides[0]
+    lab = np.ascontiguousarray(labels, np.uint32).reshape(-1)
+    if lab.size != n:
+        raise ValueError("labels must hold one entry per pixel")
+    return f, d, c, lab
+
+
+def _region_rows(buf, n_regions):
+    if buf is None:
+        return np.empty(int(n_regions), REGION_ROW_DTYPE)
+    if not (isinstance(buf, np.ndarray) and buf.dtype == REGION_ROW_DTYPE and buf.flags.c_contiguous and buf.size == int(n_regions)):
+        raise ValueError("rows_out must be a contiguous REGION_ROW_DTYPE array with one entry per region")
+    return buf
+
+
+def region_table_host(depth, labels, n_regions, fmt, color=None):
+    """f3ds_region_table_host: (rows, RegionTableResult) -- one REGION_ROW_DTYPE row per region of the label image: pixel count, first pixel, pixel box, box of
+    the points, centroid and mean colour (0 without ``color``).  Host arithmetic only: what Context.region_table computes on the device, bit for bit."""
+    lib = load_library()
+    f, d, c, lab = _region_inputs(fmt, depth, labels, color)
+    rows, res = _region_rows(None, n_regions), RegionTableResult()
+    _check(lib, lib.f3ds_region_table_host(ctypes.byref(f), d.ctypes.data, None if c is None else c.ctypes.data, lab.ctypes.data, int(n_regions),
+                                           rows.ctypes.data if len(rows) else None, ctypes.byref(res)))
+    return rows, res
+
+
 # ---- device context ------------------------------------------------------------------------------
 class Context(_Handle):
     """One (device, stream) pair with its grow-only scratch.  Not thread-safe; one per GPU/stream."""
@@ -616,6 +682,23 @@ class Context(_Handle):
                                                     ctypes.byref(self.result)))
         self._n = n
         return labels
+
+    def region_table(self, depth, labels, n_regions, fmt, color=None, rows_out=None, on_device=False):
+        """f3ds_region_table: (rows, RegionTableResult) -- one REGION_ROW_DTYPE row per region of a label image of the frame (what segment_rgbd wrote, a level
+        of labels_at_thresholds, ...), computed on the device in one read of the images; row i is region i, so its track id is ``Tracker.ids()[i]``.  depth,
+        color, labels as in segment_rgbd / Tracker.update (color may be None: mean_rgb is then 0), or device pointers (ints, the pitches of ``fmt`` apply) with
+        ``on_device=True``: ``rows_out`` is then a device pointer to n_regions rows and the rows returned are None.  Leaves the context's frame as it is."""
+        res = RegionTableResult()
+        if on_device:
+            _check(self.lib, self.lib.f3ds_region_table(self.handle, ctypes.byref(fmt), ctypes.c_void_p(int(depth)), ctypes.c_void_p(int(color)) if color is not None else None,
+                                                        ctypes.c_void_p(int(labels)), int(n_regions), 1, ctypes.c_void_p(int(rows_out)) if rows_out is not None else None, 1,
+                                                        ctypes.byref(res)))
+            return None, res
+        f, d, c, lab = _region_inputs(fmt, depth, labels, color)
+        rows = _region_rows(rows_out, n_regions)
+        _check(self.lib, self.lib.f3ds_region_table(self.handle, ctypes.byref(f), d.ctypes.data, None if c is None else c.ctypes.data, lab.ctypes.data, int(n_regions), 0,
+                                                    rows.ctypes.data if len(rows) else None, 0, ctypes.byref(res)))
+        return rows, res
 
     def points(self):
         """f3ds_get_points: the (N, 4) float32 records the last segment call ran on, when the context holds them (segment_rgbd, or segment

@@ -49,6 +49,7 @@
 #include "f3ds_eval_levels.h"
 #include "f3ds_rgbd.h"
 #include "f3ds_track.h"
+#include "f3ds_regions.h"
 
 using namespace f3ds;
 
@@ -56,6 +57,7 @@ using namespace f3ds;
 #include "f3ds_levels.inc"
 #include "f3ds_eval_levels.inc"
 #include "f3ds_track.inc"
+#include "f3ds_regions.inc"
 
 // ================================================================================================
 // batched launch machinery
@@ -174,7 +176,9 @@ const int g_merge_shared_res = [] { const char* e = dev_getenv("F3DS_MERGE_SHARE
     X(uint64_t, evl_k0) X(uint64_t, evl_k1) X(uint32_t, evl_v0) X(uint32_t, evl_v1) X(uint32_t, evl_flag) X(uint64_t, evl_bkey) X(uint32_t, evl_bcnt) X(uint64_t, evl_ukey) X(uint32_t, evl_ucnt) X(uint32_t, evl_glist) \
     X(uint32_t, evl_ssize) X(unsigned char, evl_used) X(float, evl_hterm) X(float, evl_mterm) X(float, evl_tterm) X(uint32_t, evl_tsize) X(uint32_t, evl_order) X(uint32_t, evl_slot) X(uint32_t, evl_counts) X(uint32_t, evl_out) \
     /* label tracker (f3ds_track.inc; the sort and the reduction use the evl_ buffers of the tracker's private context): labels as uploaded, the ends of the entries' runs, the packed entries, id[], the ids of a host caller */ \
-    X(uint32_t, trk_lab) X(uint32_t, trk_end) X(uint32_t, trk_out) X(uint32_t, trk_id) X(uint32_t, trk_tid)
+    X(uint32_t, trk_lab) X(uint32_t, trk_end) X(uint32_t, trk_out) X(uint32_t, trk_id) X(uint32_t, trk_tid) \
+    /* region table (f3ds_regions.inc), its own so that the call leaves every other one alone: the images and labels as uploaded, the accumulators, the head and the rows of a host caller */ \
+    X(unsigned char, rgt_depth) X(unsigned char, rgt_color) X(uint32_t, rgt_lab) X(RgAcc, rgt_acc) X(unsigned char, rgt_out)
 template <class T> struct Scratch { T* p = nullptr; size_t cap = 0; int slot = -1; };      // cap: bytes allocated; slot: position in F3DS_SCRATCH
 #define F3DS_SCRATCH_SLOT(T, name) S_##name,
 #define F3DS_SCRATCH_MEMBER(T, name) Scratch<T> name{nullptr, 0, S_##name};
@@ -203,6 +207,7 @@ struct f3ds_ctx {
     hipEvent_t ev_args[2] = {nullptr, nullptr}; bool args_used[2] = {false, false}; int args_flip = 0;
     hipEvent_t ev_copy[3] = {nullptr, nullptr, nullptr};      // uploads queued on the device's copy stream / labels ready on the call's stream / downloads done on the copy stream
     DevCounters* d_dcblk = nullptr; DevCounters* h_dcblk = nullptr; size_t dcblk_cap = 0;      // the batch's counters, one slot per frame
+    unsigned char* h_rgt = nullptr; size_t h_rgt_cap = 0;      // pinned: the head (and a host caller's rows) of f3ds_region_table on their way down
     // frame state
     bool have_frame = false;
     bool live = false;
@@ -1206,6 +1211,7 @@ void f3ds_destroy(f3ds_ctx* c) {
     for (auto& e : c->ev_copy) if (e) (void)hipEventDestroy(e);
     if (c->d_dcblk) (void)hipFree(c->d_dcblk);
     if (c->h_dcblk) (void)hipHostFree(c->h_dcblk);
+    if (c->h_rgt) (void)hipHostFree(c->h_rgt);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -2501,5 +2507,68 @@ extern "C" int f3ds_tracker_update(f3ds_tracker* t, const f3ds_rgbd_format* fmt_
     t->cur = nxt; t->have_prev = true; t->have_fmt = true; t->fmt = fmt;
     t->prev_id = ids; t->ids.swap(ids); t->have_ids = true; t->next_id = next;
     if (result) *result = r;
+    return F3DS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// region table (f3ds_regions.h / .inc): one row per region of a label image over an RGB-D frame.  Three kernels in one flush --
+// d_region_init, d_region_accum (the one read of the images), d_region_finish -- then ONE download, the call's only wait: the head (counts, the bad-label
+// flag) and, for a host caller, the rows behind it (72 B per region: they ride with the head on the call's stream, not through the copy stream).  The
+// scratch is the call's own (rgt_*), so nothing another call of the context reads is touched.
+// ------------------------------------------------------------------------------------------------
+extern "C" int f3ds_region_table(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const void* color, const uint32_t* labels, uint32_t n_regions, int inputs_on_device,
+                                 f3ds_region_row* rows, int rows_on_device, f3ds_region_table_result* result) {
+    if (!c) return F3DS_ERR_ARG;
+    f3ds_rgbd_format fmt; f3ds::RgbdLayout lay;
+    if (const int rc = rg_check(fmt_, depth, color, labels, n_regions, rows, &fmt, &lay)) return rc;
+    g_sw.read();
+    HIPCHECK(hipSetDevice(c->device));
+    Batch b = batch_of(c);
+    const uint32_t n = (uint32_t)lay.n, K = n_regions, copies = rgt_copies(K);
+    constexpr size_t HEAD_BYTES = 64;      // RGT_HEAD words, and the rows behind them 8-byte aligned
+    const size_t out_bytes = HEAD_BYTES + (rows_on_device ? 0u : (size_t)K * sizeof(f3ds_region_row));
+    // every buffer of the call before anything is recorded
+    RgAcc* acc; unsigned char *out, *ud = nullptr, *uc = nullptr; uint32_t* ul = nullptr;
+    ENSURE(c->rgt_acc, K ? (size_t)K * copies : 1u, acc); ENSURE(c->rgt_out, out_bytes, out);
+    if (c->h_rgt_cap < out_bytes) {
+        if (c->h_rgt) { HIPCHECK(hipHostFree(c->h_rgt)); c->h_rgt = nullptr; c->h_rgt_cap = 0; }
+        HIPCHECK(hipHostMalloc(&c->h_rgt, out_bytes + out_bytes / 4, hipHostMallocDefault));
+        c->h_rgt_cap = out_bytes + out_bytes / 4;
+    }
+    const unsigned char* d_depth = static_cast<const unsigned char*>(depth);
+    const unsigned char* d_color = static_cast<const unsigned char*>(color);
+    const uint32_t* d_lab = labels;
+    if (!inputs_on_device) {      // host images go through the device's copy stream, like those of f3ds_tracker_update
+        ENSURE(c->rgt_depth, lay.depth_bytes, ud); ENSURE(c->rgt_lab, n, ul);
+        if (color) ENSURE(c->rgt_color, lay.color_bytes, uc);
+        hipStream_t up = g_sw.copy_stream ? copy_stream_of(c->device) : nullptr;
+        HIPCHECK(hipMemcpyAsync(ud, depth, lay.depth_bytes, hipMemcpyHostToDevice, up ? up : b.st));
+        if (color) HIPCHECK(hipMemcpyAsync(uc, color, lay.color_bytes, hipMemcpyHostToDevice, up ? up : b.st));
+        HIPCHECK(hipMemcpyAsync(ul, labels, (size_t)n * 4, hipMemcpyHostToDevice, up ? up : b.st));
+        if (up) { if (const int urc = await_uploads(b, up)) return urc; }
+        d_depth = ud; d_color = uc; d_lab = ul;
+    }
+    RegionArgs a;
+    memset(&a, 0, sizeof a);
+    a.width = fmt.width; a.n = n; a.depth_pitch = lay.depth_pitch; a.color_pitch = lay.color_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
+    a.color_format = color ? fmt.color_format : -1; a.K = K; a.copies = copies;
+    a.depth_scale = fmt.depth_scale; a.fx = fmt.fx; a.fy = fmt.fy; a.cx = fmt.cx; a.cy = fmt.cy;
+    uint32_t* head = reinterpret_cast<uint32_t*>(out);
+    f3ds_region_row* d_rows = rows_on_device ? rows : reinterpret_cast<f3ds_region_row*>(out + HEAD_BYTES);
+    rec<d_region_init>(c, grid_for((size_t)K * copies * RG_WORDS, 256), 0u, reinterpret_cast<uint32_t*>(acc), K * copies, head);
+    rec<d_region_accum>(c, grid_for((n + RGT_TRIPS - 1u) / RGT_TRIPS, 256), 0u, d_depth, d_color, d_lab, a, acc, head);
+    rec<d_region_finish>(c, grid_for(K, 256), 0u, acc, K, copies, head, d_rows);
+    if (const int rc = flush(b)) return rc;
+    HIPCHECK(hipMemcpyAsync(c->h_rgt, out, out_bytes, hipMemcpyDeviceToHost, b.st));
+    HIPCHECK(timed_sync(b.st));
+    HIPCHECK(hipGetLastError());
+    uint32_t h[RGT_HEAD];
+    memcpy(h, c->h_rgt, sizeof h);
+    if (h[1]) return F3DS_ERR_ARG;      // a label >= n_regions: d_region_finish wrote no row, and none is copied out
+    if (!rows_on_device && K) memcpy(rows, c->h_rgt + HEAD_BYTES, (size_t)K * sizeof(f3ds_region_row));
+    if (result) {
+        result->n_regions = K; result->n_nonempty = h[0];
+        memcpy(&result->n_labelled, h + 2, 8); memcpy(&result->n_clamped, h + 4, 8);
+    }
     return F3DS_OK;
 }

@@ -18,6 +18,7 @@
 #include "f3ds_numerics.h"
 #include "f3ds_rgbd.h"
 #include "f3ds_track.h"
+#include "f3ds_regions.h"
 
 extern "C" {
 
@@ -172,6 +173,47 @@ int f3ds_track_assign(const f3ds_track_params* params, const uint32_t* size, uin
         result->n_regions = n_regions; result->n_nonempty = n_nonempty; result->n_matched = n_matched; result->n_new = n_new; result->n_retired = n_retired;
         result->n_entries = (uint32_t)n_entries; result->next_id = next; result->first_frame = 0u; result->n_labelled = n_labelled; result->n_votes = n_votes;
     }
+    return F3DS_OK;
+}
+
+// ---- region table: the definition (the rules are in f3ds_regions.h, which d_region_accum and d_region_finish call too) ----
+// Two passes: the labels are checked before a row is written.  Pixels are read with memcpy, as in f3ds_deproject.
+int f3ds_region_table_host(const f3ds_rgbd_format* fmt_, const void* depth, const void* color, const uint32_t* labels, uint32_t n_regions, f3ds_region_row* rows,
+                           f3ds_region_table_result* result) {
+    f3ds_rgbd_format fmt; f3ds::RgbdLayout l;
+    if (const int rc = f3ds::rg_check(fmt_, depth, color, labels, n_regions, rows, &fmt, &l)) return rc;
+    for (size_t p = 0; p < l.n; ++p) if (labels[p] != F3DS_NO_LABEL && labels[p] >= n_regions) return F3DS_ERR_ARG;
+    std::vector<f3ds::RgAcc> acc(n_regions);
+    for (f3ds::RgAcc& a : acc) f3ds::rg_empty(a);
+    const unsigned char* dimg = static_cast<const unsigned char*>(depth);
+    const unsigned char* cimg = static_cast<const unsigned char*>(color);
+    uint64_t n_labelled = 0, n_clamped = 0;
+    for (uint32_t v = 0; v < fmt.height; ++v) {
+        const unsigned char* drow = dimg + (size_t)v * l.depth_pitch;
+        const unsigned char* crow = cimg ? cimg + (size_t)v * l.color_pitch : nullptr;
+        for (uint32_t u = 0; u < fmt.width; ++u) {
+            const uint32_t p = v * fmt.width + u, lab = labels[p];
+            float z = 0.0f; bool valid;
+            if (fmt.depth_type == F3DS_DEPTH_F32) { float d; memcpy(&d, drow + 4u * (size_t)u, 4); valid = f3ds::n_depth_to_z(d, fmt.depth_scale, z); }
+            else { uint16_t d; memcpy(&d, drow + 2u * (size_t)u, 2); valid = f3ds::n_depth_to_z(d, fmt.depth_scale, z); }
+            if (!valid || lab == F3DS_NO_LABEL) continue;
+            uint32_t rgba = 0u;
+            if (crow) {
+                const unsigned char* q = crow + (size_t)l.color_elem * u;
+                if (fmt.color_format == F3DS_COLOR_PACKED) memcpy(&rgba, q, 4);
+                else rgba = f3ds::n_color_word(q[0], q[1], q[2], 255u);      // (alpha is not part of a row)
+            }
+            float x, y, zo;
+            f3ds::n_deproject(u, v, valid, z, fmt.fx, fmt.fy, fmt.cx, fmt.cy, x, y, zo);
+            f3ds::RgAcc one;
+            if (f3ds::rg_pixel(p, u, v, x, y, zo, rgba, one)) ++n_clamped;
+            f3ds::rg_merge(acc[lab], one);
+            ++n_labelled;
+        }
+    }
+    uint32_t n_nonempty = 0;
+    for (uint32_t r = 0; r < n_regions; ++r) { f3ds::rg_finish(acc[r], &rows[r]); if (acc[r].w[0]) ++n_nonempty; }
+    if (result) { result->n_regions = n_regions; result->n_nonempty = n_nonempty; result->n_labelled = n_labelled; result->n_clamped = n_clamped; }
     return F3DS_OK;
 }
 

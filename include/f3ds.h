@@ -255,6 +255,44 @@ int f3ds_track_reproject(const f3ds_rgbd_format* fmt, const float* pose12, const
 int f3ds_track_assign(const f3ds_track_params* params, const uint32_t* size, uint32_t n_regions, const uint32_t* entries, size_t n_entries,
                       const uint32_t* prev_id, uint32_t n_prev, uint32_t* next_id, uint32_t* id_of_region, f3ds_track_result* result);
 
+/* ---- region table: one fixed-size row per region of a label image over an RGB-D frame ----------------------------------------
+ * What a consumer that follows objects asks of a frame: where each region is in the image, where it is in space, how big it is and what colour it has,
+ * without downloading the label image.  labels: one u32 per pixel, < n_regions or F3DS_NO_LABEL -- what f3ds_segment_rgbd wrote, a level of
+ * f3ds_labels_at_thresholds, or any other label image of the frame.  Row i is region i, so the row of a tracked region has the track id
+ * id_of_region[i] of f3ds_tracker_get_ids.  The definition, bit for bit (csrc/f3ds_regions.h):
+ *   point    pixel p = v * width + u gets (x, y, z) by the rule of f3ds_deproject; it is LABELLED iff its depth is valid and label[p] != F3DS_NO_LABEL
+ *            (as in the tracker).  A pixel with a label and an invalid depth contributes to nothing.
+ *   fixed    for a finite f32 a, fix(a) = (int64_t)rint(clamp((double)a, -32768.0, 32768.0) * 65536.0), rint rounding half to even: units of 2^-16 m.  A
+ *            labelled pixel is CLAMPED iff the clamp changed one of its three coordinates.
+ *   order    minima and maxima of floats are taken in the total order of key(bits) = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000): -0 is below +0.
+ *   row      the fields below over the labelled pixels of the region; with color == NULL mean_rgb is 0.0f in every non-empty row.
+ *   empty    a region without a labelled pixel has first_pixel = u_min = v_min = 0xFFFFFFFF, u_max = v_max = 0, lo = +inf, hi = -inf and
+ *            centroid = mean_rgb = the quiet NaN 0x7FC00000.
+ * Every field is an integer count, a minimum, a maximum or a sum of integers: the result does not depend on the order of evaluation, and the device
+ * gives the bits of the host function.
+ * Errors (both functions alike): F3DS_ERR_ARG for a NULL fmt, depth or labels, for NULL rows unless n_regions == 0, for what f3ds_deproject refuses of
+ * a format (the two colour fields are looked at only when color != NULL) and for a label >= n_regions other than F3DS_NO_LABEL (the device function finds
+ * it on the device and reports it at the call's one wait); rows and result are then not written, on the host or on the device.  F3DS_ERR_UNSUPPORTED for
+ * n_regions > 0x00FFFFFF.  n_regions == 0, or a frame without a labelled pixel, is F3DS_OK: the rows, if there are any, are all empty. */
+typedef struct f3ds_region_row {
+    uint32_t n_pixels;                   /* labelled pixels of the region                                  */
+    uint32_t first_pixel;                /* smallest pixel index among them                                */
+    uint32_t u_min, v_min, u_max, v_max; /* inclusive pixel box                                            */
+    float lo[3], hi[3];                  /* box of the points (x, y, z), in the order of key               */
+    float centroid[3];                   /* (float)(((double)sum_fix / (double)n_pixels) / 65536.0)        */
+    float mean_rgb[3];                   /* (float)((double)sum_channel / (double)n_pixels); r, g, b of the colour word */
+} f3ds_region_row;
+typedef struct f3ds_region_table_result { uint32_t n_regions, n_nonempty; uint64_t n_labelled, n_clamped; } f3ds_region_table_result;
+/* host arithmetic only, no device needed: the definition */
+int f3ds_region_table_host(const f3ds_rgbd_format* fmt, const void* depth, const void* color /* may be NULL */, const uint32_t* labels,
+                           uint32_t n_regions, f3ds_region_row* rows, f3ds_region_table_result* result /* may be NULL */);
+/* the same rows from the device, in one read of the images (csrc/f3ds_regions.inc).  inputs_on_device: depth, color and labels are device memory and
+ * read where they are; host inputs go through the device's copy stream like those of f3ds_tracker_update.  rows_on_device: rows is device memory;
+ * host rows arrive with the call's one small download.  Synchronous.  Runs on ctx's stream and uses scratch of its own only: every other call on the
+ * context behaves as if this one never happened (as f3ds_evaluate_levels).  Also F3DS_ERR_ARG for a NULL ctx. */
+int f3ds_region_table(f3ds_ctx* ctx, const f3ds_rgbd_format* fmt, const void* depth, const void* color, const uint32_t* labels, uint32_t n_regions,
+                      int inputs_on_device, f3ds_region_row* rows, int rows_on_device, f3ds_region_table_result* result);
+
 /* Clustering::cluster(threshold) again on the supervoxels of the last f3ds_segment call, with
  * possibly different metric / merging settings (src/clustering.cpp:670-679).  Only the merge
  * fields of `params` are read. */
