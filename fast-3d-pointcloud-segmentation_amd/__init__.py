@@ -130,6 +130,24 @@ REGION_ROW_DTYPE = np.dtype([(k, np.uint32) for k in ("n_pixels", "first_pixel",
 assert REGION_ROW_DTYPE.itemsize == ctypes.sizeof(RegionRow) == 72
 
 
+class RegionContact(ctypes.Structure):
+    """f3ds_region_contact (include/f3ds.h): one pair of regions of a label image that touch, 32 bytes."""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("a", "b", "n_pairs", "n_close", "n_a_front", "n_horizontal", "first_pixel")] + [("mean_gap", ctypes.c_float)]
+
+
+class RegionContactsResult(ctypes.Structure):
+    """f3ds_region_contacts_result (include/f3ds.h): the counts of one call for the region contacts."""
+    _fields_ = [("n_regions", ctypes.c_uint32), ("n_contacts", ctypes.c_uint32), ("n_pairs", ctypes.c_uint64), ("n_close", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+# the same 32 bytes as a numpy structured dtype: what region_contacts_host and Context.region_contacts return their rows in
+REGION_CONTACT_DTYPE = np.dtype([(k, np.uint32) for k in ("a", "b", "n_pairs", "n_close", "n_a_front", "n_horizontal", "first_pixel")] + [("mean_gap", np.float32)])
+assert REGION_CONTACT_DTYPE.itemsize == ctypes.sizeof(RegionContact) == 32
+
+
 class SupervoxelSet(ctypes.Structure):
     """f3ds_supervoxel_set (include/f3ds.h): the supervoxel_clusters map of the reference as plain arrays."""
     _fields_ = [("n_supervoxels", ctypes.c_uint32), ("label", ctypes.c_void_p), ("voxel_offset", ctypes.c_void_p), ("voxel_xyz", ctypes.c_void_p),
@@ -200,6 +218,12 @@ def load_library(path=None):
         lib.f3ds_region_table_host.argtypes = [ctypes.POINTER(RgbdFormat), vp, vp, vp, ctypes.c_uint32, vp, rtp]; lib.f3ds_region_table_host.restype = ctypes.c_int
         lib.f3ds_region_table.argtypes = [vp, ctypes.POINTER(RgbdFormat), vp, vp, vp, ctypes.c_uint32, ctypes.c_int, vp, ctypes.c_int, rtp]
         lib.f3ds_region_table.restype = ctypes.c_int
+    if hasattr(lib, "f3ds_region_contacts"):
+        rcp = ctypes.POINTER(RegionContactsResult)
+        lib.f3ds_region_contacts_host.argtypes = [ctypes.POINTER(RgbdFormat), vp, vp, ctypes.c_uint32, ctypes.c_float, vp, sz, ctypes.POINTER(sz), rcp]
+        lib.f3ds_region_contacts_host.restype = ctypes.c_int
+        lib.f3ds_region_contacts.argtypes = [vp, ctypes.POINTER(RgbdFormat), vp, vp, ctypes.c_uint32, ctypes.c_float, ctypes.c_int, vp, sz, ctypes.c_int, ctypes.POINTER(sz), rcp]
+        lib.f3ds_region_contacts.restype = ctypes.c_int
     lib.f3ds_recluster.argtypes = [vp, ctypes.POINTER(Params), vp, ctypes.c_int, ctypes.POINTER(Result)]
     lib.f3ds_recluster.restype = ctypes.c_int
     lib.f3ds_evaluate.argtypes = [vp, vp, ctypes.POINTER(Performance)]; lib.f3ds_evaluate.restype = ctypes.c_int
@@ -626,6 +650,42 @@ def region_table_host(depth, labels, n_regions, fmt, color=None):
     return rows, res
 
 
+# ---- region contacts -------------------------------------------------------------------------------
+_CONTACT_ROWS_FIRST = 1024      # rows the first call of the package's two functions has room for; more: the buffer grows from n_out and the call is repeated
+
+
+def _contact_rows(call, rows_out):
+    """the rows of call(pointer, cap, byref(n_out)) -> rc: into ``rows_out`` (too small: CapacityError), or into a buffer grown from n_out"""
+    n_out = ctypes.c_size_t(0)
+    if rows_out is not None:
+        if not (isinstance(rows_out, np.ndarray) and rows_out.dtype == REGION_CONTACT_DTYPE and rows_out.flags.c_contiguous and rows_out.ndim == 1):
+            raise ValueError("rows_out must be a contiguous one-dimensional REGION_CONTACT_DTYPE array")
+        rc = call(rows_out.ctypes.data if len(rows_out) else None, len(rows_out), ctypes.byref(n_out))
+        if rc == 0 and n_out.value > len(rows_out):      # (an empty buffer is a NULL pointer: the call only counted)
+            rc = ERR_CAPACITY
+        return rc, rows_out[:n_out.value] if rc == 0 else None
+    rows = np.empty(_CONTACT_ROWS_FIRST, REGION_CONTACT_DTYPE)
+    rc = call(rows.ctypes.data, len(rows), ctypes.byref(n_out))
+    if rc == ERR_CAPACITY:
+        rows = np.empty(n_out.value, REGION_CONTACT_DTYPE)
+        rc = call(rows.ctypes.data, len(rows), ctypes.byref(n_out))
+    return rc, rows[:n_out.value].copy() if rc == 0 else None
+
+
+def region_contacts_host(depth, labels, n_regions, fmt, depth_tol=0.05):
+    """f3ds_region_contacts_host: (rows, RegionContactsResult) -- one REGION_CONTACT_DTYPE row per pair of regions (a < b) of the label image that touch
+    (4-connectivity), by a and then b: contact pairs, how many of them are close in depth (|za - zb| <= depth_tol * min(za, zb)), in how many of the others a
+    is in front, how many are horizontal, the first pixel and the mean gap.  Host arithmetic only: what Context.region_contacts computes on the device, bit
+    for bit."""
+    lib = load_library()
+    f, d, _, lab = _region_inputs(fmt, depth, labels, None)
+    res = RegionContactsResult()
+    rc, rows = _contact_rows(lambda ptr, cap, n_out: lib.f3ds_region_contacts_host(ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), float(depth_tol), ptr, cap,
+                                                                                    n_out, ctypes.byref(res)), None)
+    _check(lib, rc)
+    return rows, res
+
+
 # ---- device context ------------------------------------------------------------------------------
 class Context(_Handle):
     """One (device, stream) pair with its grow-only scratch.  Not thread-safe; one per GPU/stream."""
@@ -698,6 +758,26 @@ class Context(_Handle):
         rows = _region_rows(rows_out, n_regions)
         _check(self.lib, self.lib.f3ds_region_table(self.handle, ctypes.byref(f), d.ctypes.data, None if c is None else c.ctypes.data, lab.ctypes.data, int(n_regions), 0,
                                                     rows.ctypes.data if len(rows) else None, 0, ctypes.byref(res)))
+        return rows, res
+
+    def region_contacts(self, depth, labels, n_regions, fmt, depth_tol=0.05, rows_out=None, on_device=False):
+        """f3ds_region_contacts: (rows, RegionContactsResult) -- what region_contacts_host returns, computed on the device; a and b index the rows of
+        region_table and ``Tracker.ids()``.  depth and labels as in region_table, or device pointers (ints, the depth pitch of ``fmt`` applies) with
+        ``on_device=True``: ``rows_out`` is then ``(device pointer, capacity in rows)`` or None (count only), the rows returned are None and
+        ``result.n_contacts`` says how many were written (CapacityError, and none written, when there are more than the capacity).  With host arrays
+        ``rows_out`` may be a REGION_CONTACT_DTYPE array to fill (the rows returned are a view of it); without it a buffer that turns out too small is grown
+        from the count and the call repeated: one device pass when it suffices.  Leaves the context's frame as it is."""
+        res = RegionContactsResult()
+        if on_device:
+            ptr, cap = (None, 0) if rows_out is None else (ctypes.c_void_p(int(rows_out[0])), int(rows_out[1]))
+            n_out = ctypes.c_size_t(0)
+            _check(self.lib, self.lib.f3ds_region_contacts(self.handle, ctypes.byref(fmt), ctypes.c_void_p(int(depth)), ctypes.c_void_p(int(labels)), int(n_regions),
+                                                           float(depth_tol), 1, ptr, cap, 1, ctypes.byref(n_out), ctypes.byref(res)))
+            return None, res
+        f, d, _, lab = _region_inputs(fmt, depth, labels, None)
+        rc, rows = _contact_rows(lambda ptr, cap, n_out: self.lib.f3ds_region_contacts(self.handle, ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions),
+                                                                                       float(depth_tol), 0, ptr, cap, 0, n_out, ctypes.byref(res)), rows_out)
+        _check(self.lib, rc)
         return rows, res
 
     def points(self):

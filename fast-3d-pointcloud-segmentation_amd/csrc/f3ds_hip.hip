@@ -50,6 +50,7 @@
 #include "f3ds_rgbd.h"
 #include "f3ds_track.h"
 #include "f3ds_regions.h"
+#include "f3ds_contacts.h"
 
 using namespace f3ds;
 
@@ -58,6 +59,7 @@ using namespace f3ds;
 #include "f3ds_eval_levels.inc"
 #include "f3ds_track.inc"
 #include "f3ds_regions.inc"
+#include "f3ds_contacts.inc"
 
 // ================================================================================================
 // batched launch machinery
@@ -133,7 +135,7 @@ const int g_inc_shift = [] { const char* e = dev_getenv("F3DS_INC_SHIFT"); retur
 // where hundreds of getenv() scans per call would also race with a setenv from another thread.  Tests still see per-call values.
 struct Switches {
     bool direct_labels = false, copy_stream = true, copy_duplex = false, split_voxel_accum = false, sweep_tiles = true, merge_spec = true, force_global_merge = false, no_stream_pool = false, sort_pairs = false, host_prof = false, trace_err = false, vox_hash = true, vox_tiles_forced = false, levels_global = false;
-    int normals_threads = 0, merge_nw = 0, merge_keys = -1; uint32_t tile_holes = 0, ilist_slack = 32, r_rounds = F3DS_R_ROUNDS, grid_cap = 0; long relabel_lds_cap = -1;
+    int normals_threads = 0, merge_nw = 0, merge_keys = -1; uint32_t tile_holes = 0, ilist_slack = 32, r_rounds = F3DS_R_ROUNDS, grid_cap = 0, rgc_first_cap = 0; long relabel_lds_cap = -1;
     void read() {
         auto on = [](const char* n) { return dev_getenv(n) != nullptr; };
         auto num = [](const char* n, long dflt) { const char* e = dev_getenv(n); return e ? atol(e) : dflt; };
@@ -150,6 +152,7 @@ struct Switches {
         { const long v = num("F3DS_R_ROUNDS_RUN", F3DS_R_ROUNDS); r_rounds = v >= 1 && v <= F3DS_R_ROUNDS ? (uint32_t)v : (uint32_t)F3DS_R_ROUNDS; }
         { const long v = num("F3DS_ILIST_SLACK", 32); ilist_slack = v >= 1 && v <= 32 ? (uint32_t)v : 32u; }      // tests: a short incident-list pool (the merge stage then reruns with a larger one)
         { const long v = num("F3DS_GRID_CAP", 0); grid_cap = v >= 1 && v <= 2048 ? (uint32_t)v : 0u; }      // tests: 1 ... 2048 workgroups per frame, exactly, for grid_for() and grid_wide(): the grid-stride loops make several trips on small frames (0: unset)
+        { const long v = num("F3DS_RGC_FIRST_CAP", 0); rgc_first_cap = v >= 1 && v <= 0x7fffffffl ? (uint32_t)v : 0u; }      // tests: a short first record buffer of f3ds_region_contacts (the frame then runs again with room for all; 0: unset)
     }
 };
 thread_local Switches g_sw;
@@ -178,7 +181,9 @@ const int g_merge_shared_res = [] { const char* e = dev_getenv("F3DS_MERGE_SHARE
     /* label tracker (f3ds_track.inc; the sort and the reduction use the evl_ buffers of the tracker's private context): labels as uploaded, the ends of the entries' runs, the packed entries, id[], the ids of a host caller */ \
     X(uint32_t, trk_lab) X(uint32_t, trk_end) X(uint32_t, trk_out) X(uint32_t, trk_id) X(uint32_t, trk_tid) \
     /* region table (f3ds_regions.inc), its own so that the call leaves every other one alone: the images and labels as uploaded, the accumulators, the head and the rows of a host caller */ \
-    X(unsigned char, rgt_depth) X(unsigned char, rgt_color) X(uint32_t, rgt_lab) X(RgAcc, rgt_acc) X(unsigned char, rgt_out)
+    X(unsigned char, rgt_depth) X(unsigned char, rgt_color) X(uint32_t, rgt_lab) X(RgAcc, rgt_acc) X(unsigned char, rgt_out) \
+    /* region contacts (f3ds_contacts.inc), its own likewise: the image and labels as uploaded, the records' keys and indices (twice: the sort), the records, the runs' flags, keys, starts and ends, the run count, the head and the rows of a host caller */ \
+    X(unsigned char, rgc_depth) X(uint32_t, rgc_lab) X(uint64_t, rgc_k0) X(uint64_t, rgc_k1) X(uint32_t, rgc_v0) X(uint32_t, rgc_v1) X(uint32_t, rgc_rec) X(uint32_t, rgc_flag) X(uint64_t, rgc_ukey) X(uint32_t, rgc_ustart) X(uint32_t, rgc_uend) X(uint32_t, rgc_cnt) X(unsigned char, rgc_out)
 template <class T> struct Scratch { T* p = nullptr; size_t cap = 0; int slot = -1; };      // cap: bytes allocated; slot: position in F3DS_SCRATCH
 #define F3DS_SCRATCH_SLOT(T, name) S_##name,
 #define F3DS_SCRATCH_MEMBER(T, name) Scratch<T> name{nullptr, 0, S_##name};
@@ -208,6 +213,7 @@ struct f3ds_ctx {
     hipEvent_t ev_copy[3] = {nullptr, nullptr, nullptr};      // uploads queued on the device's copy stream / labels ready on the call's stream / downloads done on the copy stream
     DevCounters* d_dcblk = nullptr; DevCounters* h_dcblk = nullptr; size_t dcblk_cap = 0;      // the batch's counters, one slot per frame
     unsigned char* h_rgt = nullptr; size_t h_rgt_cap = 0;      // pinned: the head (and a host caller's rows) of f3ds_region_table on their way down
+    unsigned char* h_rgc = nullptr; size_t h_rgc_cap = 0;      // pinned: the same of f3ds_region_contacts
     // frame state
     bool have_frame = false;
     bool live = false;
@@ -1212,6 +1218,7 @@ void f3ds_destroy(f3ds_ctx* c) {
     if (c->d_dcblk) (void)hipFree(c->d_dcblk);
     if (c->h_dcblk) (void)hipHostFree(c->h_dcblk);
     if (c->h_rgt) (void)hipHostFree(c->h_rgt);
+    if (c->h_rgc) (void)hipHostFree(c->h_rgc);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -2569,6 +2576,102 @@ extern "C" int f3ds_region_table(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, cons
     if (result) {
         result->n_regions = K; result->n_nonempty = h[0];
         memcpy(&result->n_labelled, h + 2, 8); memcpy(&result->n_clamped, h + 4, 8);
+    }
+    return F3DS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// region contacts (f3ds_contacts.h / .inc): one row per pair of regions of a label image that touch.  One flush -- d_contact_init,
+// d_contact_accum (the one pass over the images: records of (pair, seven words)), the radix sort of the record keys, d_evl_heads / scan, d_track_runs,
+// d_contact_finish -- then ONE download, the call's only wait in the ordinary case: the head (row count, the bad-label flag, the records asked for, the sums) and,
+// for a host caller, the first RGC_FIRST_ROWS rows behind it.  A frame with more records than the first buffer holds says so in the head and runs once more
+// with room for all (every contact pair a record of its own: fewer than 2n); a host caller with more rows gets the rest in a second download.  The scratch is
+// the call's own (rgc_*) but for the sort's histogram and the scan's tile sums, which hold nothing between calls.
+// ------------------------------------------------------------------------------------------------
+extern "C" int f3ds_region_contacts(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, float depth_tol,
+                                    int inputs_on_device, f3ds_region_contact* rows, size_t cap, int rows_on_device, size_t* n_out, f3ds_region_contacts_result* result) {
+    if (!c) return F3DS_ERR_ARG;
+    f3ds_rgbd_format fmt; f3ds::RgbdLayout lay;
+    if (const int rc = ct_check(fmt_, depth, labels, n_regions, depth_tol, n_out, &fmt, &lay)) return rc;
+    g_sw.read();
+    HIPCHECK(hipSetDevice(c->device));
+    Batch b = batch_of(c);
+    const uint32_t n = (uint32_t)lay.n, K = n_regions;
+    const uint32_t rec_all = 2u * n;      // (n < 2^31: rgbd_layout)  every contact pair a record of its own is fewer than this
+    const uint32_t first = g_sw.rgc_first_cap ? g_sw.rgc_first_cap : RGC_FIRST_CAP;
+    uint32_t rec_cap = first < rec_all ? first : rec_all;
+    constexpr size_t HEAD_BYTES = 64;      // RGC_HEAD words, and the rows behind them 8-byte aligned
+    const bool host_rows = rows && !rows_on_device;
+    const unsigned char* d_depth = static_cast<const unsigned char*>(depth);
+    const uint32_t* d_lab = labels;
+    if (!inputs_on_device) {      // host images go through the device's copy stream, like those of f3ds_region_table
+        unsigned char* ud; uint32_t* ul;
+        ENSURE(c->rgc_depth, lay.depth_bytes, ud); ENSURE(c->rgc_lab, n, ul);
+        hipStream_t up = g_sw.copy_stream ? copy_stream_of(c->device) : nullptr;
+        HIPCHECK(hipMemcpyAsync(ud, depth, lay.depth_bytes, hipMemcpyHostToDevice, up ? up : b.st));
+        HIPCHECK(hipMemcpyAsync(ul, labels, (size_t)n * 4, hipMemcpyHostToDevice, up ? up : b.st));
+        if (up) { if (const int urc = await_uploads(b, up)) return urc; }
+        d_depth = ud; d_lab = ul;
+    }
+    ContactArgs a;
+    memset(&a, 0, sizeof a);
+    a.width = fmt.width; a.height = fmt.height; a.n = n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
+    a.K = K; a.kb = ct_bits(K); a.depth_scale = fmt.depth_scale; a.depth_tol = depth_tol;
+    const uint64_t hole = ct_hole(K, a.kb);
+    const int sort_bits = ct_sort_bits(K);
+    uint32_t h[RGC_HEAD];
+    size_t stage_rows = 0;
+    unsigned char* out = nullptr;
+    for (int run = 0;; ++run) {
+        a.rec_cap = rec_cap;
+        stage_rows = host_rows ? (cap < rec_cap ? cap : (size_t)rec_cap) : 0u;      // (rows <= records <= rec_cap)
+        const size_t out_bytes = HEAD_BYTES + stage_rows * sizeof(f3ds_region_contact);
+        // every buffer of the run before anything is recorded
+        uint64_t *k0, *k1, *ukey; uint32_t *v0, *v1, *rec_words, *flag, *ustart, *uend, *cnt, *hist, *tiles;
+        ENSURE(c->rgc_k0, rec_cap, k0); ENSURE(c->rgc_k1, rec_cap, k1); ENSURE(c->rgc_v0, rec_cap, v0); ENSURE(c->rgc_v1, rec_cap, v1);
+        ENSURE(c->rgc_rec, (size_t)rec_cap * CT_WORDS, rec_words); ENSURE(c->rgc_flag, rec_cap, flag); ENSURE(c->rgc_ukey, rec_cap, ukey);
+        ENSURE(c->rgc_ustart, rec_cap, ustart); ENSURE(c->rgc_uend, rec_cap, uend); ENSURE(c->rgc_cnt, 4, cnt); ENSURE(c->rgc_out, out_bytes, out);
+        ENSURE(c->hist, (size_t)RS_BINS * ((rec_cap + RS_TILE - 1) / RS_TILE + 1), hist); ENSURE(c->tiles, (rec_cap + SCAN_TILE - 1) / SCAN_TILE + 1, tiles);
+        if (c->h_rgc_cap < out_bytes) {
+            if (c->h_rgc) { HIPCHECK(hipHostFree(c->h_rgc)); c->h_rgc = nullptr; c->h_rgc_cap = 0; }
+            HIPCHECK(hipHostMalloc(&c->h_rgc, out_bytes + out_bytes / 4, hipHostMallocDefault));
+            c->h_rgc_cap = out_bytes + out_bytes / 4;
+        }
+        uint32_t* head = reinterpret_cast<uint32_t*>(out);
+        f3ds_region_contact* d_rows = rows_on_device ? rows : (host_rows ? reinterpret_cast<f3ds_region_contact*>(out + HEAD_BYTES) : nullptr);
+        int rc;
+        rec<d_contact_init>(c, grid_for(rec_cap, 256), 0u, k0, v0, rec_cap, head);
+        rec<d_contact_accum>(c, grid_for((n + RGC_TRIPS - 1u) / RGC_TRIPS, 256), 0u, d_depth, d_lab, a, k0, rec_words, head);
+        uint64_t* ks; uint32_t* vs;
+        if ((rc = radix_sort(c, k0, v0, k1, v1, rec_cap, sort_bits, &ks, &vs))) return rc;
+        rec<d_evl_heads>(c, grid_for(rec_cap, 256), 0u, ks, rec_cap, hole, flag);
+        if ((rc = scan_u32(c, flag, flag, rec_cap))) return rc;
+        rec<d_track_runs>(c, grid_for(rec_cap, 256), 0u, ks, rec_cap, hole, flag, ukey, ustart, uend, cnt);
+        rec<d_contact_finish>(c, grid_for((size_t)(rec_cap < 8192u ? rec_cap : 8192u) * 64u, 256), 0u, ukey, ustart, uend, cnt, vs, rec_words, a.kb, rec_cap, head, d_rows, (uint64_t)cap);
+        if ((rc = flush(b))) return rc;
+        const size_t first_rows = stage_rows < RGC_FIRST_ROWS ? stage_rows : (size_t)RGC_FIRST_ROWS;
+        HIPCHECK(hipMemcpyAsync(c->h_rgc, out, HEAD_BYTES + first_rows * sizeof(f3ds_region_contact), hipMemcpyDeviceToHost, b.st));
+        HIPCHECK(timed_sync(b.st));
+        HIPCHECK(hipGetLastError());
+        memcpy(h, c->h_rgc, sizeof h);
+        if (h[1]) return F3DS_ERR_ARG;      // a label >= n_regions: d_contact_finish wrote no row, and nothing is copied out
+        if (h[2] <= rec_cap) break;
+        if (run || rec_cap >= rec_all) return F3DS_ERR_LOGIC;
+        rec_cap = rec_all;      // (rare: more records than the first buffer holds)
+    }
+    const size_t count = h[0];
+    if (count > rec_cap) return F3DS_ERR_LOGIC;
+    *n_out = count;
+    if (result) { result->n_regions = K; result->n_contacts = h[0]; memcpy(&result->n_pairs, h + 4, 8); memcpy(&result->n_close, h + 6, 8); }
+    if (!rows) return F3DS_OK;
+    if (cap < count) return F3DS_ERR_CAPACITY;
+    if (host_rows && count) {
+        if (count > RGC_FIRST_ROWS) {      // (rare: the rows behind the first download)
+            const size_t off = HEAD_BYTES + (size_t)RGC_FIRST_ROWS * sizeof(f3ds_region_contact);
+            HIPCHECK(hipMemcpyAsync(c->h_rgc + off, out + off, (count - RGC_FIRST_ROWS) * sizeof(f3ds_region_contact), hipMemcpyDeviceToHost, b.st));
+            HIPCHECK(timed_sync(b.st));
+        }
+        memcpy(rows, c->h_rgc + HEAD_BYTES, count * sizeof(f3ds_region_contact));
     }
     return F3DS_OK;
 }

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -19,6 +20,7 @@
 #include "f3ds_rgbd.h"
 #include "f3ds_track.h"
 #include "f3ds_regions.h"
+#include "f3ds_contacts.h"
 
 extern "C" {
 
@@ -214,6 +216,51 @@ int f3ds_region_table_host(const f3ds_rgbd_format* fmt_, const void* depth, cons
     uint32_t n_nonempty = 0;
     for (uint32_t r = 0; r < n_regions; ++r) { f3ds::rg_finish(acc[r], &rows[r]); if (acc[r].w[0]) ++n_nonempty; }
     if (result) { result->n_regions = n_regions; result->n_nonempty = n_nonempty; result->n_labelled = n_labelled; result->n_clamped = n_clamped; }
+    return F3DS_OK;
+}
+
+// ---- region contacts: the definition (the rules are in f3ds_contacts.h, which d_contact_accum and d_contact_finish call too) ----
+// The labels are checked before anything is written.  One ordered map from the pair's key to its accumulator: the rows come out by a, then b.
+int f3ds_region_contacts_host(const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, float depth_tol, f3ds_region_contact* rows,
+                              size_t cap, size_t* n_out, f3ds_region_contacts_result* result) {
+    f3ds_rgbd_format fmt; f3ds::RgbdLayout l;
+    if (const int rc = f3ds::ct_check(fmt_, depth, labels, n_regions, depth_tol, n_out, &fmt, &l)) return rc;
+    for (size_t p = 0; p < l.n; ++p) if (labels[p] != F3DS_NO_LABEL && labels[p] >= n_regions) return F3DS_ERR_ARG;
+    const unsigned char* dimg = static_cast<const unsigned char*>(depth);
+    auto pixel = [&](uint32_t u, uint32_t v, float& z) {      // labelled?
+        const unsigned char* q = dimg + (size_t)v * l.depth_pitch;
+        bool valid;
+        if (fmt.depth_type == F3DS_DEPTH_F32) { float d; memcpy(&d, q + 4u * (size_t)u, 4); valid = f3ds::n_depth_to_z(d, fmt.depth_scale, z); }
+        else { uint16_t d; memcpy(&d, q + 2u * (size_t)u, 2); valid = f3ds::n_depth_to_z(d, fmt.depth_scale, z); }
+        return valid && labels[(size_t)v * fmt.width + u] != F3DS_NO_LABEL;
+    };
+    const int kb = f3ds::ct_bits(n_regions);
+    std::map<uint64_t, f3ds::CtAcc> acc;
+    auto contact = [&](uint32_t p, bool horizontal, float zp, uint32_t q, float zq) {
+        if (labels[p] == labels[q]) return;
+        uint32_t a, b; f3ds::CtAcc one;
+        f3ds::ct_pair(p, horizontal, labels[p], zp, labels[q], zq, depth_tol, a, b, one);
+        auto it = acc.find(f3ds::ct_key(a, b, kb));
+        if (it == acc.end()) acc.emplace(f3ds::ct_key(a, b, kb), one); else f3ds::ct_merge(it->second, one);
+    };
+    for (uint32_t v = 0; v < fmt.height; ++v)
+        for (uint32_t u = 0; u < fmt.width; ++u) {
+            const uint32_t p = v * fmt.width + u;
+            float zp = 0.0f, zq = 0.0f;
+            if (!pixel(u, v, zp)) continue;
+            if (u + 1u < fmt.width && pixel(u + 1u, v, zq)) contact(p, true, zp, p + 1u, zq);
+            if (v + 1u < fmt.height && pixel(u, v + 1u, zq)) contact(p, false, zp, p + fmt.width, zq);
+        }
+    const size_t count = acc.size();
+    uint64_t n_pairs = 0, n_close = 0;
+    for (const auto& kv : acc) { n_pairs += kv.second.w[0]; n_close += kv.second.w[1]; }
+    *n_out = count;
+    if (result) { result->n_regions = n_regions; result->n_contacts = (uint32_t)count; result->n_pairs = n_pairs; result->n_close = n_close; }
+    if (!rows) return F3DS_OK;
+    if (cap < count) return F3DS_ERR_CAPACITY;
+    size_t e = 0;
+    const uint64_t bmask = (1ull << kb) - 1ull;
+    for (const auto& kv : acc) f3ds::ct_finish((uint32_t)(kv.first >> kb), (uint32_t)(kv.first & bmask), kv.second, &rows[e++]);
     return F3DS_OK;
 }
 

@@ -293,6 +293,53 @@ int f3ds_region_table_host(const f3ds_rgbd_format* fmt, const void* depth, const
 int f3ds_region_table(f3ds_ctx* ctx, const f3ds_rgbd_format* fmt, const void* depth, const void* color, const uint32_t* labels, uint32_t n_regions,
                       int inputs_on_device, f3ds_region_row* rows, int rows_on_device, f3ds_region_table_result* result);
 
+/* ---- region contacts: one fixed-size row per pair of regions of a label image that touch ------------------------------------
+ * The region table's companion: which regions touch in the image, along how long a border, and whether the border is a surface contact or one object in
+ * front of another -- without downloading the label image.  labels, n_regions and the region ids are the region table's (any label image of the frame; a
+ * row's a and b index the table's rows and f3ds_tracker_get_ids).  The definition, bit for bit (csrc/f3ds_contacts.h):
+ *   point    pixel p = v * width + u gets z by the rule of f3ds_deproject; it is LABELLED iff its depth is valid and label[p] != F3DS_NO_LABEL (as in the
+ *            tracker and the table).  The colour fields of the format are not looked at.
+ *   pairs    every pixel p forms a pair with its right neighbour p + 1 when u + 1 < width and with its lower neighbour p + width when v + 1 < height:
+ *            4-connectivity, each unordered pixel pair once.  A pair is a CONTACT iff both pixels are labelled and their labels differ; it belongs to
+ *            (a, b) = (smaller label, larger label).  A label over an invalid depth takes part in nothing.
+ *   class    za, zb: the depths of a's and b's pixel.  g = fabsf(za - zb) (one rounded f32 subtraction), zn = za < zb ? za : zb.  The pair is CLOSE iff
+ *            g <= depth_tol * zn (one rounded f32 product; the comparison fails on NaN).  A pair that is not close has a in front iff za < zb, else b.
+ *            Nothing is fused.
+ *   gap      sum_fix_gap adds fix(g) of the region table (units of 2^-16 m, g clamped to 32768 m; rint rounds half to even).
+ *   rows     one row per (a, b) with at least one contact, by a ascending, then b ascending.  result->n_contacts = the number of rows, result->n_pairs
+ *            and result->n_close the sums of those two fields over the rows.
+ *   capacity *n_out receives the row count on F3DS_OK and on F3DS_ERR_CAPACITY.  rows == NULL: count only, cap is ignored.  cap smaller than the count:
+ *            F3DS_ERR_CAPACITY, no row is written, result is written.
+ * Every field is an integer count, a minimum or a sum of integers: the result does not depend on the order of evaluation, and the device gives the bits
+ * of the host function.  4-connectivity in the image only: no diagonal pairs, no contact normals in space.
+ * Errors (both functions alike): F3DS_ERR_ARG for a NULL fmt, depth, labels or n_out, for what f3ds_deproject refuses of a format (the two colour fields
+ * are neutralised as in f3ds_tracker_update), for a depth_tol that is negative or not finite, and for a label >= n_regions other than F3DS_NO_LABEL on any
+ * pixel, also one without a neighbour or over an invalid depth (the device function finds it on the device and reports it at the call's one wait); rows,
+ * n_out and result are then not written, on the host or on the device.  F3DS_ERR_UNSUPPORTED for n_regions > 0x00FFFFFF.  n_regions == 0 with every label
+ * F3DS_NO_LABEL, one region, a 1 x 1 image and a frame without a labelled pixel are F3DS_OK with zero rows. */
+typedef struct f3ds_region_contact {          /* 32 bytes */
+    uint32_t a, b;            /* region ids, a < b                                                      */
+    uint32_t n_pairs;         /* contact pairs between a and b                                          */
+    uint32_t n_close;         /* ... whose two depths agree                                             */
+    uint32_t n_a_front;       /* ... not close, and a's pixel is the nearer one; b is in front in the   */
+                              /*     remaining n_pairs - n_close - n_a_front                            */
+    uint32_t n_horizontal;    /* ... whose pixels are left/right neighbours (the rest: upper/lower)     */
+    uint32_t first_pixel;     /* smallest index p of a pair's first (left or upper) pixel               */
+    float    mean_gap;        /* (float)(((double)sum_fix_gap / (double)n_pairs) * 2^-16), metres       */
+} f3ds_region_contact;
+typedef struct f3ds_region_contacts_result { uint32_t n_regions, n_contacts; uint64_t n_pairs, n_close; } f3ds_region_contacts_result;
+/* host arithmetic only, no device needed: the definition */
+int f3ds_region_contacts_host(const f3ds_rgbd_format* fmt, const void* depth, const uint32_t* labels, uint32_t n_regions, float depth_tol,
+                              f3ds_region_contact* rows, size_t cap, size_t* n_out, f3ds_region_contacts_result* result /* may be NULL */);
+/* the same rows from the device (csrc/f3ds_contacts.inc).  inputs_on_device: depth and labels are device memory and read where they are; host inputs go
+ * through the device's copy stream like those of f3ds_region_table.  rows_on_device: rows is device memory (cap rows of it); host rows arrive with the
+ * call's one download (a second one only for more than 2048 rows).  Synchronous.  Runs on ctx's stream and uses scratch of its own (and the sort's
+ * histogram and scan buffers, which hold nothing between calls): every other call on the context behaves as if this one never happened.  Also
+ * F3DS_ERR_ARG for a NULL ctx.  result may be NULL. */
+int f3ds_region_contacts(f3ds_ctx* ctx, const f3ds_rgbd_format* fmt, const void* depth, const uint32_t* labels, uint32_t n_regions, float depth_tol,
+                         int inputs_on_device, f3ds_region_contact* rows, size_t cap, int rows_on_device, size_t* n_out,
+                         f3ds_region_contacts_result* result);
+
 /* Clustering::cluster(threshold) again on the supervoxels of the last f3ds_segment call, with
  * possibly different metric / merging settings (src/clustering.cpp:670-679).  Only the merge
  * fields of `params` are read. */
