@@ -148,6 +148,26 @@ REGION_CONTACT_DTYPE = np.dtype([(k, np.uint32) for k in ("a", "b", "n_pairs", "
 assert REGION_CONTACT_DTYPE.itemsize == ctypes.sizeof(RegionContact) == 32
 
 
+class RegionShape(ctypes.Structure):
+    """f3ds_region_shape (include/f3ds.h): covariance, eigenvalues, plane and long axis of one region of a label image, 84 bytes."""
+    _fields_ = [("n_pixels", ctypes.c_uint32), ("centroid", ctypes.c_float * 3), ("cov", ctypes.c_float * 6), ("eigenvalue", ctypes.c_float * 3),
+                ("normal", ctypes.c_float * 3), ("axis", ctypes.c_float * 3), ("plane_d", ctypes.c_float), ("curvature", ctypes.c_float)]
+
+
+class RegionShapesResult(ctypes.Structure):
+    """f3ds_region_shapes_result (include/f3ds.h): the counts of one call for the region shapes."""
+    _fields_ = [("n_regions", ctypes.c_uint32), ("n_nonempty", ctypes.c_uint32), ("n_labelled", ctypes.c_uint64), ("n_clamped", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+# the same 84 bytes as a numpy structured dtype: what region_shapes_host and Context.region_shapes return their rows in
+REGION_SHAPE_DTYPE = np.dtype([("n_pixels", np.uint32), ("centroid", np.float32, (3,)), ("cov", np.float32, (6,)), ("eigenvalue", np.float32, (3,)),
+                               ("normal", np.float32, (3,)), ("axis", np.float32, (3,)), ("plane_d", np.float32), ("curvature", np.float32)])
+assert REGION_SHAPE_DTYPE.itemsize == ctypes.sizeof(RegionShape) == 84
+
+
 class SupervoxelSet(ctypes.Structure):
     """f3ds_supervoxel_set (include/f3ds.h): the supervoxel_clusters map of the reference as plain arrays."""
     _fields_ = [("n_supervoxels", ctypes.c_uint32), ("label", ctypes.c_void_p), ("voxel_offset", ctypes.c_void_p), ("voxel_xyz", ctypes.c_void_p),
@@ -224,6 +244,11 @@ def load_library(path=None):
         lib.f3ds_region_contacts_host.restype = ctypes.c_int
         lib.f3ds_region_contacts.argtypes = [vp, ctypes.POINTER(RgbdFormat), vp, vp, ctypes.c_uint32, ctypes.c_float, ctypes.c_int, vp, sz, ctypes.c_int, ctypes.POINTER(sz), rcp]
         lib.f3ds_region_contacts.restype = ctypes.c_int
+    if hasattr(lib, "f3ds_region_shapes"):
+        rsp = ctypes.POINTER(RegionShapesResult)
+        lib.f3ds_region_shapes_host.argtypes = [ctypes.POINTER(RgbdFormat), vp, vp, ctypes.c_uint32, vp, rsp]; lib.f3ds_region_shapes_host.restype = ctypes.c_int
+        lib.f3ds_region_shapes.argtypes = [vp, ctypes.POINTER(RgbdFormat), vp, vp, ctypes.c_uint32, ctypes.c_int, vp, ctypes.c_int, rsp]
+        lib.f3ds_region_shapes.restype = ctypes.c_int
     lib.f3ds_recluster.argtypes = [vp, ctypes.POINTER(Params), vp, ctypes.c_int, ctypes.POINTER(Result)]
     lib.f3ds_recluster.restype = ctypes.c_int
     lib.f3ds_evaluate.argtypes = [vp, vp, ctypes.POINTER(Performance)]; lib.f3ds_evaluate.restype = ctypes.c_int
@@ -686,6 +711,26 @@ def region_contacts_host(depth, labels, n_regions, fmt, depth_tol=0.05):
     return rows, res
 
 
+# ---- region shapes ---------------------------------------------------------------------------------
+def _shape_rows(buf, n_regions):
+    if buf is None:
+        return np.empty(int(n_regions), REGION_SHAPE_DTYPE)
+    if not (isinstance(buf, np.ndarray) and buf.dtype == REGION_SHAPE_DTYPE and buf.flags.c_contiguous and buf.size == int(n_regions)):
+        raise ValueError("rows_out must be a contiguous REGION_SHAPE_DTYPE array with one entry per region")
+    return buf
+
+
+def region_shapes_host(depth, labels, n_regions, fmt):
+    """f3ds_region_shapes_host: (rows, RegionShapesResult) -- one REGION_SHAPE_DTYPE row per region of the label image: pixel count, centroid, covariance of
+    the points, its eigenvalues (ascending), the normal and plane_d of the plane through the centroid, the long axis and the surface variation.  Host
+    arithmetic only: what Context.region_shapes computes on the device, bit for bit."""
+    lib = load_library()
+    f, d, _, lab = _region_inputs(fmt, depth, labels, None)
+    rows, res = _shape_rows(None, n_regions), RegionShapesResult()
+    _check(lib, lib.f3ds_region_shapes_host(ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), rows.ctypes.data if len(rows) else None, ctypes.byref(res)))
+    return rows, res
+
+
 # ---- device context ------------------------------------------------------------------------------
 class Context(_Handle):
     """One (device, stream) pair with its grow-only scratch.  Not thread-safe; one per GPU/stream."""
@@ -778,6 +823,22 @@ class Context(_Handle):
         rc, rows = _contact_rows(lambda ptr, cap, n_out: self.lib.f3ds_region_contacts(self.handle, ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions),
                                                                                        float(depth_tol), 0, ptr, cap, 0, n_out, ctypes.byref(res)), rows_out)
         _check(self.lib, rc)
+        return rows, res
+
+    def region_shapes(self, depth, labels, n_regions, fmt, rows_out=None, on_device=False):
+        """f3ds_region_shapes: (rows, RegionShapesResult) -- what region_shapes_host returns, computed on the device in one read of the depth image and the
+        labels; row i is region i, the row i of region_table and ``Tracker.ids()[i]``.  depth and labels as in region_table, or device pointers (ints, the depth
+        pitch of ``fmt`` applies) with ``on_device=True``: ``rows_out`` is then a device pointer to n_regions rows and the rows returned are None.  With host
+        arrays ``rows_out`` may be a REGION_SHAPE_DTYPE array to fill.  Leaves the context's frame as it is."""
+        res = RegionShapesResult()
+        if on_device:
+            _check(self.lib, self.lib.f3ds_region_shapes(self.handle, ctypes.byref(fmt), ctypes.c_void_p(int(depth)), ctypes.c_void_p(int(labels)), int(n_regions), 1,
+                                                         ctypes.c_void_p(int(rows_out)) if rows_out is not None else None, 1, ctypes.byref(res)))
+            return None, res
+        f, d, _, lab = _region_inputs(fmt, depth, labels, None)
+        rows = _shape_rows(rows_out, n_regions)
+        _check(self.lib, self.lib.f3ds_region_shapes(self.handle, ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), 0,
+                                                     rows.ctypes.data if len(rows) else None, 0, ctypes.byref(res)))
         return rows, res
 
     def points(self):

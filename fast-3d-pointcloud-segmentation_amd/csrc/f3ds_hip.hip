@@ -51,6 +51,7 @@
 #include "f3ds_track.h"
 #include "f3ds_regions.h"
 #include "f3ds_contacts.h"
+#include "f3ds_shapes.h"
 
 using namespace f3ds;
 
@@ -60,6 +61,7 @@ using namespace f3ds;
 #include "f3ds_track.inc"
 #include "f3ds_regions.inc"
 #include "f3ds_contacts.inc"
+#include "f3ds_shapes.inc"
 
 // ================================================================================================
 // batched launch machinery
@@ -183,7 +185,9 @@ const int g_merge_shared_res = [] { const char* e = dev_getenv("F3DS_MERGE_SHARE
     /* region table (f3ds_regions.inc), its own so that the call leaves every other one alone: the images and labels as uploaded, the accumulators, the head and the rows of a host caller */ \
     X(unsigned char, rgt_depth) X(unsigned char, rgt_color) X(uint32_t, rgt_lab) X(RgAcc, rgt_acc) X(unsigned char, rgt_out) \
     /* region contacts (f3ds_contacts.inc), its own likewise: the image and labels as uploaded, the records' keys and indices (twice: the sort), the records, the runs' flags, keys, starts and ends, the run count, the head and the rows of a host caller */ \
-    X(unsigned char, rgc_depth) X(uint32_t, rgc_lab) X(uint64_t, rgc_k0) X(uint64_t, rgc_k1) X(uint32_t, rgc_v0) X(uint32_t, rgc_v1) X(uint32_t, rgc_rec) X(uint32_t, rgc_flag) X(uint64_t, rgc_ukey) X(uint32_t, rgc_ustart) X(uint32_t, rgc_uend) X(uint32_t, rgc_cnt) X(unsigned char, rgc_out)
+    X(unsigned char, rgc_depth) X(uint32_t, rgc_lab) X(uint64_t, rgc_k0) X(uint64_t, rgc_k1) X(uint32_t, rgc_v0) X(uint32_t, rgc_v1) X(uint32_t, rgc_rec) X(uint32_t, rgc_flag) X(uint64_t, rgc_ukey) X(uint32_t, rgc_ustart) X(uint32_t, rgc_uend) X(uint32_t, rgc_cnt) X(unsigned char, rgc_out) \
+    /* region shapes (f3ds_shapes.inc), its own likewise: the image and labels as uploaded, the accumulators, the head and the rows of a host caller */ \
+    X(unsigned char, rgs_depth) X(uint32_t, rgs_lab) X(ShAcc, rgs_acc) X(unsigned char, rgs_out)
 template <class T> struct Scratch { T* p = nullptr; size_t cap = 0; int slot = -1; };      // cap: bytes allocated; slot: position in F3DS_SCRATCH
 #define F3DS_SCRATCH_SLOT(T, name) S_##name,
 #define F3DS_SCRATCH_MEMBER(T, name) Scratch<T> name{nullptr, 0, S_##name};
@@ -214,6 +218,7 @@ struct f3ds_ctx {
     DevCounters* d_dcblk = nullptr; DevCounters* h_dcblk = nullptr; size_t dcblk_cap = 0;      // the batch's counters, one slot per frame
     unsigned char* h_rgt = nullptr; size_t h_rgt_cap = 0;      // pinned: the head (and a host caller's rows) of f3ds_region_table on their way down
     unsigned char* h_rgc = nullptr; size_t h_rgc_cap = 0;      // pinned: the same of f3ds_region_contacts
+    unsigned char* h_rgs = nullptr; size_t h_rgs_cap = 0;      // pinned: the same of f3ds_region_shapes
     // frame state
     bool have_frame = false;
     bool live = false;
@@ -1219,6 +1224,7 @@ void f3ds_destroy(f3ds_ctx* c) {
     if (c->h_dcblk) (void)hipHostFree(c->h_dcblk);
     if (c->h_rgt) (void)hipHostFree(c->h_rgt);
     if (c->h_rgc) (void)hipHostFree(c->h_rgc);
+    if (c->h_rgs) (void)hipHostFree(c->h_rgs);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -2672,6 +2678,66 @@ extern "C" int f3ds_region_contacts(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, c
             HIPCHECK(timed_sync(b.st));
         }
         memcpy(rows, c->h_rgc + HEAD_BYTES, count * sizeof(f3ds_region_contact));
+    }
+    return F3DS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// region shapes (f3ds_shapes.h / .inc): one row per region of a label image over a depth image -- covariance, eigenvalues, plane and long
+// axis.  The call has the region table's shape: three kernels in one flush -- d_shape_init, d_shape_accum (the one read of the image and the labels),
+// d_shape_finish -- then ONE download, the call's only wait: the head (counts, the bad-label flag) and, for a host caller, the rows behind it (84 B per
+// region).  The scratch is the call's own (rgs_*), so nothing another call of the context reads is touched.
+// ------------------------------------------------------------------------------------------------
+extern "C" int f3ds_region_shapes(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, int inputs_on_device,
+                                  f3ds_region_shape* rows, int rows_on_device, f3ds_region_shapes_result* result) {
+    if (!c) return F3DS_ERR_ARG;
+    f3ds_rgbd_format fmt; f3ds::RgbdLayout lay;
+    if (const int rc = sh_check(fmt_, depth, labels, n_regions, rows, &fmt, &lay)) return rc;
+    g_sw.read();
+    HIPCHECK(hipSetDevice(c->device));
+    Batch b = batch_of(c);
+    const uint32_t n = (uint32_t)lay.n, K = n_regions, copies = rgt_copies(K);
+    constexpr size_t HEAD_BYTES = 64;      // RGS_HEAD words, and the rows behind them 8-byte aligned
+    const size_t out_bytes = HEAD_BYTES + (rows_on_device ? 0u : (size_t)K * sizeof(f3ds_region_shape));
+    // every buffer of the call before anything is recorded
+    ShAcc* acc; unsigned char *out, *ud = nullptr; uint32_t* ul = nullptr;
+    ENSURE(c->rgs_acc, K ? (size_t)K * copies : 1u, acc); ENSURE(c->rgs_out, out_bytes, out);
+    if (c->h_rgs_cap < out_bytes) {
+        if (c->h_rgs) { HIPCHECK(hipHostFree(c->h_rgs)); c->h_rgs = nullptr; c->h_rgs_cap = 0; }
+        HIPCHECK(hipHostMalloc(&c->h_rgs, out_bytes + out_bytes / 4, hipHostMallocDefault));
+        c->h_rgs_cap = out_bytes + out_bytes / 4;
+    }
+    const unsigned char* d_depth = static_cast<const unsigned char*>(depth);
+    const uint32_t* d_lab = labels;
+    if (!inputs_on_device) {      // host images go through the device's copy stream, like those of f3ds_region_table
+        ENSURE(c->rgs_depth, lay.depth_bytes, ud); ENSURE(c->rgs_lab, n, ul);
+        hipStream_t up = g_sw.copy_stream ? copy_stream_of(c->device) : nullptr;
+        HIPCHECK(hipMemcpyAsync(ud, depth, lay.depth_bytes, hipMemcpyHostToDevice, up ? up : b.st));
+        HIPCHECK(hipMemcpyAsync(ul, labels, (size_t)n * 4, hipMemcpyHostToDevice, up ? up : b.st));
+        if (up) { if (const int urc = await_uploads(b, up)) return urc; }
+        d_depth = ud; d_lab = ul;
+    }
+    ShapeArgs a;
+    memset(&a, 0, sizeof a);
+    a.width = fmt.width; a.n = n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
+    a.K = K; a.copies = copies;
+    a.depth_scale = fmt.depth_scale; a.fx = fmt.fx; a.fy = fmt.fy; a.cx = fmt.cx; a.cy = fmt.cy;
+    uint32_t* head = reinterpret_cast<uint32_t*>(out);
+    f3ds_region_shape* d_rows = rows_on_device ? rows : reinterpret_cast<f3ds_region_shape*>(out + HEAD_BYTES);
+    rec<d_shape_init>(c, grid_for((size_t)K * copies * SH_WORDS, 256), 0u, reinterpret_cast<uint32_t*>(acc), K * copies, head);
+    rec<d_shape_accum>(c, grid_for((n + RGS_TRIPS - 1u) / RGS_TRIPS, 256), 0u, d_depth, d_lab, a, acc, head);
+    rec<d_shape_finish>(c, grid_for(K, 256), 0u, acc, K, copies, head, d_rows);
+    if (const int rc = flush(b)) return rc;
+    HIPCHECK(hipMemcpyAsync(c->h_rgs, out, out_bytes, hipMemcpyDeviceToHost, b.st));
+    HIPCHECK(timed_sync(b.st));
+    HIPCHECK(hipGetLastError());
+    uint32_t h[RGS_HEAD];
+    memcpy(h, c->h_rgs, sizeof h);
+    if (h[1]) return F3DS_ERR_ARG;      // a label >= n_regions: d_shape_finish wrote no row, and none is copied out
+    if (!rows_on_device && K) memcpy(rows, c->h_rgs + HEAD_BYTES, (size_t)K * sizeof(f3ds_region_shape));
+    if (result) {
+        result->n_regions = K; result->n_nonempty = h[0];
+        memcpy(&result->n_labelled, h + 2, 8); memcpy(&result->n_clamped, h + 4, 8);
     }
     return F3DS_OK;
 }

@@ -21,6 +21,7 @@
 #include "f3ds_track.h"
 #include "f3ds_regions.h"
 #include "f3ds_contacts.h"
+#include "f3ds_shapes.h"
 
 extern "C" {
 
@@ -261,6 +262,39 @@ int f3ds_region_contacts_host(const f3ds_rgbd_format* fmt_, const void* depth, c
     size_t e = 0;
     const uint64_t bmask = (1ull << kb) - 1ull;
     for (const auto& kv : acc) f3ds::ct_finish((uint32_t)(kv.first >> kb), (uint32_t)(kv.first & bmask), kv.second, &rows[e++]);
+    return F3DS_OK;
+}
+
+// ---- region shapes: the definition (the rules are in f3ds_shapes.h, which d_shape_accum and d_shape_finish call too) ----
+// Two passes: the labels are checked before a row is written.  Pixels are read with memcpy, as in f3ds_deproject.
+int f3ds_region_shapes_host(const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, f3ds_region_shape* rows,
+                            f3ds_region_shapes_result* result) {
+    f3ds_rgbd_format fmt; f3ds::RgbdLayout l;
+    if (const int rc = f3ds::sh_check(fmt_, depth, labels, n_regions, rows, &fmt, &l)) return rc;
+    for (size_t p = 0; p < l.n; ++p) if (labels[p] != F3DS_NO_LABEL && labels[p] >= n_regions) return F3DS_ERR_ARG;
+    std::vector<f3ds::ShAcc> acc(n_regions);
+    for (f3ds::ShAcc& a : acc) f3ds::sh_empty(a);
+    const unsigned char* dimg = static_cast<const unsigned char*>(depth);
+    uint64_t n_labelled = 0, n_clamped = 0;
+    for (uint32_t v = 0; v < fmt.height; ++v) {
+        const unsigned char* drow = dimg + (size_t)v * l.depth_pitch;
+        for (uint32_t u = 0; u < fmt.width; ++u) {
+            const uint32_t lab = labels[(size_t)v * fmt.width + u];
+            float z = 0.0f; bool valid;
+            if (fmt.depth_type == F3DS_DEPTH_F32) { float d; memcpy(&d, drow + 4u * (size_t)u, 4); valid = f3ds::n_depth_to_z(d, fmt.depth_scale, z); }
+            else { uint16_t d; memcpy(&d, drow + 2u * (size_t)u, 2); valid = f3ds::n_depth_to_z(d, fmt.depth_scale, z); }
+            if (!valid || lab == F3DS_NO_LABEL) continue;
+            float x, y, zo;
+            f3ds::n_deproject(u, v, valid, z, fmt.fx, fmt.fy, fmt.cx, fmt.cy, x, y, zo);
+            f3ds::ShAcc one;
+            if (f3ds::sh_pixel(x, y, zo, one)) ++n_clamped;
+            f3ds::sh_merge(acc[lab], one);
+            ++n_labelled;
+        }
+    }
+    uint32_t n_nonempty = 0;
+    for (uint32_t r = 0; r < n_regions; ++r) { f3ds::sh_finish(acc[r], &rows[r]); if (acc[r].n) ++n_nonempty; }
+    if (result) { result->n_regions = n_regions; result->n_nonempty = n_nonempty; result->n_labelled = n_labelled; result->n_clamped = n_clamped; }
     return F3DS_OK;
 }
 

@@ -340,6 +340,70 @@ int f3ds_region_contacts(f3ds_ctx* ctx, const f3ds_rgbd_format* fmt, const void*
                          int inputs_on_device, f3ds_region_contact* rows, size_t cap, int rows_on_device, size_t* n_out,
                          f3ds_region_contacts_result* result);
 
+/* ---- region shapes: one fixed-size row per region of a label image: covariance, plane and principal axes -----------------------
+ * The third member of the family: is a region a plane, which way does it face, how thick is it and along which direction is it long -- without
+ * downloading the label image.  labels, n_regions and the region ids are the region table's: row i is region i, the table's row i and
+ * f3ds_tracker_get_ids()[i].  No colour image; the two colour fields of the format are not looked at.  With a plane per row, a contact row (a, b) joins
+ * two shape rows and says convex, concave or coplanar.  The definition, bit for bit (csrc/f3ds_shapes.h):
+ *   point     the region table's: pixel p = v * width + u gets (x, y, z) by the rule of f3ds_deproject; it is LABELLED iff its depth is valid and
+ *             label[p] != F3DS_NO_LABEL.
+ *   fixed     the table's: f_a = fix(a) for a in x, y, z, units of 2^-16 m, |f_a| <= 2^31; a labelled pixel is CLAMPED iff the clamp changed one of its three
+ *             coordinates.  So n_labelled, n_clamped, n_pixels and centroid are the table's bits.
+ *   moments   per region, as exact integers over its labelled pixels: n (the count), S_a = sum f_a, M_ab = sum f_a * f_b for the six pairs ab in
+ *             xx, xy, xz, yy, yz, zz.  n < 2^31, so |S_a| < 2^62 and |M_ab| < 2^93.
+ *   scatter   N_ab = n * M_ab - S_a * S_b, exactly (|N_ab| < 2^125: a signed 128-bit integer).  There is no cancellation error: a flat region at constant
+ *             depth has N_zz == 0 and cov[5] the bits of +0.0, however far away it is.
+ *   cov       in f64, C_ab = (((double)N_ab / (double)n) / (double)n) * 2^-32, where (double)N_ab is the exact integer rounded to nearest, ties to even,
+ *             once; (double)n is exact; the two divisions are IEEE; the scaling is exact.  cov[k] = (float)C_k in the order xx, xy, xz, yy, yz, zz.
+ *   eigen     cyclic Jacobi on the symmetric f64 matrix C (indices 0, 1, 2 = x, y, z) with V = the identity.  Exactly 8 sweeps, each over (p, q) = (0, 1),
+ *             (0, 2), (1, 2) in this order.  A rotation is skipped iff C[p][q] == 0.0.  Otherwise, in this order:
+ *               theta = (C[q][q] - C[p][p]) / (2.0 * C[p][q])
+ *               t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0)), negated if theta < 0
+ *               c = 1.0 / sqrt(t * t + 1.0), s = t * c
+ *               C[p][p] -= t * C[p][q];  C[q][q] += t * C[p][q]  (the old C[p][q] in both);  C[p][q] = C[q][p] = 0
+ *               for the third index r: C[r][p], C[r][q] = c * C[r][p] - s * C[r][q], s * C[r][p] + c * C[r][q], both from the old values, and mirrored
+ *               for k = 0, 1, 2: V[k][p], V[k][q] = c * V[k][p] - s * V[k][q], s * V[k][p] + c * V[k][q], both from the old values
+ *             Only f64 + - * / and sqrt, every operation rounded once and nothing fused; nothing data-dependent ends the loop but the exact-zero skip.
+ *             Afterwards lambda_k = C[k][k] belongs to column k of V.
+ *   order     a lambda below 0 becomes +0.0.  The three (lambda, column) pairs are sorted by lambda ascending, ties by column index ascending.
+ *             eigenvalue[k] = (float)lambda_k.
+ *   normal    v = the column of lambda_0 as Jacobi left it (not renormalised).  With the f64 centroid c_a = ((double)S_a / (double)n) * 2^-16 (centroid[a] is
+ *             (float)c_a), d = (v_x * c_x + v_y * c_y) + v_z * c_z in f64.  If d > 0, v and d are negated.  normal = (float)v, plane_d = (float)(-d).
+ *   axis      w = the column of lambda_2.  Its component of largest magnitude, the first in x, y, z order among equal magnitudes, decides: w is negated iff
+ *             that component is < 0.  axis = (float)w.
+ *   curvature sum = (lambda_0 + lambda_1) + lambda_2 (after the clamp); curvature = sum > 0 ? (float)(lambda_0 / sum) : 0.0f.
+ *   empty     a region without a labelled pixel has n_pixels = 0 and the quiet NaN 0x7FC00000 in all twenty floats.
+ * A region of one point, of identical points, has an all-zero C: nothing rotates, V stays the identity, the eigenvalues are 0, 0, 0 and normal is
+ * (-1, 0, 0) or (1, 0, 0) by the flip rule.  That, and the normal of a region whose points lie on a line, is defined but MEANINGLESS: look at
+ * eigenvalue[1] before believing a normal, and at eigenvalue[2] before believing an axis.
+ * Everything that meets more than one pixel is a sum of integers: the result does not depend on the order of evaluation, and the device gives the bits of
+ * the host function.
+ * Errors (both functions alike): F3DS_ERR_ARG for a NULL fmt, depth or labels, for NULL rows unless n_regions == 0, for what f3ds_deproject refuses of
+ * a format (the two colour fields are neutralised as in f3ds_region_contacts) and for a label >= n_regions other than F3DS_NO_LABEL (the device function
+ * finds it on the device and reports it at the call's one wait); rows and result are then not written, on the host or on the device.
+ * F3DS_ERR_UNSUPPORTED for n_regions > 0x00FFFFFF.  n_regions == 0, or a frame without a labelled pixel, is F3DS_OK: the rows, if there are any, are all
+ * empty. */
+typedef struct f3ds_region_shape {      /* 84 bytes, 21 words */
+    uint32_t n_pixels;        /* labelled pixels of the region (the table's n_pixels)                     */
+    float centroid[3];        /* the table's centroid, the same bits                                      */
+    float cov[6];             /* xx, xy, xz, yy, yz, zz: population covariance (divided by n), m^2        */
+    float eigenvalue[3];      /* of cov, ascending, negatives clamped to +0                               */
+    float normal[3];          /* unit eigenvector of eigenvalue[0], turned towards the camera (origin)    */
+    float axis[3];            /* unit eigenvector of eigenvalue[2]: the direction the region is long in   */
+    float plane_d;            /* normal . p + plane_d = 0 is the plane through the centroid; >= 0         */
+    float curvature;          /* eigenvalue[0] / (sum of the three): PCL's surface variation; 0 if sum 0  */
+} f3ds_region_shape;
+typedef struct f3ds_region_shapes_result { uint32_t n_regions, n_nonempty; uint64_t n_labelled, n_clamped; } f3ds_region_shapes_result;
+/* host arithmetic only, no device needed: the definition */
+int f3ds_region_shapes_host(const f3ds_rgbd_format* fmt, const void* depth, const uint32_t* labels, uint32_t n_regions,
+                            f3ds_region_shape* rows, f3ds_region_shapes_result* result /* may be NULL */);
+/* the same rows from the device, in one read of the image and the labels (csrc/f3ds_shapes.inc).  inputs_on_device: depth and labels are device memory
+ * and read where they are; host inputs go through the device's copy stream like those of f3ds_region_table.  rows_on_device: rows is device memory; host
+ * rows arrive with the call's one small download.  Synchronous.  Runs on ctx's stream and uses scratch of its own only: every other call on the context
+ * behaves as if this one never happened.  Also F3DS_ERR_ARG for a NULL ctx.  result may be NULL. */
+int f3ds_region_shapes(f3ds_ctx* ctx, const f3ds_rgbd_format* fmt, const void* depth, const uint32_t* labels, uint32_t n_regions,
+                       int inputs_on_device, f3ds_region_shape* rows, int rows_on_device, f3ds_region_shapes_result* result);
+
 /* Clustering::cluster(threshold) again on the supervoxels of the last f3ds_segment call, with
  * possibly different metric / merging settings (src/clustering.cpp:670-679).  Only the merge
  * fields of `params` are read. */
