@@ -168,6 +168,29 @@ REGION_SHAPE_DTYPE = np.dtype([("n_pixels", np.uint32), ("centroid", np.float32,
 assert REGION_SHAPE_DTYPE.itemsize == ctypes.sizeof(RegionShape) == 84
 
 
+class ComponentParams(ctypes.Structure):
+    """f3ds_component_params (include/f3ds.h): the depth tolerance of a link and the smallest component that is kept."""
+    _fields_ = [("depth_tol", ctypes.c_float), ("min_pixels", ctypes.c_uint32)]
+
+
+class RegionComponent(ctypes.Structure):
+    """f3ds_region_component (include/f3ds.h): one connected component of a label image, 12 bytes."""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("region", "first_pixel", "n_pixels")]
+
+
+class RegionComponentsResult(ctypes.Structure):
+    """f3ds_region_components_result (include/f3ds.h): the counts of one call for the region components."""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("n_regions", "n_components", "n_dropped", "reserved")] + [("n_labelled", ctypes.c_uint64), ("n_kept", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+# the same 12 bytes as a numpy structured dtype: what region_components_host and Context.region_components return their rows in
+REGION_COMPONENT_DTYPE = np.dtype([(k, np.uint32) for k in ("region", "first_pixel", "n_pixels")])
+assert REGION_COMPONENT_DTYPE.itemsize == ctypes.sizeof(RegionComponent) == 12
+
+
 class SupervoxelSet(ctypes.Structure):
     """f3ds_supervoxel_set (include/f3ds.h): the supervoxel_clusters map of the reference as plain arrays."""
     _fields_ = [("n_supervoxels", ctypes.c_uint32), ("label", ctypes.c_void_p), ("voxel_offset", ctypes.c_void_p), ("voxel_xyz", ctypes.c_void_p),
@@ -249,6 +272,15 @@ def load_library(path=None):
         lib.f3ds_region_shapes_host.argtypes = [ctypes.POINTER(RgbdFormat), vp, vp, ctypes.c_uint32, vp, rsp]; lib.f3ds_region_shapes_host.restype = ctypes.c_int
         lib.f3ds_region_shapes.argtypes = [vp, ctypes.POINTER(RgbdFormat), vp, vp, ctypes.c_uint32, ctypes.c_int, vp, ctypes.c_int, rsp]
         lib.f3ds_region_shapes.restype = ctypes.c_int
+    if hasattr(lib, "f3ds_region_components"):
+        rkp, ckp = ctypes.POINTER(RegionComponentsResult), ctypes.POINTER(ComponentParams)
+        lib.f3ds_default_component_params.argtypes = [ckp]; lib.f3ds_default_component_params.restype = None
+        lib.f3ds_region_components_host.argtypes = [ctypes.POINTER(RgbdFormat), vp, vp, ctypes.c_uint32, ckp, vp, vp, sz, ctypes.POINTER(sz), rkp]
+        lib.f3ds_region_components_host.restype = ctypes.c_int
+        lib.f3ds_region_components_tiled.argtypes = [ctypes.POINTER(RgbdFormat), vp, vp, ctypes.c_uint32, ckp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, sz, ctypes.POINTER(sz), rkp]
+        lib.f3ds_region_components_tiled.restype = ctypes.c_int
+        lib.f3ds_region_components.argtypes = [vp, ctypes.POINTER(RgbdFormat), vp, vp, ctypes.c_uint32, ckp, ctypes.c_int, vp, vp, sz, ctypes.c_int, ctypes.POINTER(sz), rkp]
+        lib.f3ds_region_components.restype = ctypes.c_int
     lib.f3ds_recluster.argtypes = [vp, ctypes.POINTER(Params), vp, ctypes.c_int, ctypes.POINTER(Result)]
     lib.f3ds_recluster.restype = ctypes.c_int
     lib.f3ds_evaluate.argtypes = [vp, vp, ctypes.POINTER(Performance)]; lib.f3ds_evaluate.restype = ctypes.c_int
@@ -679,20 +711,20 @@ def region_table_host(depth, labels, n_regions, fmt, color=None):
 _CONTACT_ROWS_FIRST = 1024      # rows the first call of the package's two functions has room for; more: the buffer grows from n_out and the call is repeated
 
 
-def _contact_rows(call, rows_out):
+def _contact_rows(call, rows_out, dtype=REGION_CONTACT_DTYPE):
     """the rows of call(pointer, cap, byref(n_out)) -> rc: into ``rows_out`` (too small: CapacityError), or into a buffer grown from n_out"""
     n_out = ctypes.c_size_t(0)
     if rows_out is not None:
-        if not (isinstance(rows_out, np.ndarray) and rows_out.dtype == REGION_CONTACT_DTYPE and rows_out.flags.c_contiguous and rows_out.ndim == 1):
-            raise ValueError("rows_out must be a contiguous one-dimensional REGION_CONTACT_DTYPE array")
+        if not (isinstance(rows_out, np.ndarray) and rows_out.dtype == dtype and rows_out.flags.c_contiguous and rows_out.ndim == 1):
+            raise ValueError("rows_out must be a contiguous one-dimensional array of the rows' dtype (%d bytes per row)" % dtype.itemsize)
         rc = call(rows_out.ctypes.data if len(rows_out) else None, len(rows_out), ctypes.byref(n_out))
         if rc == 0 and n_out.value > len(rows_out):      # (an empty buffer is a NULL pointer: the call only counted)
             rc = ERR_CAPACITY
         return rc, rows_out[:n_out.value] if rc == 0 else None
-    rows = np.empty(_CONTACT_ROWS_FIRST, REGION_CONTACT_DTYPE)
+    rows = np.empty(_CONTACT_ROWS_FIRST, dtype)
     rc = call(rows.ctypes.data, len(rows), ctypes.byref(n_out))
     if rc == ERR_CAPACITY:
-        rows = np.empty(n_out.value, REGION_CONTACT_DTYPE)
+        rows = np.empty(n_out.value, dtype)
         rc = call(rows.ctypes.data, len(rows), ctypes.byref(n_out))
     return rc, rows[:n_out.value].copy() if rc == 0 else None
 
@@ -729,6 +761,31 @@ def region_shapes_host(depth, labels, n_regions, fmt):
     rows, res = _shape_rows(None, n_regions), RegionShapesResult()
     _check(lib, lib.f3ds_region_shapes_host(ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), rows.ctypes.data if len(rows) else None, ctypes.byref(res)))
     return rows, res
+
+
+# ---- region components -----------------------------------------------------------------------------
+def default_component_params(**overrides):
+    p = ComponentParams()
+    load_library().f3ds_default_component_params(ctypes.byref(p))
+    for k, v in overrides.items():
+        setattr(p, k, v)
+    return p
+
+
+def region_components_host(depth, labels, n_regions, fmt, depth_tol=0.05, min_pixels=1, rows_out=None):
+    """f3ds_region_components_host: (comp_labels, rows, RegionComponentsResult) -- the connected components (4-connectivity) of the label image: two
+    neighbouring labelled pixels belong together iff their labels are equal and their depths are close (|za - zb| <= depth_tol * min(za, zb); depth_tol may be
+    inf).  comp_labels is a (height, width) uint32 image of component numbers (0xFFFFFFFF where the pixel is not labelled or its component has fewer than
+    ``min_pixels`` pixels), numbered in raster order of their first pixels; rows holds one REGION_COMPONENT_DTYPE row per component: the region it came from,
+    its first pixel and its size.  Host arithmetic only: what Context.region_components computes on the device, bit for bit."""
+    lib = load_library()
+    f, d, _, lab = _region_inputs(fmt, depth, labels, None)
+    prm, res = ComponentParams(float(depth_tol), int(min_pixels)), RegionComponentsResult()
+    comp = np.empty((int(fmt.height), int(fmt.width)), np.uint32)
+    rc, rows = _contact_rows(lambda ptr, cap, n_out: lib.f3ds_region_components_host(ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), ctypes.byref(prm),
+                                                                                      comp.ctypes.data, ptr, cap, n_out, ctypes.byref(res)), rows_out, REGION_COMPONENT_DTYPE)
+    _check(lib, rc)
+    return comp, rows, res
 
 
 # ---- device context ------------------------------------------------------------------------------
@@ -840,6 +897,30 @@ class Context(_Handle):
         _check(self.lib, self.lib.f3ds_region_shapes(self.handle, ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), 0,
                                                      rows.ctypes.data if len(rows) else None, 0, ctypes.byref(res)))
         return rows, res
+
+    def region_components(self, depth, labels, n_regions, fmt, depth_tol=0.05, min_pixels=1, rows_out=None, comp_out=None, on_device=False):
+        """f3ds_region_components: (comp_labels, rows, RegionComponentsResult) -- what region_components_host returns, computed on the device.  The image is a
+        label image again: region_table, region_contacts, region_shapes and Tracker.update run on it with ``n_regions = result.n_components``.  depth and
+        labels as in region_table, or device pointers (ints, the depth pitch of ``fmt`` applies) with ``on_device=True``: ``comp_out`` is then a device pointer to
+        width * height words, ``rows_out`` is ``(device pointer, capacity in rows)`` or None (no rows), image and rows returned are None and
+        ``result.n_components`` says how many rows were written (CapacityError, and none written, when there are more than the capacity).  With host arrays
+        ``rows_out`` may be a REGION_COMPONENT_DTYPE array to fill; without it a buffer that turns out too small is grown from the count and the call
+        repeated: one device pass when it suffices.  Leaves the context's frame as it is."""
+        prm, res = ComponentParams(float(depth_tol), int(min_pixels)), RegionComponentsResult()
+        if on_device:
+            ptr, cap = (None, 0) if rows_out is None else (ctypes.c_void_p(int(rows_out[0])), int(rows_out[1]))
+            n_out = ctypes.c_size_t(0)
+            _check(self.lib, self.lib.f3ds_region_components(self.handle, ctypes.byref(fmt), ctypes.c_void_p(int(depth)), ctypes.c_void_p(int(labels)), int(n_regions),
+                                                             ctypes.byref(prm), 1, ctypes.c_void_p(int(comp_out)) if comp_out is not None else None, ptr, cap, 1,
+                                                             ctypes.byref(n_out), ctypes.byref(res)))
+            return None, None, res
+        f, d, _, lab = _region_inputs(fmt, depth, labels, None)
+        comp = np.empty((int(fmt.height), int(fmt.width)), np.uint32)
+        rc, rows = _contact_rows(lambda ptr, cap, n_out: self.lib.f3ds_region_components(self.handle, ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions),
+                                                                                         ctypes.byref(prm), 0, comp.ctypes.data, ptr, cap, 0, n_out, ctypes.byref(res)),
+                                 rows_out, REGION_COMPONENT_DTYPE)
+        _check(self.lib, rc)
+        return comp, rows, res
 
     def points(self):
         """f3ds_get_points: the (N, 4) float32 records the last segment call ran on, when the context holds them (segment_rgbd, or segment

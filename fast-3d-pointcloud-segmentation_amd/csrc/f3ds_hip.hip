@@ -52,6 +52,7 @@
 #include "f3ds_regions.h"
 #include "f3ds_contacts.h"
 #include "f3ds_shapes.h"
+#include "f3ds_components.h"
 
 using namespace f3ds;
 
@@ -62,6 +63,7 @@ using namespace f3ds;
 #include "f3ds_regions.inc"
 #include "f3ds_contacts.inc"
 #include "f3ds_shapes.inc"
+#include "f3ds_components.inc"
 
 // ================================================================================================
 // batched launch machinery
@@ -187,7 +189,9 @@ const int g_merge_shared_res = [] { const char* e = dev_getenv("F3DS_MERGE_SHARE
     /* region contacts (f3ds_contacts.inc), its own likewise: the image and labels as uploaded, the records' keys and indices (twice: the sort), the records, the runs' flags, keys, starts and ends, the run count, the head and the rows of a host caller */ \
     X(unsigned char, rgc_depth) X(uint32_t, rgc_lab) X(uint64_t, rgc_k0) X(uint64_t, rgc_k1) X(uint32_t, rgc_v0) X(uint32_t, rgc_v1) X(uint32_t, rgc_rec) X(uint32_t, rgc_flag) X(uint64_t, rgc_ukey) X(uint32_t, rgc_ustart) X(uint32_t, rgc_uend) X(uint32_t, rgc_cnt) X(unsigned char, rgc_out) \
     /* region shapes (f3ds_shapes.inc), its own likewise: the image and labels as uploaded, the accumulators, the head and the rows of a host caller */ \
-    X(unsigned char, rgs_depth) X(uint32_t, rgs_lab) X(ShAcc, rgs_acc) X(unsigned char, rgs_out)
+    X(unsigned char, rgs_depth) X(uint32_t, rgs_lab) X(ShAcc, rgs_acc) X(unsigned char, rgs_out) \
+    /* region components (f3ds_components.inc), its own likewise: the image and labels as uploaded, a parent, a size and a flag word per pixel, the head and the image and rows of a host caller */ \
+    X(unsigned char, rgk_depth) X(uint32_t, rgk_lab) X(uint32_t, rgk_parent) X(uint32_t, rgk_cnt) X(uint32_t, rgk_flag) X(unsigned char, rgk_out)
 template <class T> struct Scratch { T* p = nullptr; size_t cap = 0; int slot = -1; };      // cap: bytes allocated; slot: position in F3DS_SCRATCH
 #define F3DS_SCRATCH_SLOT(T, name) S_##name,
 #define F3DS_SCRATCH_MEMBER(T, name) Scratch<T> name{nullptr, 0, S_##name};
@@ -219,6 +223,7 @@ struct f3ds_ctx {
     unsigned char* h_rgt = nullptr; size_t h_rgt_cap = 0;      // pinned: the head (and a host caller's rows) of f3ds_region_table on their way down
     unsigned char* h_rgc = nullptr; size_t h_rgc_cap = 0;      // pinned: the same of f3ds_region_contacts
     unsigned char* h_rgs = nullptr; size_t h_rgs_cap = 0;      // pinned: the same of f3ds_region_shapes
+    unsigned char* h_rgk = nullptr; size_t h_rgk_cap = 0;      // pinned: the same of f3ds_region_components (and a host caller's image)
     // frame state
     bool have_frame = false;
     bool live = false;
@@ -1225,6 +1230,7 @@ void f3ds_destroy(f3ds_ctx* c) {
     if (c->h_rgt) (void)hipHostFree(c->h_rgt);
     if (c->h_rgc) (void)hipHostFree(c->h_rgc);
     if (c->h_rgs) (void)hipHostFree(c->h_rgs);
+    if (c->h_rgk) (void)hipHostFree(c->h_rgk);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -2738,6 +2744,92 @@ extern "C" int f3ds_region_shapes(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, con
     if (result) {
         result->n_regions = K; result->n_nonempty = h[0];
         memcpy(&result->n_labelled, h + 2, 8); memcpy(&result->n_clamped, h + 4, 8);
+    }
+    return F3DS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// region components (f3ds_components.h / .inc): the connected components of a label image over a depth image, as a label image and one
+// row per component.  One flush -- the head's zeros, d_comp_local (the one read of the images: tiles resolved in LDS), d_comp_seam, d_comp_flatten,
+// d_comp_flag, the scan of the flags, d_comp_write -- then ONE download, the call's only wait in the ordinary case: the head (counts, the bad-label flag) and,
+// for a host caller, the image and the first RGK_FIRST_ROWS rows behind it; a host caller with more rows gets the rest in a second download.  The scratch is
+// the call's own (rgk_*: twelve bytes per pixel) but for the scan's tile sums, which hold nothing between calls.
+// ------------------------------------------------------------------------------------------------
+extern "C" int f3ds_region_components(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, const f3ds_component_params* params,
+                                      int inputs_on_device, uint32_t* comp_labels, f3ds_region_component* rows, size_t cap, int outputs_on_device, size_t* n_out,
+                                      f3ds_region_components_result* result) {
+    if (!c) return F3DS_ERR_ARG;
+    f3ds_rgbd_format fmt; f3ds::RgbdLayout lay; f3ds_component_params prm;
+    if (const int rc = cc_check(fmt_, depth, labels, n_regions, params, comp_labels, n_out, &fmt, &lay, &prm)) return rc;
+    g_sw.read();
+    HIPCHECK(hipSetDevice(c->device));
+    Batch b = batch_of(c);
+    const uint32_t n = (uint32_t)lay.n, K = n_regions;
+    constexpr size_t HEAD_BYTES = 64;      // RGK_HEAD words, and what follows 8-byte aligned
+    const bool host_out = !outputs_on_device, host_rows = rows && host_out;
+    const size_t image_bytes = host_out ? (size_t)n * 4 : 0u;
+    const size_t stage_rows = host_rows ? (cap < n ? cap : (size_t)n) : 0u;      // (components <= pixels)
+    const size_t out_bytes = HEAD_BYTES + image_bytes + stage_rows * sizeof(f3ds_region_component);
+    // every buffer of the call before anything is recorded
+    uint32_t *parent, *cnt, *flag, *ul = nullptr; unsigned char *out, *ud = nullptr;
+    ENSURE(c->rgk_parent, n, parent); ENSURE(c->rgk_cnt, n, cnt); ENSURE(c->rgk_flag, n, flag); ENSURE(c->rgk_out, out_bytes, out);
+    if (c->h_rgk_cap < out_bytes) {
+        if (c->h_rgk) { HIPCHECK(hipHostFree(c->h_rgk)); c->h_rgk = nullptr; c->h_rgk_cap = 0; }
+        HIPCHECK(hipHostMalloc(&c->h_rgk, out_bytes + out_bytes / 4, hipHostMallocDefault));
+        c->h_rgk_cap = out_bytes + out_bytes / 4;
+    }
+    const unsigned char* d_depth = static_cast<const unsigned char*>(depth);
+    const uint32_t* d_lab = labels;
+    if (!inputs_on_device) {      // host images go through the device's copy stream, like those of f3ds_region_table
+        ENSURE(c->rgk_depth, lay.depth_bytes, ud); ENSURE(c->rgk_lab, n, ul);
+        hipStream_t up = g_sw.copy_stream ? copy_stream_of(c->device) : nullptr;
+        HIPCHECK(hipMemcpyAsync(ud, depth, lay.depth_bytes, hipMemcpyHostToDevice, up ? up : b.st));
+        HIPCHECK(hipMemcpyAsync(ul, labels, (size_t)n * 4, hipMemcpyHostToDevice, up ? up : b.st));
+        if (up) { if (const int urc = await_uploads(b, up)) return urc; }
+        d_depth = ud; d_lab = ul;
+    }
+    CompArgs a;
+    memset(&a, 0, sizeof a);
+    a.width = fmt.width; a.height = fmt.height; a.n = n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
+    a.K = K; a.min_pixels = prm.min_pixels; a.tiles_x = (fmt.width + CC_TILE_W - 1u) / CC_TILE_W; a.tiles_y = (fmt.height + CC_TILE_H - 1u) / CC_TILE_H;
+    a.depth_scale = fmt.depth_scale; a.depth_tol = prm.depth_tol;
+    uint32_t* head = reinterpret_cast<uint32_t*>(out);
+    uint32_t* d_comp = host_out ? reinterpret_cast<uint32_t*>(out + HEAD_BYTES) : comp_labels;
+    f3ds_region_component* d_rows = !rows ? nullptr : (host_out ? reinterpret_cast<f3ds_region_component*>(out + HEAD_BYTES + image_bytes) : rows);
+    const size_t seams = (size_t)(a.tiles_x - 1u) * fmt.height + (size_t)(a.tiles_y - 1u) * fmt.width;
+    rec_fill(c, head, 0u, HEAD_BYTES);
+    rec<d_comp_local>(c, grid_for((size_t)a.tiles_x * a.tiles_y, 1), 0u, d_depth, d_lab, a, parent, cnt, head);
+    rec<d_comp_seam>(c, grid_for(seams, 256), 0u, d_depth, d_lab, a, parent);
+    rec<d_comp_flatten>(c, grid_for(n, 256), 0u, n, parent, cnt);
+    rec<d_comp_flag>(c, grid_for(n, 256), 0u, n, parent, cnt, a.min_pixels, flag, head);
+    if (const int rc = scan_u32(c, flag, flag, n)) return rc;
+    rec<d_comp_write>(c, grid_for(n, 256), 0u, n, d_lab, parent, cnt, flag, a.min_pixels, head, d_comp, d_rows, (uint64_t)cap);
+    if (const int rc = flush(b)) return rc;
+    const size_t first_rows = stage_rows < RGK_FIRST_ROWS ? stage_rows : (size_t)RGK_FIRST_ROWS;
+    HIPCHECK(hipMemcpyAsync(c->h_rgk, out, HEAD_BYTES + image_bytes + first_rows * sizeof(f3ds_region_component), hipMemcpyDeviceToHost, b.st));
+    HIPCHECK(timed_sync(b.st));
+    HIPCHECK(hipGetLastError());
+    uint32_t h[RGK_HEAD];
+    memcpy(h, c->h_rgk, sizeof h);
+    if (h[1]) return F3DS_ERR_ARG;      // a label >= n_regions: d_comp_write wrote nothing, and nothing is copied out
+    const size_t count = h[0];
+    if (count > n) return F3DS_ERR_LOGIC;
+    if (host_out) memcpy(comp_labels, c->h_rgk + HEAD_BYTES, image_bytes);
+    *n_out = count;
+    if (result) {
+        result->n_regions = K; result->n_components = h[0]; result->n_dropped = h[2]; result->reserved = 0u;
+        memcpy(&result->n_labelled, h + 4, 8); memcpy(&result->n_kept, h + 6, 8);
+    }
+    if (!rows) return F3DS_OK;
+    if (cap < count) return F3DS_ERR_CAPACITY;
+    if (host_rows && count) {
+        const size_t rows_at = HEAD_BYTES + image_bytes;
+        if (count > RGK_FIRST_ROWS) {      // (rare: the rows behind the first download)
+            const size_t off = rows_at + (size_t)RGK_FIRST_ROWS * sizeof(f3ds_region_component);
+            HIPCHECK(hipMemcpyAsync(c->h_rgk + off, out + off, (count - RGK_FIRST_ROWS) * sizeof(f3ds_region_component), hipMemcpyDeviceToHost, b.st));
+            HIPCHECK(timed_sync(b.st));
+        }
+        memcpy(rows, c->h_rgk + rows_at, count * sizeof(f3ds_region_component));
     }
     return F3DS_OK;
 }

@@ -22,6 +22,7 @@
 #include "f3ds_regions.h"
 #include "f3ds_contacts.h"
 #include "f3ds_shapes.h"
+#include "f3ds_components.h"
 
 extern "C" {
 
@@ -296,6 +297,171 @@ int f3ds_region_shapes_host(const f3ds_rgbd_format* fmt_, const void* depth, con
     for (uint32_t r = 0; r < n_regions; ++r) { f3ds::sh_finish(acc[r], &rows[r]); if (acc[r].n) ++n_nonempty; }
     if (result) { result->n_regions = n_regions; result->n_nonempty = n_nonempty; result->n_labelled = n_labelled; result->n_clamped = n_clamped; }
     return F3DS_OK;
+}
+
+// ---- region components: the definition (the rules are in f3ds_components.h, which the kernels of f3ds_components.inc call too) ----
+void f3ds_default_component_params(f3ds_component_params* p) { if (p) { p->depth_tol = 0.05f; p->min_pixels = 1u; } }
+
+}  // extern "C"
+
+namespace {
+// what the two host functions share: the pixels as the rules see them (the label of a labelled pixel, CC_NONE for any other; its depth), after the checks
+struct CcFrame { f3ds_rgbd_format fmt; f3ds_component_params prm; uint32_t w, h, n; std::vector<uint32_t> lab; std::vector<float> z; };
+int cc_frame(const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, const f3ds_component_params* params, const uint32_t* comp_labels,
+             const size_t* n_out, CcFrame& f) {
+    f3ds::RgbdLayout l;
+    if (const int rc = f3ds::cc_check(fmt_, depth, labels, n_regions, params, comp_labels, n_out, &f.fmt, &l, &f.prm)) return rc;
+    for (size_t p = 0; p < l.n; ++p) if (labels[p] != F3DS_NO_LABEL && labels[p] >= n_regions) return F3DS_ERR_ARG;
+    f.w = f.fmt.width; f.h = f.fmt.height; f.n = (uint32_t)l.n;
+    f.lab.assign(l.n, f3ds::CC_NONE); f.z.assign(l.n, 0.0f);
+    const unsigned char* dimg = static_cast<const unsigned char*>(depth);
+    for (uint32_t v = 0; v < f.h; ++v) {
+        const unsigned char* drow = dimg + (size_t)v * l.depth_pitch;
+        for (uint32_t u = 0; u < f.w; ++u) {
+            float z = 0.0f; bool valid;
+            if (f.fmt.depth_type == F3DS_DEPTH_F32) { float d; memcpy(&d, drow + 4u * (size_t)u, 4); valid = f3ds::n_depth_to_z(d, f.fmt.depth_scale, z); }
+            else { uint16_t d; memcpy(&d, drow + 2u * (size_t)u, 2); valid = f3ds::n_depth_to_z(d, f.fmt.depth_scale, z); }
+            const size_t p = (size_t)v * f.w + u;
+            if (valid && labels[p] != F3DS_NO_LABEL) { f.lab[p] = labels[p]; f.z[p] = z; }
+        }
+    }
+    return F3DS_OK;
+}
+// the outputs of both, from the image and the rows of the kept components in order
+int cc_deliver(const CcFrame& f, uint32_t n_regions, const std::vector<uint32_t>& image, const std::vector<f3ds_region_component>& kept, uint32_t n_dropped, uint64_t n_labelled,
+               uint32_t* comp_labels, f3ds_region_component* rows, size_t cap, size_t* n_out, f3ds_region_components_result* result) {
+    memcpy(comp_labels, image.data(), (size_t)f.n * 4);
+    uint64_t n_kept = 0;
+    for (const f3ds_region_component& r : kept) n_kept += r.n_pixels;
+    *n_out = kept.size();
+    if (result) {
+        result->n_regions = n_regions; result->n_components = (uint32_t)kept.size(); result->n_dropped = n_dropped; result->reserved = 0u;
+        result->n_labelled = n_labelled; result->n_kept = n_kept;
+    }
+    if (!rows) return F3DS_OK;
+    if (cap < kept.size()) return F3DS_ERR_CAPACITY;
+    if (!kept.empty()) memcpy(rows, kept.data(), kept.size() * sizeof(f3ds_region_component));
+    return F3DS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// A raster scan that flood-fills from every labelled pixel not yet reached: the pixel the scan meets first is the component's root, and the numbering is
+// the order of the scan.  (On purpose another algorithm than the device's union-find.)
+int f3ds_region_components_host(const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, const f3ds_component_params* params,
+                                uint32_t* comp_labels, f3ds_region_component* rows, size_t cap, size_t* n_out, f3ds_region_components_result* result) {
+    CcFrame f;
+    if (const int rc = cc_frame(fmt_, depth, labels, n_regions, params, comp_labels, n_out, f)) return rc;
+    const float tol = f.prm.depth_tol;
+    std::vector<uint32_t> image(f.n, F3DS_NO_LABEL), members;
+    std::vector<unsigned char> seen(f.n, 0);
+    std::vector<f3ds_region_component> kept;
+    uint32_t n_dropped = 0; uint64_t n_labelled = 0;
+    for (uint32_t s = 0; s < f.n; ++s) {
+        if (seen[s] || f.lab[s] == f3ds::CC_NONE) continue;
+        members.clear(); members.push_back(s); seen[s] = 1;
+        for (size_t k = 0; k < members.size(); ++k) {
+            const uint32_t p = members[k], v = p / f.w, u = p - v * f.w;
+            auto reach = [&](uint32_t a, uint32_t b, uint32_t q) {      // a: the pair's first pixel, b its second; q: the one of them that is not p
+                if (!seen[q] && f3ds::cc_link(f.lab[a], f.z[a], f.lab[b], f.z[b], tol)) { seen[q] = 1; members.push_back(q); }
+            };
+            if (u + 1u < f.w) reach(p, p + 1u, p + 1u);
+            if (u > 0u) reach(p - 1u, p, p - 1u);
+            if (v + 1u < f.h) reach(p, p + f.w, p + f.w);
+            if (v > 0u) reach(p - f.w, p, p - f.w);
+        }
+        n_labelled += members.size();
+        if (!f3ds::cc_kept((uint32_t)members.size(), f.prm.min_pixels)) { ++n_dropped; continue; }
+        for (const uint32_t p : members) image[p] = (uint32_t)kept.size();
+        kept.push_back(f3ds_region_component{f.lab[s], s, (uint32_t)members.size()});
+    }
+    return cc_deliver(f, n_regions, image, kept, n_dropped, n_labelled, comp_labels, rows, cap, n_out, result);
+}
+
+// The device's algorithm, one step after the other (f3ds_components.inc has the same phases): per tile the run heads of every row and the unions with the row
+// above, in tile-local indices; the tile's roots and sizes written out; the seams; every pixel to its root, the sizes of the tiles' roots onto it; the flags of
+// the kept roots and their scan; the image and the rows.
+int f3ds_region_components_tiled(const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, const f3ds_component_params* params,
+                                 uint32_t tile_w, uint32_t tile_h, uint32_t* comp_labels, f3ds_region_component* rows, size_t cap, size_t* n_out,
+                                 f3ds_region_components_result* result) {
+    if (tile_w < 1u || tile_w > 64u || tile_h < 1u) return F3DS_ERR_ARG;
+    CcFrame f;
+    if (const int rc = cc_frame(fmt_, depth, labels, n_regions, params, comp_labels, n_out, f)) return rc;
+    const float tol = f.prm.depth_tol;
+    const uint32_t w = f.w, h = f.h, n = f.n, tiles_x = (w + tile_w - 1u) / tile_w, tiles_y = (h + tile_h - 1u) / tile_h;
+    std::vector<uint32_t> parent(n, f3ds::CC_NONE), cnt(n, 0u);
+    auto image_pix = [&](uint32_t u, uint32_t v, uint32_t& lab, float& z) { lab = f.lab[(size_t)v * w + u]; z = f.z[(size_t)v * w + u]; };
+    // d_comp_local
+    std::vector<uint32_t> t_lab((size_t)tile_w * tile_h), t_par(t_lab.size()), t_cnt(t_lab.size()), t_root(t_lab.size());
+    std::vector<float> t_z(t_lab.size());
+    for (uint32_t ty = 0; ty < tiles_y; ++ty)
+        for (uint32_t tx = 0; tx < tiles_x; ++tx) {
+            const uint32_t u0 = tx * tile_w, v0 = ty * tile_h;
+            for (uint32_t r = 0; r < tile_h; ++r)
+                for (uint32_t c = 0; c < tile_w; ++c) {
+                    const uint32_t li = r * tile_w + c;
+                    t_lab[li] = f3ds::CC_NONE; t_z[li] = 0.0f; t_cnt[li] = 0u;
+                    if (u0 + c < w && v0 + r < h) image_pix(u0 + c, v0 + r, t_lab[li], t_z[li]);
+                }
+            auto tile_pix = [&](uint32_t c, uint32_t r, uint32_t& lab, float& z) { lab = t_lab[r * tile_w + c]; z = t_z[r * tile_w + c]; };
+            const f3ds::CcPlain mem{t_par.data()};
+            for (uint32_t r = 0; r < tile_h; ++r) {
+                uint64_t linked = 0ull;      // the ballot of "linked to my left neighbour"
+                for (uint32_t c = 1; c < tile_w; ++c) {
+                    const uint32_t li = r * tile_w + c;
+                    if (f3ds::cc_link(t_lab[li - 1u], t_z[li - 1u], t_lab[li], t_z[li], tol)) linked |= 1ull << c;
+                }
+                for (uint32_t c = 0; c < tile_w; ++c) t_par[r * tile_w + c] = r * tile_w + f3ds::cc_run_head(linked, c);
+            }
+            for (uint32_t r = 1; r < tile_h; ++r)
+                for (uint32_t c = 0; c < tile_w; ++c)
+                    if (f3ds::cc_joins(tile_pix, c, r - 1u, true, c != 0u, tol)) f3ds::cc_unite(mem, t_par[r * tile_w + c], (r - 1u) * tile_w + c);
+            for (uint32_t li = 0; li < t_lab.size(); ++li)
+                if (t_lab[li] != f3ds::CC_NONE) { t_root[li] = f3ds::cc_find(mem, li); ++t_cnt[t_root[li]]; }
+            for (uint32_t r = 0; r < tile_h && v0 + r < h; ++r)
+                for (uint32_t c = 0; c < tile_w && u0 + c < w; ++c) {
+                    const uint32_t li = r * tile_w + c, p = (v0 + r) * w + u0 + c;
+                    if (t_lab[li] == f3ds::CC_NONE) continue;
+                    parent[p] = (v0 + t_root[li] / tile_w) * w + u0 + t_root[li] % tile_w;
+                    cnt[p] = t_root[li] == li ? t_cnt[li] : 0u;
+                }
+        }
+    // d_comp_seam: the right column and the bottom row of every tile but the last ones
+    const f3ds::CcPlain mem{parent.data()};
+    for (uint32_t tx = 0; tx + 1u < tiles_x; ++tx)
+        for (uint32_t v = 0; v < h; ++v) {
+            const uint32_t u = (tx + 1u) * tile_w - 1u;
+            if (f3ds::cc_joins(image_pix, u, v, false, v % tile_h != 0u, tol)) f3ds::cc_unite(mem, v * w + u, v * w + u + 1u);
+        }
+    for (uint32_t ty = 0; ty + 1u < tiles_y; ++ty)
+        for (uint32_t u = 0; u < w; ++u) {
+            const uint32_t v = (ty + 1u) * tile_h - 1u;
+            if (f3ds::cc_joins(image_pix, u, v, true, u % tile_w != 0u, tol)) f3ds::cc_unite(mem, v * w + u, (v + 1u) * w + u);
+        }
+    // d_comp_flatten
+    for (uint32_t p = 0; p < n; ++p) {
+        if (parent[p] == f3ds::CC_NONE) continue;
+        const uint32_t r = f3ds::cc_find(mem, p);
+        parent[p] = r;
+        if (cnt[p] && r != p) cnt[r] += cnt[p];
+    }
+    // d_comp_flag, the scan, d_comp_write
+    std::vector<uint32_t> incl(n), image(n, F3DS_NO_LABEL);
+    uint32_t run = 0, n_dropped = 0; uint64_t n_labelled = 0;
+    for (uint32_t p = 0; p < n; ++p) {
+        const bool root = parent[p] == p;
+        if (root) { n_labelled += cnt[p]; if (f3ds::cc_kept(cnt[p], f.prm.min_pixels)) ++run; else ++n_dropped; }
+        incl[p] = run;
+    }
+    std::vector<f3ds_region_component> kept(run);
+    for (uint32_t p = 0; p < n; ++p) {
+        const uint32_t r = parent[p];
+        if (r == f3ds::CC_NONE || !f3ds::cc_kept(cnt[r], f.prm.min_pixels)) continue;
+        image[p] = incl[r] - 1u;
+        if (r == p) kept[incl[r] - 1u] = f3ds_region_component{f.lab[p], p, cnt[p]};
+    }
+    return cc_deliver(f, n_regions, image, kept, n_dropped, n_labelled, comp_labels, rows, cap, n_out, result);
 }
 
 }  // extern "C"

@@ -404,6 +404,61 @@ int f3ds_region_shapes_host(const f3ds_rgbd_format* fmt, const void* depth, cons
 int f3ds_region_shapes(f3ds_ctx* ctx, const f3ds_rgbd_format* fmt, const void* depth, const uint32_t* labels, uint32_t n_regions,
                        int inputs_on_device, f3ds_region_shape* rows, int rows_on_device, f3ds_region_shapes_result* result);
 
+/* ---- region components: split the regions of a label image into their connected parts -----------------------------------------
+ * A region of the segmenter is merged in space, so in the image one label regularly covers disjoint pieces: a table top left and right of the object
+ * on it, a wall behind a chair, speckles around depth holes.  The table, the contacts, the shapes and the tracker describe region i as one thing; run
+ * on the image this function writes -- with n_regions = n_components -- they describe each piece.  The output is a label image again, and one row per
+ * component says which region it came from.  The definition, bit for bit (csrc/f3ds_components.h):
+ *   point      the family's: pixel p = v * width + u gets z by the rule of f3ds_deproject; it is LABELLED iff its depth is valid and
+ *              label[p] != F3DS_NO_LABEL.  The colour fields of the format are not looked at.
+ *   pairs      the contacts': p with p + 1 when u + 1 < width, with p + width when v + 1 < height.  4-connectivity, no diagonals.
+ *   link       a pair is a LINK iff both pixels are labelled, their labels are equal, and the pair is CLOSE by the contacts' rule: g = fabsf(za - zb),
+ *              zn = za < zb ? za : zb, g <= depth_tol * zn (one rounded f32 subtraction, one rounded f32 product, false on NaN).  depth_tol = +inf
+ *              links every equal-label pair of finite depths; depth_tol = 0 links equal depths only.
+ *   component  a class of the labelled pixels under the transitive closure of the links.  Its root is its smallest pixel index, its size its pixel count.
+ *   kept       a component is kept iff its size is at least max(min_pixels, 1).
+ *   numbering  kept components are numbered 0, 1, ... by ascending root: raster order of the first pixel.  comp_labels[p] = the number of p's component
+ *              if p is labelled and the component is kept, else F3DS_NO_LABEL (also for a label over an invalid depth).  Row k describes component k.
+ *   result     n_components kept and n_dropped dropped components; n_labelled labelled pixels, n_kept of them in kept components; reserved = 0.
+ *   capacity   the contacts': *n_out receives n_components on F3DS_OK and on F3DS_ERR_CAPACITY.  rows == NULL: no rows, cap is ignored.  cap smaller
+ *              than the count: F3DS_ERR_CAPACITY; the image and the result are written and no row is.
+ * Everything is a class of an equivalence relation, a minimum or an integer count: the result does not depend on the order of evaluation, and the
+ * device gives the bits of the host function.
+ * Errors (both functions alike): F3DS_ERR_ARG for a NULL fmt, depth, labels, comp_labels or n_out, for comp_labels == labels, for what f3ds_deproject
+ * refuses of a format (the two colour fields are neutralised as in f3ds_region_contacts), for a depth_tol that is negative or NaN, and for a label
+ * >= n_regions other than F3DS_NO_LABEL on any pixel (the device function finds it on the device and reports it at the call's one wait); then nothing is
+ * written: no image, no row, no n_out, no result.  F3DS_ERR_UNSUPPORTED for n_regions > 0x00FFFFFF.  n_regions == 0 with every label F3DS_NO_LABEL, a
+ * 1 x 1 image and a frame without a labelled pixel are F3DS_OK with zero components. */
+typedef struct f3ds_component_params { float depth_tol; uint32_t min_pixels; } f3ds_component_params;   /* defaults 0.05f, 1 */
+typedef struct f3ds_region_component {      /* 12 bytes */
+    uint32_t region;        /* the input label of the component's pixels          */
+    uint32_t first_pixel;   /* its smallest pixel index                            */
+    uint32_t n_pixels;      /* its labelled pixels                                 */
+} f3ds_region_component;
+typedef struct f3ds_region_components_result {
+    uint32_t n_regions, n_components, n_dropped, reserved;   /* kept / dropped components; reserved = 0 */
+    uint64_t n_labelled, n_kept;                              /* labelled pixels; those in kept components */
+} f3ds_region_components_result;
+void f3ds_default_component_params(f3ds_component_params* params);
+/* host arithmetic only, no device needed: the definition (a raster scan that flood-fills from every labelled pixel not yet reached).  params == NULL:
+ * the defaults.  comp_labels: width * height words. */
+int f3ds_region_components_host(const f3ds_rgbd_format* fmt, const void* depth, const uint32_t* labels, uint32_t n_regions,
+                                const f3ds_component_params* params, uint32_t* comp_labels, f3ds_region_component* rows, size_t cap, size_t* n_out,
+                                f3ds_region_components_result* result /* may be NULL */);
+/* the same image and rows from the device (csrc/f3ds_components.inc: a tiled union-find).  inputs_on_device: depth and labels are device memory and read
+ * where they are; host inputs go through the device's copy stream like those of f3ds_region_table.  outputs_on_device: comp_labels and rows (cap rows of
+ * it) are device memory; host outputs arrive with the call's one download (a second one only for more than 2048 rows).  Synchronous.  Runs on ctx's
+ * stream and uses scratch of its own (and the scan's tile sums, which hold nothing between calls): every other call on the context behaves as if this
+ * one never happened.  Also F3DS_ERR_ARG for a NULL ctx. */
+int f3ds_region_components(f3ds_ctx* ctx, const f3ds_rgbd_format* fmt, const void* depth, const uint32_t* labels, uint32_t n_regions,
+                           const f3ds_component_params* params, int inputs_on_device, uint32_t* comp_labels, f3ds_region_component* rows, size_t cap,
+                           int outputs_on_device, size_t* n_out, f3ds_region_components_result* result);
+/* development: the device's algorithm (tiles, seams, flatten, numbering: the step functions of csrc/f3ds_components.h) run sequentially on the host at a
+ * tile size of tile_w x tile_h pixels (1 <= tile_w <= 64); the contract of f3ds_region_components_host.  No device needed. */
+int f3ds_region_components_tiled(const f3ds_rgbd_format* fmt, const void* depth, const uint32_t* labels, uint32_t n_regions,
+                                 const f3ds_component_params* params, uint32_t tile_w, uint32_t tile_h, uint32_t* comp_labels,
+                                 f3ds_region_component* rows, size_t cap, size_t* n_out, f3ds_region_components_result* result);
+
 /* Clustering::cluster(threshold) again on the supervoxels of the last f3ds_segment call, with
  * possibly different metric / merging settings (src/clustering.cpp:670-679).  Only the merge
  * fields of `params` are read. */
