@@ -94,18 +94,16 @@ F3DS_HD bool cc_joins(const Pix& pix, uint32_t u, uint32_t v, bool below, bool i
     return !(cc_link(lp1, zp1, lp, zp, depth_tol) && cc_link(lq1, zq1, lq, zq, depth_tol) && cc_link(lp1, zp1, lq1, zq1, depth_tol));
 }
 
-// What both entry points refuse before they look at a pixel, in this order; *use = the format they work with (the colour fields neutral: as ct_check);
-// *prm = the parameters (the defaults for NULL).  depth_tol may be +inf.
+// What both entry points refuse before they look at a pixel, in ct_check's order: the outputs and li_check's arguments, depth_tol, li_check's region cap; *use =
+// the format they work with; *prm = the parameters (the defaults for NULL).  depth_tol may be +inf.
 inline int cc_check(const f3ds_rgbd_format* fmt, const void* depth, const uint32_t* labels, uint32_t n_regions, const f3ds_component_params* params,
                     const uint32_t* comp_labels, const size_t* n_out, f3ds_rgbd_format* use, RgbdLayout* lay, f3ds_component_params* prm) {
-    if (!fmt || !depth || !labels || !comp_labels || !n_out || comp_labels == labels) return F3DS_ERR_ARG;
-    *use = *fmt;
-    use->color_format = F3DS_COLOR_RGB8; use->color_pitch = 0;
-    if (const int rc = rgbd_layout(use, lay)) return rc;
+    if (!comp_labels || !n_out || comp_labels == labels) return F3DS_ERR_ARG;
+    const int rc = li_check(fmt, depth, nullptr, labels, n_regions, use, lay);
+    if (rc == F3DS_ERR_ARG) return rc;
     if (params) *prm = *params; else { prm->depth_tol = 0.05f; prm->min_pixels = 1u; }
     if (!(prm->depth_tol >= 0.0f)) return F3DS_ERR_ARG;      // (false on NaN)
-    if (n_regions > CC_MAX_REGIONS) return F3DS_ERR_UNSUPPORTED;
-    return F3DS_OK;
+    return rc;
 }
 
 }  // namespace f3ds

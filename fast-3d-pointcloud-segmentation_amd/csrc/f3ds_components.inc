@@ -26,7 +26,7 @@ struct CompArgs {
     uint32_t tiles_x, tiles_y;
     float depth_scale, depth_tol;
 };
-constexpr uint32_t RGK_HEAD = 8;       // words of the head: [0] kept components, [1] 1 if a label was >= K, [2] dropped components, [3] spare, [4..5] labelled pixels (u64), [6..7] those in kept components (u64)
+// the head (LI_HEAD_WORDS, f3ds_label_image.h): [0] kept components, [1] 1 if a label was >= K, [2] dropped components, [3] spare, [4..5] labelled pixels (u64), [6..7] those in kept components (u64)
 constexpr uint32_t RGK_FIRST_ROWS = 2048;      // rows of a host caller that ride with the head and the image; a frame with more gets a second download
 constexpr uint32_t CC_TILE = CC_TILE_W * CC_TILE_H, CC_PER_THREAD = CC_TILE / 256u;
 static_assert(CC_TILE_W == 64u && CC_TILE % 256u == 0u, "a tile row is a wave; a workgroup of 256 takes whole rows per trip");
@@ -49,11 +49,8 @@ struct CcImagePix {
     const unsigned char* depth; const uint32_t* label; uint32_t width, depth_pitch, K; float depth_scale;
     __device__ void operator()(uint32_t u, uint32_t v, uint32_t& lab, float& z) const {
         const uint32_t l = label[v * width + u];
-        const unsigned char* drow = depth + (size_t)v * depth_pitch;
         z = 0.0f;
-        bool valid;
-        if constexpr (DEPTH_F32) valid = n_depth_to_z(reinterpret_cast<const float*>(drow)[u], depth_scale, z);
-        else valid = n_depth_to_z(reinterpret_cast<const uint16_t*>(drow)[u], depth_scale, z);
+        const bool valid = li_read_depth<DEPTH_F32>(depth, depth_pitch, depth_scale, u, v, z);
         lab = valid && l < K ? l : CC_NONE;      // (K <= CC_MAX_REGIONS: CC_NONE is never below it)
     }
 };

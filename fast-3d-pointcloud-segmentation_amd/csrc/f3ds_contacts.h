@@ -79,16 +79,15 @@ F3DS_HD void ct_finish(uint32_t a, uint32_t b, const CtAcc& acc, f3ds_region_con
     *row = r;
 }
 
-// What both entry points refuse before they look at a pixel, in this order; *use = the format they work with (the colour fields neutral: no colour image).
+// What both entry points refuse before they look at a pixel, in this order: a missing n_out and li_check's arguments, depth_tol, li_check's region cap; *use =
+// the format they work with.
 inline int ct_check(const f3ds_rgbd_format* fmt, const void* depth, const uint32_t* labels, uint32_t n_regions, float depth_tol, const size_t* n_out,
                     f3ds_rgbd_format* use, RgbdLayout* lay) {
-    if (!fmt || !depth || !labels || !n_out) return F3DS_ERR_ARG;
-    *use = *fmt;
-    use->color_format = F3DS_COLOR_RGB8; use->color_pitch = 0;      // (no colour image is passed: the two colour fields are not looked at)
-    if (const int rc = rgbd_layout(use, lay)) return rc;
+    if (!n_out) return F3DS_ERR_ARG;
+    const int rc = li_check(fmt, depth, nullptr, labels, n_regions, use, lay);
+    if (rc == F3DS_ERR_ARG) return rc;
     if (!m_isfinitef(depth_tol) || !(depth_tol >= 0.0f)) return F3DS_ERR_ARG;
-    if (n_regions > CT_MAX_REGIONS) return F3DS_ERR_UNSUPPORTED;
-    return F3DS_OK;
+    return rc;
 }
 
 }  // namespace f3ds

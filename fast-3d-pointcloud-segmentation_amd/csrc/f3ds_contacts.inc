@@ -22,7 +22,7 @@ struct ContactArgs {
     uint32_t rec_cap;                  // records the buffers hold
     float depth_scale, depth_tol;
 };
-constexpr uint32_t RGC_HEAD = 8;       // words of the head: [0] rows, [1] 1 if a label was >= K, [2] records asked for (more than rec_cap: nothing else holds), [3] spare, [4..5] contact pairs (u64), [6..7] close ones (u64)
+// the head (LI_HEAD_WORDS, f3ds_label_image.h): [0] rows, [1] 1 if a label was >= K, [2] records asked for (more than rec_cap: nothing else holds), [3] spare, [4..5] contact pairs (u64), [6..7] close ones (u64)
 constexpr int RGC_SLOT_BITS = 8, RGC_SLOTS = 1 << RGC_SLOT_BITS;      // LDS table: 256 slots of a key + a CtAcc (36 B), 9 KiB; slot k is thread k's at the flush
 constexpr int RGC_PROBES = 8;          // a pair that finds neither its slot nor a free one in this many steps becomes a record of its own
 constexpr uint32_t RGC_TRIPS = 8;      // trips of a workgroup the grid is sized for: longer spans, fewer records of the same pair
@@ -33,14 +33,14 @@ struct d_contact_init {
     static constexpr int BLOCK = 256;
     __device__ void operator()(uint64_t* keys, uint32_t* vals, uint32_t rec_cap, uint32_t* head) const {
         for (uint32_t i = BIX * blockDim.x + threadIdx.x; i < rec_cap; i += gridDim.x * blockDim.x) { keys[i] = CT_NO_KEY; vals[i] = i; }
-        if (BIX == 0u && threadIdx.x < RGC_HEAD) head[threadIdx.x] = 0u;
+        if (BIX == 0u && threadIdx.x < LI_HEAD_WORDS) head[threadIdx.x] = 0u;
     }
 };
 
 // the LDS table of a workgroup: field-major, as RgTable
 struct CtTable { rg_u64 key[RGC_SLOTS]; uint32_t w[CT_W][RGC_SLOTS]; rg_u64 s[RGC_SLOTS]; };
 
-// the slot of a key, claimed on the way if it is new; -1: none within RGC_PROBES steps (slots are never given back within a span: as rg_slot)
+// the slot of a key, claimed on the way if it is new; -1: none within RGC_PROBES steps (slots are never given back within a span: as li_slot)
 __device__ __forceinline__ int ct_slot(CtTable& t, uint64_t key) {
     uint32_t h = ((uint32_t)(key ^ (key >> 29)) * 0x9E3779B1u) >> (32 - RGC_SLOT_BITS);
     for (int k = 0; k < RGC_PROBES; ++k) {
@@ -63,14 +63,8 @@ __device__ __forceinline__ void ct_record(uint64_t* keys, uint32_t* rec, uint32_
     for (int k = 0; k < CT_W; ++k) r[k] = a.w[k];
     r[CT_W] = (uint32_t)a.s; r[CT_W + 1] = (uint32_t)(a.s >> 32);
 }
-template <bool DEPTH_F32>
-__device__ __forceinline__ bool ct_depth(const unsigned char* depth, const ContactArgs& a, uint32_t u, uint32_t v, float& z) {
-    const unsigned char* drow = depth + (size_t)v * a.depth_pitch;
-    if constexpr (DEPTH_F32) return n_depth_to_z(reinterpret_cast<const float*>(drow)[u], a.depth_scale, z);
-    else return n_depth_to_z(reinterpret_cast<const uint16_t*>(drow)[u], a.depth_scale, z);
-}
 
-// Span of workgroup b: [b * span, min(n, (b + 1) * span)), span = ceil(n / gridDim.x) rounded up to a multiple of the block (as region_accum_span): every lane of
+// Span of workgroup b: [b * span, min(n, (b + 1) * span)), span = ceil(n / gridDim.x) rounded up to a multiple of the block (as label_accum_span): every lane of
 // the workgroup makes the same number of trips, so the ballots and barriers below are uniform.  A pixel's right and lower neighbours are read wherever they
 // lie: in the next lane's pixel, in another trip or in another workgroup's span -- the pair belongs to its first pixel.
 template <bool DEPTH_F32>
@@ -105,9 +99,9 @@ __device__ __forceinline__ void contact_accum_span(const unsigned char* depth, c
         has[1] = l < a.K && lq[1] < a.K && lq[1] != l;
         if (__ballot(has[0] || has[1]) != 0ull) {      // (wave-uniform, and so are the branches on ballots below)  Inside a region no depth is read.
             float z = 0.0f, zq[2] = {0.0f, 0.0f};
-            const bool valid = (has[0] || has[1]) && ct_depth<DEPTH_F32>(depth, a, u, v, z);
-            has[0] = has[0] && valid && ct_depth<DEPTH_F32>(depth, a, u + 1u, v, zq[0]);
-            has[1] = has[1] && valid && ct_depth<DEPTH_F32>(depth, a, u, v + 1u, zq[1]);
+            const bool valid = (has[0] || has[1]) && li_read_depth<DEPTH_F32>(depth, a.depth_pitch, a.depth_scale, u, v, z);
+            has[0] = has[0] && valid && li_read_depth<DEPTH_F32>(depth, a.depth_pitch, a.depth_scale, u + 1u, v, zq[0]);
+            has[1] = has[1] && valid && li_read_depth<DEPTH_F32>(depth, a.depth_pitch, a.depth_scale, u, v + 1u, zq[1]);
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 const uint64_t m = __ballot(has[k]);

@@ -48,6 +48,7 @@
 #include "f3ds_levels.h"
 #include "f3ds_eval_levels.h"
 #include "f3ds_rgbd.h"
+#include "f3ds_label_image.h"
 #include "f3ds_track.h"
 #include "f3ds_regions.h"
 #include "f3ds_contacts.h"
@@ -182,16 +183,19 @@ const int g_merge_shared_res = [] { const char* e = dev_getenv("F3DS_MERGE_SHARE
     /* level scores (f3ds_eval_levels.inc): sort buffers, base table, reduced level entries, ghost list, per-level sizes / flags / terms, truth sizes and visiting order, matches, counts and results of a batch */ \
     X(uint64_t, evl_k0) X(uint64_t, evl_k1) X(uint32_t, evl_v0) X(uint32_t, evl_v1) X(uint32_t, evl_flag) X(uint64_t, evl_bkey) X(uint32_t, evl_bcnt) X(uint64_t, evl_ukey) X(uint32_t, evl_ucnt) X(uint32_t, evl_glist) \
     X(uint32_t, evl_ssize) X(unsigned char, evl_used) X(float, evl_hterm) X(float, evl_mterm) X(float, evl_tterm) X(uint32_t, evl_tsize) X(uint32_t, evl_order) X(uint32_t, evl_slot) X(uint32_t, evl_counts) X(uint32_t, evl_out) \
-    /* label tracker (f3ds_track.inc; the sort and the reduction use the evl_ buffers of the tracker's private context): labels as uploaded, the ends of the entries' runs, the packed entries, id[], the ids of a host caller */ \
-    X(uint32_t, trk_lab) X(uint32_t, trk_end) X(uint32_t, trk_out) X(uint32_t, trk_id) X(uint32_t, trk_tid) \
-    /* region table (f3ds_regions.inc), its own so that the call leaves every other one alone: the images and labels as uploaded, the accumulators, the head and the rows of a host caller */ \
-    X(unsigned char, rgt_depth) X(unsigned char, rgt_color) X(uint32_t, rgt_lab) X(RgAcc, rgt_acc) X(unsigned char, rgt_out) \
-    /* region contacts (f3ds_contacts.inc), its own likewise: the image and labels as uploaded, the records' keys and indices (twice: the sort), the records, the runs' flags, keys, starts and ends, the run count, the head and the rows of a host caller */ \
-    X(unsigned char, rgc_depth) X(uint32_t, rgc_lab) X(uint64_t, rgc_k0) X(uint64_t, rgc_k1) X(uint32_t, rgc_v0) X(uint32_t, rgc_v1) X(uint32_t, rgc_rec) X(uint32_t, rgc_flag) X(uint64_t, rgc_ukey) X(uint32_t, rgc_ustart) X(uint32_t, rgc_uend) X(uint32_t, rgc_cnt) X(unsigned char, rgc_out) \
-    /* region shapes (f3ds_shapes.inc), its own likewise: the image and labels as uploaded, the accumulators, the head and the rows of a host caller */ \
-    X(unsigned char, rgs_depth) X(uint32_t, rgs_lab) X(ShAcc, rgs_acc) X(unsigned char, rgs_out) \
-    /* region components (f3ds_components.inc), its own likewise: the image and labels as uploaded, a parent, a size and a flag word per pixel, the head and the image and rows of a host caller */ \
-    X(unsigned char, rgk_depth) X(uint32_t, rgk_lab) X(uint32_t, rgk_parent) X(uint32_t, rgk_cnt) X(uint32_t, rgk_flag) X(unsigned char, rgk_out)
+    /* the label-image calls (the tracker update and the four region calls): family-wide staging, which holds nothing once a call has returned (every call waits before it returns) -- the images and labels of a host caller as uploaded, and the head with what a host caller gets behind it on its way down */ \
+    X(unsigned char, li_depth) X(unsigned char, li_color) X(uint32_t, li_lab) X(unsigned char, li_out) \
+    /* ... and below it each call's private working state, which a run of the call that replays (the contacts' second run) finds as it left it */ \
+    /* label tracker (f3ds_track.inc; the sort and the reduction use the evl_ buffers of the tracker's private context): the ends of the entries' runs, the packed entries, id[], the ids of a host caller */ \
+    X(uint32_t, trk_end) X(uint32_t, trk_out) X(uint32_t, trk_id) X(uint32_t, trk_tid) \
+    /* region table (f3ds_regions.inc): the accumulators */ \
+    X(RgAcc, rgt_acc) \
+    /* region contacts (f3ds_contacts.inc): the records' keys and indices (twice: the sort), the records, the runs' flags, keys, starts and ends, the run count */ \
+    X(uint64_t, rgc_k0) X(uint64_t, rgc_k1) X(uint32_t, rgc_v0) X(uint32_t, rgc_v1) X(uint32_t, rgc_rec) X(uint32_t, rgc_flag) X(uint64_t, rgc_ukey) X(uint32_t, rgc_ustart) X(uint32_t, rgc_uend) X(uint32_t, rgc_cnt) \
+    /* region shapes (f3ds_shapes.inc): the accumulators */ \
+    X(ShAcc, rgs_acc) \
+    /* region components (f3ds_components.inc): a parent, a size and a flag word per pixel */ \
+    X(uint32_t, rgk_parent) X(uint32_t, rgk_cnt) X(uint32_t, rgk_flag)
 template <class T> struct Scratch { T* p = nullptr; size_t cap = 0; int slot = -1; };      // cap: bytes allocated; slot: position in F3DS_SCRATCH
 #define F3DS_SCRATCH_SLOT(T, name) S_##name,
 #define F3DS_SCRATCH_MEMBER(T, name) Scratch<T> name{nullptr, 0, S_##name};
@@ -220,10 +224,7 @@ struct f3ds_ctx {
     hipEvent_t ev_args[2] = {nullptr, nullptr}; bool args_used[2] = {false, false}; int args_flip = 0;
     hipEvent_t ev_copy[3] = {nullptr, nullptr, nullptr};      // uploads queued on the device's copy stream / labels ready on the call's stream / downloads done on the copy stream
     DevCounters* d_dcblk = nullptr; DevCounters* h_dcblk = nullptr; size_t dcblk_cap = 0;      // the batch's counters, one slot per frame
-    unsigned char* h_rgt = nullptr; size_t h_rgt_cap = 0;      // pinned: the head (and a host caller's rows) of f3ds_region_table on their way down
-    unsigned char* h_rgc = nullptr; size_t h_rgc_cap = 0;      // pinned: the same of f3ds_region_contacts
-    unsigned char* h_rgs = nullptr; size_t h_rgs_cap = 0;      // pinned: the same of f3ds_region_shapes
-    unsigned char* h_rgk = nullptr; size_t h_rgk_cap = 0;      // pinned: the same of f3ds_region_components (and a host caller's image)
+    unsigned char* h_li = nullptr; size_t h_li_cap = 0;      // pinned: the head of a region call (and a host caller's rows and image) on their way down (li_out_buffers)
     // frame state
     bool have_frame = false;
     bool live = false;
@@ -1060,6 +1061,64 @@ int download_begin(Batch& b, hipStream_t* dl) {
 }
 int download_queued(Batch& b, hipStream_t dl) { if (dl) HIPCHECK(hipEventRecord(b.owner->ev_copy[2], dl)); return F3DS_OK; }
 int download_wait(Batch& b, hipStream_t dl) { if (dl) HIPCHECK(timed_sync(b.owner->ev_copy[2])); return F3DS_OK; }
+
+// ---- the label-image frame (f3ds_label_image.h, DESIGN.md "the label-image frame"): what the tracker update and the four region calls do alike.  A region call
+// reads: check -> li_begin -> its buffers (li_out_buffers) -> li_upload -> its arguments and kernels -> flush -> li_download_head -> deliver (li_rows_behind). ----
+// Start of a label-image call, after its checks: the switches, the device, the batch of the one context
+int li_begin(f3ds_ctx* c, Batch* b) {
+    g_sw.read();
+    HIPCHECK(hipSetDevice(c->device));
+    *b = batch_of(c);
+    return F3DS_OK;
+}
+// The images as the kernels read them: device inputs where they are; host inputs in the family's staging, uploaded through the device's copy stream like
+// those of f3ds_segment_rgbd.  color may be NULL.
+struct LiImages { const unsigned char* depth; const unsigned char* color; const uint32_t* labels; };
+int li_upload(f3ds_ctx* c, Batch& b, const RgbdLayout& lay, const void* depth, const void* color, const uint32_t* labels, int inputs_on_device, LiImages* im) {
+    *im = LiImages{static_cast<const unsigned char*>(depth), static_cast<const unsigned char*>(color), labels};
+    if (inputs_on_device) return F3DS_OK;
+    unsigned char *ud, *uc = nullptr; uint32_t* ul;
+    ENSURE(c->li_depth, lay.depth_bytes, ud); ENSURE(c->li_lab, lay.n, ul);
+    if (color) ENSURE(c->li_color, lay.color_bytes, uc);
+    hipStream_t up = g_sw.copy_stream ? copy_stream_of(c->device) : nullptr;
+    HIPCHECK(hipMemcpyAsync(ud, depth, lay.depth_bytes, hipMemcpyHostToDevice, up ? up : b.st));
+    if (color) HIPCHECK(hipMemcpyAsync(uc, color, lay.color_bytes, hipMemcpyHostToDevice, up ? up : b.st));
+    HIPCHECK(hipMemcpyAsync(ul, labels, lay.n * 4, hipMemcpyHostToDevice, up ? up : b.st));
+    if (up) { if (const int urc = await_uploads(b, up)) return urc; }
+    *im = LiImages{ud, uc, ul};
+    return F3DS_OK;
+}
+// Where a region call's kernels write what goes down: *out = out_bytes of device staging (the head first), and the context's one pinned buffer behind it,
+// grown by a quarter beyond the request when it is too short (its contents are lost)
+int li_out_buffers(f3ds_ctx* c, size_t out_bytes, unsigned char** out) {
+    ENSURE(c->li_out, out_bytes, *out);
+    if (c->h_li_cap < out_bytes) {
+        if (c->h_li) { HIPCHECK(hipHostFree(c->h_li)); c->h_li = nullptr; c->h_li_cap = 0; }
+        HIPCHECK(hipHostMalloc(&c->h_li, out_bytes + out_bytes / 4, hipHostMallocDefault));
+        c->h_li_cap = out_bytes + out_bytes / 4;
+    }
+    return F3DS_OK;
+}
+// ONE download, the call's only wait in the ordinary case: the head and `behind` bytes behind it.  h = the head's words; F3DS_ERR_ARG when a label was
+// >= n_regions: the kernels wrote nothing but the head then, and nothing is copied out.
+int li_download_head(f3ds_ctx* c, Batch& b, const unsigned char* out, size_t behind, uint32_t (&h)[LI_HEAD_WORDS]) {
+    HIPCHECK(hipMemcpyAsync(c->h_li, out, LI_HEAD_BYTES + behind, hipMemcpyDeviceToHost, b.st));
+    HIPCHECK(timed_sync(b.st));
+    HIPCHECK(hipGetLastError());
+    memcpy(h, c->h_li, LI_HEAD_BYTES);
+    return h[1] ? F3DS_ERR_ARG : F3DS_OK;
+}
+// A host caller's `count` rows, which start `rows_at` bytes into the staging: the first download brought `first` of them, a frame with more (rare) gets the rest
+// in a second one
+int li_rows_behind(f3ds_ctx* c, Batch& b, const unsigned char* out, size_t rows_at, size_t row_bytes, size_t count, size_t first, void* rows) {
+    if (count > first) {
+        const size_t off = rows_at + first * row_bytes;
+        HIPCHECK(hipMemcpyAsync(c->h_li + off, out + off, (count - first) * row_bytes, hipMemcpyDeviceToHost, b.st));
+        HIPCHECK(timed_sync(b.st));
+    }
+    memcpy(rows, c->h_li + rows_at, count * row_bytes);
+    return F3DS_OK;
+}
 // Start of every accessor: ARG for no context, LOGIC for a context that does not hold what the call needs -- both before any HIP call --, then the
 // context's device and everything queued on its stream.
 enum FrameNeed { NEED_NOTHING = 0, NEED_FRAME = 1, NEED_VOXEL_GRID = 2 /* not caller-supplied supervoxels */, NEED_REFINED = 4 };
@@ -1227,10 +1286,7 @@ void f3ds_destroy(f3ds_ctx* c) {
     for (auto& e : c->ev_copy) if (e) (void)hipEventDestroy(e);
     if (c->d_dcblk) (void)hipFree(c->d_dcblk);
     if (c->h_dcblk) (void)hipHostFree(c->h_dcblk);
-    if (c->h_rgt) (void)hipHostFree(c->h_rgt);
-    if (c->h_rgc) (void)hipHostFree(c->h_rgc);
-    if (c->h_rgs) (void)hipHostFree(c->h_rgs);
-    if (c->h_rgk) (void)hipHostFree(c->h_rgk);
+    if (c->h_li) (void)hipHostFree(c->h_li);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -2361,7 +2417,8 @@ struct f3ds_tracker {
 };
 
 namespace {
-constexpr size_t TRK_FIRST_CAP = 1024;      // entries the first download has room for; a frame with more is packed again with room for twice its count
+static_assert(TK_MAX_REGIONS == LI_MAX_REGIONS, "li_check applies the tracker's cap");
+constexpr size_t TRK_FIRST_CAP = 1024;     // entries the first download has room for; a frame with more is packed again with room for twice its count
 int trk_pinned(uint32_t** p, size_t* cap, size_t want) {
     if (*cap >= want && *p) return F3DS_OK;
     if (*p) { HIPCHECK(hipHostFree(*p)); *p = nullptr; *cap = 0; }
@@ -2431,40 +2488,32 @@ extern "C" int f3ds_tracker_get_ids(f3ds_tracker* t, uint32_t* id_of_region, siz
 
 extern "C" int f3ds_tracker_update(f3ds_tracker* t, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, int inputs_on_device,
                                    const float* pose12, uint32_t* track_ids, int ids_on_device, f3ds_track_result* result) {
-    if (!t || !fmt_ || !depth || !labels || !track_ids) return F3DS_ERR_ARG;
-    f3ds_rgbd_format fmt = *fmt_;
-    fmt.color_format = F3DS_COLOR_RGB8; fmt.color_pitch = 0;      // (no colour image is passed: the two colour fields are not looked at)
-    f3ds::RgbdLayout lay;
-    if (const int rc = f3ds::rgbd_layout(&fmt, &lay)) return rc;
+    if (!t || !track_ids) return F3DS_ERR_ARG;
+    f3ds_rgbd_format fmt; f3ds::RgbdLayout lay;
+    const int crc = li_check(fmt_, depth, nullptr, labels, n_regions, &fmt, &lay);
+    if (crc == F3DS_ERR_ARG) return crc;
     if (pose12) for (int k = 0; k < 12; ++k) if (!m_isfinitef(pose12[k])) return F3DS_ERR_ARG;
     if (t->have_fmt && (fmt.width != t->fmt.width || fmt.height != t->fmt.height || fmt.fx != t->fmt.fx || fmt.fy != t->fmt.fy || fmt.cx != t->fmt.cx || fmt.cy != t->fmt.cy))
         return F3DS_ERR_ARG;      // (the state is an image of the remembered camera: the caller resets first)
-    if (n_regions > TK_MAX_REGIONS) return F3DS_ERR_UNSUPPORTED;
+    if (crc) return crc;      // (more than TK_MAX_REGIONS regions)
     f3ds_ctx* c = t->c;
-    g_sw.read();
-    HIPCHECK(hipSetDevice(c->device));
-    Batch b = batch_of(c);
+    Batch b;
+    if (const int rc = li_begin(c, &b)) return rc;
     const uint32_t n = (uint32_t)lay.n, Kc = n_regions, Kp = t->have_prev ? (uint32_t)t->prev_id.size() : 0u;
     const int jb = tk_bits(Kp), sort_bits = tk_bits(Kc) + jb;
     if (const int rc = trk_state(t, n)) return rc;
     if (!t->h_out) { if (const int rc = trk_pinned(&t->h_out, &t->out_cap, TRK_HEAD + 3 * TRK_FIRST_CAP)) return rc; }
     size_t cap = (t->out_cap - TRK_HEAD) / 3;
     // every buffer of the update before anything is recorded
-    uint64_t *k0, *k1, *ukey; uint32_t *flag, *ustart, *uend, *out, *d_id, *cnt, *hist, *tiles, *tid = nullptr, *ul = nullptr; unsigned char* ud = nullptr;
+    uint64_t *k0, *k1, *ukey; uint32_t *flag, *ustart, *uend, *out, *d_id, *cnt, *hist, *tiles, *tid = nullptr;
     ENSURE(c->evl_k0, n, k0); ENSURE(c->evl_k1, n, k1); ENSURE(c->evl_flag, n, flag); ENSURE(c->evl_ukey, n, ukey); ENSURE(c->evl_ucnt, n, ustart); ENSURE(c->trk_end, n, uend);
     ENSURE(c->trk_out, TRK_HEAD + 3 * cap, out); ENSURE(c->trk_id, Kc ? Kc : 1u, d_id); ENSURE(c->evl_counts, 4, cnt);
     ENSURE(c->hist, (size_t)RS_BINS * ((n + RS_TILE - 1) / RS_TILE + 1), hist); ENSURE(c->tiles, (n + SCAN_TILE - 1) / SCAN_TILE + 1, tiles);
     if (!ids_on_device) ENSURE(c->trk_tid, n, tid);
-    const unsigned char* d_depth = static_cast<const unsigned char*>(depth);
-    const uint32_t* d_lab = labels;
-    if (!inputs_on_device) {      // host images go through the device's copy stream, like those of f3ds_segment_rgbd
-        ENSURE(c->img_depth, lay.depth_bytes, ud); ENSURE(c->trk_lab, n, ul);
-        hipStream_t up = g_sw.copy_stream ? copy_stream_of(c->device) : nullptr;
-        HIPCHECK(hipMemcpyAsync(ud, depth, lay.depth_bytes, hipMemcpyHostToDevice, up ? up : b.st));
-        HIPCHECK(hipMemcpyAsync(ul, labels, (size_t)n * 4, hipMemcpyHostToDevice, up ? up : b.st));
-        if (up) { if (const int urc = await_uploads(b, up)) return urc; }
-        d_depth = ud; d_lab = ul;
-    }
+    LiImages im;
+    if (const int urc = li_upload(c, b, lay, depth, nullptr, labels, inputs_on_device, &im)) return urc;
+    const unsigned char* d_depth = im.depth;
+    const uint32_t* d_lab = im.labels;
     TrackArgs a;
     memset(&a, 0, sizeof a);
     a.width = fmt.width; a.height = fmt.height; a.n = n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
@@ -2530,61 +2579,42 @@ extern "C" int f3ds_tracker_update(f3ds_tracker* t, const f3ds_rgbd_format* fmt_
 }
 
 // ------------------------------------------------------------------------------------------------
-// region table (f3ds_regions.h / .inc): one row per region of a label image over an RGB-D frame.  Three kernels in one flush --
-// d_region_init, d_region_accum (the one read of the images), d_region_finish -- then ONE download, the call's only wait: the head (counts, the bad-label
-// flag) and, for a host caller, the rows behind it (72 B per region: they ride with the head on the call's stream, not through the copy stream).  The
-// scratch is the call's own (rgt_*), so nothing another call of the context reads is touched.
+// The four region calls share the label-image frame (li_begin ... li_rows_behind, above): the images of a host caller go up through the family's staging, the
+// kernels of a call are recorded into one flush, and what goes down -- the head and, for a host caller, what rides behind it on the call's stream, not through the
+// copy stream -- is ONE download, the call's only wait in the ordinary case.  The staging (li_*) holds nothing once a call has returned; the working state between
+// a call's kernels is the call's own (rgt_acc, rgc_*, rgs_acc, rgk_*), so no call disturbs what another one of the context reads.
+//
+// region table (f3ds_regions.h / .inc): one row per region of a label image over an RGB-D frame.  Three kernels -- d_region_init,
+// d_region_accum (the one read of the images), d_region_finish; behind the head the rows of a host caller (72 B per region).
 // ------------------------------------------------------------------------------------------------
 extern "C" int f3ds_region_table(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const void* color, const uint32_t* labels, uint32_t n_regions, int inputs_on_device,
                                  f3ds_region_row* rows, int rows_on_device, f3ds_region_table_result* result) {
     if (!c) return F3DS_ERR_ARG;
     f3ds_rgbd_format fmt; f3ds::RgbdLayout lay;
     if (const int rc = rg_check(fmt_, depth, color, labels, n_regions, rows, &fmt, &lay)) return rc;
-    g_sw.read();
-    HIPCHECK(hipSetDevice(c->device));
-    Batch b = batch_of(c);
+    Batch b;
+    if (const int rc = li_begin(c, &b)) return rc;
     const uint32_t n = (uint32_t)lay.n, K = n_regions, copies = rgt_copies(K);
-    constexpr size_t HEAD_BYTES = 64;      // RGT_HEAD words, and the rows behind them 8-byte aligned
-    const size_t out_bytes = HEAD_BYTES + (rows_on_device ? 0u : (size_t)K * sizeof(f3ds_region_row));
+    const size_t row_bytes = rows_on_device ? 0u : (size_t)K * sizeof(f3ds_region_row);
     // every buffer of the call before anything is recorded
-    RgAcc* acc; unsigned char *out, *ud = nullptr, *uc = nullptr; uint32_t* ul = nullptr;
-    ENSURE(c->rgt_acc, K ? (size_t)K * copies : 1u, acc); ENSURE(c->rgt_out, out_bytes, out);
-    if (c->h_rgt_cap < out_bytes) {
-        if (c->h_rgt) { HIPCHECK(hipHostFree(c->h_rgt)); c->h_rgt = nullptr; c->h_rgt_cap = 0; }
-        HIPCHECK(hipHostMalloc(&c->h_rgt, out_bytes + out_bytes / 4, hipHostMallocDefault));
-        c->h_rgt_cap = out_bytes + out_bytes / 4;
-    }
-    const unsigned char* d_depth = static_cast<const unsigned char*>(depth);
-    const unsigned char* d_color = static_cast<const unsigned char*>(color);
-    const uint32_t* d_lab = labels;
-    if (!inputs_on_device) {      // host images go through the device's copy stream, like those of f3ds_tracker_update
-        ENSURE(c->rgt_depth, lay.depth_bytes, ud); ENSURE(c->rgt_lab, n, ul);
-        if (color) ENSURE(c->rgt_color, lay.color_bytes, uc);
-        hipStream_t up = g_sw.copy_stream ? copy_stream_of(c->device) : nullptr;
-        HIPCHECK(hipMemcpyAsync(ud, depth, lay.depth_bytes, hipMemcpyHostToDevice, up ? up : b.st));
-        if (color) HIPCHECK(hipMemcpyAsync(uc, color, lay.color_bytes, hipMemcpyHostToDevice, up ? up : b.st));
-        HIPCHECK(hipMemcpyAsync(ul, labels, (size_t)n * 4, hipMemcpyHostToDevice, up ? up : b.st));
-        if (up) { if (const int urc = await_uploads(b, up)) return urc; }
-        d_depth = ud; d_color = uc; d_lab = ul;
-    }
+    RgAcc* acc; unsigned char* out; LiImages im;
+    ENSURE(c->rgt_acc, K ? (size_t)K * copies : 1u, acc);
+    if (const int rc = li_out_buffers(c, LI_HEAD_BYTES + row_bytes, &out)) return rc;
+    if (const int rc = li_upload(c, b, lay, depth, color, labels, inputs_on_device, &im)) return rc;
     RegionArgs a;
     memset(&a, 0, sizeof a);
     a.width = fmt.width; a.n = n; a.depth_pitch = lay.depth_pitch; a.color_pitch = lay.color_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
     a.color_format = color ? fmt.color_format : -1; a.K = K; a.copies = copies;
     a.depth_scale = fmt.depth_scale; a.fx = fmt.fx; a.fy = fmt.fy; a.cx = fmt.cx; a.cy = fmt.cy;
     uint32_t* head = reinterpret_cast<uint32_t*>(out);
-    f3ds_region_row* d_rows = rows_on_device ? rows : reinterpret_cast<f3ds_region_row*>(out + HEAD_BYTES);
+    f3ds_region_row* d_rows = rows_on_device ? rows : reinterpret_cast<f3ds_region_row*>(out + LI_HEAD_BYTES);
     rec<d_region_init>(c, grid_for((size_t)K * copies * RG_WORDS, 256), 0u, reinterpret_cast<uint32_t*>(acc), K * copies, head);
-    rec<d_region_accum>(c, grid_for((n + RGT_TRIPS - 1u) / RGT_TRIPS, 256), 0u, d_depth, d_color, d_lab, a, acc, head);
+    rec<d_region_accum>(c, grid_for((n + LI_TRIPS - 1u) / LI_TRIPS, 256), 0u, im.depth, im.color, im.labels, a, acc, head);
     rec<d_region_finish>(c, grid_for(K, 256), 0u, acc, K, copies, head, d_rows);
     if (const int rc = flush(b)) return rc;
-    HIPCHECK(hipMemcpyAsync(c->h_rgt, out, out_bytes, hipMemcpyDeviceToHost, b.st));
-    HIPCHECK(timed_sync(b.st));
-    HIPCHECK(hipGetLastError());
-    uint32_t h[RGT_HEAD];
-    memcpy(h, c->h_rgt, sizeof h);
-    if (h[1]) return F3DS_ERR_ARG;      // a label >= n_regions: d_region_finish wrote no row, and none is copied out
-    if (!rows_on_device && K) memcpy(rows, c->h_rgt + HEAD_BYTES, (size_t)K * sizeof(f3ds_region_row));
+    uint32_t h[LI_HEAD_WORDS];
+    if (const int rc = li_download_head(c, b, out, row_bytes, h)) return rc;      // (a label >= n_regions: d_region_finish wrote no row)
+    if (row_bytes) memcpy(rows, c->h_li + LI_HEAD_BYTES, row_bytes);
     if (result) {
         result->n_regions = K; result->n_nonempty = h[0];
         memcpy(&result->n_labelled, h + 2, 8); memcpy(&result->n_clamped, h + 4, 8);
@@ -2593,67 +2623,49 @@ extern "C" int f3ds_region_table(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, cons
 }
 
 // ------------------------------------------------------------------------------------------------
-// region contacts (f3ds_contacts.h / .inc): one row per pair of regions of a label image that touch.  One flush -- d_contact_init,
-// d_contact_accum (the one pass over the images: records of (pair, seven words)), the radix sort of the record keys, d_evl_heads / scan, d_track_runs,
-// d_contact_finish -- then ONE download, the call's only wait in the ordinary case: the head (row count, the bad-label flag, the records asked for, the sums) and,
-// for a host caller, the first RGC_FIRST_ROWS rows behind it.  A frame with more records than the first buffer holds says so in the head and runs once more
-// with room for all (every contact pair a record of its own: fewer than 2n); a host caller with more rows gets the rest in a second download.  The scratch is
-// the call's own (rgc_*) but for the sort's histogram and the scan's tile sums, which hold nothing between calls.
+// region contacts (f3ds_contacts.h / .inc): one row per pair of regions of a label image that touch.  d_contact_init, d_contact_accum
+// (the one pass over the images: records of (pair, seven words)), the radix sort of the record keys, d_evl_heads / scan, d_track_runs, d_contact_finish; behind
+// the head (row count, the bad-label flag, the records asked for, the sums) the first RGC_FIRST_ROWS rows of a host caller.  A frame with more records than the
+// first buffer holds says so in the head and runs once more with room for all (every contact pair a record of its own: fewer than 2n); a host caller with
+// more rows gets the rest in a second download.  Beside rgc_* the call uses the sort's histogram and the scan's tile sums, which hold nothing between calls.
 // ------------------------------------------------------------------------------------------------
 extern "C" int f3ds_region_contacts(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, float depth_tol,
                                     int inputs_on_device, f3ds_region_contact* rows, size_t cap, int rows_on_device, size_t* n_out, f3ds_region_contacts_result* result) {
     if (!c) return F3DS_ERR_ARG;
     f3ds_rgbd_format fmt; f3ds::RgbdLayout lay;
     if (const int rc = ct_check(fmt_, depth, labels, n_regions, depth_tol, n_out, &fmt, &lay)) return rc;
-    g_sw.read();
-    HIPCHECK(hipSetDevice(c->device));
-    Batch b = batch_of(c);
+    Batch b;
+    if (const int rc = li_begin(c, &b)) return rc;
     const uint32_t n = (uint32_t)lay.n, K = n_regions;
     const uint32_t rec_all = 2u * n;      // (n < 2^31: rgbd_layout)  every contact pair a record of its own is fewer than this
     const uint32_t first = g_sw.rgc_first_cap ? g_sw.rgc_first_cap : RGC_FIRST_CAP;
     uint32_t rec_cap = first < rec_all ? first : rec_all;
-    constexpr size_t HEAD_BYTES = 64;      // RGC_HEAD words, and the rows behind them 8-byte aligned
     const bool host_rows = rows && !rows_on_device;
-    const unsigned char* d_depth = static_cast<const unsigned char*>(depth);
-    const uint32_t* d_lab = labels;
-    if (!inputs_on_device) {      // host images go through the device's copy stream, like those of f3ds_region_table
-        unsigned char* ud; uint32_t* ul;
-        ENSURE(c->rgc_depth, lay.depth_bytes, ud); ENSURE(c->rgc_lab, n, ul);
-        hipStream_t up = g_sw.copy_stream ? copy_stream_of(c->device) : nullptr;
-        HIPCHECK(hipMemcpyAsync(ud, depth, lay.depth_bytes, hipMemcpyHostToDevice, up ? up : b.st));
-        HIPCHECK(hipMemcpyAsync(ul, labels, (size_t)n * 4, hipMemcpyHostToDevice, up ? up : b.st));
-        if (up) { if (const int urc = await_uploads(b, up)) return urc; }
-        d_depth = ud; d_lab = ul;
-    }
+    LiImages im;
+    if (const int rc = li_upload(c, b, lay, depth, nullptr, labels, inputs_on_device, &im)) return rc;
     ContactArgs a;
     memset(&a, 0, sizeof a);
     a.width = fmt.width; a.height = fmt.height; a.n = n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
     a.K = K; a.kb = ct_bits(K); a.depth_scale = fmt.depth_scale; a.depth_tol = depth_tol;
     const uint64_t hole = ct_hole(K, a.kb);
     const int sort_bits = ct_sort_bits(K);
-    uint32_t h[RGC_HEAD];
-    size_t stage_rows = 0;
+    uint32_t h[LI_HEAD_WORDS];
     unsigned char* out = nullptr;
     for (int run = 0;; ++run) {
         a.rec_cap = rec_cap;
-        stage_rows = host_rows ? (cap < rec_cap ? cap : (size_t)rec_cap) : 0u;      // (rows <= records <= rec_cap)
-        const size_t out_bytes = HEAD_BYTES + stage_rows * sizeof(f3ds_region_contact);
+        const size_t stage_rows = host_rows ? (cap < rec_cap ? cap : (size_t)rec_cap) : 0u;      // (rows <= records <= rec_cap)
         // every buffer of the run before anything is recorded
         uint64_t *k0, *k1, *ukey; uint32_t *v0, *v1, *rec_words, *flag, *ustart, *uend, *cnt, *hist, *tiles;
         ENSURE(c->rgc_k0, rec_cap, k0); ENSURE(c->rgc_k1, rec_cap, k1); ENSURE(c->rgc_v0, rec_cap, v0); ENSURE(c->rgc_v1, rec_cap, v1);
         ENSURE(c->rgc_rec, (size_t)rec_cap * CT_WORDS, rec_words); ENSURE(c->rgc_flag, rec_cap, flag); ENSURE(c->rgc_ukey, rec_cap, ukey);
-        ENSURE(c->rgc_ustart, rec_cap, ustart); ENSURE(c->rgc_uend, rec_cap, uend); ENSURE(c->rgc_cnt, 4, cnt); ENSURE(c->rgc_out, out_bytes, out);
+        ENSURE(c->rgc_ustart, rec_cap, ustart); ENSURE(c->rgc_uend, rec_cap, uend); ENSURE(c->rgc_cnt, 4, cnt);
         ENSURE(c->hist, (size_t)RS_BINS * ((rec_cap + RS_TILE - 1) / RS_TILE + 1), hist); ENSURE(c->tiles, (rec_cap + SCAN_TILE - 1) / SCAN_TILE + 1, tiles);
-        if (c->h_rgc_cap < out_bytes) {
-            if (c->h_rgc) { HIPCHECK(hipHostFree(c->h_rgc)); c->h_rgc = nullptr; c->h_rgc_cap = 0; }
-            HIPCHECK(hipHostMalloc(&c->h_rgc, out_bytes + out_bytes / 4, hipHostMallocDefault));
-            c->h_rgc_cap = out_bytes + out_bytes / 4;
-        }
-        uint32_t* head = reinterpret_cast<uint32_t*>(out);
-        f3ds_region_contact* d_rows = rows_on_device ? rows : (host_rows ? reinterpret_cast<f3ds_region_contact*>(out + HEAD_BYTES) : nullptr);
         int rc;
+        if ((rc = li_out_buffers(c, LI_HEAD_BYTES + stage_rows * sizeof(f3ds_region_contact), &out))) return rc;
+        uint32_t* head = reinterpret_cast<uint32_t*>(out);
+        f3ds_region_contact* d_rows = rows_on_device ? rows : (host_rows ? reinterpret_cast<f3ds_region_contact*>(out + LI_HEAD_BYTES) : nullptr);
         rec<d_contact_init>(c, grid_for(rec_cap, 256), 0u, k0, v0, rec_cap, head);
-        rec<d_contact_accum>(c, grid_for((n + RGC_TRIPS - 1u) / RGC_TRIPS, 256), 0u, d_depth, d_lab, a, k0, rec_words, head);
+        rec<d_contact_accum>(c, grid_for((n + RGC_TRIPS - 1u) / RGC_TRIPS, 256), 0u, im.depth, im.labels, a, k0, rec_words, head);
         uint64_t* ks; uint32_t* vs;
         if ((rc = radix_sort(c, k0, v0, k1, v1, rec_cap, sort_bits, &ks, &vs))) return rc;
         rec<d_evl_heads>(c, grid_for(rec_cap, 256), 0u, ks, rec_cap, hole, flag);
@@ -2662,11 +2674,7 @@ extern "C" int f3ds_region_contacts(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, c
         rec<d_contact_finish>(c, grid_for((size_t)(rec_cap < 8192u ? rec_cap : 8192u) * 64u, 256), 0u, ukey, ustart, uend, cnt, vs, rec_words, a.kb, rec_cap, head, d_rows, (uint64_t)cap);
         if ((rc = flush(b))) return rc;
         const size_t first_rows = stage_rows < RGC_FIRST_ROWS ? stage_rows : (size_t)RGC_FIRST_ROWS;
-        HIPCHECK(hipMemcpyAsync(c->h_rgc, out, HEAD_BYTES + first_rows * sizeof(f3ds_region_contact), hipMemcpyDeviceToHost, b.st));
-        HIPCHECK(timed_sync(b.st));
-        HIPCHECK(hipGetLastError());
-        memcpy(h, c->h_rgc, sizeof h);
-        if (h[1]) return F3DS_ERR_ARG;      // a label >= n_regions: d_contact_finish wrote no row, and nothing is copied out
+        if ((rc = li_download_head(c, b, out, first_rows * sizeof(f3ds_region_contact), h))) return rc;      // (a label >= n_regions: d_contact_finish wrote no row)
         if (h[2] <= rec_cap) break;
         if (run || rec_cap >= rec_all) return F3DS_ERR_LOGIC;
         rec_cap = rec_all;      // (rare: more records than the first buffer holds)
@@ -2677,70 +2685,43 @@ extern "C" int f3ds_region_contacts(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, c
     if (result) { result->n_regions = K; result->n_contacts = h[0]; memcpy(&result->n_pairs, h + 4, 8); memcpy(&result->n_close, h + 6, 8); }
     if (!rows) return F3DS_OK;
     if (cap < count) return F3DS_ERR_CAPACITY;
-    if (host_rows && count) {
-        if (count > RGC_FIRST_ROWS) {      // (rare: the rows behind the first download)
-            const size_t off = HEAD_BYTES + (size_t)RGC_FIRST_ROWS * sizeof(f3ds_region_contact);
-            HIPCHECK(hipMemcpyAsync(c->h_rgc + off, out + off, (count - RGC_FIRST_ROWS) * sizeof(f3ds_region_contact), hipMemcpyDeviceToHost, b.st));
-            HIPCHECK(timed_sync(b.st));
-        }
-        memcpy(rows, c->h_rgc + HEAD_BYTES, count * sizeof(f3ds_region_contact));
-    }
+    if (host_rows && count) return li_rows_behind(c, b, out, LI_HEAD_BYTES, sizeof(f3ds_region_contact), count, RGC_FIRST_ROWS, rows);
     return F3DS_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
 // region shapes (f3ds_shapes.h / .inc): one row per region of a label image over a depth image -- covariance, eigenvalues, plane and long
-// axis.  The call has the region table's shape: three kernels in one flush -- d_shape_init, d_shape_accum (the one read of the image and the labels),
-// d_shape_finish -- then ONE download, the call's only wait: the head (counts, the bad-label flag) and, for a host caller, the rows behind it (84 B per
-// region).  The scratch is the call's own (rgs_*), so nothing another call of the context reads is touched.
+// axis.  The call has the region table's shape: d_shape_init, d_shape_accum (the one read of the image and the labels), d_shape_finish; behind the head the
+// rows of a host caller (84 B per region).
 // ------------------------------------------------------------------------------------------------
 extern "C" int f3ds_region_shapes(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, int inputs_on_device,
                                   f3ds_region_shape* rows, int rows_on_device, f3ds_region_shapes_result* result) {
     if (!c) return F3DS_ERR_ARG;
     f3ds_rgbd_format fmt; f3ds::RgbdLayout lay;
     if (const int rc = sh_check(fmt_, depth, labels, n_regions, rows, &fmt, &lay)) return rc;
-    g_sw.read();
-    HIPCHECK(hipSetDevice(c->device));
-    Batch b = batch_of(c);
+    Batch b;
+    if (const int rc = li_begin(c, &b)) return rc;
     const uint32_t n = (uint32_t)lay.n, K = n_regions, copies = rgt_copies(K);
-    constexpr size_t HEAD_BYTES = 64;      // RGS_HEAD words, and the rows behind them 8-byte aligned
-    const size_t out_bytes = HEAD_BYTES + (rows_on_device ? 0u : (size_t)K * sizeof(f3ds_region_shape));
+    const size_t row_bytes = rows_on_device ? 0u : (size_t)K * sizeof(f3ds_region_shape);
     // every buffer of the call before anything is recorded
-    ShAcc* acc; unsigned char *out, *ud = nullptr; uint32_t* ul = nullptr;
-    ENSURE(c->rgs_acc, K ? (size_t)K * copies : 1u, acc); ENSURE(c->rgs_out, out_bytes, out);
-    if (c->h_rgs_cap < out_bytes) {
-        if (c->h_rgs) { HIPCHECK(hipHostFree(c->h_rgs)); c->h_rgs = nullptr; c->h_rgs_cap = 0; }
-        HIPCHECK(hipHostMalloc(&c->h_rgs, out_bytes + out_bytes / 4, hipHostMallocDefault));
-        c->h_rgs_cap = out_bytes + out_bytes / 4;
-    }
-    const unsigned char* d_depth = static_cast<const unsigned char*>(depth);
-    const uint32_t* d_lab = labels;
-    if (!inputs_on_device) {      // host images go through the device's copy stream, like those of f3ds_region_table
-        ENSURE(c->rgs_depth, lay.depth_bytes, ud); ENSURE(c->rgs_lab, n, ul);
-        hipStream_t up = g_sw.copy_stream ? copy_stream_of(c->device) : nullptr;
-        HIPCHECK(hipMemcpyAsync(ud, depth, lay.depth_bytes, hipMemcpyHostToDevice, up ? up : b.st));
-        HIPCHECK(hipMemcpyAsync(ul, labels, (size_t)n * 4, hipMemcpyHostToDevice, up ? up : b.st));
-        if (up) { if (const int urc = await_uploads(b, up)) return urc; }
-        d_depth = ud; d_lab = ul;
-    }
+    ShAcc* acc; unsigned char* out; LiImages im;
+    ENSURE(c->rgs_acc, K ? (size_t)K * copies : 1u, acc);
+    if (const int rc = li_out_buffers(c, LI_HEAD_BYTES + row_bytes, &out)) return rc;
+    if (const int rc = li_upload(c, b, lay, depth, nullptr, labels, inputs_on_device, &im)) return rc;
     ShapeArgs a;
     memset(&a, 0, sizeof a);
     a.width = fmt.width; a.n = n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
     a.K = K; a.copies = copies;
     a.depth_scale = fmt.depth_scale; a.fx = fmt.fx; a.fy = fmt.fy; a.cx = fmt.cx; a.cy = fmt.cy;
     uint32_t* head = reinterpret_cast<uint32_t*>(out);
-    f3ds_region_shape* d_rows = rows_on_device ? rows : reinterpret_cast<f3ds_region_shape*>(out + HEAD_BYTES);
+    f3ds_region_shape* d_rows = rows_on_device ? rows : reinterpret_cast<f3ds_region_shape*>(out + LI_HEAD_BYTES);
     rec<d_shape_init>(c, grid_for((size_t)K * copies * SH_WORDS, 256), 0u, reinterpret_cast<uint32_t*>(acc), K * copies, head);
-    rec<d_shape_accum>(c, grid_for((n + RGS_TRIPS - 1u) / RGS_TRIPS, 256), 0u, d_depth, d_lab, a, acc, head);
+    rec<d_shape_accum>(c, grid_for((n + LI_TRIPS - 1u) / LI_TRIPS, 256), 0u, im.depth, im.labels, a, acc, head);
     rec<d_shape_finish>(c, grid_for(K, 256), 0u, acc, K, copies, head, d_rows);
     if (const int rc = flush(b)) return rc;
-    HIPCHECK(hipMemcpyAsync(c->h_rgs, out, out_bytes, hipMemcpyDeviceToHost, b.st));
-    HIPCHECK(timed_sync(b.st));
-    HIPCHECK(hipGetLastError());
-    uint32_t h[RGS_HEAD];
-    memcpy(h, c->h_rgs, sizeof h);
-    if (h[1]) return F3DS_ERR_ARG;      // a label >= n_regions: d_shape_finish wrote no row, and none is copied out
-    if (!rows_on_device && K) memcpy(rows, c->h_rgs + HEAD_BYTES, (size_t)K * sizeof(f3ds_region_shape));
+    uint32_t h[LI_HEAD_WORDS];
+    if (const int rc = li_download_head(c, b, out, row_bytes, h)) return rc;      // (a label >= n_regions: d_shape_finish wrote no row)
+    if (row_bytes) memcpy(rows, c->h_li + LI_HEAD_BYTES, row_bytes);
     if (result) {
         result->n_regions = K; result->n_nonempty = h[0];
         memcpy(&result->n_labelled, h + 2, 8); memcpy(&result->n_clamped, h + 4, 8);
@@ -2750,10 +2731,9 @@ extern "C" int f3ds_region_shapes(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, con
 
 // ------------------------------------------------------------------------------------------------
 // region components (f3ds_components.h / .inc): the connected components of a label image over a depth image, as a label image and one
-// row per component.  One flush -- the head's zeros, d_comp_local (the one read of the images: tiles resolved in LDS), d_comp_seam, d_comp_flatten,
-// d_comp_flag, the scan of the flags, d_comp_write -- then ONE download, the call's only wait in the ordinary case: the head (counts, the bad-label flag) and,
-// for a host caller, the image and the first RGK_FIRST_ROWS rows behind it; a host caller with more rows gets the rest in a second download.  The scratch is
-// the call's own (rgk_*: twelve bytes per pixel) but for the scan's tile sums, which hold nothing between calls.
+// row per component.  The head's zeros, d_comp_local (the one read of the images: tiles resolved in LDS), d_comp_seam, d_comp_flatten, d_comp_flag, the scan
+// of the flags, d_comp_write; behind the head the image and the first RGK_FIRST_ROWS rows of a host caller, who gets further rows in a second download.
+// Beside rgk_* (twelve bytes per pixel) the call uses the scan's tile sums, which hold nothing between calls.
 // ------------------------------------------------------------------------------------------------
 extern "C" int f3ds_region_components(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, const f3ds_component_params* params,
                                       int inputs_on_device, uint32_t* comp_labels, f3ds_region_component* rows, size_t cap, int outputs_on_device, size_t* n_out,
@@ -2761,60 +2741,41 @@ extern "C" int f3ds_region_components(f3ds_ctx* c, const f3ds_rgbd_format* fmt_,
     if (!c) return F3DS_ERR_ARG;
     f3ds_rgbd_format fmt; f3ds::RgbdLayout lay; f3ds_component_params prm;
     if (const int rc = cc_check(fmt_, depth, labels, n_regions, params, comp_labels, n_out, &fmt, &lay, &prm)) return rc;
-    g_sw.read();
-    HIPCHECK(hipSetDevice(c->device));
-    Batch b = batch_of(c);
+    Batch b;
+    if (const int rc = li_begin(c, &b)) return rc;
     const uint32_t n = (uint32_t)lay.n, K = n_regions;
-    constexpr size_t HEAD_BYTES = 64;      // RGK_HEAD words, and what follows 8-byte aligned
     const bool host_out = !outputs_on_device, host_rows = rows && host_out;
     const size_t image_bytes = host_out ? (size_t)n * 4 : 0u;
     const size_t stage_rows = host_rows ? (cap < n ? cap : (size_t)n) : 0u;      // (components <= pixels)
-    const size_t out_bytes = HEAD_BYTES + image_bytes + stage_rows * sizeof(f3ds_region_component);
+    const size_t rows_at = LI_HEAD_BYTES + image_bytes;
     // every buffer of the call before anything is recorded
-    uint32_t *parent, *cnt, *flag, *ul = nullptr; unsigned char *out, *ud = nullptr;
-    ENSURE(c->rgk_parent, n, parent); ENSURE(c->rgk_cnt, n, cnt); ENSURE(c->rgk_flag, n, flag); ENSURE(c->rgk_out, out_bytes, out);
-    if (c->h_rgk_cap < out_bytes) {
-        if (c->h_rgk) { HIPCHECK(hipHostFree(c->h_rgk)); c->h_rgk = nullptr; c->h_rgk_cap = 0; }
-        HIPCHECK(hipHostMalloc(&c->h_rgk, out_bytes + out_bytes / 4, hipHostMallocDefault));
-        c->h_rgk_cap = out_bytes + out_bytes / 4;
-    }
-    const unsigned char* d_depth = static_cast<const unsigned char*>(depth);
-    const uint32_t* d_lab = labels;
-    if (!inputs_on_device) {      // host images go through the device's copy stream, like those of f3ds_region_table
-        ENSURE(c->rgk_depth, lay.depth_bytes, ud); ENSURE(c->rgk_lab, n, ul);
-        hipStream_t up = g_sw.copy_stream ? copy_stream_of(c->device) : nullptr;
-        HIPCHECK(hipMemcpyAsync(ud, depth, lay.depth_bytes, hipMemcpyHostToDevice, up ? up : b.st));
-        HIPCHECK(hipMemcpyAsync(ul, labels, (size_t)n * 4, hipMemcpyHostToDevice, up ? up : b.st));
-        if (up) { if (const int urc = await_uploads(b, up)) return urc; }
-        d_depth = ud; d_lab = ul;
-    }
+    uint32_t *parent, *cnt, *flag; unsigned char* out; LiImages im;
+    ENSURE(c->rgk_parent, n, parent); ENSURE(c->rgk_cnt, n, cnt); ENSURE(c->rgk_flag, n, flag);
+    if (const int rc = li_out_buffers(c, rows_at + stage_rows * sizeof(f3ds_region_component), &out)) return rc;
+    if (const int rc = li_upload(c, b, lay, depth, nullptr, labels, inputs_on_device, &im)) return rc;
     CompArgs a;
     memset(&a, 0, sizeof a);
     a.width = fmt.width; a.height = fmt.height; a.n = n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
     a.K = K; a.min_pixels = prm.min_pixels; a.tiles_x = (fmt.width + CC_TILE_W - 1u) / CC_TILE_W; a.tiles_y = (fmt.height + CC_TILE_H - 1u) / CC_TILE_H;
     a.depth_scale = fmt.depth_scale; a.depth_tol = prm.depth_tol;
     uint32_t* head = reinterpret_cast<uint32_t*>(out);
-    uint32_t* d_comp = host_out ? reinterpret_cast<uint32_t*>(out + HEAD_BYTES) : comp_labels;
-    f3ds_region_component* d_rows = !rows ? nullptr : (host_out ? reinterpret_cast<f3ds_region_component*>(out + HEAD_BYTES + image_bytes) : rows);
+    uint32_t* d_comp = host_out ? reinterpret_cast<uint32_t*>(out + LI_HEAD_BYTES) : comp_labels;
+    f3ds_region_component* d_rows = !rows ? nullptr : (host_out ? reinterpret_cast<f3ds_region_component*>(out + rows_at) : rows);
     const size_t seams = (size_t)(a.tiles_x - 1u) * fmt.height + (size_t)(a.tiles_y - 1u) * fmt.width;
-    rec_fill(c, head, 0u, HEAD_BYTES);
-    rec<d_comp_local>(c, grid_for((size_t)a.tiles_x * a.tiles_y, 1), 0u, d_depth, d_lab, a, parent, cnt, head);
-    rec<d_comp_seam>(c, grid_for(seams, 256), 0u, d_depth, d_lab, a, parent);
+    rec_fill(c, head, 0u, LI_HEAD_BYTES);
+    rec<d_comp_local>(c, grid_for((size_t)a.tiles_x * a.tiles_y, 1), 0u, im.depth, im.labels, a, parent, cnt, head);
+    rec<d_comp_seam>(c, grid_for(seams, 256), 0u, im.depth, im.labels, a, parent);
     rec<d_comp_flatten>(c, grid_for(n, 256), 0u, n, parent, cnt);
     rec<d_comp_flag>(c, grid_for(n, 256), 0u, n, parent, cnt, a.min_pixels, flag, head);
     if (const int rc = scan_u32(c, flag, flag, n)) return rc;
-    rec<d_comp_write>(c, grid_for(n, 256), 0u, n, d_lab, parent, cnt, flag, a.min_pixels, head, d_comp, d_rows, (uint64_t)cap);
+    rec<d_comp_write>(c, grid_for(n, 256), 0u, n, im.labels, parent, cnt, flag, a.min_pixels, head, d_comp, d_rows, (uint64_t)cap);
     if (const int rc = flush(b)) return rc;
     const size_t first_rows = stage_rows < RGK_FIRST_ROWS ? stage_rows : (size_t)RGK_FIRST_ROWS;
-    HIPCHECK(hipMemcpyAsync(c->h_rgk, out, HEAD_BYTES + image_bytes + first_rows * sizeof(f3ds_region_component), hipMemcpyDeviceToHost, b.st));
-    HIPCHECK(timed_sync(b.st));
-    HIPCHECK(hipGetLastError());
-    uint32_t h[RGK_HEAD];
-    memcpy(h, c->h_rgk, sizeof h);
-    if (h[1]) return F3DS_ERR_ARG;      // a label >= n_regions: d_comp_write wrote nothing, and nothing is copied out
+    uint32_t h[LI_HEAD_WORDS];
+    if (const int rc = li_download_head(c, b, out, image_bytes + first_rows * sizeof(f3ds_region_component), h)) return rc;      // (a label >= n_regions: d_comp_write wrote nothing)
     const size_t count = h[0];
     if (count > n) return F3DS_ERR_LOGIC;
-    if (host_out) memcpy(comp_labels, c->h_rgk + HEAD_BYTES, image_bytes);
+    if (host_out) memcpy(comp_labels, c->h_li + LI_HEAD_BYTES, image_bytes);
     *n_out = count;
     if (result) {
         result->n_regions = K; result->n_components = h[0]; result->n_dropped = h[2]; result->reserved = 0u;
@@ -2822,14 +2783,6 @@ extern "C" int f3ds_region_components(f3ds_ctx* c, const f3ds_rgbd_format* fmt_,
     }
     if (!rows) return F3DS_OK;
     if (cap < count) return F3DS_ERR_CAPACITY;
-    if (host_rows && count) {
-        const size_t rows_at = HEAD_BYTES + image_bytes;
-        if (count > RGK_FIRST_ROWS) {      // (rare: the rows behind the first download)
-            const size_t off = rows_at + (size_t)RGK_FIRST_ROWS * sizeof(f3ds_region_component);
-            HIPCHECK(hipMemcpyAsync(c->h_rgk + off, out + off, (count - RGK_FIRST_ROWS) * sizeof(f3ds_region_component), hipMemcpyDeviceToHost, b.st));
-            HIPCHECK(timed_sync(b.st));
-        }
-        memcpy(rows, c->h_rgk + rows_at, count * sizeof(f3ds_region_component));
-    }
+    if (host_rows && count) return li_rows_behind(c, b, out, rows_at, sizeof(f3ds_region_component), count, RGK_FIRST_ROWS, rows);
     return F3DS_OK;
 }

@@ -18,6 +18,7 @@
 #include "f3ds_dev.h"
 #include "f3ds_numerics.h"
 #include "f3ds_rgbd.h"
+#include "f3ds_label_image.h"
 #include "f3ds_track.h"
 #include "f3ds_regions.h"
 #include "f3ds_contacts.h"
@@ -181,25 +182,22 @@ int f3ds_track_assign(const f3ds_track_params* params, const uint32_t* size, uin
 }
 
 // ---- region table: the definition (the rules are in f3ds_regions.h, which d_region_accum and d_region_finish call too) ----
-// Two passes: the labels are checked before a row is written.  Pixels are read with memcpy, as in f3ds_deproject.
+// Two passes: the labels are checked before a row is written.
 int f3ds_region_table_host(const f3ds_rgbd_format* fmt_, const void* depth, const void* color, const uint32_t* labels, uint32_t n_regions, f3ds_region_row* rows,
                            f3ds_region_table_result* result) {
     f3ds_rgbd_format fmt; f3ds::RgbdLayout l;
     if (const int rc = f3ds::rg_check(fmt_, depth, color, labels, n_regions, rows, &fmt, &l)) return rc;
-    for (size_t p = 0; p < l.n; ++p) if (labels[p] != F3DS_NO_LABEL && labels[p] >= n_regions) return F3DS_ERR_ARG;
+    if (!f3ds::li_labels_in_range(labels, l.n, n_regions)) return F3DS_ERR_ARG;
     std::vector<f3ds::RgAcc> acc(n_regions);
     for (f3ds::RgAcc& a : acc) f3ds::rg_empty(a);
-    const unsigned char* dimg = static_cast<const unsigned char*>(depth);
     const unsigned char* cimg = static_cast<const unsigned char*>(color);
     uint64_t n_labelled = 0, n_clamped = 0;
     for (uint32_t v = 0; v < fmt.height; ++v) {
-        const unsigned char* drow = dimg + (size_t)v * l.depth_pitch;
         const unsigned char* crow = cimg ? cimg + (size_t)v * l.color_pitch : nullptr;
         for (uint32_t u = 0; u < fmt.width; ++u) {
             const uint32_t p = v * fmt.width + u, lab = labels[p];
-            float z = 0.0f; bool valid;
-            if (fmt.depth_type == F3DS_DEPTH_F32) { float d; memcpy(&d, drow + 4u * (size_t)u, 4); valid = f3ds::n_depth_to_z(d, fmt.depth_scale, z); }
-            else { uint16_t d; memcpy(&d, drow + 2u * (size_t)u, 2); valid = f3ds::n_depth_to_z(d, fmt.depth_scale, z); }
+            float z = 0.0f;
+            const bool valid = f3ds::li_read_depth(fmt, l, depth, u, v, z);
             if (!valid || lab == F3DS_NO_LABEL) continue;
             uint32_t rgba = 0u;
             if (crow) {
@@ -227,14 +225,9 @@ int f3ds_region_contacts_host(const f3ds_rgbd_format* fmt_, const void* depth, c
                               size_t cap, size_t* n_out, f3ds_region_contacts_result* result) {
     f3ds_rgbd_format fmt; f3ds::RgbdLayout l;
     if (const int rc = f3ds::ct_check(fmt_, depth, labels, n_regions, depth_tol, n_out, &fmt, &l)) return rc;
-    for (size_t p = 0; p < l.n; ++p) if (labels[p] != F3DS_NO_LABEL && labels[p] >= n_regions) return F3DS_ERR_ARG;
-    const unsigned char* dimg = static_cast<const unsigned char*>(depth);
+    if (!f3ds::li_labels_in_range(labels, l.n, n_regions)) return F3DS_ERR_ARG;
     auto pixel = [&](uint32_t u, uint32_t v, float& z) {      // labelled?
-        const unsigned char* q = dimg + (size_t)v * l.depth_pitch;
-        bool valid;
-        if (fmt.depth_type == F3DS_DEPTH_F32) { float d; memcpy(&d, q + 4u * (size_t)u, 4); valid = f3ds::n_depth_to_z(d, fmt.depth_scale, z); }
-        else { uint16_t d; memcpy(&d, q + 2u * (size_t)u, 2); valid = f3ds::n_depth_to_z(d, fmt.depth_scale, z); }
-        return valid && labels[(size_t)v * fmt.width + u] != F3DS_NO_LABEL;
+        return f3ds::li_read_depth(fmt, l, depth, u, v, z) && labels[(size_t)v * fmt.width + u] != F3DS_NO_LABEL;
     };
     const int kb = f3ds::ct_bits(n_regions);
     std::map<uint64_t, f3ds::CtAcc> acc;
@@ -267,23 +260,20 @@ int f3ds_region_contacts_host(const f3ds_rgbd_format* fmt_, const void* depth, c
 }
 
 // ---- region shapes: the definition (the rules are in f3ds_shapes.h, which d_shape_accum and d_shape_finish call too) ----
-// Two passes: the labels are checked before a row is written.  Pixels are read with memcpy, as in f3ds_deproject.
+// Two passes: the labels are checked before a row is written.
 int f3ds_region_shapes_host(const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, f3ds_region_shape* rows,
                             f3ds_region_shapes_result* result) {
     f3ds_rgbd_format fmt; f3ds::RgbdLayout l;
     if (const int rc = f3ds::sh_check(fmt_, depth, labels, n_regions, rows, &fmt, &l)) return rc;
-    for (size_t p = 0; p < l.n; ++p) if (labels[p] != F3DS_NO_LABEL && labels[p] >= n_regions) return F3DS_ERR_ARG;
+    if (!f3ds::li_labels_in_range(labels, l.n, n_regions)) return F3DS_ERR_ARG;
     std::vector<f3ds::ShAcc> acc(n_regions);
     for (f3ds::ShAcc& a : acc) f3ds::sh_empty(a);
-    const unsigned char* dimg = static_cast<const unsigned char*>(depth);
     uint64_t n_labelled = 0, n_clamped = 0;
     for (uint32_t v = 0; v < fmt.height; ++v) {
-        const unsigned char* drow = dimg + (size_t)v * l.depth_pitch;
         for (uint32_t u = 0; u < fmt.width; ++u) {
             const uint32_t lab = labels[(size_t)v * fmt.width + u];
-            float z = 0.0f; bool valid;
-            if (fmt.depth_type == F3DS_DEPTH_F32) { float d; memcpy(&d, drow + 4u * (size_t)u, 4); valid = f3ds::n_depth_to_z(d, fmt.depth_scale, z); }
-            else { uint16_t d; memcpy(&d, drow + 2u * (size_t)u, 2); valid = f3ds::n_depth_to_z(d, fmt.depth_scale, z); }
+            float z = 0.0f;
+            const bool valid = f3ds::li_read_depth(fmt, l, depth, u, v, z);
             if (!valid || lab == F3DS_NO_LABEL) continue;
             float x, y, zo;
             f3ds::n_deproject(u, v, valid, z, fmt.fx, fmt.fy, fmt.cx, fmt.cy, x, y, zo);
@@ -311,20 +301,15 @@ int cc_frame(const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* la
              const size_t* n_out, CcFrame& f) {
     f3ds::RgbdLayout l;
     if (const int rc = f3ds::cc_check(fmt_, depth, labels, n_regions, params, comp_labels, n_out, &f.fmt, &l, &f.prm)) return rc;
-    for (size_t p = 0; p < l.n; ++p) if (labels[p] != F3DS_NO_LABEL && labels[p] >= n_regions) return F3DS_ERR_ARG;
+    if (!f3ds::li_labels_in_range(labels, l.n, n_regions)) return F3DS_ERR_ARG;
     f.w = f.fmt.width; f.h = f.fmt.height; f.n = (uint32_t)l.n;
     f.lab.assign(l.n, f3ds::CC_NONE); f.z.assign(l.n, 0.0f);
-    const unsigned char* dimg = static_cast<const unsigned char*>(depth);
-    for (uint32_t v = 0; v < f.h; ++v) {
-        const unsigned char* drow = dimg + (size_t)v * l.depth_pitch;
+    for (uint32_t v = 0; v < f.h; ++v)
         for (uint32_t u = 0; u < f.w; ++u) {
-            float z = 0.0f; bool valid;
-            if (f.fmt.depth_type == F3DS_DEPTH_F32) { float d; memcpy(&d, drow + 4u * (size_t)u, 4); valid = f3ds::n_depth_to_z(d, f.fmt.depth_scale, z); }
-            else { uint16_t d; memcpy(&d, drow + 2u * (size_t)u, 2); valid = f3ds::n_depth_to_z(d, f.fmt.depth_scale, z); }
+            float z = 0.0f;
             const size_t p = (size_t)v * f.w + u;
-            if (valid && labels[p] != F3DS_NO_LABEL) { f.lab[p] = labels[p]; f.z[p] = z; }
+            if (f3ds::li_read_depth(f.fmt, l, depth, u, v, z) && labels[p] != F3DS_NO_LABEL) { f.lab[p] = labels[p]; f.z[p] = z; }
         }
-    }
     return F3DS_OK;
 }
 // the outputs of both, from the image and the rows of the kept components in order

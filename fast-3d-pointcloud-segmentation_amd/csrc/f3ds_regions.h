@@ -19,11 +19,12 @@
 #include "../../include/f3ds.h"
 #include "f3ds_math.h"
 #include "f3ds_rgbd.h"
+#include "f3ds_label_image.h"
 
 namespace f3ds {
 
 constexpr uint32_t RG_NONE = 0xFFFFFFFFu;         // F3DS_NO_LABEL; the empty first_pixel, u_min, v_min
-constexpr uint32_t RG_MAX_REGIONS = 0x00FFFFFFu;  // as the tracker's
+constexpr uint32_t RG_MAX_REGIONS = LI_MAX_REGIONS;
 constexpr uint32_t RG_QNAN = 0x7FC00000u;
 constexpr uint32_t RG_KEY_POS_INF = 0xFF800000u;  // rg_key(+inf): the empty minimum
 constexpr uint32_t RG_KEY_NEG_INF = 0x007FFFFFu;  // rg_key(-inf): the empty maximum
@@ -90,15 +91,11 @@ F3DS_HD void rg_finish(const RgAcc& a, f3ds_region_row* row) {
     *row = r;
 }
 
-// What both entry points refuse before they look at a pixel, in this order; *use = the format they work with (the colour fields neutral without a colour image).
+// What both entry points refuse before they look at a pixel: missing rows, then li_check; *use = the format they work with.
 inline int rg_check(const f3ds_rgbd_format* fmt, const void* depth, const void* color, const uint32_t* labels, uint32_t n_regions, const f3ds_region_row* rows,
                     f3ds_rgbd_format* use, RgbdLayout* lay) {
-    if (!fmt || !depth || !labels || (!rows && n_regions)) return F3DS_ERR_ARG;
-    *use = *fmt;
-    if (!color) { use->color_format = F3DS_COLOR_RGB8; use->color_pitch = 0; }      // (no colour image is passed: the two colour fields are not looked at)
-    if (const int rc = rgbd_layout(use, lay)) return rc;
-    if (n_regions > RG_MAX_REGIONS) return F3DS_ERR_UNSUPPORTED;
-    return F3DS_OK;
+    if (!rows && n_regions) return F3DS_ERR_ARG;
+    return li_check(fmt, depth, color, labels, n_regions, use, lay);
 }
 
 }  // namespace f3ds

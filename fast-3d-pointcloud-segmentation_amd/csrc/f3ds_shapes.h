@@ -161,15 +161,11 @@ F3DS_HD void sh_finish(const ShAcc& a, f3ds_region_shape* row) {
     *row = r;
 }
 
-// What both entry points refuse before they look at a pixel, in the region table's order; *use = the format they work with (the colour fields neutral).
+// What both entry points refuse before they look at a pixel, as the region table: missing rows, then li_check; *use = the format they work with.
 inline int sh_check(const f3ds_rgbd_format* fmt, const void* depth, const uint32_t* labels, uint32_t n_regions, const f3ds_region_shape* rows, f3ds_rgbd_format* use,
                     RgbdLayout* lay) {
-    if (!fmt || !depth || !labels || (!rows && n_regions)) return F3DS_ERR_ARG;
-    *use = *fmt;
-    use->color_format = F3DS_COLOR_RGB8; use->color_pitch = 0;      // (no colour image is passed: the two colour fields are not looked at)
-    if (const int rc = rgbd_layout(use, lay)) return rc;
-    if (n_regions > RG_MAX_REGIONS) return F3DS_ERR_UNSUPPORTED;
-    return F3DS_OK;
+    if (!rows && n_regions) return F3DS_ERR_ARG;
+    return li_check(fmt, depth, nullptr, labels, n_regions, use, lay);
 }
 
 }  // namespace f3ds

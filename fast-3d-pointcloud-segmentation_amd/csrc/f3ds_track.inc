@@ -31,11 +31,8 @@ __device__ inline void track_keys_loop(const unsigned char* depth, const uint32_
     uint32_t v = i / a.width, u = i - v * a.width;
     const uint64_t hole = tk_hole(a.Kc, a.jb);
     for (; i < a.n; i += stride) {
-        const unsigned char* drow = depth + (size_t)v * a.depth_pitch;
         float z = 0.0f;
-        bool valid;
-        if constexpr (DEPTH_F32) valid = n_depth_to_z(reinterpret_cast<const float*>(drow)[u], a.depth_scale, z);
-        else valid = n_depth_to_z(reinterpret_cast<const uint16_t*>(drow)[u], a.depth_scale, z);
+        const bool valid = li_read_depth<DEPTH_F32>(depth, a.depth_pitch, a.depth_scale, u, v, z);
         const uint32_t l = label[i];
         float x, y, zo;
         n_deproject(u, v, valid, z, a.fx, a.fy, a.cx, a.cy, x, y, zo);
