@@ -121,9 +121,19 @@ def test_capi_merge_only_entry_argument_checks_need_no_gpu(P):
 
 
 # ------------------------------------------------------------------------------------------------ GPU: the HIP merge loop on the oracle's supervoxels
-def check_against(ctx, h, region, vlab, sv, P):
+def check_against(ctx, h, region, vlab, sv, P, ores=None, oregion=None, ovlab=None):
+    """Everything the merge half leaves behind against the oracle handle h; with the oracle's own outputs (result, region_of_sv, voxel_labels) also the counts,
+    lambda (NaN canonicalised) and the two returned arrays."""
     for what in MERGE_ARRAYS:
         assert first_mismatch(what, ctx.debug(what), h.get(what)) is None
+    if ores is not None:
+        r = ctx.result
+        assert (r.n_merges, r.n_regions, r.n_edges, r.n_supervoxels) == (ores.n_merges, ores.n_regions, ores.n_edges, len(sv["label"]))
+        assert bits_equal(canon(np.float32(r.lambda_)), canon(np.float32(ores.lambda_))), (r.lambda_, ores.lambda_)
+    if oregion is not None:
+        assert np.array_equal(region, oregion)
+    if ovlab is not None:
+        assert np.array_equal(vlab, ovlab)
     assert np.array_equal(region, h.get("SV_REGION")[np.searchsorted(h.get("SV_LABELS"), sv["label"])])
     for a, b in zip(ctx.voxel_cloud(), h.voxel_cloud()):
         assert bits_equal(a, b)
