@@ -58,6 +58,11 @@ struct f3ds_emul {
     std::vector<uint32_t> rhead, lnext;
     std::vector<uint8_t> ralive;
     uint32_t sweep_stats[4] = {0u, 0u, 0u, 0u};      // the last run of sweeps, as the device counts them (F3DS_DBG_SWEEP_STATS): full from their start / incremental / fallback / idle
+    // The last run of sweeps, chains deeper than the walkers' stack (F3DS_R_STACK).  r_deep: voxels the walkers the device runs too (a_eval_R_mask after the pre-pass,
+    // a_eval_R of the fallback) put off, once per pass, in THIS emulation's order -- ascending ordinals, one voxel after the other, each finding what the ones before it
+    // memoised.  r_deep_cold (only with F3DS_EMUL_R_COLD set: a copy of the memo per voxel): voxels whose a_eval_R_mask overflows when it starts from the memo as the
+    // pre-pass left it -- what a device thread meets that runs before any other has settled part of its chain; the device evaluates a work list in no particular order.
+    uint32_t r_deep = 0u, r_deep_cold = 0u;
     f3ds_result res;
 };
 
@@ -259,20 +264,22 @@ int stage_sweeps(f3ds_emul& E, const std::vector<int>& seeds, bool reseed) {
     uint32_t n_changed = 0, sweep_full = 0, sweep_pre = 0, sweep_marks = 0, sweep_idle = 0;
     const SweepCtl ctl{&n_changed, &sweep_full, &sweep_pre, &sweep_marks, &sweep_idle};
     for (uint32_t& n : E.sweep_stats) n = 0u;
+    E.r_deep = 0u; E.r_deep_cold = 0u;
+    const bool cold_probe = getenv("F3DS_EMUL_R_COLD") != nullptr;
     long stat_r_evals = 0, stat_c_evals = 0, stat_h_evals = 0;
     auto mark = [&](int v, std::vector<uint32_t>& a, std::vector<uint32_t>& b, uint32_t stamp) {
         for (int k = 0; k < 27; ++k) { int u = nbrT[(size_t)k * V + v]; if (u >= 0) { a[u >> 6] = stamp; b[u >> 6] = stamp; } }
     };
     // like d_sweep_R and d_sweep_R_tail: voxels whose chain is deeper than the walker's stack are retried in later passes over the memo (the device: F3DS_R_PASSES
     // grid passes, then one workgroup until done).  eval(v, &overflow) = R(v); out[v] = owner | R bit
-    auto walk = [&](std::vector<int> todo, std::vector<uint32_t>& out, auto&& eval) {
+    auto walk = [&](std::vector<int> todo, std::vector<uint32_t>& out, auto&& eval, bool device_walker) {
         std::vector<int> again;
         while (!todo.empty()) {
             again.clear();
             for (int v : todo) {
                 int overflow = 0;
                 const bool r = eval(v, &overflow);
-                if (overflow) again.push_back(v); else out[v] = E.owner[v] | (r ? F3DS_OWNR_RTRUE : 0u);
+                if (overflow) { again.push_back(v); if (device_walker) E.r_deep++; } else out[v] = E.owner[v] | (r ? F3DS_OWNR_RTRUE : 0u);
             }
             if (again.size() == todo.size()) return false;      // no progress: cannot happen
             todo.swap(again);
@@ -324,15 +331,21 @@ int stage_sweeps(f3ds_emul& E, const std::vector<int>& seeds, bool reseed) {
                     if (mask == 0u) { ownR[v] = E.owner[v] | F3DS_OWNR_RTRUE; R[v] = (unsigned char)((tag << 2) | F3DS_R_TRUE); }
                     else { tmask[v] = mask; todo.push_back(v); }
                 }
-                if (!walk(todo, ownR, [&](int v, int* overflow) { return a_eval_R_mask(s, v, R.data(), tag, tmask.data(), overflow); })) return F3DS_ERR_UNSUPPORTED;
+                if (cold_probe) for (int v : todo) {
+                    std::vector<unsigned char> Rcold = R;
+                    int overflow = 0;
+                    a_eval_R_mask(s, v, Rcold.data(), tag, tmask.data(), &overflow);
+                    if (overflow) E.r_deep_cold++;
+                }
+                if (!walk(todo, ownR, [&](int v, int* overflow) { return a_eval_R_mask(s, v, R.data(), tag, tmask.data(), overflow); }, true)) return F3DS_ERR_UNSUPPORTED;
                 // cross-check: R from the defining equation (a_eval_R, a memo of its own) says the same of every voxel
                 std::vector<uint32_t> chk = ownR;
                 std::fill(Rchk.begin(), Rchk.end(), (unsigned char)0);
-                if (!walk(owned, chk, [&](int v, int* overflow) { return a_eval_R(s, v, Rchk.data(), tag, overflow); })) return F3DS_ERR_UNSUPPORTED;
+                if (!walk(owned, chk, [&](int v, int* overflow) { return a_eval_R(s, v, Rchk.data(), tag, overflow); }, false)) return F3DS_ERR_UNSUPPORTED;
                 if (chk != ownR) return F3DS_ERR_LOGIC;
             } else {
                 // the fallback of d_sweep_R: no pre-pass has run; R of every owned voxel from the memoised walker (no ghost leaf is active in an incremental sweep)
-                if (!walk(owned, ownR, [&](int v, int* overflow) { return a_eval_R(s, v, R.data(), tag, overflow, false); })) return F3DS_ERR_UNSUPPORTED;
+                if (!walk(owned, ownR, [&](int v, int* overflow) { return a_eval_R(s, v, R.data(), tag, overflow, false); }, true)) return F3DS_ERR_UNSUPPORTED;
             }
         }
         // claim, in place
@@ -738,6 +751,9 @@ int f3ds_emul_refine(f3ds_emul* Ep, int num_itr, uint32_t* voxel_sv_label, float
 int f3ds_emul_sweep_begin(uint32_t* words, uint32_t t, uint32_t n_ghosts, uint32_t thr) {
     return a_sweep_begin(SweepCtl{&words[0], &words[1], &words[2], &words[3], &words[4]}, t, n_ghosts, thr) ? 1 : 0;
 }
+// chains deeper than the walkers' stack in the last run of sweeps (f3ds_emul::r_deep, r_deep_cold; tests/vccs_clouds_common.py: the deep-chain cases)
+uint32_t f3ds_emul_r_deep(const f3ds_emul* E) { return E->r_deep; }
+uint32_t f3ds_emul_r_deep_cold(const f3ds_emul* E) { return E->r_deep_cold; }
 uint32_t f3ds_emul_sweep_thr(uint32_t V, int inc_shift) { return a_sweep_thr(V, inc_shift); }
 
 // numerics probes for tests/test_numerics.py (device arithmetic evaluated on the host)

@@ -1101,8 +1101,9 @@ def test_cli_gpus_unreadable_file_and_bench_flag(P, oracle, tmp_path):
 def test_voxel_normals_kernel_widths_agree_with_the_golden_normals(P, monkeypatch, threads):
     """d_normals_t<384> builds a tile's tables with six waves (lone frames, small calls), d_normals_t<256> with four (calls of 16 frames or more:
     a four-wave workgroup fits on a unit beside another call's merge loop).  Each forced here (F3DS_NORMALS_THREADS, read per call) on golden
-    cases -- small noisy frames whose tiles overflow the one-ring / two-ring tables take the global-memory path inside the same launch -- and on the
-    1M-point frame: normals, and what the sweeps make of the tile tables the kernel writes for them."""
+    cases and on the 1M-point frame: normals, and what the sweeps make of the tile tables the kernel writes for them.  No tile of these golden cases overflows the
+    one-ring / two-ring tables (largest one-ring 347 of 448, largest two-ring 528 of 896), and the assertion below holds as well when every tile of the big frame fits:
+    the kernel's global-memory accumulation for overflowed tiles is run by the solid blocks of tests/test_vccs_clouds_gpu.py, not here."""
     monkeypatch.setenv("F3DS_NORMALS_THREADS", threads)
     big = json.load(open(os.path.join(ROOT, "tests", "golden", "oracle_golden_big.json")))
     ctx = P.Context(0)

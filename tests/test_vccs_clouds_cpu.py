@@ -1,0 +1,156 @@
+"""The synthetic lattice clouds of vccs_clouds_common.py, checked without a GPU: the generator is deterministic and puts every point a quarter of a cell inside its
+voxel, the census counts what a hand count gives, the oracle's run of every case meets the condition the case is for (so no case can stop exercising its path
+unnoticed), the emulation of the device pipeline equals the oracle byte for byte on every case -- once more with every sweep full where sweeps are the subject --, the
+kernel constants the cases are sized by are the ones in the sources, and the golden cases reach none of these paths (when one starts to, that test says so and the case
+list can shrink).
+
+Oracle seconds on the development machine: 1.4 s for the 50 cases together (r-tiny-supervoxels-desc 0.3, the blocks of 4 000 to 8 000 voxels 0.06 - 0.11 each, everything else
+under 0.03); the emulation takes about as long again."""
+import os
+
+import numpy as np
+import pytest
+
+import vccs_clouds_common as C
+from conftest import ROOT
+from golden_cases import GOLDEN_CASES, case_params, case_points
+from sweep_control_common import emul_run as golden_emul_run
+from test_devprobe_cpu import hostprobe  # noqa: F401  (the fixture: the host build of the device headers, n_voxel_distance among them)
+
+
+def test_generator_is_deterministic_and_every_point_lies_inside_its_cell():
+    cells = C.block(5, 4, 3, at=(-2, 7, 1))
+    kw = dict(rgba="random", per_cell=3, order="shuffle", nan_every=5, seed=4)
+    a, b, c = C.cloud(cells, 0.01, **kw), C.cloud(cells, 0.01, **kw), C.cloud(cells, 0.01, **dict(kw, seed=5))
+    assert a.dtype == np.float32 and a.shape[1] == 4 and a.tobytes() == b.tobytes() and a.tobytes() != c.tobytes()
+    finite = ~np.isnan(a[:, 0])
+    assert int((~finite).sum()) == (60 * 3 + 4) // 5 and np.isnan(a[~finite]).all()
+    assert int(finite.sum()) == 60 * 3 + 2                                      # the two anchors
+    q = a[finite, :3].astype(np.float64) / 0.01
+    frac = q - np.floor(q)
+    assert (frac > 0.24).all() and (frac < 0.76).all()                          # a quarter of a cell from every border
+    got = {tuple(x) for x in np.floor(q[:-2]).astype(np.int64).tolist()}
+    assert got == {tuple(x) for x in cells.tolist()}
+    lo, hi = np.floor(q[-2]).astype(np.int64), np.floor(q[-1]).astype(np.int64)
+    assert lo.tolist() == [-2, 7, 1] and hi.tolist() == [-2 + 6 - 1, 7 + 4 - 1, 1 + 4 - 1]      # the box rounded up to even spans: 6 x 4 x 4
+    assert (a[finite, 3].view(np.uint32) >> 24 == 0).all()
+    one = C.cloud(cells, 0.01, rgba=C.pack_rgb(1, 2, 3), anchor=False)
+    assert len(one) == 60 and (one[:, 3].view(np.uint32) == 0x010203).all()
+    r = C.cloud(C.block(3, 1, 1), 0.01, per_cell=[2, 1, 3], order="round", anchor=False)
+    assert np.floor(r[:, 0].astype(np.float64) / 0.01).astype(int).tolist() == [0, 1, 2, 0, 2, 2]
+
+
+def test_shapes_are_what_their_names_say():
+    s = C.serpentine(3, 10, 2)
+    assert len(s) == 3 * 10 + 2 * 2 and len({tuple(x) for x in s.tolist()}) == len(s)
+    assert {(9, 1, 0), (9, 2, 0), (0, 4, 0), (0, 5, 0)} <= {tuple(x) for x in s.tolist()}      # joined at alternating ends
+    assert len(C.serpentine(2, 10, 3, width=3)) == 2 * 30 + 3 * 3
+    lat = C.lattice(3, 3)
+    assert len(lat) == 27 and np.abs(lat[:, None, :] - lat[None, :, :]).max(axis=2)[~np.eye(27, dtype=bool)].min() == 3
+    assert len(C.comb(4, 5)) == 8 + 20
+
+
+def test_census_counts_what_a_hand_count_gives(oracle, P):
+    """A 3 x 3 x 3 block: 27 voxels and the two anchors' share.  The centre voxel has all 27 slots, the one tile's rings are the whole frame, the lower anchor is the
+    corner cell's second point and the upper one a voxel of its own (the box is rounded up to 4 x 4 x 4)."""
+    pts = C.cloud(C.block(3, 3, 3), C.R)
+    prm = P.launch_params(voxel_res=C.R, seed_res=5 * C.R, use_transform=0)
+    rc, lab, res, h = oracle.segment(pts, prm)
+    assert rc == 0
+    cen = C.census(P, h, res)
+    assert (cen.V, cen.n_points, cen.max_points_per_voxel) == (28, 29, 2) and cen.full27 == 1
+    assert cen.ring1.tolist() == [28] and cen.ring2.tolist() == [28] and not cen.overflow.any() and cen.tile_voxels.tolist() == [28]
+    assert cen.leaves.sum() <= 28 and cen.S0 == res.n_seeds and not cen.first_last_tile and not cen.chunk_straddle
+    # two runs of one voxel inside one 256-point step: the corner cell's point leads the frame, the lower anchor comes 27 points later
+    assert cen.disorder
+
+
+def test_kernel_constants_the_cases_are_sized_by():
+    """NT_RING1, NT_SLOTS, VL_MAX_RUN, VT_ENT_MAX, F3DS_VT_TILE, VG_CHUNK, RL_LDS_CAP, HT_CAP, QL, the 63 of a_sweep_tag, F3DS_R_STACK, F3DS_R_ROUNDS and the 48 of the
+    wave-per-helper switch, read from their defining lines -- and the comparisons at the four table limits (> / >= / <), which decide on which side 256, 1280, 448 and 896 fall."""
+    got = C.read_kernel_constants(os.path.join(ROOT, "fast-3d-pointcloud-segmentation_amd", "csrc"))
+    assert len(got) == 24
+    for name, pat, have, want in got:
+        assert have == want, "%s: %s gives %r, the tests assume %r" % (name, pat, have, want)
+    assert C.VT_ENT_MAX == C.VT_TILE // 2 * 5 // 8
+
+
+def test_the_case_list_is_the_one_the_issue_names():
+    fam = {c.family for c in C.CASES}
+    assert fam == set(range(1, 8)) and len(C.CASES) == 50
+    desc = [c for c in C.CASES if c.params.get("leaf_order") == 1]
+    assert {c.family for c in desc} >= {1, 2, 3, 4, 5, 6}                       # one case per family with descending leaves
+    assert any(c.params["use_transform"] == 1 for c in C.CASES) and "v-depth13" in C.CASE
+    for n in ("n-line-V127", "n-line-V128", "n-line-V129", "s-voxel-of-255-points", "s-voxel-of-256-points", "s-voxel-of-257-points", "s-tile-of-1280-voxels",
+              "s-tile-of-1281-voxels", "s-4096-points", "s-4097-points", "r-every-voxel-a-seed-12287", "r-every-voxel-a-seed-12288", "r-tile-lists-of-15-and-17"):
+        assert n in C.CASE
+    assert all(c.also_full for c in C.CASES if c.family == 4)
+
+
+@pytest.mark.parametrize("name", C.NAMES)
+def test_oracle_run_meets_the_condition_and_the_emulation_equals_it(oracle, emul, hostprobe, P, name):  # noqa: F811
+    r = C.oracle_run(oracle, P, name)
+    er = C.emul_run_of(emul, P, name)
+    assert er.rc == 0
+    ties = C.tie_count(hostprobe, r.h, r.prm) if r.case.cond[0] == "ties" else None
+    print("%s: V %d, S0 %d, sweeps %d %s, deep %d (cold %s), runs out of order %d, longest tile lists %s, largest rings %d / %d, most points per voxel %d, most voxels per tile %d, ties %s, %.2f s" % (
+        name, r.census.V, r.census.S0, r.census.sweeps, er.stats, er.deep, er.cold, r.census.disorder_runs, sorted(r.census.helper_tiles)[-3:], r.census.ring1.max(), r.census.ring2.max(), r.census.max_points_per_voxel, r.census.max_tile_voxels, ties, r.seconds))
+    C.check_condition(r, er, ties)
+    assert r.seconds < 1.0, "%s: %.1f s of oracle time" % (name, r.seconds)
+    assert C.emul_equals_oracle(er, r.labels, r.h) is None
+    for f in ("n_points", "n_finite", "n_voxels", "octree_depth", "n_seed_cells", "n_seeds", "n_supervoxels", "n_edges", "n_merges", "n_regions", "sweeps"):
+        assert getattr(er.res, f) == getattr(r.res, f), f
+
+
+@pytest.mark.parametrize("name", [c.name for c in C.CASES if c.also_full])
+def test_emulation_with_every_sweep_full_equals_the_oracle(oracle, emul, P, name):
+    r = C.oracle_run(oracle, P, name)
+    er = C.emul_run_of(emul, P, name, "-1")
+    assert er.rc == 0 and er.stats[C.INCREMENTAL] == 0 and er.stats[C.FALLBACK] == 0 and sum(er.stats) == r.census.sweeps, er.stats
+    if r.case.cond[0] == "long":
+        assert er.stats[C.FULL] > r.case.cond[2], er.stats                         # every busy sweep runs the memoised walker: the tag wraps inside full sweeps
+    assert C.emul_equals_oracle(er, r.labels, r.h) is None
+
+
+def _distinct_golden():
+    """The golden cases that differ in what the supervoxel half reads (frame, resolutions, transform, leaf order): those that differ in metric, merging or threshold alone share one census."""
+    seen, out = set(), []
+    for name, (spec, kw) in GOLDEN_CASES.items():
+        key = (spec, kw.get("voxel_res"), kw.get("seed_res"), kw.get("use_transform", 1), kw.get("leaf_order", 0))
+        if key not in seen:
+            seen.add(key); out.append(name)
+    return out
+
+
+GOLDEN_CENSUS = {      # name: (largest one-ring, largest two-ring, sweeps, idle sweeps, most points in a voxel) of the oracle's run
+    "rgbd_160x120": (220, 324, 17, 0, 9), "rgbd_320x240_ghosts": (347, 468, 13, 0, 16), "rgbd_160x120_desc_leaf_order": (216, 305, 17, 0, 9),
+    "rgbd_160x120_no_transform": (291, 388, 17, 0, 9), "fused_200k_nan_lambda": (314, 528, 17, 0, 12), "rgbd_320x240_large_supervoxels": (256, 392, 56, 27, 16),
+    "fixture_launch_flags": (313, 508, 16, 0, 25),
+}
+
+
+@pytest.mark.parametrize("name", _distinct_golden())
+def test_the_golden_cases_reach_none_of_these_paths(oracle, emul, P, name):
+    """The census of the golden cases: no tile of d_normals_t overflows (largest one-ring 347 of 448, largest two-ring 528 of 896), no sweep falls back at the default
+    F3DS_R_ROUNDS, no run is longer than 56 sweeps (the tag wraps at 63), no voxel holds more than 25 points (256).  A golden case that starts to reach one of these
+    paths fails here: the synthetic case for that path can then go."""
+    rc, lab, res, h = oracle.segment(case_points(P, name), case_params(P, name))
+    assert rc == 0
+    cen = C.census(P, h, res)
+    rc, n, stats = golden_emul_run(P, emul, name)
+    assert rc == 0 and n == cen.sweeps and stats[C.FALLBACK] == 0, (name, stats)
+    assert not cen.overflow.any() and cen.sweeps < C.TAG_PERIOD and cen.max_points_per_voxel <= C.VL_MAX_RUN and cen.max_tile_voxels <= C.VT_TILE
+    got = (int(cen.ring1.max()), int(cen.ring2.max()), cen.sweeps, stats[C.IDLE], cen.max_points_per_voxel)
+    print(name, got)
+    assert got == GOLDEN_CENSUS[name]
+
+
+def test_the_golden_census_is_the_one_design_md_quotes():
+    """DESIGN.md section 7 quotes the largest figures of the census above: when a golden case moves, the document moves with it."""
+    text = " ".join(open(os.path.join(ROOT, "DESIGN.md")).read().split())
+    ring1, ring2, sweeps, ppv = (max(v[k] for v in GOLDEN_CENSUS.values()) for k in (0, 1, 2, 4))
+    idle = max(v[3] for v in GOLDEN_CENSUS.values() if v[2] == sweeps)
+    assert sorted(GOLDEN_CENSUS) == sorted(_distinct_golden())
+    for phrase in ("is %d of `NT_RING1` = %d" % (ring1, C.NT_RING1), "two-ring %d of `NT_SLOTS` = %d" % (ring2, C.NT_SLOTS), "has %d sweeps, %d of them idle" % (sweeps, idle),
+                   "more than %d points (`VL_MAX_RUN` = %d)" % (ppv, C.VL_MAX_RUN)):
+        assert phrase in text, phrase
