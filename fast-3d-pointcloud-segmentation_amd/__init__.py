@@ -168,6 +168,27 @@ REGION_SHAPE_DTYPE = np.dtype([("n_pixels", np.uint32), ("centroid", np.float32,
 assert REGION_SHAPE_DTYPE.itemsize == ctypes.sizeof(RegionShape) == 84
 
 
+class RegionBox(ctypes.Structure):
+    """f3ds_region_box (include/f3ds.h): the box of one region of a label image along the region's own axes and its plane residuals, 96 bytes."""
+    _fields_ = [("n_pixels", ctypes.c_uint32), ("n_inliers", ctypes.c_uint32)] + \
+               [(k, ctypes.c_float * 3) for k in ("center", "axis_n", "axis_m", "axis_l", "lo", "hi", "half")] + [("mean_abs_residual", ctypes.c_float)]
+
+
+class RegionBoxesResult(ctypes.Structure):
+    """f3ds_region_boxes_result (include/f3ds.h): the counts of one call for the region boxes."""
+    _fields_ = [("n_regions", ctypes.c_uint32), ("n_nonempty", ctypes.c_uint32), ("n_labelled", ctypes.c_uint64), ("n_clamped", ctypes.c_uint64),
+                ("n_inliers", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+# the same 96 bytes as a numpy structured dtype: what region_boxes_host and Context.region_boxes return their rows in
+REGION_BOX_DTYPE = np.dtype([("n_pixels", np.uint32), ("n_inliers", np.uint32)] +
+                            [(k, np.float32, (3,)) for k in ("center", "axis_n", "axis_m", "axis_l", "lo", "hi", "half")] + [("mean_abs_residual", np.float32)])
+assert REGION_BOX_DTYPE.itemsize == ctypes.sizeof(RegionBox) == 96
+
+
 class ComponentParams(ctypes.Structure):
     """f3ds_component_params (include/f3ds.h): the depth tolerance of a link and the smallest component that is kept."""
     _fields_ = [("depth_tol", ctypes.c_float), ("min_pixels", ctypes.c_uint32)]
@@ -272,6 +293,11 @@ def load_library(path=None):
         lib.f3ds_region_shapes_host.argtypes = [ctypes.POINTER(RgbdFormat), vp, vp, ctypes.c_uint32, vp, rsp]; lib.f3ds_region_shapes_host.restype = ctypes.c_int
         lib.f3ds_region_shapes.argtypes = [vp, ctypes.POINTER(RgbdFormat), vp, vp, ctypes.c_uint32, ctypes.c_int, vp, ctypes.c_int, rsp]
         lib.f3ds_region_shapes.restype = ctypes.c_int
+    if hasattr(lib, "f3ds_region_boxes"):
+        rbp = ctypes.POINTER(RegionBoxesResult)
+        lib.f3ds_region_boxes_host.argtypes = [ctypes.POINTER(RgbdFormat), vp, vp, ctypes.c_uint32, ctypes.c_float, vp, vp, rbp]; lib.f3ds_region_boxes_host.restype = ctypes.c_int
+        lib.f3ds_region_boxes.argtypes = [vp, ctypes.POINTER(RgbdFormat), vp, vp, ctypes.c_uint32, ctypes.c_float, ctypes.c_int, vp, vp, ctypes.c_int, rbp]
+        lib.f3ds_region_boxes.restype = ctypes.c_int
     if hasattr(lib, "f3ds_region_components"):
         rkp, ckp = ctypes.POINTER(RegionComponentsResult), ctypes.POINTER(ComponentParams)
         lib.f3ds_default_component_params.argtypes = [ckp]; lib.f3ds_default_component_params.restype = None
@@ -763,6 +789,29 @@ def region_shapes_host(depth, labels, n_regions, fmt):
     return rows, res
 
 
+# ---- region boxes ----------------------------------------------------------------------------------
+def _box_rows(buf, n_regions):
+    if buf is None:
+        return np.empty(int(n_regions), REGION_BOX_DTYPE)
+    if not (isinstance(buf, np.ndarray) and buf.dtype == REGION_BOX_DTYPE and buf.flags.c_contiguous and buf.size == int(n_regions)):
+        raise ValueError("rows_out must be a contiguous REGION_BOX_DTYPE array with one entry per region")
+    return buf
+
+
+def region_boxes_host(depth, labels, n_regions, fmt, plane_tol=0.01, want_shapes=False):
+    """f3ds_region_boxes_host: (rows, RegionBoxesResult), or (rows, shapes, RegionBoxesResult) with ``want_shapes`` -- one REGION_BOX_DTYPE row per region
+    of the label image: the box of the region's points along the region's own axes (the normal, the long axis of its shape row and their cross product),
+    the count of pixels within ``plane_tol`` metres of the region's plane and the mean distance to it; shapes: the REGION_SHAPE_DTYPE rows of
+    region_shapes_host, the same bits.  Host arithmetic only: what Context.region_boxes computes on the device, bit for bit."""
+    lib = load_library()
+    f, d, _, lab = _region_inputs(fmt, depth, labels, None)
+    rows, res = _box_rows(None, n_regions), RegionBoxesResult()
+    shapes = _shape_rows(None, n_regions) if want_shapes else None
+    _check(lib, lib.f3ds_region_boxes_host(ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), float(plane_tol), rows.ctypes.data if len(rows) else None,
+                                           shapes.ctypes.data if want_shapes and len(shapes) else None, ctypes.byref(res)))
+    return (rows, shapes, res) if want_shapes else (rows, res)
+
+
 # ---- region components -----------------------------------------------------------------------------
 def default_component_params(**overrides):
     p = ComponentParams()
@@ -897,6 +946,27 @@ class Context(_Handle):
         _check(self.lib, self.lib.f3ds_region_shapes(self.handle, ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), 0,
                                                      rows.ctypes.data if len(rows) else None, 0, ctypes.byref(res)))
         return rows, res
+
+    def region_boxes(self, depth, labels, n_regions, fmt, plane_tol=0.01, rows_out=None, shapes_out=None, on_device=False):
+        """f3ds_region_boxes: (rows, RegionBoxesResult) -- what region_boxes_host returns, computed on the device in two reads of the depth image and the
+        labels with one wait; row i is region i, the row i of region_table and region_shapes.  With ``shapes_out`` the shape rows come too and the answer is
+        (rows, shapes, RegionBoxesResult): ``True`` for a new REGION_SHAPE_DTYPE array, or such an array to fill.  depth and labels as in region_table, or
+        device pointers (ints, the depth pitch of ``fmt`` applies) with ``on_device=True``: ``rows_out`` and ``shapes_out`` are then device pointers to
+        n_regions rows each (``shapes_out`` may be None) and the rows returned are None.  With host arrays ``rows_out`` may be a REGION_BOX_DTYPE array to
+        fill.  Leaves the context's frame as it is."""
+        res = RegionBoxesResult()
+        if on_device:
+            _check(self.lib, self.lib.f3ds_region_boxes(self.handle, ctypes.byref(fmt), ctypes.c_void_p(int(depth)), ctypes.c_void_p(int(labels)), int(n_regions), float(plane_tol),
+                                                        1, ctypes.c_void_p(int(rows_out)) if rows_out is not None else None,
+                                                        ctypes.c_void_p(int(shapes_out)) if shapes_out is not None else None, 1, ctypes.byref(res)))
+            return (None, res) if shapes_out is None else (None, None, res)
+        f, d, _, lab = _region_inputs(fmt, depth, labels, None)
+        rows = _box_rows(rows_out, n_regions)
+        want = shapes_out is not None and shapes_out is not False
+        shapes = _shape_rows(None if shapes_out is True else shapes_out, n_regions) if want else None
+        _check(self.lib, self.lib.f3ds_region_boxes(self.handle, ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), float(plane_tol), 0,
+                                                    rows.ctypes.data if len(rows) else None, shapes.ctypes.data if want and len(shapes) else None, 0, ctypes.byref(res)))
+        return (rows, shapes, res) if want else (rows, res)
 
     def region_components(self, depth, labels, n_regions, fmt, depth_tol=0.05, min_pixels=1, rows_out=None, comp_out=None, on_device=False):
         """f3ds_region_components: (comp_labels, rows, RegionComponentsResult) -- what region_components_host returns, computed on the device.  The image is a

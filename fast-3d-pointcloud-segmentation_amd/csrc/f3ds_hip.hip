@@ -53,6 +53,7 @@
 #include "f3ds_regions.h"
 #include "f3ds_contacts.h"
 #include "f3ds_shapes.h"
+#include "f3ds_boxes.h"
 #include "f3ds_components.h"
 
 using namespace f3ds;
@@ -64,6 +65,7 @@ using namespace f3ds;
 #include "f3ds_regions.inc"
 #include "f3ds_contacts.inc"
 #include "f3ds_shapes.inc"
+#include "f3ds_boxes.inc"
 #include "f3ds_components.inc"
 
 // ================================================================================================
@@ -183,7 +185,7 @@ const int g_merge_shared_res = [] { const char* e = dev_getenv("F3DS_MERGE_SHARE
     /* level scores (f3ds_eval_levels.inc): sort buffers, base table, reduced level entries, ghost list, per-level sizes / flags / terms, truth sizes and visiting order, matches, counts and results of a batch */ \
     X(uint64_t, evl_k0) X(uint64_t, evl_k1) X(uint32_t, evl_v0) X(uint32_t, evl_v1) X(uint32_t, evl_flag) X(uint64_t, evl_bkey) X(uint32_t, evl_bcnt) X(uint64_t, evl_ukey) X(uint32_t, evl_ucnt) X(uint32_t, evl_glist) \
     X(uint32_t, evl_ssize) X(unsigned char, evl_used) X(float, evl_hterm) X(float, evl_mterm) X(float, evl_tterm) X(uint32_t, evl_tsize) X(uint32_t, evl_order) X(uint32_t, evl_slot) X(uint32_t, evl_counts) X(uint32_t, evl_out) \
-    /* the label-image calls (the tracker update and the four region calls): family-wide staging, which holds nothing once a call has returned (every call waits before it returns) -- the images and labels of a host caller as uploaded, and the head with what a host caller gets behind it on its way down */ \
+    /* the label-image calls (the tracker update and the five region calls): family-wide staging, which holds nothing once a call has returned (every call waits before it returns) -- the images and labels of a host caller as uploaded, and the head with what a host caller gets behind it on its way down */ \
     X(unsigned char, li_depth) X(unsigned char, li_color) X(uint32_t, li_lab) X(unsigned char, li_out) \
     /* ... and below it each call's private working state, which a run of the call that replays (the contacts' second run) finds as it left it */ \
     /* label tracker (f3ds_track.inc; the sort and the reduction use the evl_ buffers of the tracker's private context): the ends of the entries' runs, the packed entries, id[], the ids of a host caller */ \
@@ -194,6 +196,8 @@ const int g_merge_shared_res = [] { const char* e = dev_getenv("F3DS_MERGE_SHARE
     X(uint64_t, rgc_k0) X(uint64_t, rgc_k1) X(uint32_t, rgc_v0) X(uint32_t, rgc_v1) X(uint32_t, rgc_rec) X(uint32_t, rgc_flag) X(uint64_t, rgc_ukey) X(uint32_t, rgc_ustart) X(uint32_t, rgc_uend) X(uint32_t, rgc_cnt) \
     /* region shapes (f3ds_shapes.inc): the accumulators */ \
     X(ShAcc, rgs_acc) \
+    /* region boxes (f3ds_boxes.inc; pass one adds into rgs_acc): the frames, the accumulators of pass two, its head, the shape rows of a caller who wants none */ \
+    X(BxFrame, rgx_frame) X(BxAcc, rgx_acc) X(uint32_t, rgx_head) X(f3ds_region_shape, rgx_shape) \
     /* region components (f3ds_components.inc): a parent, a size and a flag word per pixel */ \
     X(uint32_t, rgk_parent) X(uint32_t, rgk_cnt) X(uint32_t, rgk_flag)
 template <class T> struct Scratch { T* p = nullptr; size_t cap = 0; int slot = -1; };      // cap: bytes allocated; slot: position in F3DS_SCRATCH
@@ -1062,7 +1066,7 @@ int download_begin(Batch& b, hipStream_t* dl) {
 int download_queued(Batch& b, hipStream_t dl) { if (dl) HIPCHECK(hipEventRecord(b.owner->ev_copy[2], dl)); return F3DS_OK; }
 int download_wait(Batch& b, hipStream_t dl) { if (dl) HIPCHECK(timed_sync(b.owner->ev_copy[2])); return F3DS_OK; }
 
-// ---- the label-image frame (f3ds_label_image.h, DESIGN.md "the label-image frame"): what the tracker update and the four region calls do alike.  A region call
+// ---- the label-image frame (f3ds_label_image.h, DESIGN.md "the label-image frame"): what the tracker update and the five region calls do alike.  A region call
 // reads: check -> li_begin -> its buffers (li_out_buffers) -> li_upload -> its arguments and kernels -> flush -> li_download_head -> deliver (li_rows_behind). ----
 // Start of a label-image call, after its checks: the switches, the device, the batch of the one context
 int li_begin(f3ds_ctx* c, Batch* b) {
@@ -2579,10 +2583,11 @@ extern "C" int f3ds_tracker_update(f3ds_tracker* t, const f3ds_rgbd_format* fmt_
 }
 
 // ------------------------------------------------------------------------------------------------
-// The four region calls share the label-image frame (li_begin ... li_rows_behind, above): the images of a host caller go up through the family's staging, the
+// The five region calls share the label-image frame (li_begin ... li_rows_behind, above): the images of a host caller go up through the family's staging, the
 // kernels of a call are recorded into one flush, and what goes down -- the head and, for a host caller, what rides behind it on the call's stream, not through the
 // copy stream -- is ONE download, the call's only wait in the ordinary case.  The staging (li_*) holds nothing once a call has returned; the working state between
-// a call's kernels is the call's own (rgt_acc, rgc_*, rgs_acc, rgk_*), so no call disturbs what another one of the context reads.
+// a call's kernels is the call's own (rgt_acc, rgc_*, rgs_acc, rgx_*, rgk_*; pass one of the boxes adds into rgs_acc, which both of its users zero first and which
+// holds nothing between calls), so no call disturbs what another one of the context reads.
 //
 // region table (f3ds_regions.h / .inc): one row per region of a label image over an RGB-D frame.  Three kernels -- d_region_init,
 // d_region_accum (the one read of the images), d_region_finish; behind the head the rows of a host caller (72 B per region).
@@ -2725,6 +2730,59 @@ extern "C" int f3ds_region_shapes(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, con
     if (result) {
         result->n_regions = K; result->n_nonempty = h[0];
         memcpy(&result->n_labelled, h + 2, 8); memcpy(&result->n_clamped, h + 4, 8);
+    }
+    return F3DS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// region boxes (f3ds_boxes.h / .inc): one row per region of a label image over a depth image -- the box along the region's own axes and
+// its plane residuals.  The family's first call with TWO reads of the images, the second depending on the finish of the first; both are recorded into the one
+// flush: d_shape_init, d_shape_accum, d_shape_finish as they are (into rgs_acc, which holds nothing between calls), d_box_frame (a frame per region from its
+// shape row), d_box_accum (the second read, every pixel in the frame of its label), d_box_finish.  Behind the head the box rows of a host caller (96 B per
+// region) and behind them the shape rows (84 B) if they were asked for; the shape rows of a caller who wants none stay in scratch.
+// ------------------------------------------------------------------------------------------------
+extern "C" int f3ds_region_boxes(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, float plane_tol, int inputs_on_device,
+                                 f3ds_region_box* rows, f3ds_region_shape* shapes, int rows_on_device, f3ds_region_boxes_result* result) {
+    if (!c) return F3DS_ERR_ARG;
+    f3ds_rgbd_format fmt; f3ds::RgbdLayout lay;
+    if (const int rc = bx_check(fmt_, depth, labels, n_regions, plane_tol, rows, &fmt, &lay)) return rc;
+    Batch b;
+    if (const int rc = li_begin(c, &b)) return rc;
+    const uint32_t n = (uint32_t)lay.n, K = n_regions, copies = rgt_copies(K);
+    const size_t box_bytes = rows_on_device ? 0u : (size_t)K * sizeof(f3ds_region_box);      // (a multiple of 8: the shape rows behind them are aligned)
+    const size_t shape_bytes = rows_on_device || !shapes ? 0u : (size_t)K * sizeof(f3ds_region_shape);
+    // every buffer of the call before anything is recorded
+    ShAcc* acc; BxAcc* acc2; BxFrame* frames; uint32_t* head2; f3ds_region_shape* d_shapes; unsigned char* out; LiImages im;
+    ENSURE(c->rgs_acc, K ? (size_t)K * copies : 1u, acc);
+    ENSURE(c->rgx_acc, K ? (size_t)K * copies : 1u, acc2);
+    ENSURE(c->rgx_frame, K ? K : 1u, frames);
+    ENSURE(c->rgx_head, LI_HEAD_WORDS, head2);
+    if (!shapes) ENSURE(c->rgx_shape, K ? K : 1u, d_shapes);
+    if (const int rc = li_out_buffers(c, LI_HEAD_BYTES + box_bytes + shape_bytes, &out)) return rc;
+    if (const int rc = li_upload(c, b, lay, depth, nullptr, labels, inputs_on_device, &im)) return rc;
+    ShapeArgs a;
+    memset(&a, 0, sizeof a);
+    a.width = fmt.width; a.n = n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
+    a.K = K; a.copies = copies;
+    a.depth_scale = fmt.depth_scale; a.fx = fmt.fx; a.fy = fmt.fy; a.cx = fmt.cx; a.cy = fmt.cy;
+    uint32_t* head = reinterpret_cast<uint32_t*>(out);
+    f3ds_region_box* d_rows = rows_on_device ? rows : reinterpret_cast<f3ds_region_box*>(out + LI_HEAD_BYTES);
+    if (shapes) d_shapes = rows_on_device ? shapes : reinterpret_cast<f3ds_region_shape*>(out + LI_HEAD_BYTES + box_bytes);
+    const uint32_t accum_grid = grid_for((n + LI_TRIPS - 1u) / LI_TRIPS, 256);
+    rec<d_shape_init>(c, grid_for((size_t)K * copies * SH_WORDS, 256), 0u, reinterpret_cast<uint32_t*>(acc), K * copies, head);
+    rec<d_shape_accum>(c, accum_grid, 0u, im.depth, im.labels, a, acc, head);
+    rec<d_shape_finish>(c, grid_for(K, 256), 0u, acc, K, copies, head, d_shapes);
+    rec<d_box_frame>(c, grid_for(K, 256), 0u, d_shapes, K, copies, plane_tol, head, frames, acc2, head2);
+    rec<d_box_accum>(c, accum_grid, 0u, im.depth, im.labels, a, frames, acc2, head, head2);
+    rec<d_box_finish>(c, grid_for(K, 256), 0u, acc2, frames, K, copies, head, d_rows);
+    if (const int rc = flush(b)) return rc;
+    uint32_t h[LI_HEAD_WORDS];
+    if (const int rc = li_download_head(c, b, out, box_bytes + shape_bytes, h)) return rc;      // (a label >= n_regions: no finish kernel wrote a row)
+    if (box_bytes) memcpy(rows, c->h_li + LI_HEAD_BYTES, box_bytes);
+    if (shape_bytes) memcpy(shapes, c->h_li + LI_HEAD_BYTES + box_bytes, shape_bytes);
+    if (result) {
+        result->n_regions = K; result->n_nonempty = h[0];
+        memcpy(&result->n_labelled, h + 2, 8); memcpy(&result->n_clamped, h + 4, 8); memcpy(&result->n_inliers, h + 6, 8);
     }
     return F3DS_OK;
 }

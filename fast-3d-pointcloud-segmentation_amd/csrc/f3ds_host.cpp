@@ -23,6 +23,7 @@
 #include "f3ds_regions.h"
 #include "f3ds_contacts.h"
 #include "f3ds_shapes.h"
+#include "f3ds_boxes.h"
 #include "f3ds_components.h"
 
 extern "C" {
@@ -286,6 +287,42 @@ int f3ds_region_shapes_host(const f3ds_rgbd_format* fmt_, const void* depth, con
     uint32_t n_nonempty = 0;
     for (uint32_t r = 0; r < n_regions; ++r) { f3ds::sh_finish(acc[r], &rows[r]); if (acc[r].n) ++n_nonempty; }
     if (result) { result->n_regions = n_regions; result->n_nonempty = n_nonempty; result->n_labelled = n_labelled; result->n_clamped = n_clamped; }
+    return F3DS_OK;
+}
+
+// ---- region boxes: the definition (the rules are in f3ds_boxes.h, which d_box_frame, d_box_accum and d_box_finish call too) ----
+// The shapes' host function first (it checks the labels before it writes a row), then a second loop over the pixels, each measured in the frame of its region.
+int f3ds_region_boxes_host(const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, float plane_tol, f3ds_region_box* rows,
+                           f3ds_region_shape* shapes, f3ds_region_boxes_result* result) {
+    f3ds_rgbd_format fmt; f3ds::RgbdLayout l;
+    if (const int rc = f3ds::bx_check(fmt_, depth, labels, n_regions, plane_tol, rows, &fmt, &l)) return rc;
+    std::vector<f3ds_region_shape> own(shapes ? 0u : n_regions);
+    f3ds_region_shape* S = shapes ? shapes : own.data();
+    f3ds_region_shapes_result sres;
+    if (const int rc = f3ds_region_shapes_host(fmt_, depth, labels, n_regions, n_regions ? S : nullptr, &sres)) return rc;      // (a bad label: nothing written)
+    std::vector<f3ds::BxFrame> frames(n_regions);
+    std::vector<f3ds::BxAcc> acc(n_regions);
+    for (uint32_t r = 0; r < n_regions; ++r) { f3ds::bx_frame(S[r], plane_tol, frames[r]); f3ds::bx_empty(acc[r]); }
+    for (uint32_t v = 0; v < fmt.height; ++v) {
+        for (uint32_t u = 0; u < fmt.width; ++u) {
+            const uint32_t lab = labels[(size_t)v * fmt.width + u];
+            float z = 0.0f;
+            const bool valid = f3ds::li_read_depth(fmt, l, depth, u, v, z);
+            if (!valid || lab == F3DS_NO_LABEL) continue;
+            float x, y, zo;
+            f3ds::n_deproject(u, v, valid, z, fmt.fx, fmt.fy, fmt.cx, fmt.cy, x, y, zo);
+            f3ds::BxAcc one;
+            f3ds::bx_empty(one);
+            f3ds::bx_pixel(x, y, zo, frames[lab], one);
+            f3ds::bx_merge(acc[lab], one);
+        }
+    }
+    uint64_t n_inliers = 0;
+    for (uint32_t r = 0; r < n_regions; ++r) { f3ds::bx_finish(acc[r], frames[r], &rows[r]); n_inliers += acc[r].w[1]; }
+    if (result) {
+        result->n_regions = n_regions; result->n_nonempty = sres.n_nonempty; result->n_labelled = sres.n_labelled; result->n_clamped = sres.n_clamped;
+        result->n_inliers = n_inliers;
+    }
     return F3DS_OK;
 }
 

@@ -45,12 +45,14 @@ F3DS_HD void rg_empty(RgAcc& a) {
 
 F3DS_HD uint32_t rg_key(uint32_t bits) { return bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
 F3DS_HD uint32_t rg_unkey(uint32_t key) { return key ^ ((key >> 31) ? 0x80000000u : 0xFFFFFFFFu); }
-F3DS_HD int64_t rg_fix(float a, bool& clamped) {
+// the clamp of rg_fix: a as a double inside [-32768, 32768] (the value itself or one of the two ends)
+F3DS_HD double rg_clamp(float a, bool& clamped) {
     double d = (double)a;
     if (!(d >= -32768.0)) { d = -32768.0; clamped = true; }      // (NaN too)
     else if (d > 32768.0) { d = 32768.0; clamped = true; }
-    return (int64_t)__builtin_rint(d * 65536.0);
+    return d;
 }
+F3DS_HD int64_t rg_fix(float a, bool& clamped) { return (int64_t)__builtin_rint(rg_clamp(a, clamped) * 65536.0); }
 
 // what one labelled pixel adds to its region: every word of `a` is written.  rgba: the colour word of n_color_word (0 without a colour image).  Returns: clamped?
 F3DS_HD bool rg_pixel(uint32_t p, uint32_t u, uint32_t v, float x, float y, float z, uint32_t rgba, RgAcc& a) {

@@ -18,12 +18,17 @@
 //   Table            the LDS table of a workgroup: uint32_t key[LI_SLOTS] and the accumulators' fields, field-major, so the lanes of a wave that update
 //                    different slots touch different banks
 //   WORDS, empty_word(k), empty(acc), table_reset(tab, slot)      the size of an accumulator and its empty values, in global memory, in registers and in LDS
-//   aux(u, v), pixel(i, u, v, x, y, z, aux, acc)                  what a pixel needs besides its depth (loaded before the depth is known to be valid), and what a
-//                                                                 labelled pixel adds to its region (returns: clamped?)
+//   aux(u, v), pixel(i, u, v, x, y, z, aux, l, one_label, acc)    what a pixel needs besides its depth (loaded before the depth is known to be valid), and what a
+//                                                                 labelled pixel adds to its region (returns: clamped?).  l: the pixel's label, for a rule that
+//                                                                 keeps something per region to measure the pixel with (BoxRule: the region's frame); one_label
+//                                                                 (wave-uniform): every labelled lane of the wave holds this l, and l is then passed as
+//                                                                 one value for the whole wave.  The table and the shapes ignore both.
 //   wave_reduce(acc, m)                                           the accumulators of a wave into one, m = the ballot of its labelled lanes
 //   lds_add, table_get, global_add                                an accumulator into a slot, out of a slot, into the region's global accumulator
-//   merge, finish, nonempty                                       the rules' own (rg_merge / rg_finish, sh_merge / sh_finish)
-// The head of both calls: [0] non-empty regions, [1] 1 if a label was >= K, [2..3] labelled pixels (u64), [4..5] clamped pixels (u64), [6] [7] spare.
+//   merge, finish(acc, r, row), nonempty                          the rules' own (rg_merge / rg_finish, sh_merge / sh_finish, bx_merge / bx_finish); r: the region
+//   TALLY, tally(acc)                                             TALLY: the finish kernel adds the sum of tally(acc) over the regions into words 6 ... 7 of the head
+// The head of the calls: [0] non-empty regions, [1] 1 if a label was >= K, [2..3] labelled pixels (u64), [4..5] clamped pixels (u64), [6..7] the rule's tally
+// (u64; spare without one).
 // ------------------------------------------------------------------------------------------------
 constexpr int LI_SLOT_BITS = 7, LI_SLOTS = 1 << LI_SLOT_BITS;      // LDS table: 128 slots of a label + an accumulator (RgAcc: 100 B a slot, 12.5 KiB; ShAcc: 128 B, 16 KiB)
 constexpr int LI_PROBES = 8;           // a label that finds neither its slot nor a free one in this many steps goes straight to the global accumulator
@@ -107,25 +112,29 @@ __device__ __forceinline__ void label_accum_span(const Rule& rule, const unsigne
         }
         bad = bad || (l != LI_NONE && l >= a.K);
         const bool labelled = valid && l < a.K;      // (K <= LI_MAX_REGIONS: LI_NONE is never below it)
+        // one label in the wave (the usual case inside a region)?  Known before the pixels are measured: a rule that looks something up by label then does so once a wave
+        const uint64_t m = __ballot(labelled);
+        uint32_t l0 = LI_NONE;
+        bool one_label = false;
+        if (m) {      // (wave-uniform, and so is one_label)
+            l0 = (uint32_t)__builtin_amdgcn_readlane((int)l, (int)__builtin_ctzll(m));
+            one_label = __ballot(labelled && l != l0) == 0ull;
+        }
         Acc one;
         Rule::empty(one);
         if (labelled) {
             float x, y, zo;
             n_deproject(u, v, true, z, a.fx, a.fy, a.cx, a.cy, x, y, zo);
-            if (Rule::pixel(i, u, v, x, y, zo, aux, one)) ++my_clamped;
+            if (rule.pixel(i, u, v, x, y, zo, aux, one_label ? l0 : l, one_label, one)) ++my_clamped;      // (the label is < K; l0: the same value in every lane)
             ++my_labelled;
         }
-        // one label in the wave (the usual case inside a region): reduce across the wave -- the lanes without a labelled pixel hold the empty values -- and lane 0
-        // sends the sum; otherwise every labelled lane sends its own pixel
-        const uint64_t m = __ballot(labelled);
+        // one label: reduce across the wave -- the lanes without a labelled pixel hold the empty values -- and lane 0 sends the sum; otherwise every labelled
+        // lane sends its own pixel
         uint32_t target = l;
         bool send = labelled;
-        if (m) {      // (wave-uniform, and so is the next one)
-            const uint32_t l0 = (uint32_t)__builtin_amdgcn_readlane((int)l, (int)__builtin_ctzll(m));
-            if (__ballot(labelled && l != l0) == 0ull) {
-                Rule::wave_reduce(one, m);
-                target = l0; send = lane_id() == 0;
-            }
+        if (one_label) {
+            Rule::wave_reduce(one, m);
+            target = l0; send = lane_id() == 0;
         }
         if (send) {
             const int slot = li_slot(tab.key, target);
@@ -152,17 +161,23 @@ __device__ __forceinline__ void label_accum_span(const Rule& rule, const unsigne
 }
 
 template <class Rule>
-__device__ __forceinline__ void label_finish(const typename Rule::Acc* acc, uint32_t K, uint32_t copies, uint32_t* head, typename Rule::Row* rows) {
+__device__ __forceinline__ void label_finish(const Rule& rule, const typename Rule::Acc* acc, uint32_t K, uint32_t copies, uint32_t* head, typename Rule::Row* rows) {
     if (head[1]) return;      // a label was out of range: the rows stay as they are
     uint32_t nonempty = 0u;
+    uint64_t tally = 0ull;
     for (uint32_t r = BIX * blockDim.x + threadIdx.x; r < K; r += gridDim.x * blockDim.x) {
         typename Rule::Acc a = acc[r];
         for (uint32_t c = 1; c < copies; ++c) Rule::merge(a, acc[(size_t)c * K + r]);
-        Rule::finish(a, &rows[r]);
+        rule.finish(a, r, &rows[r]);
         nonempty += Rule::nonempty(a) ? 1u : 0u;
+        if constexpr (Rule::TALLY) tally += Rule::tally(a);
     }
     const uint32_t wn = rg_wave_u32(nonempty, RgAdd{});
     if (lane_id() == 0 && wn) atomicAdd(&head[0], wn);
+    if constexpr (Rule::TALLY) {
+        const uint64_t wt = rg_wave_add_u64(tally);
+        if (lane_id() == 0 && wt) atomicAdd(reinterpret_cast<rg_u64*>(head + 6), (rg_u64)wt);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -182,6 +197,7 @@ template <int COLOR = -1>      // -1: no colour image, else F3DS_COLOR_* (only a
 struct RegionRule {
     using Acc = RgAcc; using Row = f3ds_region_row; using Args = RegionArgs; using Table = RgTable;
     static constexpr int WORDS = RG_WORDS;
+    static constexpr bool TALLY = false;
     const unsigned char* color; uint32_t color_pitch;
 
     static __device__ __forceinline__ uint32_t empty_word(uint32_t k) { return rg_empty_word(k); }
@@ -201,7 +217,7 @@ struct RegionRule {
         }
         else return 0u;
     }
-    static __device__ __forceinline__ bool pixel(uint32_t p, uint32_t u, uint32_t v, float x, float y, float z, uint32_t rgba, RgAcc& a) { return rg_pixel(p, u, v, x, y, z, rgba, a); }
+    static __device__ __forceinline__ bool pixel(uint32_t p, uint32_t u, uint32_t v, float x, float y, float z, uint32_t rgba, uint32_t, bool, RgAcc& a) { return rg_pixel(p, u, v, x, y, z, rgba, a); }
     static __device__ __forceinline__ void wave_reduce(RgAcc& one, uint64_t) {
         one.w[0] = rg_wave_u32(one.w[0], RgAdd{});
 #pragma unroll
@@ -250,7 +266,7 @@ struct RegionRule {
         for (int k = 0; k < RG_S; ++k) if (a.s[k]) atomicAdd(reinterpret_cast<rg_u64*>(&dst->s[k]), (rg_u64)a.s[k]);
     }
     static __device__ __forceinline__ void merge(RgAcc& a, const RgAcc& b) { rg_merge(a, b); }
-    static __device__ __forceinline__ void finish(const RgAcc& a, f3ds_region_row* row) { rg_finish(a, row); }
+    static __device__ __forceinline__ void finish(const RgAcc& a, uint32_t, f3ds_region_row* row) { rg_finish(a, row); }
     static __device__ __forceinline__ bool nonempty(const RgAcc& a) { return a.w[0] != 0u; }
 };
 
@@ -283,5 +299,5 @@ struct d_region_accum {
 };
 struct d_region_finish {
     static constexpr int BLOCK = 256;
-    __device__ void operator()(const RgAcc* acc, uint32_t K, uint32_t copies, uint32_t* head, f3ds_region_row* rows) const { label_finish<RegionRule<>>(acc, K, copies, head, rows); }
+    __device__ void operator()(const RgAcc* acc, uint32_t K, uint32_t copies, uint32_t* head, f3ds_region_row* rows) const { label_finish<RegionRule<>>(RegionRule<>{nullptr, 0u}, acc, K, copies, head, rows); }
 };

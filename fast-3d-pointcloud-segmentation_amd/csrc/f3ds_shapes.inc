@@ -24,6 +24,7 @@ struct ShTable { uint32_t key[LI_SLOTS]; uint32_t n[LI_SLOTS]; rg_u64 s[SH_S][LI
 struct ShapeRule {
     using Acc = ShAcc; using Row = f3ds_region_shape; using Args = ShapeArgs; using Table = ShTable;
     static constexpr int WORDS = SH_WORDS;
+    static constexpr bool TALLY = false;
 
     static __device__ __forceinline__ uint32_t empty_word(uint32_t) { return 0u; }
     static __device__ __forceinline__ void empty(ShAcc& a) { sh_empty(a); }
@@ -33,7 +34,7 @@ struct ShapeRule {
         for (int f = 0; f < SH_S; ++f) t.s[f][k] = 0ull;
     }
     static __device__ __forceinline__ uint32_t aux(uint32_t, uint32_t) { return 0u; }      // (nothing but the depth)
-    static __device__ __forceinline__ bool pixel(uint32_t, uint32_t, uint32_t, float x, float y, float z, uint32_t, ShAcc& a) { return sh_pixel(x, y, z, a); }
+    static __device__ __forceinline__ bool pixel(uint32_t, uint32_t, uint32_t, float x, float y, float z, uint32_t, uint32_t, bool, ShAcc& a) { return sh_pixel(x, y, z, a); }
     static __device__ __forceinline__ void wave_reduce(ShAcc& one, uint64_t m) {
         one.n = (uint32_t)__popcll(m);
 #pragma unroll
@@ -56,7 +57,7 @@ struct ShapeRule {
         for (int k = 0; k < SH_S; ++k) if (a.s[k]) atomicAdd(reinterpret_cast<rg_u64*>(&dst->s[k]), (rg_u64)a.s[k]);
     }
     static __device__ __forceinline__ void merge(ShAcc& a, const ShAcc& b) { sh_merge(a, b); }
-    static __device__ __forceinline__ void finish(const ShAcc& a, f3ds_region_shape* row) { sh_finish(a, row); }
+    static __device__ __forceinline__ void finish(const ShAcc& a, uint32_t, f3ds_region_shape* row) { sh_finish(a, row); }
     static __device__ __forceinline__ bool nonempty(const ShAcc& a) { return a.n != 0u; }
 };
 
@@ -75,5 +76,5 @@ struct d_shape_accum {
 };
 struct d_shape_finish {
     static constexpr int BLOCK = 256;
-    __device__ void operator()(const ShAcc* acc, uint32_t K, uint32_t copies, uint32_t* head, f3ds_region_shape* rows) const { label_finish<ShapeRule>(acc, K, copies, head, rows); }
+    __device__ void operator()(const ShAcc* acc, uint32_t K, uint32_t copies, uint32_t* head, f3ds_region_shape* rows) const { label_finish<ShapeRule>(ShapeRule{}, acc, K, copies, head, rows); }
 };

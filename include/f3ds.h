@@ -404,6 +404,67 @@ int f3ds_region_shapes_host(const f3ds_rgbd_format* fmt, const void* depth, cons
 int f3ds_region_shapes(f3ds_ctx* ctx, const f3ds_rgbd_format* fmt, const void* depth, const uint32_t* labels, uint32_t n_regions,
                        int inputs_on_device, f3ds_region_shape* rows, int rows_on_device, f3ds_region_shapes_result* result);
 
+/* ---- region boxes: one fixed-size row per region of a label image: the box along the region's own axes, and its plane residuals ---
+ * A member of the family for the question the others leave open: how big is a region along its OWN axes, and is it a plane or does it merely have most of
+ * its mass near one.  The table's lo / hi is a box in camera axes (a table top seen at an angle gets a box that is mostly air); the shapes' eigenvalues are
+ * variances, not extents.  labels, n_regions and the region ids are the region table's: row i is region i.  No colour image; the two colour fields of the
+ * format are not looked at.  Two passes over the pixels -- the shapes, then every pixel measured in the frame of its region -- in one call.  The
+ * definition, bit for bit (csrc/f3ds_boxes.h):
+ *   point      the family's: pixel p = v * width + u gets (x, y, z) by the rule of f3ds_deproject; it is LABELLED iff its depth is valid and
+ *              label[p] != F3DS_NO_LABEL.  fixed and CLAMPED are the table's.  n_labelled, n_clamped, n_nonempty and n_pixels are the bits of
+ *              f3ds_region_shapes.
+ *   shape      S_i = the row f3ds_region_shapes defines for region i.  A non-NULL `shapes` receives exactly those rows, the same bits as that call.
+ *   frame      of a non-empty region, from the public floats of S_i only: c = S_i.centroid, n = S_i.normal, l = S_i.axis, m = n x l with
+ *              m_x = n_y * l_z - n_z * l_y, m_y = n_z * l_x - n_x * l_z, m_z = n_x * l_y - n_y * l_x: each component two rounded f32 products and one
+ *              rounded f32 subtraction.  n, m, l go into the row as they are: unit and orthogonal to f32 accuracy only (some 2^-22), not exactly.
+ *   coordinate q_a for a in x, y, z = (float)((double)f_a * 2^-16) with the f_a of `fixed`: the coordinate on the grid of 2^-16 m, clamped to +-32768 (a NaN
+ *              to -32768), converted once.  These are the points the shape row was computed from: its centroid lives on the same grid, so a pixel is
+ *              measured against the frame in the units the frame was made in.  Every q_a is finite, so nothing below produces a NaN from a valid frame.
+ *   projection d_a = q_a - c_a; for each axis e in n, m, l: t_e = (d_x * e_x + d_y * e_y) + d_z * e_z.  Every operation is one rounded f32 operation, in
+ *              this order, nothing fused.  The bits of t_e are canonicalised (t != t ? 0x7FC00000 : bits): a frame nobody foresaw cannot make host and
+ *              device differ in a NaN's sign or payload.
+ *   extents    lo[k], hi[k] (k = 0, 1, 2 for n, m, l) = the minimum and maximum of t over the region's labelled pixels in the total order of
+ *              key(bits) = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000), the table's: -0 below +0.  They are relative to the CENTROID, not to center.
+ *   plane      r = fabsf(t_n).  The pixel is an INLIER iff r <= plane_tol (plane_tol may be 0 and may be +inf).  sum_fix_r adds fix(r), units of 2^-16 m;
+ *              mean_abs_residual = (float)(((double)sum_fix_r / (double)n_pixels) * 2^-16).
+ *   box        half[k] = (hi[k] - lo[k]) * 0.5f, mid[k] = (lo[k] + hi[k]) * 0.5f, center_a = ((c_a + mid[0] * n_a) + mid[1] * m_a) + mid[2] * l_a, each
+ *              operation rounded once.  The box is the eight points center +- half[0] n +- half[1] m +- half[2] l.
+ *   empty      a region without a labelled pixel has n_pixels = n_inliers = 0 and the quiet NaN 0x7FC00000 in all 22 floats.
+ * A region of one point or of points on a line has a frame that is defined but MEANINGLESS, as in the shapes: look at S_i.eigenvalue[1] before believing
+ * axis_n and half[0], at eigenvalue[2] before believing axis_l.  A region at one constant depth z has half[0] == 0 exactly: cov has an exactly zero z row, the
+ * Jacobi sweeps leave n = (0, 0, -1), q_z == c_z for every pixel (both are the one depth on the grid), and t_n is +-0 for every pixel: lo[0], hi[0] and
+ * mean_abs_residual are zeros and every pixel is an inlier even at plane_tol == 0.
+ * Everything that meets more than one pixel is a count, a minimum, a maximum or a sum of integers: the result does not depend on the order of evaluation,
+ * and the device gives the bits of the host function.
+ * Errors (both functions alike, in this order): what f3ds_region_shapes answers with F3DS_ERR_ARG before it looks at a pixel, with `rows` in the role of
+ * its rows (`shapes` may always be NULL); F3DS_ERR_ARG for a plane_tol that is negative or NaN; F3DS_ERR_UNSUPPORTED for n_regions > 0x00FFFFFF;
+ * F3DS_ERR_ARG for a label >= n_regions other than F3DS_NO_LABEL (the device function finds it on the device and reports it at the call's one wait).
+ * After an error neither rows, shapes nor result is written, on the host or on the device.  n_regions == 0, or a frame without a labelled pixel, is
+ * F3DS_OK: the rows, if there are any, are all empty. */
+typedef struct f3ds_region_box {      /* 96 bytes, 24 words */
+    uint32_t n_pixels;        /* labelled pixels of the region (the table's / the shapes' n_pixels)   */
+    uint32_t n_inliers;       /* ... whose distance to the region's plane is <= plane_tol             */
+    float center[3];          /* centre of the box, camera coordinates                                 */
+    float axis_n[3];          /* the shape row's normal, the same bits                                 */
+    float axis_m[3];          /* axis_n x axis_l                                                       */
+    float axis_l[3];          /* the shape row's axis, the same bits                                   */
+    float lo[3], hi[3];       /* extent of the points along n, m, l, relative to the CENTROID          */
+    float half[3];            /* half extents along n, m, l; half[0] is half the region's thickness    */
+    float mean_abs_residual;  /* mean |distance to the plane|, metres                                  */
+} f3ds_region_box;
+typedef struct f3ds_region_boxes_result { uint32_t n_regions, n_nonempty; uint64_t n_labelled, n_clamped, n_inliers; } f3ds_region_boxes_result;
+/* host arithmetic only, no device needed: the definition */
+int f3ds_region_boxes_host(const f3ds_rgbd_format* fmt, const void* depth, const uint32_t* labels, uint32_t n_regions, float plane_tol,
+                           f3ds_region_box* rows, f3ds_region_shape* shapes /* may be NULL */, f3ds_region_boxes_result* result /* may be NULL */);
+/* the same rows from the device: the kernels of f3ds_region_shapes, a frame per region and a second read of the image and the labels in those frames,
+ * recorded back to back with ONE wait (csrc/f3ds_boxes.inc).  inputs_on_device: depth and labels are device memory and read where they are; host inputs go
+ * through the device's copy stream like those of f3ds_region_table.  rows_on_device covers both outputs: rows, and shapes unless it is NULL, are device
+ * memory; host rows arrive with the call's one download.  Synchronous.  Runs on ctx's stream and uses scratch of its own only: every other call on the
+ * context behaves as if this one never happened.  Also F3DS_ERR_ARG for a NULL ctx.  result may be NULL. */
+int f3ds_region_boxes(f3ds_ctx* ctx, const f3ds_rgbd_format* fmt, const void* depth, const uint32_t* labels, uint32_t n_regions, float plane_tol,
+                      int inputs_on_device, f3ds_region_box* rows, f3ds_region_shape* shapes /* may be NULL */, int rows_on_device,
+                      f3ds_region_boxes_result* result);
+
 /* ---- region components: split the regions of a label image into their connected parts -----------------------------------------
  * A region of the segmenter is merged in space, so in the image one label regularly covers disjoint pieces: a table top left and right of the object
  * on it, a wall behind a chair, speckles around depth holes.  The table, the contacts, the shapes and the tracker describe region i as one thing; run
