@@ -1,5 +1,5 @@
 """The label-image calls share their staging on a context (csrc/f3ds_hip.hip, "the label-image frame": one upload trio, one device-side out buffer, one
-pinned download buffer for f3ds_region_table, f3ds_region_shapes, f3ds_region_contacts and f3ds_region_components; the tracker's private context has the
+pinned download buffer for f3ds_region_table, f3ds_region_shapes, f3ds_region_boxes, f3ds_region_contacts and f3ds_region_components; the tracker's private context has the
 same upload trio).  So the calls are run here INTERLEAVED on one context and one tracker: two frame sizes in turn (97 x 61 and 33 x 17: the small call runs in
 buffers the large one grew, and the reverse), host inputs and rows in turn with device inputs and rows, the table with and without colour, one call in the
 middle that fails on a label >= n_regions.  Every result equals the Python references bit for bit, and rows a caller holds on the device from an earlier call
@@ -7,6 +7,7 @@ are unchanged after all the later ones.  Once at the default launch width and on
 import numpy as np
 import pytest
 
+import region_boxes_common as B
 import region_components_common as C
 import region_contacts_common as CT
 import region_shapes_common as S
@@ -28,8 +29,8 @@ def frame(P, name):
         color = R.make_color(w, h, color_kind)
         f = dict(fmt=fmt, depth=depth, labels=lab, K=K, color=color, n=w * h,
                  table=R.ref_table(P, fmt, depth, lab, K), table_color=R.ref_table(P, fmt, depth, lab, K, color), shapes=S.ref_shapes(P, fmt, depth, lab, K)[:3],
-                 contacts=CT.ref_contacts(P, fmt, depth, lab, K, TOL), components=C.ref_components(P, fmt, depth, lab, K, TOL, 1))
-        assert all(f[k][0] == 0 for k in ("table", "table_color", "shapes", "contacts", "components")) and len(f["contacts"][1]) > 0
+                 contacts=CT.ref_contacts(P, fmt, depth, lab, K, TOL), components=C.ref_components(P, fmt, depth, lab, K, TOL, 1), boxes=B.ref_boxes(P, fmt, depth, lab, K))
+        assert all(f[k][0] == 0 for k in ("table", "table_color", "shapes", "contacts", "components", "boxes")) and len(f["contacts"][1]) > 0
         _refs[name] = f
     return _refs[name]
 
@@ -90,6 +91,22 @@ def run_sequence(P):
                 S.assert_rows_equal(P, rows, want[1], "shapes %s" % name)
             assert res.as_dict() == want[2]
 
+        def boxes(f, name, where):      # (the shape rows ride along: the boxes' first pass is the shapes' kernels on the shapes' accumulators)
+            want = f["boxes"]
+            if where == "device":
+                d = dev[name]; dr, ds = d.out(24 * f["K"]), d.out(21 * f["K"])
+                _, _, res = ctx.region_boxes(d.depth.data_ptr(), d.labels.data_ptr(), f["K"], f["fmt"], rows_out=dr.data_ptr(), shapes_out=ds.data_ptr(), on_device=True)
+
+                def check():
+                    B.assert_rows_equal(P, d.get(dr, P.REGION_BOX_DTYPE, f["K"]), want[1], "boxes %s" % name)
+                    S.assert_rows_equal(P, d.get(ds, P.REGION_SHAPE_DTYPE, f["K"]), want[2], "boxes' shapes %s" % name)
+                check(); held.append(check)
+            else:
+                rows, shp, res = ctx.region_boxes(f["depth"], f["labels"], f["K"], f["fmt"], shapes_out=True)
+                B.assert_rows_equal(P, rows, want[1], "boxes %s" % name)
+                S.assert_rows_equal(P, shp, want[2], "boxes' shapes %s" % name)
+            assert res.as_dict() == want[3]
+
         def contacts(f, name, where):
             want = f["contacts"]
             if where == "device":
@@ -142,10 +159,12 @@ def run_sequence(P):
 
         table(big, "big", "host", True)
         shapes(small, "small", "device")
+        boxes(big, "big", "host")
         track(big, "big", "host")
         contacts(big, "big", "device")
         components(small, "small", "host")
         table(small, "small", "device", False)
+        boxes(small, "small", "device")
         track(big, "big", "device")
         shapes(big, "big", "host")
         contacts(small, "small", "host")
@@ -154,18 +173,21 @@ def run_sequence(P):
         bad_label(big, lambda lab: ctx.region_shapes(big["depth"], lab, big["K"], big["fmt"]))
         bad_label(small, lambda lab: ctx.region_components(small["depth"], lab, small["K"], small["fmt"], TOL, 1))
         bad_label(big, lambda lab: trk.update(big["depth"], lab, big["K"], big["fmt"]))
+        bad_label(small, lambda lab: ctx.region_boxes(small["depth"], lab, small["K"], small["fmt"]))
         table(small, "small", "host", True)
         shapes(big, "big", "device")
+        boxes(small, "small", "host")
         track(small, "small", "host", reset=True)
         contacts(small, "small", "device")
         components(big, "big", "host")
         table(big, "big", "device", False)
         track(small, "small", "device")
         contacts(big, "big", "host")
+        boxes(big, "big", "device")
         components(small, "small", "device")
         shapes(small, "small", "host")
         table(big, "big", "device", True)
-        assert len(held) == 11
+        assert len(held) == 13
         for check in held:      # what the earlier calls left on the device is as they left it
             check()
     finally:
