@@ -1797,7 +1797,12 @@ struct d_seed_nn {
                 const float od = __shfl_xor(bd, d, 64); const int ob = __shfl_xor(best, d, 64);
                 if (ob != 0x7fffffff && (best == 0x7fffffff || od < bd || (od == bd && ob < best))) { bd = od; best = ob; }
             }
-            const float near = (float)(0.25 * gp->res * gp->res * (1.0 - 1e-3));
+            // The centre is a float: it lies up to half an ulp -- 2^-24 of its largest coordinate -- off the cell's true centre, so a voxel of another cell may come that much
+            // nearer than half a cell.  The half cell gives up twice that before it is squared (the 1e-3 is for the roundings of a_sqdist alone, 2.4e-7 relative), and where
+            // that takes more than half of it away (coordinates beyond 2^21 cells) no shortcut is taken: DESIGN.md 7.
+            const float cmax = fmaxf(fabsf(centre[0]), fmaxf(fabsf(centre[1]), fabsf(centre[2])));
+            const double half = 0.5 * gp->res - (double)cmax * 0x1p-23;
+            const float near = half > 0.25 * gp->res ? (float)(half * half * (1.0 - 1e-3)) : 0.0f;
             if (best != 0x7fffffff && bd < near) { if (lane == 0) seed_orig[c] = best; return; }      // (uniform: every lane holds the wave's minimum)
             bd = F3DS_FLT_MAX; best = 0x7fffffff;
         }

@@ -529,4 +529,118 @@ int kp_sv_fill(uint32_t S0, uint32_t V, const uint32_t* owner, const float* vf, 
     return (int)B.err;
 }
 
+// ---- the seed stage (d_chunkbox + d_seed_grow; d_cell_hash + d_seed_nn; d_cell_hash + d_seed_filter), launched with the widths seg_seed_grid / seg_seeds give them.
+// d_seed_grow on vf[V x 12] (xyz finite: checked).  Its loop ends: every trip moves the cursor forward or sets the error, and a_seed_grow stops at depth 22.
+// ints[7 + 5 x F3DS_MAX_SEED_EVENTS] = n_events, error, defined, depth, off[3], then (trigger, depth, off[3]) per event; dbls[7 + 3 x F3DS_MAX_SEED_EVENTS] = res, min[3], max[3], then min[3] per event;
+// dc_out[2] = the sdepth and the error d_seed_grow left in the counters
+int kp_seed_grow(const float* vf, uint32_t V, float seed_res, int* ints, double* dbls, int* dc_out) {
+    if (!vf || !ints || !dbls || !dc_out || V < 1 || V > KP_MAX_N || !(seed_res > 0.0f) || !std::isfinite(seed_res)) return KP_EARG;
+    for (size_t v = 0; v < V; ++v) for (int a = 0; a < 3; ++a) if (!std::isfinite(vf[v * 12 + a])) return KP_EARG;
+    const uint32_t nchunks = (V + SEED_CHUNK - 1) / SEED_CHUNK;
+    Bufs B;
+    const float* dvf = B.mk<float>((size_t)V * 12, vf);
+    float* boxes = B.mk<float>((size_t)nchunks * 6);
+    DevCounters hdc;
+    memset(&hdc, 0, sizeof hdc);
+    hdc.n_voxels = V;
+    DevCounters* ddc = B.mk<DevCounters>(1, &hdc);
+    SeedGrid* dg = B.mk<SeedGrid>(1);
+    if (B.err != hipSuccess) return (int)B.err;
+    hipLaunchKernelGGL((kp_call<d_chunkbox, const float*, const DevCounters*, float*>), dim3(nchunks, 1), dim3(d_chunkbox::BLOCK), 0, 0, dvf, (const DevCounters*)ddc, boxes);
+    hipLaunchKernelGGL((kp_call<d_seed_grow, const float*, const float*, DevCounters*, float, SeedGrid*>), dim3(1, 1), dim3(d_seed_grow::BLOCK), 0, 0, dvf, (const float*)boxes, ddc, seed_res, dg);
+    B.sync();
+    SeedGrid g;
+    memset(&g, 0, sizeof g);
+    B.back(&g, (const SeedGrid*)dg, 1); B.back(&hdc, (const DevCounters*)ddc, 1);
+    if (B.err != hipSuccess) return (int)B.err;
+    ints[0] = g.n_events; ints[1] = g.error; ints[2] = g.defined; ints[3] = g.depth;
+    dbls[0] = g.res;
+    for (int a = 0; a < 3; ++a) { ints[4 + a] = (int)g.off[a]; dbls[1 + a] = g.min[a]; dbls[4 + a] = g.max[a]; }
+    for (int e = 0; e < F3DS_MAX_SEED_EVENTS; ++e) {
+        const bool live = e < g.n_events;
+        ints[7 + 5 * e] = live ? g.ev[e].trigger : 0; ints[8 + 5 * e] = live ? g.ev[e].depth : 0;
+        for (int a = 0; a < 3; ++a) { ints[9 + 5 * e + a] = live ? (int)g.ev[e].off[a] : 0; dbls[7 + 3 * e + a] = live ? g.ev[e].min[a] : 0.0; }
+    }
+    dc_out[0] = hdc.sdepth; dc_out[1] = hdc.error;
+    return 0;
+}
+}  // extern "C"
+namespace {
+// the cell tables of seg_seeds: sorted_vox[n] (voxels < V), cell_start[C + 1] (0 = first, ascending strictly: no empty cell, last = n), ckey[V x 3] below 2^21 - 1 (a
+// neighbour's key still packs), one key per cell and no key twice.  The hash has pow2_ge(2 C + 16) slots, so every probe sequence meets an empty one.
+bool seed_tables_ok(const float* vf, uint32_t V, const uint32_t* ckey, const uint32_t* sorted_vox, uint32_t n, const uint32_t* cell_start, uint32_t C, const double* grid) {
+    if (!vf || !ckey || !sorted_vox || !cell_start || !grid || V < 1 || V > KP_MAX_N || n < 1 || n > V || C < 1 || C > n) return false;
+    if (!(grid[0] > 0.0) || !std::isfinite(grid[0]) || !std::isfinite(grid[1]) || !std::isfinite(grid[2]) || !std::isfinite(grid[3])) return false;
+    if (cell_start[0] != 0u || cell_start[C] != n) return false;
+    std::vector<uint64_t> keys;
+    for (uint32_t c = 0; c < C; ++c) {
+        if (cell_start[c] >= cell_start[c + 1] || cell_start[c + 1] > n) return false;
+        for (uint32_t i = cell_start[c]; i < cell_start[c + 1]; ++i) {
+            const uint32_t v = sorted_vox[i], v0 = sorted_vox[cell_start[c]];
+            if (v >= V) return false;
+            for (int a = 0; a < 3; ++a) if (ckey[v * 3 + a] >= (1u << 21) - 1u || ckey[v * 3 + a] != ckey[v0 * 3 + a]) return false;
+        }
+        const uint32_t v0 = sorted_vox[cell_start[c]];
+        keys.push_back(n_pack_key(ckey[v0 * 3], ckey[v0 * 3 + 1], ckey[v0 * 3 + 2]));
+    }
+    std::sort(keys.begin(), keys.end());
+    return std::adjacent_find(keys.begin(), keys.end()) == keys.end();
+}
+uint32_t kp_pow2_ge(size_t x) { uint32_t p = 1; while (p < x) p <<= 1; return p; }
+struct SeedTables { const float* vf; const uint32_t *ckey, *sorted_vox, *cell_start, *hvals; const uint64_t* hkeys; const DevCounters* dc; const SeedGrid* grid; uint32_t hmask; };
+// copies the tables in and builds the hash with d_cell_hash, as seg_seeds does; extra = cells' worth of workgroups beyond what C needs
+SeedTables seed_tables_on(Bufs& B, const float* vf, uint32_t V, const uint32_t* ckey, const uint32_t* sorted_vox, uint32_t n, const uint32_t* cell_start, uint32_t C, const double* grid) {
+    SeedTables t;
+    memset(&t, 0, sizeof t);
+    t.vf = B.mk<float>((size_t)V * 12, vf); t.ckey = B.mk<uint32_t>((size_t)V * 3, ckey); t.sorted_vox = B.mk<uint32_t>(n, sorted_vox); t.cell_start = B.mk<uint32_t>((size_t)C + 1, cell_start);
+    const uint32_t ccap = kp_pow2_ge((size_t)C * 2 + 16);
+    uint64_t* hk = B.mk<uint64_t>(ccap); uint32_t* hv = B.mk<uint32_t>(ccap);
+    if (B.err == hipSuccess) B.err = hipMemset(hk, 0xFF, (size_t)ccap * 8);
+    DevCounters hdc;
+    memset(&hdc, 0, sizeof hdc);
+    hdc.n_voxels = V; hdc.n_cells = C;
+    SeedGrid g;
+    memset(&g, 0, sizeof g);
+    g.defined = 1; g.res = grid[0];
+    for (int a = 0; a < 3; ++a) g.min[a] = grid[1 + a];
+    t.dc = B.mk<DevCounters>(1, &hdc); t.grid = B.mk<SeedGrid>(1, &g);
+    t.hkeys = hk; t.hvals = hv; t.hmask = ccap - 1u;
+    if (B.err != hipSuccess) return t;
+    hipLaunchKernelGGL((kp_call<d_cell_hash, const uint32_t*, const uint32_t*, const uint32_t*, const DevCounters*, uint64_t*, uint32_t*, uint32_t>), dim3(kp_grid_for(C, 256), 1), dim3(d_cell_hash::BLOCK), 0, 0,
+                       t.ckey, t.sorted_vox, t.cell_start, t.dc, hk, hv, ccap - 1u);
+    return t;
+}
+}  // namespace
+extern "C" {
+// d_seed_nn on hand-built cell tables (seed_tables_ok).  grid[4] = res, min[3] of the seed grid.  seed_orig[C + 4 extra]: the words behind C come back as they went in
+// (-1), whatever the extra workgroups do (extra: workgroups beyond (C + 3) / 4, as a batched launch has them)
+int kp_seed_nn(const float* vf, uint32_t V, const uint32_t* ckey, const uint32_t* sorted_vox, uint32_t n, const uint32_t* cell_start, uint32_t C, const double* grid, uint32_t extra, int* seed_orig) {
+    if (!seed_orig || extra > 64 || !seed_tables_ok(vf, V, ckey, sorted_vox, n, cell_start, C, grid)) return KP_EARG;
+    Bufs B;
+    const SeedTables t = seed_tables_on(B, vf, V, ckey, sorted_vox, n, cell_start, C, grid);
+    std::vector<int> init((size_t)C + 4u * extra, -1);
+    int* dso = B.mk<int>(init.size(), init.data());
+    if (B.err != hipSuccess) return (int)B.err;
+    hipLaunchKernelGGL((kp_call<d_seed_nn, const float*, const uint32_t*, const uint32_t*, const uint32_t*, const DevCounters*, const SeedGrid*, const uint64_t*, const uint32_t*, uint32_t, int*>),
+                       dim3((C + 3u) / 4u + extra, 1), dim3(d_seed_nn::BLOCK), 0, 0, t.vf, t.ckey, t.sorted_vox, t.cell_start, t.dc, t.grid, t.hkeys, t.hvals, t.hmask, dso);
+    B.sync(); B.back(seed_orig, (const int*)dso, init.size());
+    return (int)B.err;
+}
+// d_seed_filter on the same tables and seed_orig[C] (every entry a voxel < V: checked).  keep[C + 4 extra]: 0 / 1, and 0xFFFFFFFF behind C
+int kp_seed_filter(const float* vf, uint32_t V, const uint32_t* ckey, const uint32_t* sorted_vox, uint32_t n, const uint32_t* cell_start, uint32_t C, const double* grid, uint32_t extra,
+                   const int* seed_orig, float r2, float min_points, uint32_t* keep) {
+    if (!seed_orig || !keep || extra > 64 || !std::isfinite(r2) || !std::isfinite(min_points) || !seed_tables_ok(vf, V, ckey, sorted_vox, n, cell_start, C, grid)) return KP_EARG;
+    for (uint32_t c = 0; c < C; ++c) if (seed_orig[c] < 0 || (uint32_t)seed_orig[c] >= V) return KP_EARG;
+    Bufs B;
+    const SeedTables t = seed_tables_on(B, vf, V, ckey, sorted_vox, n, cell_start, C, grid);
+    const int* dso = B.mk<int>(C, seed_orig);
+    std::vector<uint32_t> init((size_t)C + 4u * extra, 0xFFFFFFFFu);
+    uint32_t* dk = B.mk<uint32_t>(init.size(), init.data());
+    if (B.err != hipSuccess) return (int)B.err;
+    hipLaunchKernelGGL((kp_call<d_seed_filter, const float*, const uint32_t*, const uint32_t*, const uint32_t*, const DevCounters*, const SeedGrid*, const uint64_t*, const uint32_t*, uint32_t, const int*, float, float, uint32_t*>),
+                       dim3((C + 3u) / 4u + extra, 1), dim3(d_seed_filter::BLOCK), 0, 0, t.vf, t.ckey, t.sorted_vox, t.cell_start, t.dc, t.grid, t.hkeys, t.hvals, t.hmask, dso, r2, min_points, dk);
+    B.sync(); B.back(keep, (const uint32_t*)dk, init.size());
+    return (int)B.err;
+}
+
 }  // extern "C"

@@ -1064,3 +1064,185 @@ def slow_sv(vf, leaves):
         for k in range(9, 12):
             acc[k] = F(acc[k] + F(inv * F(rows[j, k] - acc[k])))
     return rows, acc
+
+
+# ---- the seed stage: d_chunkbox + d_seed_grow, d_seed_nn, d_seed_filter on hand-built tables ------------------------------------------------------
+# The positions are those of the lattice cases of seed_clouds_common.py (voxel_res = 2^-6: ties and bounds are hit exactly), taken as voxel centroids directly, in the
+# order the case lists them: no voxelisation, no leaf order, no sort in front of the kernel under test.  The references are seed_clouds_common.reference() restricted to
+# the tables; slow_*: the literal point-by-point growth loop, and the search over the 27 cells around a cell (what the oracle does) against the search over all voxels.
+import seed_clouds_common as S  # noqa: E402
+
+MAX_SEED_EVENTS = S.MAX_SEED_EVENTS
+REQUIRED["seed_grow"] = ["A%d" % i for i in range(1, 8)] + ["random"]
+REQUIRED["seed_nn"] = ["B%d" % i for i in range(1, 7)] + ["D: large offsets", "D: offset 0", "in-lane ties", "in-lane ties, higher ordinal first"]
+REQUIRED["seed_filter"] = ["C%d" % i for i in range(1, 6)] + ["pruning margin", "min_points an integer"]
+
+
+def _voxels_of(name, reverse=False, shuffle=None):
+    """The distinct points of a case's frame, in frame order (reverse: last first; shuffle: the first stays -- the grid starts from it --, the others in an order drawn from that seed)."""
+    xyz = S.frame_of(name)[:, :3]
+    _, first = np.unique(xyz, axis=0, return_index=True)
+    xyz = xyz[np.sort(first)]
+    if shuffle is not None:
+        xyz = np.vstack([xyz[:1], xyz[1:][np.random.default_rng(shuffle).permutation(len(xyz) - 1)]])
+    return np.ascontiguousarray(xyz[::-1] if reverse else xyz, F)
+
+
+def vf_rows(xyz):
+    vf = np.zeros((len(xyz), 12), F)
+    vf[:, :3] = xyz
+    return vf
+
+
+def seed_grow_cases():
+    prm = lambda n: S.CASE[n].params["seed_res"]
+    out = [Case(n, cls, xyz=_voxels_of(n), seed_res=prm(n), cond=S.CASE[n].cond) for cls, n in (
+        ("A2", "a2-triggers-at-0-255-256"), ("A3", "a3-two-events-in-a-chunk"), ("A4", "a4-event-at-the-last-voxel"), ("A6", "a6-thirteen-events"),
+        ("A7", "a7-cube-edge"))]
+    # A5: the first voxel in the middle, the others below and above it on every axis (positions in voxels of 2^-6, seed_res two of them)
+    a5 = np.array([(10.5, 10.5, 10.5), (0.25, 0.25, 20.5), (20.5, 20.5, 0.25), (23.75, 20.5, 20.5), (20.5, 23.75, 20.5), (20.5, 20.5, 23.75)], F) * F(S.RD)
+    a1 = np.array([(0, 0, 0), (1, 0, 0), (0, 2, 1), (3, 3, 3), (7.5, 7.5, 7.5)], F) * F(S.RD)
+    out.append(Case("a1-single-cell", "A1", xyz=a1, seed_res=8 * S.RD, cond=("events", 1, 1)))
+    out.append(Case("a5-every-direction", "A5", xyz=a5, seed_res=2 * S.RD, cond=("directions",)))
+    rng = np.random.default_rng(77)
+    for i in range(30):
+        n = int(rng.integers(1, 3000))
+        spread = float(rng.choice([0.5, 4.0, 40.0, 600.0]))
+        xyz = (rng.normal(0.0, spread, (n, 3)) + rng.uniform(-100, 100, 3)).astype(F)
+        out.append(Case("random %d" % i, "random", xyz=xyz, seed_res=float(F(rng.choice([0.02, 0.08, 0.5]))), cond=None))
+    return out
+
+
+def ref_seed_grow(c):
+    return S.grow_grid(c.xyz, c.seed_res)
+
+
+def slow_seed_grow(c):
+    """adoptBoundingBoxToPoint point by point: (final minimum, depth, keys, [(trigger, depth)])."""
+    res = float(F(c.seed_res)); eps = S.FLT_EPS
+    mn = [0.0] * 3; mx = [0.0] * 3
+    depth, defined, keys, ev = 0, False, [], []
+    for i, p in enumerate(np.asarray(c.xyz, np.float64).tolist()):
+        while True:
+            up = [p[a] >= mx[a] for a in range(3)]
+            if defined and not any(up) and not any(p[a] < mn[a] for a in range(3)):
+                break
+            if defined:
+                side = float(1 << depth) * res
+                for a in range(3):
+                    if not up[a]:
+                        mn[a] -= side
+                        for k in keys:
+                            k[a] += 1 << depth
+                depth += 1
+                mx = [mn[a] + (float(1 << depth) * res - eps) for a in range(3)]
+            else:
+                mn = [p[a] - res - 0.0 for a in range(3)]       # (the cube of two cells a side around the first point: min = p - res / 2 - res / 2)
+                mn = [(p[a] - res / 2) - (2.0 * res - ((p[a] + res / 2) - (p[a] - res / 2))) / 2.0 for a in range(3)]
+                mx = [(p[a] + res / 2) + (2.0 * res - ((p[a] + res / 2) - (p[a] - res / 2))) / 2.0 for a in range(3)]
+                depth, defined = 1, True
+            ev.append((i, depth))
+        keys.append([int((p[a] - mn[a]) / res) for a in range(3)])
+    return mn, depth, np.array(keys, np.int64), ev
+
+
+class SeedTable:
+    """The arrays seg_seeds hands to d_seed_nn / d_seed_filter for voxel centroids xyz: the cell keys, the voxels sorted by cell (Morton order of the cells, ordinals
+    ascending inside a cell, as the stable radix sort leaves them), the cell starts, the grid."""
+
+    def __init__(self, xyz, seed_res, voxel_res, descending=False):
+        self.xyz = np.ascontiguousarray(xyz, F)
+        self.seed_res, self.voxel_res = seed_res, voxel_res
+        self.ref = S.reference(self.xyz, seed_res, voxel_res)
+        g = self.ref.grid
+        self.V = len(self.xyz)
+        self.vf = vf_rows(self.xyz)
+        self.ckey = np.ascontiguousarray(g.keys, U32)
+        self.sorted_vox = np.ascontiguousarray(np.argsort(self.ref.cell_of, kind="stable"), U32)
+        self.C = len(self.ref.cell_keys)
+        self.cell_start = np.zeros(self.C + 1, U32)
+        self.cell_start[1:] = np.cumsum(np.bincount(self.ref.cell_of, minlength=self.C))
+        if descending:      # a cell's list with the highest ordinal first: the kernels' minimum under (distance, ordinal) does not depend on the order they visit a list in
+            for c in range(self.C):
+                self.sorted_vox[self.cell_start[c]:self.cell_start[c + 1]] = self.sorted_vox[self.cell_start[c]:self.cell_start[c + 1]][::-1].copy()
+        self.grid = np.array([g.res, g.min[0], g.min[1], g.min[2]], np.float64)
+        self.r2 = S.radius_sq(seed_res)
+        self.min_points = S.min_points(seed_res, voxel_res)
+
+
+def _table_case(cls, name, reverse=False, shuffle=None):
+    p = S.CASE[name].params
+    return Case(name, cls, table=SeedTable(_voxels_of(name, reverse, shuffle), p["seed_res"], p["voxel_res"]), cond=S.CASE[name].cond)
+
+
+TIE_AT = (5, 69, 100, 261)      # list positions of the four tied voxels: 5, 69 and 261 fall to lane 5 (the second of its four entries of a round, and the next round)
+
+
+def _tie_table(descending):
+    """One cell of 304 voxels: four at distance 1 from its centre, at the list positions TIE_AT, 300 further out.  With the list descending the lane that holds three
+    of the tied voxels meets the highest ordinal first and the lowest -- the answer -- last."""
+    m = S.M
+    centre = (np.array([2, 2, 2]) + 0.5) * m
+    fill = S.cell_slots(m, (2, 2, 2))
+    fill = fill[((fill - centre) ** 2).sum(axis=1) >= 4.0][:300]
+    tied = [centre + (1, 0, 0), centre - (1, 0, 0), centre + (0, 1, 0), centre - (0, 1, 0)]
+    cell, k = [], 0
+    for pos in range(304):
+        if pos in TIE_AT:
+            cell.append(tied[TIE_AT.index(pos)])
+        else:
+            cell.append(fill[k]); k += 1
+    cell = np.array(cell)
+    q = np.vstack([[[0, 0, 0]], cell[::-1] if descending else cell])      # (voxel 0 starts the grid; descending: the list's first entry is the last voxel)
+    return SeedTable((q * S.RD).astype(F), m * S.RD, S.RD, descending=descending)
+
+
+def seed_nn_cases():
+    return [Case("ties 64 and 256 entries apart, list ascending", "in-lane ties", table=_tie_table(False), cond=None),
+            Case("ties 64 and 256 entries apart, list descending", ["in-lane ties", "in-lane ties, higher ordinal first"], table=_tie_table(True), cond=None),
+            _table_case("B1", "b1-shortcut-and-not"), _table_case(["B2", "B7"], "b2-b7-corner-cut"), _table_case("B3", "b3-ties", shuffle=3), _table_case("B4", "b4-key-zero", reverse=True),
+            _table_case("B5", "b5-cell-sizes"), _table_case("B6", "b6-big-blocks"), _table_case("D: large offsets", "d-offset-600"), _table_case("D: offset 0", "d-offset-0")]
+
+
+def seed_filter_cases():
+    return [_table_case("C1", "c1-counts"), _table_case("C2", "c2-at-the-radius"), _table_case("C3", "c3-eight-cells"), _table_case("C4", "c4-own-cell-only"),
+            _table_case("C5", "c5-pruned-neighbours"), _table_case("pruning margin", "c8-face-near-the-radius"), _table_case("min_points an integer", "c9-min-points-exactly-2"),
+            _table_case("B6 totals", "b6-big-blocks"), _table_case("B5 totals", "b5-cell-sizes")]
+
+
+def ref_seed_nn(t):
+    return t.ref.seed_orig
+
+
+def ref_seed_filter(t):
+    return t.ref.keep.astype(U32)
+
+
+def _block27(t, key):
+    by_key = {tuple(k): c for c, k in enumerate(t.ref.cell_keys.tolist())}
+    out = []
+    for dx in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            for dz in (-1, 0, 1):
+                c = by_key.get((key[0] + dx, key[1] + dy, key[2] + dz))
+                if c is not None:
+                    out.append(np.nonzero(t.ref.cell_of == c)[0])
+    return np.sort(np.concatenate(out))
+
+
+def slow_seed_nn(t):
+    """The nearest voxel among the 27 cells around each cell only (the oracle's search)."""
+    out = np.zeros(t.C, np.int32)
+    for c, key in enumerate(t.ref.cell_keys.tolist()):
+        cand = _block27(t, key)
+        d = S.sqdist(t.ref.centres[c], t.xyz[cand])
+        out[c] = cand[int(np.argmin(d))]
+    return out
+
+
+def slow_seed_filter(t, seed_orig):
+    out = np.zeros(t.C, U32)
+    for c, s in enumerate(seed_orig):
+        cand = _block27(t, t.ref.grid.keys[s].tolist())
+        out[c] = int((S.sqdist(t.xyz[s], t.xyz[cand]) < t.r2).sum()) > t.min_points
+    return out

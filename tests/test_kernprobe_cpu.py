@@ -171,7 +171,8 @@ def kp_nogpu(kp_built):
 
 CASES = {"scan64": lambda: K.scan_cases(64), "scan256": lambda: K.scan_cases(256), "minsort": K.minsort_cases, "run_of_lane": K.run_cases, "scan_single": K.scan_single_cases,
          "scan_u32": K.scan_u32_cases, "radix_pass": K.radix_pass_cases, "radix_sort": K.radix_sort_cases, "seg_table": K.seg_cases, "relabel": K.relabel_cases,
-         "tile_list": K.tile_list_cases, "row_leaves": K.row_leaves_cases, "centroid": K.centroid_states, "sv_fill": K.sv_fill_states}
+         "tile_list": K.tile_list_cases, "row_leaves": K.row_leaves_cases, "centroid": K.centroid_states, "sv_fill": K.sv_fill_states,
+         "seed_grow": K.seed_grow_cases, "seed_nn": K.seed_nn_cases, "seed_filter": K.seed_filter_cases}
 _cache = {}
 
 
