@@ -307,6 +307,15 @@ def load_library(path=None):
         lib.f3ds_region_components_tiled.restype = ctypes.c_int
         lib.f3ds_region_components.argtypes = [vp, ctypes.POINTER(RgbdFormat), vp, vp, ctypes.c_uint32, ckp, ctypes.c_int, vp, vp, sz, ctypes.c_int, ctypes.POINTER(sz), rkp]
         lib.f3ds_region_components.restype = ctypes.c_int
+    if hasattr(lib, "f3ds_region_table_batch"):      # the batch forms: arrays of per-frame pointers (void**), counts and results
+        pp, fp, i32 = ctypes.POINTER(vp), ctypes.POINTER(RgbdFormat), ctypes.c_int
+        lib.f3ds_region_table_batch.argtypes = [pp, i32, fp, pp, pp, pp, vp, i32, pp, i32, vp, vp]
+        lib.f3ds_region_shapes_batch.argtypes = [pp, i32, fp, pp, pp, vp, i32, pp, i32, vp, vp]
+        lib.f3ds_region_boxes_batch.argtypes = [pp, i32, fp, pp, pp, vp, ctypes.c_float, i32, pp, pp, i32, vp, vp]
+        lib.f3ds_region_contacts_batch.argtypes = [pp, i32, fp, pp, pp, vp, ctypes.c_float, i32, pp, vp, i32, vp, vp, vp]
+        lib.f3ds_region_components_batch.argtypes = [pp, i32, fp, pp, pp, vp, ctypes.POINTER(ComponentParams), i32, pp, pp, vp, i32, vp, vp, vp]
+        for name in ("table", "shapes", "boxes", "contacts", "components"):
+            getattr(lib, "f3ds_region_%s_batch" % name).restype = ctypes.c_int
     lib.f3ds_recluster.argtypes = [vp, ctypes.POINTER(Params), vp, ctypes.c_int, ctypes.POINTER(Result)]
     lib.f3ds_recluster.restype = ctypes.c_int
     lib.f3ds_evaluate.argtypes = [vp, vp, ctypes.POINTER(Performance)]; lib.f3ds_evaluate.restype = ctypes.c_int
@@ -1426,6 +1435,231 @@ def evaluate_levels_batch(ctxs, truths, thresholds, on_device=False):
     nreg = np.zeros((max(m, 1), max(k, 1)), np.uint32)
     _check(lib, lib.f3ds_evaluate_levels_batch(handles, m, tp, 1 if on_device else 0, t.ctypes.data, k, ps, nreg.ctypes.data))
     return [[ps[i * k + l] for l in range(k)] for i in range(m)], nreg[:m, :k]
+
+
+# ---- batch forms of the five region calls ----------------------------------------------------------
+# One call for len(ctxs) frames of ONE format (one context per frame, all on one GPU): one dispatch per kernel, one wait.  Every function returns
+# (frames, status): frames[i] is what the Context method of the same name returns for frame i, status an int32 array of the frames' outcomes (OK, ERR_ARG for a
+# label >= n_regions[i], ERR_CAPACITY); the rows (and image) of a frame that failed are None, its result too after ERR_ARG.  An exception is raised, as by the
+# Context methods, only when the call as a whole was refused.
+_STATUS_UNSET = 1      # (no error code is positive: a status array that still holds this was not written, so the call as a whole was refused)
+
+
+def _opt_ptr(p):
+    return None if p is None else _device_ptr(p)
+
+
+def _region_batch_inputs(ctxs, depths, labels, n_regions, fmt, colors, on_device):
+    """(k, handles, format, depth / colour / label pointer arrays, region counts, status, what must stay alive) of a batch call"""
+    k = len(ctxs)
+    if k < 1:
+        raise ValueError("a batch needs at least one context")
+    for name, seq in (("depths", depths), ("labels", labels), ("n_regions", n_regions)):
+        if len(seq) != k:
+            raise ValueError("%s must hold one entry per context" % name)
+    if colors is not None:
+        if len(colors) != k:
+            raise ValueError("colors must hold one entry per context")
+        if all(c is None for c in colors):
+            colors = None
+        elif any(c is None for c in colors):
+            raise ValueError("colors: an image for every frame or for none (one command sequence for the batch)")
+    vp = ctypes.c_void_p
+    handles = (vp * k)(*[c.handle for c in ctxs])
+    nr = (ctypes.c_uint32 * k)(*[int(x) for x in n_regions])
+    status = np.full(k, _STATUS_UNSET, np.int32)
+    if on_device:
+        f, keep = fmt, None
+        dp = (vp * k)(*[_device_ptr(d) for d in depths]); lp = (vp * k)(*[_device_ptr(x) for x in labels])
+        cp = None if colors is None else (vp * k)(*[_device_ptr(c) for c in colors])
+    else:
+        keep = [_region_inputs(fmt, d, lab, None if colors is None else colors[i]) for i, (d, lab) in enumerate(zip(depths, labels))]
+        f = keep[0][0]
+        for g in keep[1:]:
+            if (g[0].depth_pitch, g[0].color_pitch) != (f.depth_pitch, f.color_pitch):
+                raise ValueError("the images of a batch must share their row strides (one f3ds_rgbd_format for the batch)")
+        dp = (vp * k)(*[vp(x[1].ctypes.data) for x in keep]); lp = (vp * k)(*[vp(x[3].ctypes.data) for x in keep])
+        cp = None if colors is None else (vp * k)(*[vp(x[2].ctypes.data) for x in keep])
+    return k, handles, f, dp, cp, lp, nr, status, keep
+
+
+def _outs(seq, k, name):
+    if seq is None:
+        return [None] * k
+    if len(seq) != k:
+        raise ValueError("%s must hold one entry per context" % name)
+    return list(seq)
+
+
+def _batch_done(lib, rc, status):
+    """raise iff the call as a whole was refused (or failed): the frames' statuses were not written then"""
+    if rc != 0 and (status == _STATUS_UNSET).all():
+        _check(lib, rc)
+    return status
+
+
+def _fixed_rows_batch(fn, make_rows, res_type, ctxs, depths, labels, n_regions, fmt, colors, rows_out, on_device, lead=(), with_color=False):
+    """the batch calls with one row per region (table, shapes): fn(handles, k, fmt, depth[, color], labels, n_regions, *lead, on_device, rows, on_device, results, status)"""
+    lib = load_library()
+    k, handles, f, dp, cp, lp, nr, status, keep = _region_batch_inputs(ctxs, depths, labels, n_regions, fmt, colors, on_device)
+    vp = ctypes.c_void_p
+    outs, results = _outs(rows_out, k, "rows_out"), (res_type * k)()
+    if on_device:
+        rows = [None] * k
+        rp = (vp * k)(*[_opt_ptr(o) for o in outs])
+    else:
+        rows = [make_rows(o, nr[i]) for i, o in enumerate(outs)]
+        rp = (vp * k)(*[vp(r.ctypes.data) if len(r) else None for r in rows])
+    where = 1 if on_device else 0
+    images = (dp, cp, lp) if with_color else (dp, lp)
+    rc = fn(handles, k, ctypes.byref(f), *images, nr, *lead, where, rp, where, results, status.ctypes.data)
+    _batch_done(lib, rc, status)
+    return [(rows[i] if status[i] == 0 else None, results[i] if status[i] == 0 else None) for i in range(k)], status
+
+
+def region_table_batch(ctxs, depths, labels, n_regions, fmt, colors=None, rows_out=None, on_device=False):
+    """f3ds_region_table_batch: Context.region_table for every frame at once.  depths / labels / colors: lists of arrays, or of device pointers / torch tensors
+    with ``on_device`` (``rows_out`` is then a list of device buffers); colors: an image for every frame, or None.  Returns ([(rows, RegionTableResult)], status)."""
+    return _fixed_rows_batch(load_library().f3ds_region_table_batch, _region_rows, RegionTableResult, ctxs, depths, labels, n_regions, fmt, colors, rows_out, on_device,
+                             with_color=True)
+
+
+def region_shapes_batch(ctxs, depths, labels, n_regions, fmt, rows_out=None, on_device=False):
+    """f3ds_region_shapes_batch: Context.region_shapes for every frame at once (lists as in region_table_batch).  Returns ([(rows, RegionShapesResult)], status)."""
+    return _fixed_rows_batch(load_library().f3ds_region_shapes_batch, _shape_rows, RegionShapesResult, ctxs, depths, labels, n_regions, fmt, None, rows_out, on_device)
+
+
+def region_boxes_batch(ctxs, depths, labels, n_regions, fmt, plane_tol=0.01, rows_out=None, shapes_out=None, on_device=False):
+    """f3ds_region_boxes_batch: Context.region_boxes for every frame at once (lists as in region_table_batch).  ``shapes_out``: None, ``True`` (host form: new
+    arrays) or a list of buffers, for every frame or for none.  Returns ([(rows, RegionBoxesResult)], status), or ([(rows, shapes, RegionBoxesResult)], status)
+    with shapes."""
+    lib = load_library()
+    k, handles, f, dp, _, lp, nr, status, keep = _region_batch_inputs(ctxs, depths, labels, n_regions, fmt, None, on_device)
+    vp = ctypes.c_void_p
+    outs, results = _outs(rows_out, k, "rows_out"), (RegionBoxesResult * k)()
+    want = shapes_out is not None and shapes_out is not False
+    souts = [None] * k if (shapes_out is True or not want) else _outs(shapes_out, k, "shapes_out")
+    if want and shapes_out is not True and any(s is None for s in souts):
+        raise ValueError("shapes_out: a buffer for every frame or None (one command sequence for the batch)")
+    if on_device:
+        if shapes_out is True:
+            raise ValueError("on_device needs device buffers for the shape rows")
+        rows, shapes = [None] * k, [None] * k
+        rp = (vp * k)(*[_opt_ptr(o) for o in outs])
+        sp = (vp * k)(*[_opt_ptr(o) for o in souts]) if want else None
+    else:
+        rows = [_box_rows(o, nr[i]) for i, o in enumerate(outs)]
+        shapes = [_shape_rows(o, nr[i]) for i, o in enumerate(souts)] if want else [None] * k
+        rp = (vp * k)(*[vp(r.ctypes.data) if len(r) else None for r in rows])
+        sp = (vp * k)(*[vp(s.ctypes.data) if len(s) else None for s in shapes]) if want else None
+    where = 1 if on_device else 0
+    rc = lib.f3ds_region_boxes_batch(handles, k, ctypes.byref(f), dp, lp, nr, float(plane_tol), where, rp, sp, where, results, status.ctypes.data)
+    _batch_done(lib, rc, status)
+    ok = status == 0
+    if want:
+        return [(rows[i] if ok[i] else None, shapes[i] if ok[i] else None, results[i] if ok[i] else None) for i in range(k)], status
+    return [(rows[i] if ok[i] else None, results[i] if ok[i] else None) for i in range(k)], status
+
+
+def _capped_rows_batch(call, k, rows_out, on_device, dtype):
+    """The rows of the batch calls whose row counts the device decides (contacts, components).  call(rows pointer array or None, caps, n_out, frames) -> rc runs
+    the listed frames; host form without ``rows_out[i]``: a buffer that turns out too small is grown from the count and those frames run once more."""
+    vp, sz = ctypes.c_void_p, ctypes.c_size_t
+    outs = _outs(rows_out, k, "rows_out")
+    n_out = (sz * k)()
+    frames = list(range(k))
+    if on_device:
+        pairs = [(None, 0) if o is None else (_device_ptr(o[0]), int(o[1])) for o in outs]
+        rp = (vp * k)(*[p for p, _ in pairs]) if any(o is not None for o in outs) else None
+        rc = call(rp, (sz * k)(*[c for _, c in pairs]), n_out, frames)
+        return rc, [None] * k, n_out
+    bufs = []
+    for o in outs:
+        if o is not None and not (isinstance(o, np.ndarray) and o.dtype == dtype and o.flags.c_contiguous and o.ndim == 1):
+            raise ValueError("rows_out[i] must be a contiguous one-dimensional array of the rows' dtype (%d bytes per row)" % dtype.itemsize)
+        bufs.append(np.empty(_CONTACT_ROWS_FIRST, dtype) if o is None else o)
+    rp = (vp * k)(*[vp(b.ctypes.data) if len(b) else None for b in bufs])
+    rc = call(rp, (sz * k)(*[len(b) for b in bufs]), n_out, frames)
+    return rc, bufs, n_out
+
+
+def _capped_deliver(lib, call, rc, status, bufs, n_out, rows_out, dtype, on_device):
+    """after the first run: the frames without a buffer of the caller's that were one short run again with room for all; then the rows of the frames that are OK"""
+    _batch_done(lib, rc, status)
+    k = len(status)
+    vp, sz = ctypes.c_void_p, ctypes.c_size_t
+    outs = _outs(rows_out, k, "rows_out")
+    if not on_device:
+        again = [i for i in range(k) if status[i] == ERR_CAPACITY and outs[i] is None]
+        if again:
+            for i in again:
+                bufs[i] = np.empty(n_out[i], dtype)
+            sub = np.full(len(again), _STATUS_UNSET, np.int32)
+            sub_n = (sz * len(again))()
+            rc = call((vp * len(again))(*[vp(bufs[i].ctypes.data) for i in again]), (sz * len(again))(*[len(bufs[i]) for i in again]), sub_n, again, sub)
+            _batch_done(lib, rc, sub)
+            for j, i in enumerate(again):
+                status[i] = sub[j]; n_out[i] = sub_n[j]
+        return [(bufs[i][:n_out[i]] if outs[i] is not None else bufs[i][:n_out[i]].copy()) if status[i] == 0 else None for i in range(k)]
+    return [None] * k
+
+
+def region_contacts_batch(ctxs, depths, labels, n_regions, fmt, depth_tol=0.05, rows_out=None, on_device=False):
+    """f3ds_region_contacts_batch: Context.region_contacts for every frame at once (lists as in region_table_batch; ``rows_out``: a list of arrays to fill, or with
+    ``on_device`` of ``(device pointer, capacity in rows)`` / None).  Returns ([(rows, RegionContactsResult)], status)."""
+    lib = load_library()
+    k, handles, f, dp, _, lp, nr, status, keep = _region_batch_inputs(ctxs, depths, labels, n_regions, fmt, None, on_device)
+    vp = ctypes.c_void_p
+    results = (RegionContactsResult * k)()
+    where = 1 if on_device else 0
+
+    def call(rp, caps, n_out, frames, st=status):
+        m = len(frames)
+        pick = lambda arr, ty: (ty * m)(*[arr[i] for i in frames])
+        sub_res = (RegionContactsResult * m)()
+        rc = lib.f3ds_region_contacts_batch(pick(handles, vp), m, ctypes.byref(f), pick(dp, vp), pick(lp, vp), pick(nr, ctypes.c_uint32), float(depth_tol), where, rp, caps, where,
+                                            n_out, sub_res, st.ctypes.data)
+        for j, i in enumerate(frames):
+            if st[j] != _STATUS_UNSET:
+                results[i] = sub_res[j]
+        return rc
+
+    rc, bufs, n_out = _capped_rows_batch(call, k, rows_out, on_device, REGION_CONTACT_DTYPE)
+    rows = _capped_deliver(lib, call, rc, status, bufs, n_out, rows_out, REGION_CONTACT_DTYPE, on_device)
+    return [(rows[i], results[i] if status[i] != ERR_ARG else None) for i in range(k)], status
+
+
+def region_components_batch(ctxs, depths, labels, n_regions, fmt, depth_tol=0.05, min_pixels=1, rows_out=None, comp_out=None, on_device=False):
+    """f3ds_region_components_batch: Context.region_components for every frame at once (lists as in region_contacts_batch; ``comp_out``: with ``on_device`` a list
+    of device buffers of width * height words).  Returns ([(comp_labels, rows, RegionComponentsResult)], status)."""
+    lib = load_library()
+    k, handles, f, dp, _, lp, nr, status, keep = _region_batch_inputs(ctxs, depths, labels, n_regions, fmt, None, on_device)
+    vp = ctypes.c_void_p
+    prm, results = ComponentParams(float(depth_tol), int(min_pixels)), (RegionComponentsResult * k)()
+    where = 1 if on_device else 0
+    if on_device:
+        if comp_out is None or len(comp_out) != k:
+            raise ValueError("on_device needs one device image per context in comp_out")
+        comps = [None] * k
+        kp = (vp * k)(*[_opt_ptr(o) for o in comp_out])
+    else:
+        comps = [np.empty((int(fmt.height), int(fmt.width)), np.uint32) for _ in range(k)]
+        kp = (vp * k)(*[vp(c.ctypes.data) for c in comps])
+
+    def call(rp, caps, n_out, frames, st=status):
+        m = len(frames)
+        pick = lambda arr, ty: (ty * m)(*[arr[i] for i in frames])
+        sub_res = (RegionComponentsResult * m)()
+        rc = lib.f3ds_region_components_batch(pick(handles, vp), m, ctypes.byref(f), pick(dp, vp), pick(lp, vp), pick(nr, ctypes.c_uint32), ctypes.byref(prm), where, pick(kp, vp),
+                                              rp, caps, where, n_out, sub_res, st.ctypes.data)
+        for j, i in enumerate(frames):
+            if st[j] != _STATUS_UNSET:
+                results[i] = sub_res[j]
+        return rc
+
+    rc, bufs, n_out = _capped_rows_batch(call, k, rows_out, on_device, REGION_COMPONENT_DTYPE)
+    rows = _capped_deliver(lib, call, rc, status, bufs, n_out, rows_out, REGION_COMPONENT_DTYPE, on_device)
+    return [(comps[i] if status[i] != ERR_ARG else None, rows[i], results[i] if status[i] != ERR_ARG else None) for i in range(k)], status
 
 
 def best_level(thresholds, scores):

@@ -1067,60 +1067,86 @@ int download_queued(Batch& b, hipStream_t dl) { if (dl) HIPCHECK(hipEventRecord(
 int download_wait(Batch& b, hipStream_t dl) { if (dl) HIPCHECK(timed_sync(b.owner->ev_copy[2])); return F3DS_OK; }
 
 // ---- the label-image frame (f3ds_label_image.h, DESIGN.md "the label-image frame"): what the tracker update and the five region calls do alike.  A region call
-// reads: check -> li_begin -> its buffers (li_out_buffers) -> li_upload -> its arguments and kernels -> flush -> li_download_head -> deliver (li_rows_behind). ----
-// Start of a label-image call, after its checks: the switches, the device, the batch of the one context
+// reads: check -> li_begin -> its staging (li_out_buffers) -> li_upload -> per frame its scratch, arguments and kernels -> flush -> li_download_heads -> deliver
+// (li_rows_behind).  Every helper takes a batch of frames; a lone call is a batch of one. ----
+// Start of a label-image call, after its checks: the switches, the device, the batch of the one context ...
 int li_begin(f3ds_ctx* c, Batch* b) {
     g_sw.read();
     HIPCHECK(hipSetDevice(c->device));
     *b = batch_of(c);
     return F3DS_OK;
 }
-// The images as the kernels read them: device inputs where they are; host inputs in the family's staging, uploaded through the device's copy stream like
-// those of f3ds_segment_rgbd.  color may be NULL.
+// ... or of ctxs[0 .. nctx) (distinct_contexts_on_one_device), on the first one's stream
+int li_begin(f3ds_ctx** ctxs, int nctx, Batch* b) {
+    g_sw.read();
+    HIPCHECK(hipSetDevice(ctxs[0]->device));
+    return batch_of(ctxs, nctx, *b);
+}
+// The images as the kernels read them: device inputs where they are; host inputs in the staging of the frame's own context, uploaded through the device's copy
+// stream like those of f3ds_segment_rgbd -- the copies of all frames are queued there and awaited once.  color may be NULL (no frame has a colour image).
 struct LiImages { const unsigned char* depth; const unsigned char* color; const uint32_t* labels; };
-int li_upload(f3ds_ctx* c, Batch& b, const RgbdLayout& lay, const void* depth, const void* color, const uint32_t* labels, int inputs_on_device, LiImages* im) {
-    *im = LiImages{static_cast<const unsigned char*>(depth), static_cast<const unsigned char*>(color), labels};
+int li_upload(f3ds_ctx* const* ctxs, int nctx, Batch& b, const RgbdLayout& lay, const void* const* depth, const void* const* color, const uint32_t* const* labels, int inputs_on_device,
+              LiImages* im) {
+    for (int i = 0; i < nctx; ++i) im[i] = LiImages{static_cast<const unsigned char*>(depth[i]), color ? static_cast<const unsigned char*>(color[i]) : nullptr, labels[i]};
     if (inputs_on_device) return F3DS_OK;
-    unsigned char *ud, *uc = nullptr; uint32_t* ul;
-    ENSURE(c->li_depth, lay.depth_bytes, ud); ENSURE(c->li_lab, lay.n, ul);
-    if (color) ENSURE(c->li_color, lay.color_bytes, uc);
-    hipStream_t up = g_sw.copy_stream ? copy_stream_of(c->device) : nullptr;
-    HIPCHECK(hipMemcpyAsync(ud, depth, lay.depth_bytes, hipMemcpyHostToDevice, up ? up : b.st));
-    if (color) HIPCHECK(hipMemcpyAsync(uc, color, lay.color_bytes, hipMemcpyHostToDevice, up ? up : b.st));
-    HIPCHECK(hipMemcpyAsync(ul, labels, lay.n * 4, hipMemcpyHostToDevice, up ? up : b.st));
+    hipStream_t up = g_sw.copy_stream ? copy_stream_of(b.owner->device) : nullptr;
+    for (int i = 0; i < nctx; ++i) {
+        f3ds_ctx* c = ctxs[i];
+        unsigned char *ud, *uc = nullptr; uint32_t* ul;
+        ENSURE(c->li_depth, lay.depth_bytes, ud); ENSURE(c->li_lab, lay.n, ul);
+        if (color) ENSURE(c->li_color, lay.color_bytes, uc);
+        HIPCHECK(hipMemcpyAsync(ud, depth[i], lay.depth_bytes, hipMemcpyHostToDevice, up ? up : b.st));
+        if (color) HIPCHECK(hipMemcpyAsync(uc, color[i], lay.color_bytes, hipMemcpyHostToDevice, up ? up : b.st));
+        HIPCHECK(hipMemcpyAsync(ul, labels[i], lay.n * 4, hipMemcpyHostToDevice, up ? up : b.st));
+        im[i] = LiImages{ud, uc, ul};
+    }
     if (up) { if (const int urc = await_uploads(b, up)) return urc; }
-    *im = LiImages{ud, uc, ul};
     return F3DS_OK;
 }
-// Where a region call's kernels write what goes down: *out = out_bytes of device staging (the head first), and the context's one pinned buffer behind it,
-// grown by a quarter beyond the request when it is too short (its contents are lost)
-int li_out_buffers(f3ds_ctx* c, size_t out_bytes, unsigned char** out) {
-    ENSURE(c->li_out, out_bytes, *out);
-    if (c->h_li_cap < out_bytes) {
+int li_upload(f3ds_ctx* c, Batch& b, const RgbdLayout& lay, const void* depth, const void* color, const uint32_t* labels, int inputs_on_device, LiImages* im) {
+    return li_upload(&c, 1, b, lay, &depth, color ? &color : nullptr, &labels, inputs_on_device, im);
+}
+// Where a region call's kernels write what goes down: the staging of all frames is the OWNER's (li_stage_layout, f3ds_label_image.h: the heads first, the
+// payloads of host callers behind them), device memory and the owner's one pinned buffer of the same layout, grown by a quarter beyond the request when it is
+// too short (its contents are lost).  fixed / stage_rows: per frame, as li_stage_layout takes them.
+struct LiStage {
+    f3ds_ctx* o = nullptr; unsigned char* out = nullptr; std::vector<LiSlot> slot; size_t first_bytes = 0, total = 0;
+    uint32_t* head(int i) const { return reinterpret_cast<uint32_t*>(out + (size_t)i * LI_HEAD_BYTES); }      // device
+    const uint32_t* h_head(int i) const { return reinterpret_cast<const uint32_t*>(o->h_li + (size_t)i * LI_HEAD_BYTES); }      // after li_download_heads (8-byte aligned)
+};
+int li_out_buffers(f3ds_ctx* c, int nctx, const size_t* fixed, const size_t* stage_rows, size_t row_bytes, size_t first_rows, LiStage* s) {
+    s->o = c; s->slot.resize((size_t)nctx);
+    s->total = li_stage_layout((size_t)nctx, fixed, stage_rows, row_bytes, first_rows, s->slot.data(), &s->first_bytes);
+    ENSURE(c->li_out, s->total, s->out);
+    if (c->h_li_cap < s->total) {
         if (c->h_li) { HIPCHECK(hipHostFree(c->h_li)); c->h_li = nullptr; c->h_li_cap = 0; }
-        HIPCHECK(hipHostMalloc(&c->h_li, out_bytes + out_bytes / 4, hipHostMallocDefault));
-        c->h_li_cap = out_bytes + out_bytes / 4;
+        HIPCHECK(hipHostMalloc(&c->h_li, s->total + s->total / 4, hipHostMallocDefault));
+        c->h_li_cap = s->total + s->total / 4;
     }
     return F3DS_OK;
 }
-// ONE download, the call's only wait in the ordinary case: the head and `behind` bytes behind it.  h = the head's words; F3DS_ERR_ARG when a label was
-// >= n_regions: the kernels wrote nothing but the head then, and nothing is copied out.
-int li_download_head(f3ds_ctx* c, Batch& b, const unsigned char* out, size_t behind, uint32_t (&h)[LI_HEAD_WORDS]) {
-    HIPCHECK(hipMemcpyAsync(c->h_li, out, LI_HEAD_BYTES + behind, hipMemcpyDeviceToHost, b.st));
+// ONE download, the call's only wait in the ordinary case: the heads of all frames and what li_stage_layout put into reach behind them (with device outputs
+// the heads alone).  Word [1] of a frame's head says that one of its labels was >= n_regions: its kernels wrote nothing but the head then.
+int li_download_heads(const LiStage& s, Batch& b) {
+    HIPCHECK(hipMemcpyAsync(s.o->h_li, s.out, s.first_bytes, hipMemcpyDeviceToHost, b.st));
     HIPCHECK(timed_sync(b.st));
     HIPCHECK(hipGetLastError());
-    memcpy(h, c->h_li, LI_HEAD_BYTES);
-    return h[1] ? F3DS_ERR_ARG : F3DS_OK;
+    return F3DS_OK;
 }
-// A host caller's `count` rows, which start `rows_at` bytes into the staging: the first download brought `first` of them, a frame with more (rare) gets the rest
-// in a second one
-int li_rows_behind(f3ds_ctx* c, Batch& b, const unsigned char* out, size_t rows_at, size_t row_bytes, size_t count, size_t first, void* rows) {
-    if (count > first) {
-        const size_t off = rows_at + first * row_bytes;
-        HIPCHECK(hipMemcpyAsync(c->h_li + off, out + off, (count - first) * row_bytes, hipMemcpyDeviceToHost, b.st));
-        HIPCHECK(timed_sync(b.st));
+// The rows of host callers whose count the device decided: frame i has count[i] rows to deliver into rows[i] (0: none -- no rows asked for, or the frame
+// failed).  The first download brought slot[i].first of them; the frames with more (rare) get the rest in further copies, which are queued together and
+// awaited once.
+int li_rows_behind(const LiStage& s, Batch& b, int nctx, size_t row_bytes, const size_t* count, void* const* rows) {
+    bool more = false;
+    for (int i = 0; i < nctx; ++i) {
+        const LiSlot& sl = s.slot[(size_t)i];
+        if (count[i] <= sl.first) continue;
+        const size_t off = sl.rows_at + sl.first * row_bytes;
+        HIPCHECK(hipMemcpyAsync(s.o->h_li + off, s.out + off, (count[i] - sl.first) * row_bytes, hipMemcpyDeviceToHost, b.st));
+        more = true;
     }
-    memcpy(rows, c->h_li + rows_at, count * row_bytes);
+    if (more) HIPCHECK(timed_sync(b.st));
+    for (int i = 0; i < nctx; ++i) if (count[i]) memcpy(rows[i], s.o->h_li + s.slot[(size_t)i].rows_at, count[i] * row_bytes);
     return F3DS_OK;
 }
 // Start of every accessor: ARG for no context, LOGIC for a context that does not hold what the call needs -- both before any HIP call --, then the
@@ -2584,241 +2610,334 @@ extern "C" int f3ds_tracker_update(f3ds_tracker* t, const f3ds_rgbd_format* fmt_
 
 // ------------------------------------------------------------------------------------------------
 // The five region calls share the label-image frame (li_begin ... li_rows_behind, above): the images of a host caller go up through the family's staging, the
-// kernels of a call are recorded into one flush, and what goes down -- the head and, for a host caller, what rides behind it on the call's stream, not through the
-// copy stream -- is ONE download, the call's only wait in the ordinary case.  The staging (li_*) holds nothing once a call has returned; the working state between
-// a call's kernels is the call's own (rgt_acc, rgc_*, rgs_acc, rgx_*, rgk_*; pass one of the boxes adds into rgs_acc, which both of its users zero first and which
-// holds nothing between calls), so no call disturbs what another one of the context reads.
+// kernels of a call are recorded into one flush, and what goes down -- the heads and, for a host caller, what rides behind them on the call's stream, not through
+// the copy stream -- is ONE download, the call's only wait in the ordinary case.  The staging (li_*) holds nothing once a call has returned; the working state
+// between a call's kernels is the call's own (rgt_acc, rgc_*, rgs_acc, rgx_*, rgk_*; pass one of the boxes adds into rgs_acc, which both of its users zero first and
+// which holds nothing between calls), so no call disturbs what another one of the context reads.
 //
-// region table (f3ds_regions.h / .inc, DESIGN.md section 18): one row per region of a label image over an RGB-D frame.  Three kernels -- d_region_init,
-// d_region_accum (the one read of the images), d_region_finish; behind the head the rows of a host caller (72 B per region).
+// Every call is written ONCE, for a batch of frames: f3ds_region_<x>_batch checks, stages, records every frame through <x>_record (one
+// frame: its scratch, its argument struct, its rec<> lines), flushes -- one dispatch per kernel, grid.y = frame -- downloads once and delivers frame by frame;
+// f3ds_region_<x> is that batch of one frame, with the same kernels, grids and waits as ever.  The staging of all frames and their uploads come before the first
+// <x>_record; the scratch a frame's <x>_record ensures is its own context's, which only that context's recorded calls refer to (the regrow guard of ensure()).
+// A frame's status is what the lone call returns once it has looked at pixels; the call returns the status of the lowest failing frame.
 // ------------------------------------------------------------------------------------------------
-extern "C" int f3ds_region_table(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const void* color, const uint32_t* labels, uint32_t n_regions, int inputs_on_device,
-                                 f3ds_region_row* rows, int rows_on_device, f3ds_region_table_result* result) {
-    if (!c) return F3DS_ERR_ARG;
-    f3ds_rgbd_format fmt; f3ds::RgbdLayout lay;
-    if (const int rc = rg_check(fmt_, depth, color, labels, n_regions, rows, &fmt, &lay)) return rc;
-    Batch b;
-    if (const int rc = li_begin(c, &b)) return rc;
-    const uint32_t n = (uint32_t)lay.n, K = n_regions, copies = rgt_copies(K);
-    const size_t row_bytes = rows_on_device ? 0u : (size_t)K * sizeof(f3ds_region_row);
-    // every buffer of the call before anything is recorded
-    RgAcc* acc; unsigned char* out; LiImages im;
+namespace {
+// what every batch form refuses first: no contexts, a NULL or repeated one, contexts on different devices
+inline bool li_batch_ctxs(f3ds_ctx* const* ctxs, int nctx) { return ctxs && nctx >= 1 && distinct_contexts_on_one_device(ctxs, nctx); }
+// the end of a batch form: the frames' statuses to the caller, the lowest failing frame's as the call's
+int li_statuses(const std::vector<int>& st, int* status) {
+    int ret = F3DS_OK;
+    for (size_t i = 0; i < st.size(); ++i) { if (status) status[i] = st[i]; if (st[i] && !ret) ret = st[i]; }
+    return ret;
+}
+
+// region table (f3ds_regions.h / .inc, DESIGN.md section 18): one row per region of a label image over an RGB-D frame.  Three kernels -- d_region_init,
+// d_region_accum (the one read of the images), d_region_finish; behind the heads the rows of a host caller (72 B per region).
+int rg_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, const LiImages& im, uint32_t K, uint32_t* head, f3ds_region_row* d_rows) {
+    const uint32_t n = (uint32_t)lay.n, copies = rgt_copies(K);
+    RgAcc* acc;
     ENSURE(c->rgt_acc, K ? (size_t)K * copies : 1u, acc);
-    if (const int rc = li_out_buffers(c, LI_HEAD_BYTES + row_bytes, &out)) return rc;
-    if (const int rc = li_upload(c, b, lay, depth, color, labels, inputs_on_device, &im)) return rc;
     RegionArgs a;
     memset(&a, 0, sizeof a);
     a.width = fmt.width; a.n = n; a.depth_pitch = lay.depth_pitch; a.color_pitch = lay.color_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
-    a.color_format = color ? fmt.color_format : -1; a.K = K; a.copies = copies;
+    a.color_format = im.color ? fmt.color_format : -1; a.K = K; a.copies = copies;
     a.depth_scale = fmt.depth_scale; a.fx = fmt.fx; a.fy = fmt.fy; a.cx = fmt.cx; a.cy = fmt.cy;
-    uint32_t* head = reinterpret_cast<uint32_t*>(out);
-    f3ds_region_row* d_rows = rows_on_device ? rows : reinterpret_cast<f3ds_region_row*>(out + LI_HEAD_BYTES);
     rec<d_region_init>(c, grid_for((size_t)K * copies * RG_WORDS, 256), 0u, reinterpret_cast<uint32_t*>(acc), K * copies, head);
     rec<d_region_accum>(c, grid_for((n + LI_TRIPS - 1u) / LI_TRIPS, 256), 0u, im.depth, im.color, im.labels, a, acc, head);
     rec<d_region_finish>(c, grid_for(K, 256), 0u, acc, K, copies, head, d_rows);
-    if (const int rc = flush(b)) return rc;
-    uint32_t h[LI_HEAD_WORDS];
-    if (const int rc = li_download_head(c, b, out, row_bytes, h)) return rc;      // (a label >= n_regions: d_region_finish wrote no row)
-    if (row_bytes) memcpy(rows, c->h_li + LI_HEAD_BYTES, row_bytes);
-    if (result) {
-        result->n_regions = K; result->n_nonempty = h[0];
-        memcpy(&result->n_labelled, h + 2, 8); memcpy(&result->n_clamped, h + 4, 8);
-    }
     return F3DS_OK;
+}
+}  // namespace
+
+extern "C" int f3ds_region_table_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format* fmt_, const void* const* depth, const void* const* color, const uint32_t* const* labels,
+                                       const uint32_t* n_regions, int inputs_on_device, f3ds_region_row* const* rows, int rows_on_device, f3ds_region_table_result* results,
+                                       int* status) {
+    if (!li_batch_ctxs(ctxs, nctx) || !depth || !labels || !n_regions || !rows) return F3DS_ERR_ARG;
+    f3ds_rgbd_format fmt; f3ds::RgbdLayout lay;
+    for (int i = 0; i < nctx; ++i) {
+        if (color && !color[i]) return F3DS_ERR_ARG;      // (a colour image for every frame or for none: one command sequence)
+        if (const int rc = rg_check(fmt_, depth[i], color ? color[i] : nullptr, labels[i], n_regions[i], rows[i], &fmt, &lay)) return rc;
+    }
+    Batch b;
+    if (const int rc = li_begin(ctxs, nctx, &b)) return rc;
+    std::vector<size_t> fixed((size_t)nctx);
+    for (int i = 0; i < nctx; ++i) fixed[i] = rows_on_device ? 0u : (size_t)n_regions[i] * sizeof(f3ds_region_row);
+    LiStage s; std::vector<LiImages> im((size_t)nctx);
+    if (const int rc = li_out_buffers(ctxs[0], nctx, fixed.data(), nullptr, 0u, 0u, &s)) return rc;
+    if (const int rc = li_upload(ctxs, nctx, b, lay, depth, color, labels, inputs_on_device, im.data())) return rc;
+    for (int i = 0; i < nctx; ++i) {
+        f3ds_region_row* d_rows = rows_on_device ? rows[i] : reinterpret_cast<f3ds_region_row*>(s.out + s.slot[i].at);
+        if (const int rc = rg_record(ctxs[i], fmt, lay, im[i], n_regions[i], s.head(i), d_rows)) return rc;
+    }
+    if (const int rc = flush(b)) return rc;
+    if (const int rc = li_download_heads(s, b)) return rc;
+    std::vector<int> st((size_t)nctx, F3DS_OK);
+    for (int i = 0; i < nctx; ++i) {
+        const uint32_t* h = s.h_head(i);
+        if (h[1]) { st[i] = F3DS_ERR_ARG; continue; }      // (a label >= n_regions: d_region_finish wrote no row)
+        if (fixed[i]) memcpy(rows[i], s.o->h_li + s.slot[i].at, fixed[i]);
+        if (results) {
+            results[i].n_regions = n_regions[i]; results[i].n_nonempty = h[0];
+            memcpy(&results[i].n_labelled, h + 2, 8); memcpy(&results[i].n_clamped, h + 4, 8);
+        }
+    }
+    return li_statuses(st, status);
+}
+extern "C" int f3ds_region_table(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const void* color, const uint32_t* labels, uint32_t n_regions, int inputs_on_device,
+                                 f3ds_region_row* rows, int rows_on_device, f3ds_region_table_result* result) {
+    return f3ds_region_table_batch(&c, 1, fmt_, &depth, color ? &color : nullptr, &labels, &n_regions, inputs_on_device, &rows, rows_on_device, result, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
 // region contacts (f3ds_contacts.h / .inc): one row per pair of regions of a label image that touch.  d_contact_init, d_contact_accum
 // (the one pass over the images: records of (pair, seven words)), the radix sort of the record keys, d_evl_heads / scan, d_track_runs, d_contact_finish; behind
 // the head (row count, the bad-label flag, the records asked for, the sums) the first RGC_FIRST_ROWS rows of a host caller.  A frame with more records than the
-// first buffer holds says so in the head and runs once more with room for all (every contact pair a record of its own: fewer than 2n); a host caller with
-// more rows gets the rest in a second download.  Beside rgc_* the call uses the sort's histogram and the scan's tile sums, which hold nothing between calls.
+// first buffer holds says so in the head and runs once more, alone, with room for all (every contact pair a record of its own: fewer than 2n) once the others
+// have been delivered; a host caller with more rows gets the rest in a second download.  The frames of a batch share the record room (one n) and the sort
+// width, the largest any frame needs (zero key bits above a frame's own sort to nothing).  Beside rgc_* the call uses the sort's histogram and the scan's
+// tile sums, which hold nothing between calls.
 // ------------------------------------------------------------------------------------------------
-extern "C" int f3ds_region_contacts(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, float depth_tol,
-                                    int inputs_on_device, f3ds_region_contact* rows, size_t cap, int rows_on_device, size_t* n_out, f3ds_region_contacts_result* result) {
-    if (!c) return F3DS_ERR_ARG;
-    f3ds_rgbd_format fmt; f3ds::RgbdLayout lay;
-    if (const int rc = ct_check(fmt_, depth, labels, n_regions, depth_tol, n_out, &fmt, &lay)) return rc;
-    Batch b;
-    if (const int rc = li_begin(c, &b)) return rc;
-    const uint32_t n = (uint32_t)lay.n, K = n_regions;
-    const uint32_t rec_all = 2u * n;      // (n < 2^31: rgbd_layout)  every contact pair a record of its own is fewer than this
-    const uint32_t first = g_sw.rgc_first_cap ? g_sw.rgc_first_cap : RGC_FIRST_CAP;
-    uint32_t rec_cap = first < rec_all ? first : rec_all;
-    const bool host_rows = rows && !rows_on_device;
-    LiImages im;
-    if (const int rc = li_upload(c, b, lay, depth, nullptr, labels, inputs_on_device, &im)) return rc;
+namespace {
+int ct_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, const LiImages& im, uint32_t K, float depth_tol, uint32_t rec_cap, int sort_bits, uint32_t* head,
+              f3ds_region_contact* d_rows, size_t cap) {
+    const uint32_t n = (uint32_t)lay.n;
+    uint64_t *k0, *k1, *ukey; uint32_t *v0, *v1, *rec_words, *flag, *ustart, *uend, *cnt, *hist, *tiles;
+    ENSURE(c->rgc_k0, rec_cap, k0); ENSURE(c->rgc_k1, rec_cap, k1); ENSURE(c->rgc_v0, rec_cap, v0); ENSURE(c->rgc_v1, rec_cap, v1);
+    ENSURE(c->rgc_rec, (size_t)rec_cap * CT_WORDS, rec_words); ENSURE(c->rgc_flag, rec_cap, flag); ENSURE(c->rgc_ukey, rec_cap, ukey);
+    ENSURE(c->rgc_ustart, rec_cap, ustart); ENSURE(c->rgc_uend, rec_cap, uend); ENSURE(c->rgc_cnt, 4, cnt);
+    ENSURE(c->hist, (size_t)RS_BINS * ((rec_cap + RS_TILE - 1) / RS_TILE + 1), hist); ENSURE(c->tiles, (rec_cap + SCAN_TILE - 1) / SCAN_TILE + 1, tiles);
     ContactArgs a;
     memset(&a, 0, sizeof a);
     a.width = fmt.width; a.height = fmt.height; a.n = n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
-    a.K = K; a.kb = ct_bits(K); a.depth_scale = fmt.depth_scale; a.depth_tol = depth_tol;
+    a.K = K; a.kb = ct_bits(K); a.depth_scale = fmt.depth_scale; a.depth_tol = depth_tol; a.rec_cap = rec_cap;
     const uint64_t hole = ct_hole(K, a.kb);
-    const int sort_bits = ct_sort_bits(K);
-    uint32_t h[LI_HEAD_WORDS];
-    unsigned char* out = nullptr;
-    for (int run = 0;; ++run) {
-        a.rec_cap = rec_cap;
-        const size_t stage_rows = host_rows ? (cap < rec_cap ? cap : (size_t)rec_cap) : 0u;      // (rows <= records <= rec_cap)
-        // every buffer of the run before anything is recorded
-        uint64_t *k0, *k1, *ukey; uint32_t *v0, *v1, *rec_words, *flag, *ustart, *uend, *cnt, *hist, *tiles;
-        ENSURE(c->rgc_k0, rec_cap, k0); ENSURE(c->rgc_k1, rec_cap, k1); ENSURE(c->rgc_v0, rec_cap, v0); ENSURE(c->rgc_v1, rec_cap, v1);
-        ENSURE(c->rgc_rec, (size_t)rec_cap * CT_WORDS, rec_words); ENSURE(c->rgc_flag, rec_cap, flag); ENSURE(c->rgc_ukey, rec_cap, ukey);
-        ENSURE(c->rgc_ustart, rec_cap, ustart); ENSURE(c->rgc_uend, rec_cap, uend); ENSURE(c->rgc_cnt, 4, cnt);
-        ENSURE(c->hist, (size_t)RS_BINS * ((rec_cap + RS_TILE - 1) / RS_TILE + 1), hist); ENSURE(c->tiles, (rec_cap + SCAN_TILE - 1) / SCAN_TILE + 1, tiles);
-        int rc;
-        if ((rc = li_out_buffers(c, LI_HEAD_BYTES + stage_rows * sizeof(f3ds_region_contact), &out))) return rc;
-        uint32_t* head = reinterpret_cast<uint32_t*>(out);
-        f3ds_region_contact* d_rows = rows_on_device ? rows : (host_rows ? reinterpret_cast<f3ds_region_contact*>(out + LI_HEAD_BYTES) : nullptr);
-        rec<d_contact_init>(c, grid_for(rec_cap, 256), 0u, k0, v0, rec_cap, head);
-        rec<d_contact_accum>(c, grid_for((n + RGC_TRIPS - 1u) / RGC_TRIPS, 256), 0u, im.depth, im.labels, a, k0, rec_words, head);
-        uint64_t* ks; uint32_t* vs;
-        if ((rc = radix_sort(c, k0, v0, k1, v1, rec_cap, sort_bits, &ks, &vs))) return rc;
-        rec<d_evl_heads>(c, grid_for(rec_cap, 256), 0u, ks, rec_cap, hole, flag);
-        if ((rc = scan_u32(c, flag, flag, rec_cap))) return rc;
-        rec<d_track_runs>(c, grid_for(rec_cap, 256), 0u, ks, rec_cap, hole, flag, ukey, ustart, uend, cnt);
-        rec<d_contact_finish>(c, grid_for((size_t)(rec_cap < 8192u ? rec_cap : 8192u) * 64u, 256), 0u, ukey, ustart, uend, cnt, vs, rec_words, a.kb, rec_cap, head, d_rows, (uint64_t)cap);
-        if ((rc = flush(b))) return rc;
-        const size_t first_rows = stage_rows < RGC_FIRST_ROWS ? stage_rows : (size_t)RGC_FIRST_ROWS;
-        if ((rc = li_download_head(c, b, out, first_rows * sizeof(f3ds_region_contact), h))) return rc;      // (a label >= n_regions: d_contact_finish wrote no row)
-        if (h[2] <= rec_cap) break;
-        if (run || rec_cap >= rec_all) return F3DS_ERR_LOGIC;
-        rec_cap = rec_all;      // (rare: more records than the first buffer holds)
-    }
-    const size_t count = h[0];
-    if (count > rec_cap) return F3DS_ERR_LOGIC;
-    *n_out = count;
-    if (result) { result->n_regions = K; result->n_contacts = h[0]; memcpy(&result->n_pairs, h + 4, 8); memcpy(&result->n_close, h + 6, 8); }
-    if (!rows) return F3DS_OK;
-    if (cap < count) return F3DS_ERR_CAPACITY;
-    if (host_rows && count) return li_rows_behind(c, b, out, LI_HEAD_BYTES, sizeof(f3ds_region_contact), count, RGC_FIRST_ROWS, rows);
+    int rc;
+    rec<d_contact_init>(c, grid_for(rec_cap, 256), 0u, k0, v0, rec_cap, head);
+    rec<d_contact_accum>(c, grid_for((n + RGC_TRIPS - 1u) / RGC_TRIPS, 256), 0u, im.depth, im.labels, a, k0, rec_words, head);
+    uint64_t* ks; uint32_t* vs;
+    if ((rc = radix_sort(c, k0, v0, k1, v1, rec_cap, sort_bits, &ks, &vs))) return rc;
+    rec<d_evl_heads>(c, grid_for(rec_cap, 256), 0u, ks, rec_cap, hole, flag);
+    if ((rc = scan_u32(c, flag, flag, rec_cap))) return rc;
+    rec<d_track_runs>(c, grid_for(rec_cap, 256), 0u, ks, rec_cap, hole, flag, ukey, ustart, uend, cnt);
+    rec<d_contact_finish>(c, grid_for((size_t)(rec_cap < 8192u ? rec_cap : 8192u) * 64u, 256), 0u, ukey, ustart, uend, cnt, vs, rec_words, a.kb, rec_cap, head, d_rows, (uint64_t)cap);
     return F3DS_OK;
+}
+// the call after its checks, with room for first_cap records (at most 2n) per frame: st[i] = frame i's status; the result is a failure of the call as a whole
+int ct_run(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, const void* const* depth, const uint32_t* const* labels, const uint32_t* n_regions,
+           float depth_tol, int inputs_on_device, f3ds_region_contact* const* rows, const size_t* caps, int rows_on_device, size_t* n_out, f3ds_region_contacts_result* results,
+           uint32_t first_cap, int* st) {
+    Batch b;
+    if (const int rc = li_begin(ctxs, nctx, &b)) return rc;
+    const uint32_t n = (uint32_t)lay.n;
+    const uint32_t rec_all = 2u * n;      // (n < 2^31: rgbd_layout)  every contact pair a record of its own is fewer than this
+    const uint32_t rec_cap = first_cap < rec_all ? first_cap : rec_all;
+    int sort_bits = 0;
+    for (int i = 0; i < nctx; ++i) sort_bits = std::max(sort_bits, ct_sort_bits(n_regions[i]));
+    std::vector<size_t> fixed((size_t)nctx, 0u), stage_rows((size_t)nctx, 0u), count((size_t)nctx, 0u);
+    std::vector<void*> dst((size_t)nctx, nullptr);
+    for (int i = 0; i < nctx; ++i) if (rows && rows[i] && !rows_on_device) stage_rows[i] = caps[i] < rec_cap ? caps[i] : (size_t)rec_cap;      // (rows <= records <= rec_cap)
+    LiStage s; std::vector<LiImages> im((size_t)nctx);
+    if (const int rc = li_out_buffers(ctxs[0], nctx, fixed.data(), stage_rows.data(), sizeof(f3ds_region_contact), RGC_FIRST_ROWS, &s)) return rc;
+    if (const int rc = li_upload(ctxs, nctx, b, lay, depth, nullptr, labels, inputs_on_device, im.data())) return rc;
+    for (int i = 0; i < nctx; ++i) {
+        f3ds_region_contact* const r = rows ? rows[i] : nullptr;
+        f3ds_region_contact* d_rows = !r ? nullptr : (rows_on_device ? r : reinterpret_cast<f3ds_region_contact*>(s.out + s.slot[i].rows_at));
+        if (const int rc = ct_record(ctxs[i], fmt, lay, im[i], n_regions[i], depth_tol, rec_cap, sort_bits, s.head(i), d_rows, r ? caps[i] : 0u)) return rc;
+    }
+    if (const int rc = flush(b)) return rc;
+    if (const int rc = li_download_heads(s, b)) return rc;
+    std::vector<int> again;
+    for (int i = 0; i < nctx; ++i) {
+        const uint32_t* h = s.h_head(i);
+        st[i] = F3DS_OK;
+        if (h[1]) { st[i] = F3DS_ERR_ARG; continue; }      // (a label >= n_regions: d_contact_finish wrote no row)
+        if (h[2] > rec_cap) {      // (rare: more records than the first buffer holds)
+            if (rec_cap >= rec_all) return F3DS_ERR_LOGIC;
+            again.push_back(i); continue;
+        }
+        const size_t cnt = h[0];
+        if (cnt > rec_cap) return F3DS_ERR_LOGIC;
+        n_out[i] = cnt;
+        if (results) { results[i].n_regions = n_regions[i]; results[i].n_contacts = h[0]; memcpy(&results[i].n_pairs, h + 4, 8); memcpy(&results[i].n_close, h + 6, 8); }
+        if (!rows || !rows[i]) continue;
+        if (caps[i] < cnt) { st[i] = F3DS_ERR_CAPACITY; continue; }
+        if (!rows_on_device) { count[i] = cnt; dst[i] = rows[i]; }
+    }
+    if (const int rc = li_rows_behind(s, b, nctx, sizeof(f3ds_region_contact), count.data(), dst.data())) return rc;
+    for (const int i : again) {      // (the owner's staging is free again: everything else has been delivered)
+        if (const int rc = ct_run(ctxs + i, 1, fmt, lay, depth + i, labels + i, n_regions + i, depth_tol, inputs_on_device, rows ? rows + i : nullptr, caps ? caps + i : nullptr,
+                                  rows_on_device, n_out + i, results ? results + i : nullptr, rec_all, &st[i])) return rc;
+    }
+    return F3DS_OK;
+}
+}  // namespace
+
+extern "C" int f3ds_region_contacts_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format* fmt_, const void* const* depth, const uint32_t* const* labels, const uint32_t* n_regions,
+                                          float depth_tol, int inputs_on_device, f3ds_region_contact* const* rows, const size_t* caps, int rows_on_device, size_t* n_out,
+                                          f3ds_region_contacts_result* results, int* status) {
+    if (!li_batch_ctxs(ctxs, nctx) || !depth || !labels || !n_regions || (rows && !caps)) return F3DS_ERR_ARG;
+    f3ds_rgbd_format fmt; f3ds::RgbdLayout lay;
+    for (int i = 0; i < nctx; ++i) if (const int rc = ct_check(fmt_, depth[i], labels[i], n_regions[i], depth_tol, n_out, &fmt, &lay)) return rc;
+    std::vector<int> st((size_t)nctx, F3DS_OK);
+    g_sw.read();
+    const uint32_t first = g_sw.rgc_first_cap ? g_sw.rgc_first_cap : RGC_FIRST_CAP;
+    if (const int rc = ct_run(ctxs, nctx, fmt, lay, depth, labels, n_regions, depth_tol, inputs_on_device, rows, caps, rows_on_device, n_out, results, first, st.data())) return rc;
+    return li_statuses(st, status);
+}
+extern "C" int f3ds_region_contacts(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, float depth_tol,
+                                    int inputs_on_device, f3ds_region_contact* rows, size_t cap, int rows_on_device, size_t* n_out, f3ds_region_contacts_result* result) {
+    return f3ds_region_contacts_batch(&c, 1, fmt_, &depth, &labels, &n_regions, depth_tol, inputs_on_device, rows ? &rows : nullptr, &cap, rows_on_device, n_out, result, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
 // region shapes (f3ds_shapes.h / .inc): one row per region of a label image over a depth image -- covariance, eigenvalues, plane and long
-// axis.  The call has the region table's shape: d_shape_init, d_shape_accum (the one read of the image and the labels), d_shape_finish; behind the head the
-// rows of a host caller (84 B per region).
+// axis.  The call has the region table's shape: d_shape_init, d_shape_accum (the one read of the image and the labels), d_shape_finish; behind the heads the
+// rows of a host caller (84 B per region).  sh_record is also pass one of the boxes.
 // ------------------------------------------------------------------------------------------------
-extern "C" int f3ds_region_shapes(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, int inputs_on_device,
-                                  f3ds_region_shape* rows, int rows_on_device, f3ds_region_shapes_result* result) {
-    if (!c) return F3DS_ERR_ARG;
-    f3ds_rgbd_format fmt; f3ds::RgbdLayout lay;
-    if (const int rc = sh_check(fmt_, depth, labels, n_regions, rows, &fmt, &lay)) return rc;
-    Batch b;
-    if (const int rc = li_begin(c, &b)) return rc;
-    const uint32_t n = (uint32_t)lay.n, K = n_regions, copies = rgt_copies(K);
-    const size_t row_bytes = rows_on_device ? 0u : (size_t)K * sizeof(f3ds_region_shape);
-    // every buffer of the call before anything is recorded
-    ShAcc* acc; unsigned char* out; LiImages im;
-    ENSURE(c->rgs_acc, K ? (size_t)K * copies : 1u, acc);
-    if (const int rc = li_out_buffers(c, LI_HEAD_BYTES + row_bytes, &out)) return rc;
-    if (const int rc = li_upload(c, b, lay, depth, nullptr, labels, inputs_on_device, &im)) return rc;
+namespace {
+ShapeArgs sh_args(const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, uint32_t K) {
     ShapeArgs a;
     memset(&a, 0, sizeof a);
-    a.width = fmt.width; a.n = n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
-    a.K = K; a.copies = copies;
+    a.width = fmt.width; a.n = (uint32_t)lay.n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
+    a.K = K; a.copies = rgt_copies(K);
     a.depth_scale = fmt.depth_scale; a.fx = fmt.fx; a.fy = fmt.fy; a.cx = fmt.cx; a.cy = fmt.cy;
-    uint32_t* head = reinterpret_cast<uint32_t*>(out);
-    f3ds_region_shape* d_rows = rows_on_device ? rows : reinterpret_cast<f3ds_region_shape*>(out + LI_HEAD_BYTES);
-    rec<d_shape_init>(c, grid_for((size_t)K * copies * SH_WORDS, 256), 0u, reinterpret_cast<uint32_t*>(acc), K * copies, head);
+    return a;
+}
+int sh_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, const LiImages& im, uint32_t K, uint32_t* head, f3ds_region_shape* d_rows) {
+    const ShapeArgs a = sh_args(fmt, lay, K);
+    const uint32_t n = a.n;
+    ShAcc* acc;
+    ENSURE(c->rgs_acc, K ? (size_t)K * a.copies : 1u, acc);
+    rec<d_shape_init>(c, grid_for((size_t)K * a.copies * SH_WORDS, 256), 0u, reinterpret_cast<uint32_t*>(acc), K * a.copies, head);
     rec<d_shape_accum>(c, grid_for((n + LI_TRIPS - 1u) / LI_TRIPS, 256), 0u, im.depth, im.labels, a, acc, head);
-    rec<d_shape_finish>(c, grid_for(K, 256), 0u, acc, K, copies, head, d_rows);
-    if (const int rc = flush(b)) return rc;
-    uint32_t h[LI_HEAD_WORDS];
-    if (const int rc = li_download_head(c, b, out, row_bytes, h)) return rc;      // (a label >= n_regions: d_shape_finish wrote no row)
-    if (row_bytes) memcpy(rows, c->h_li + LI_HEAD_BYTES, row_bytes);
-    if (result) {
-        result->n_regions = K; result->n_nonempty = h[0];
-        memcpy(&result->n_labelled, h + 2, 8); memcpy(&result->n_clamped, h + 4, 8);
-    }
+    rec<d_shape_finish>(c, grid_for(K, 256), 0u, acc, K, a.copies, head, d_rows);
     return F3DS_OK;
+}
+}  // namespace
+
+extern "C" int f3ds_region_shapes_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format* fmt_, const void* const* depth, const uint32_t* const* labels, const uint32_t* n_regions,
+                                        int inputs_on_device, f3ds_region_shape* const* rows, int rows_on_device, f3ds_region_shapes_result* results, int* status) {
+    if (!li_batch_ctxs(ctxs, nctx) || !depth || !labels || !n_regions || !rows) return F3DS_ERR_ARG;
+    f3ds_rgbd_format fmt; f3ds::RgbdLayout lay;
+    for (int i = 0; i < nctx; ++i) if (const int rc = sh_check(fmt_, depth[i], labels[i], n_regions[i], rows[i], &fmt, &lay)) return rc;
+    Batch b;
+    if (const int rc = li_begin(ctxs, nctx, &b)) return rc;
+    std::vector<size_t> fixed((size_t)nctx);
+    for (int i = 0; i < nctx; ++i) fixed[i] = rows_on_device ? 0u : (size_t)n_regions[i] * sizeof(f3ds_region_shape);
+    LiStage s; std::vector<LiImages> im((size_t)nctx);
+    if (const int rc = li_out_buffers(ctxs[0], nctx, fixed.data(), nullptr, 0u, 0u, &s)) return rc;
+    if (const int rc = li_upload(ctxs, nctx, b, lay, depth, nullptr, labels, inputs_on_device, im.data())) return rc;
+    for (int i = 0; i < nctx; ++i) {
+        f3ds_region_shape* d_rows = rows_on_device ? rows[i] : reinterpret_cast<f3ds_region_shape*>(s.out + s.slot[i].at);
+        if (const int rc = sh_record(ctxs[i], fmt, lay, im[i], n_regions[i], s.head(i), d_rows)) return rc;
+    }
+    if (const int rc = flush(b)) return rc;
+    if (const int rc = li_download_heads(s, b)) return rc;
+    std::vector<int> st((size_t)nctx, F3DS_OK);
+    for (int i = 0; i < nctx; ++i) {
+        const uint32_t* h = s.h_head(i);
+        if (h[1]) { st[i] = F3DS_ERR_ARG; continue; }      // (a label >= n_regions: d_shape_finish wrote no row)
+        if (fixed[i]) memcpy(rows[i], s.o->h_li + s.slot[i].at, fixed[i]);
+        if (results) {
+            results[i].n_regions = n_regions[i]; results[i].n_nonempty = h[0];
+            memcpy(&results[i].n_labelled, h + 2, 8); memcpy(&results[i].n_clamped, h + 4, 8);
+        }
+    }
+    return li_statuses(st, status);
+}
+extern "C" int f3ds_region_shapes(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, int inputs_on_device,
+                                  f3ds_region_shape* rows, int rows_on_device, f3ds_region_shapes_result* result) {
+    return f3ds_region_shapes_batch(&c, 1, fmt_, &depth, &labels, &n_regions, inputs_on_device, &rows, rows_on_device, result, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
 // region boxes (f3ds_boxes.h / .inc): one row per region of a label image over a depth image -- the box along the region's own axes and
 // its plane residuals.  The family's first call with TWO reads of the images, the second depending on the finish of the first; both are recorded into the one
-// flush: d_shape_init, d_shape_accum, d_shape_finish as they are (into rgs_acc, which holds nothing between calls), d_box_frame (a frame per region from its
-// shape row), d_box_accum (the second read, every pixel in the frame of its label), d_box_finish.  Behind the head the box rows of a host caller (96 B per
-// region) and behind them the shape rows (84 B) if they were asked for; the shape rows of a caller who wants none stay in scratch.
+// flush: d_shape_init, d_shape_accum, d_shape_finish as they are (sh_record, into rgs_acc, which holds nothing between calls), d_box_frame (a frame per region
+// from its shape row), d_box_accum (the second read, every pixel in the frame of its label), d_box_finish.  Behind the heads the box rows of a host caller (96 B
+// per region) and behind them the shape rows (84 B) if they were asked for; the shape rows of a caller who wants none stay in scratch.
 // ------------------------------------------------------------------------------------------------
-extern "C" int f3ds_region_boxes(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, float plane_tol, int inputs_on_device,
-                                 f3ds_region_box* rows, f3ds_region_shape* shapes, int rows_on_device, f3ds_region_boxes_result* result) {
-    if (!c) return F3DS_ERR_ARG;
-    f3ds_rgbd_format fmt; f3ds::RgbdLayout lay;
-    if (const int rc = bx_check(fmt_, depth, labels, n_regions, plane_tol, rows, &fmt, &lay)) return rc;
-    Batch b;
-    if (const int rc = li_begin(c, &b)) return rc;
-    const uint32_t n = (uint32_t)lay.n, K = n_regions, copies = rgt_copies(K);
-    const size_t box_bytes = rows_on_device ? 0u : (size_t)K * sizeof(f3ds_region_box);      // (a multiple of 8: the shape rows behind them are aligned)
-    const size_t shape_bytes = rows_on_device || !shapes ? 0u : (size_t)K * sizeof(f3ds_region_shape);
-    // every buffer of the call before anything is recorded
-    ShAcc* acc; BxAcc* acc2; BxFrame* frames; uint32_t* head2; f3ds_region_shape* d_shapes; unsigned char* out; LiImages im;
-    ENSURE(c->rgs_acc, K ? (size_t)K * copies : 1u, acc);
-    ENSURE(c->rgx_acc, K ? (size_t)K * copies : 1u, acc2);
+namespace {
+int bx_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, const LiImages& im, uint32_t K, float plane_tol, uint32_t* head, f3ds_region_box* d_rows,
+              f3ds_region_shape* d_shapes /* NULL: the context's scratch */) {
+    const ShapeArgs a = sh_args(fmt, lay, K);
+    const uint32_t n = a.n;
+    const uint32_t accum_grid = grid_for((n + LI_TRIPS - 1u) / LI_TRIPS, 256);      // (pass one, sh_record, asks for the same)
+    BxAcc* acc2; BxFrame* frames; uint32_t* head2;
+    ENSURE(c->rgx_acc, K ? (size_t)K * a.copies : 1u, acc2);
     ENSURE(c->rgx_frame, K ? K : 1u, frames);
     ENSURE(c->rgx_head, LI_HEAD_WORDS, head2);
-    if (!shapes) ENSURE(c->rgx_shape, K ? K : 1u, d_shapes);
-    if (const int rc = li_out_buffers(c, LI_HEAD_BYTES + box_bytes + shape_bytes, &out)) return rc;
-    if (const int rc = li_upload(c, b, lay, depth, nullptr, labels, inputs_on_device, &im)) return rc;
-    ShapeArgs a;
-    memset(&a, 0, sizeof a);
-    a.width = fmt.width; a.n = n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
-    a.K = K; a.copies = copies;
-    a.depth_scale = fmt.depth_scale; a.fx = fmt.fx; a.fy = fmt.fy; a.cx = fmt.cx; a.cy = fmt.cy;
-    uint32_t* head = reinterpret_cast<uint32_t*>(out);
-    f3ds_region_box* d_rows = rows_on_device ? rows : reinterpret_cast<f3ds_region_box*>(out + LI_HEAD_BYTES);
-    if (shapes) d_shapes = rows_on_device ? shapes : reinterpret_cast<f3ds_region_shape*>(out + LI_HEAD_BYTES + box_bytes);
-    const uint32_t accum_grid = grid_for((n + LI_TRIPS - 1u) / LI_TRIPS, 256);
-    rec<d_shape_init>(c, grid_for((size_t)K * copies * SH_WORDS, 256), 0u, reinterpret_cast<uint32_t*>(acc), K * copies, head);
-    rec<d_shape_accum>(c, accum_grid, 0u, im.depth, im.labels, a, acc, head);
-    rec<d_shape_finish>(c, grid_for(K, 256), 0u, acc, K, copies, head, d_shapes);
-    rec<d_box_frame>(c, grid_for(K, 256), 0u, d_shapes, K, copies, plane_tol, head, frames, acc2, head2);
+    if (!d_shapes) ENSURE(c->rgx_shape, K ? K : 1u, d_shapes);
+    if (const int rc = sh_record(c, fmt, lay, im, K, head, d_shapes)) return rc;      // (rgs_acc is ensured before its first rec<>, and nothing recorded refers to it yet)
+    rec<d_box_frame>(c, grid_for(K, 256), 0u, d_shapes, K, a.copies, plane_tol, head, frames, acc2, head2);
     rec<d_box_accum>(c, accum_grid, 0u, im.depth, im.labels, a, frames, acc2, head, head2);
-    rec<d_box_finish>(c, grid_for(K, 256), 0u, acc2, frames, K, copies, head, d_rows);
-    if (const int rc = flush(b)) return rc;
-    uint32_t h[LI_HEAD_WORDS];
-    if (const int rc = li_download_head(c, b, out, box_bytes + shape_bytes, h)) return rc;      // (a label >= n_regions: no finish kernel wrote a row)
-    if (box_bytes) memcpy(rows, c->h_li + LI_HEAD_BYTES, box_bytes);
-    if (shape_bytes) memcpy(shapes, c->h_li + LI_HEAD_BYTES + box_bytes, shape_bytes);
-    if (result) {
-        result->n_regions = K; result->n_nonempty = h[0];
-        memcpy(&result->n_labelled, h + 2, 8); memcpy(&result->n_clamped, h + 4, 8); memcpy(&result->n_inliers, h + 6, 8);
-    }
+    rec<d_box_finish>(c, grid_for(K, 256), 0u, acc2, frames, K, a.copies, head, d_rows);
     return F3DS_OK;
+}
+}  // namespace
+
+extern "C" int f3ds_region_boxes_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format* fmt_, const void* const* depth, const uint32_t* const* labels, const uint32_t* n_regions,
+                                       float plane_tol, int inputs_on_device, f3ds_region_box* const* rows, f3ds_region_shape* const* shapes, int rows_on_device,
+                                       f3ds_region_boxes_result* results, int* status) {
+    if (!li_batch_ctxs(ctxs, nctx) || !depth || !labels || !n_regions || !rows) return F3DS_ERR_ARG;
+    f3ds_rgbd_format fmt; f3ds::RgbdLayout lay;
+    for (int i = 0; i < nctx; ++i) {
+        if (shapes && !shapes[i] && n_regions[i]) return F3DS_ERR_ARG;      // (shape rows for every frame or for none)
+        if (const int rc = bx_check(fmt_, depth[i], labels[i], n_regions[i], plane_tol, rows[i], &fmt, &lay)) return rc;
+    }
+    Batch b;
+    if (const int rc = li_begin(ctxs, nctx, &b)) return rc;
+    std::vector<size_t> fixed((size_t)nctx), box_bytes((size_t)nctx), shape_bytes((size_t)nctx);
+    for (int i = 0; i < nctx; ++i) {
+        box_bytes[i] = rows_on_device ? 0u : (size_t)n_regions[i] * sizeof(f3ds_region_box);      // (a multiple of 8: the shape rows behind them are aligned)
+        shape_bytes[i] = rows_on_device || !shapes || !shapes[i] ? 0u : (size_t)n_regions[i] * sizeof(f3ds_region_shape);
+        fixed[i] = box_bytes[i] + shape_bytes[i];
+    }
+    LiStage s; std::vector<LiImages> im((size_t)nctx);
+    if (const int rc = li_out_buffers(ctxs[0], nctx, fixed.data(), nullptr, 0u, 0u, &s)) return rc;
+    if (const int rc = li_upload(ctxs, nctx, b, lay, depth, nullptr, labels, inputs_on_device, im.data())) return rc;
+    for (int i = 0; i < nctx; ++i) {
+        f3ds_region_box* d_rows = rows_on_device ? rows[i] : reinterpret_cast<f3ds_region_box*>(s.out + s.slot[i].at);
+        f3ds_region_shape* d_shapes = !shapes || !shapes[i] ? nullptr : (rows_on_device ? shapes[i] : reinterpret_cast<f3ds_region_shape*>(s.out + s.slot[i].at + box_bytes[i]));
+        if (const int rc = bx_record(ctxs[i], fmt, lay, im[i], n_regions[i], plane_tol, s.head(i), d_rows, d_shapes)) return rc;
+    }
+    if (const int rc = flush(b)) return rc;
+    if (const int rc = li_download_heads(s, b)) return rc;
+    std::vector<int> st((size_t)nctx, F3DS_OK);
+    for (int i = 0; i < nctx; ++i) {
+        const uint32_t* h = s.h_head(i);
+        if (h[1]) { st[i] = F3DS_ERR_ARG; continue; }      // (a label >= n_regions: no finish kernel wrote a row)
+        if (box_bytes[i]) memcpy(rows[i], s.o->h_li + s.slot[i].at, box_bytes[i]);
+        if (shape_bytes[i]) memcpy(shapes[i], s.o->h_li + s.slot[i].at + box_bytes[i], shape_bytes[i]);
+        if (results) {
+            results[i].n_regions = n_regions[i]; results[i].n_nonempty = h[0];
+            memcpy(&results[i].n_labelled, h + 2, 8); memcpy(&results[i].n_clamped, h + 4, 8); memcpy(&results[i].n_inliers, h + 6, 8);
+        }
+    }
+    return li_statuses(st, status);
+}
+extern "C" int f3ds_region_boxes(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, float plane_tol, int inputs_on_device,
+                                 f3ds_region_box* rows, f3ds_region_shape* shapes, int rows_on_device, f3ds_region_boxes_result* result) {
+    return f3ds_region_boxes_batch(&c, 1, fmt_, &depth, &labels, &n_regions, plane_tol, inputs_on_device, &rows, shapes ? &shapes : nullptr, rows_on_device, result, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
 // region components (f3ds_components.h / .inc): the connected components of a label image over a depth image, as a label image and one
 // row per component.  The head's zeros, d_comp_local (the one read of the images: tiles resolved in LDS), d_comp_seam, d_comp_flatten, d_comp_flag, the scan
-// of the flags, d_comp_write; behind the head the image and the first RGK_FIRST_ROWS rows of a host caller, who gets further rows in a second download.
+// of the flags, d_comp_write; behind the heads the image and the first RGK_FIRST_ROWS rows of a host caller, who gets further rows in a second download.
 // Beside rgk_* (twelve bytes per pixel) the call uses the scan's tile sums, which hold nothing between calls.
 // ------------------------------------------------------------------------------------------------
-extern "C" int f3ds_region_components(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, const f3ds_component_params* params,
-                                      int inputs_on_device, uint32_t* comp_labels, f3ds_region_component* rows, size_t cap, int outputs_on_device, size_t* n_out,
-                                      f3ds_region_components_result* result) {
-    if (!c) return F3DS_ERR_ARG;
-    f3ds_rgbd_format fmt; f3ds::RgbdLayout lay; f3ds_component_params prm;
-    if (const int rc = cc_check(fmt_, depth, labels, n_regions, params, comp_labels, n_out, &fmt, &lay, &prm)) return rc;
-    Batch b;
-    if (const int rc = li_begin(c, &b)) return rc;
-    const uint32_t n = (uint32_t)lay.n, K = n_regions;
-    const bool host_out = !outputs_on_device, host_rows = rows && host_out;
-    const size_t image_bytes = host_out ? (size_t)n * 4 : 0u;
-    const size_t stage_rows = host_rows ? (cap < n ? cap : (size_t)n) : 0u;      // (components <= pixels)
-    const size_t rows_at = LI_HEAD_BYTES + image_bytes;
-    // every buffer of the call before anything is recorded
-    uint32_t *parent, *cnt, *flag; unsigned char* out; LiImages im;
+namespace {
+int cc_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, const f3ds_component_params& prm, const LiImages& im, uint32_t K, uint32_t* head, uint32_t* d_comp,
+              f3ds_region_component* d_rows, size_t cap) {
+    const uint32_t n = (uint32_t)lay.n;
+    uint32_t *parent, *cnt, *flag;
     ENSURE(c->rgk_parent, n, parent); ENSURE(c->rgk_cnt, n, cnt); ENSURE(c->rgk_flag, n, flag);
-    if (const int rc = li_out_buffers(c, rows_at + stage_rows * sizeof(f3ds_region_component), &out)) return rc;
-    if (const int rc = li_upload(c, b, lay, depth, nullptr, labels, inputs_on_device, &im)) return rc;
     CompArgs a;
     memset(&a, 0, sizeof a);
     a.width = fmt.width; a.height = fmt.height; a.n = n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
     a.K = K; a.min_pixels = prm.min_pixels; a.tiles_x = (fmt.width + CC_TILE_W - 1u) / CC_TILE_W; a.tiles_y = (fmt.height + CC_TILE_H - 1u) / CC_TILE_H;
     a.depth_scale = fmt.depth_scale; a.depth_tol = prm.depth_tol;
-    uint32_t* head = reinterpret_cast<uint32_t*>(out);
-    uint32_t* d_comp = host_out ? reinterpret_cast<uint32_t*>(out + LI_HEAD_BYTES) : comp_labels;
-    f3ds_region_component* d_rows = !rows ? nullptr : (host_out ? reinterpret_cast<f3ds_region_component*>(out + rows_at) : rows);
     const size_t seams = (size_t)(a.tiles_x - 1u) * fmt.height + (size_t)(a.tiles_y - 1u) * fmt.width;
     rec_fill(c, head, 0u, LI_HEAD_BYTES);
     rec<d_comp_local>(c, grid_for((size_t)a.tiles_x * a.tiles_y, 1), 0u, im.depth, im.labels, a, parent, cnt, head);
@@ -2827,20 +2946,57 @@ extern "C" int f3ds_region_components(f3ds_ctx* c, const f3ds_rgbd_format* fmt_,
     rec<d_comp_flag>(c, grid_for(n, 256), 0u, n, parent, cnt, a.min_pixels, flag, head);
     if (const int rc = scan_u32(c, flag, flag, n)) return rc;
     rec<d_comp_write>(c, grid_for(n, 256), 0u, n, im.labels, parent, cnt, flag, a.min_pixels, head, d_comp, d_rows, (uint64_t)cap);
-    if (const int rc = flush(b)) return rc;
-    const size_t first_rows = stage_rows < RGK_FIRST_ROWS ? stage_rows : (size_t)RGK_FIRST_ROWS;
-    uint32_t h[LI_HEAD_WORDS];
-    if (const int rc = li_download_head(c, b, out, image_bytes + first_rows * sizeof(f3ds_region_component), h)) return rc;      // (a label >= n_regions: d_comp_write wrote nothing)
-    const size_t count = h[0];
-    if (count > n) return F3DS_ERR_LOGIC;
-    if (host_out) memcpy(comp_labels, c->h_li + LI_HEAD_BYTES, image_bytes);
-    *n_out = count;
-    if (result) {
-        result->n_regions = K; result->n_components = h[0]; result->n_dropped = h[2]; result->reserved = 0u;
-        memcpy(&result->n_labelled, h + 4, 8); memcpy(&result->n_kept, h + 6, 8);
-    }
-    if (!rows) return F3DS_OK;
-    if (cap < count) return F3DS_ERR_CAPACITY;
-    if (host_rows && count) return li_rows_behind(c, b, out, rows_at, sizeof(f3ds_region_component), count, RGK_FIRST_ROWS, rows);
     return F3DS_OK;
+}
+}  // namespace
+
+extern "C" int f3ds_region_components_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format* fmt_, const void* const* depth, const uint32_t* const* labels, const uint32_t* n_regions,
+                                            const f3ds_component_params* params, int inputs_on_device, uint32_t* const* comp_labels, f3ds_region_component* const* rows,
+                                            const size_t* caps, int outputs_on_device, size_t* n_out, f3ds_region_components_result* results, int* status) {
+    if (!li_batch_ctxs(ctxs, nctx) || !depth || !labels || !n_regions || !comp_labels || (rows && !caps)) return F3DS_ERR_ARG;
+    f3ds_rgbd_format fmt; f3ds::RgbdLayout lay; f3ds_component_params prm;
+    for (int i = 0; i < nctx; ++i) if (const int rc = cc_check(fmt_, depth[i], labels[i], n_regions[i], params, comp_labels[i], n_out, &fmt, &lay, &prm)) return rc;
+    Batch b;
+    if (const int rc = li_begin(ctxs, nctx, &b)) return rc;
+    const uint32_t n = (uint32_t)lay.n;
+    const bool host_out = !outputs_on_device;
+    const size_t image_bytes = host_out ? (size_t)n * 4 : 0u;
+    std::vector<size_t> fixed((size_t)nctx, image_bytes), stage_rows((size_t)nctx, 0u), count((size_t)nctx, 0u);
+    std::vector<void*> dst((size_t)nctx, nullptr);
+    for (int i = 0; i < nctx; ++i) if (rows && rows[i] && host_out) stage_rows[i] = caps[i] < n ? caps[i] : (size_t)n;      // (components <= pixels)
+    LiStage s; std::vector<LiImages> im((size_t)nctx);
+    if (const int rc = li_out_buffers(ctxs[0], nctx, fixed.data(), stage_rows.data(), sizeof(f3ds_region_component), RGK_FIRST_ROWS, &s)) return rc;
+    if (const int rc = li_upload(ctxs, nctx, b, lay, depth, nullptr, labels, inputs_on_device, im.data())) return rc;
+    for (int i = 0; i < nctx; ++i) {
+        f3ds_region_component* const r = rows ? rows[i] : nullptr;
+        uint32_t* d_comp = host_out ? reinterpret_cast<uint32_t*>(s.out + s.slot[i].at) : comp_labels[i];
+        f3ds_region_component* d_rows = !r ? nullptr : (host_out ? reinterpret_cast<f3ds_region_component*>(s.out + s.slot[i].rows_at) : r);
+        if (const int rc = cc_record(ctxs[i], fmt, lay, prm, im[i], n_regions[i], s.head(i), d_comp, d_rows, r ? caps[i] : 0u)) return rc;
+    }
+    if (const int rc = flush(b)) return rc;
+    if (const int rc = li_download_heads(s, b)) return rc;
+    std::vector<int> st((size_t)nctx, F3DS_OK);
+    for (int i = 0; i < nctx; ++i) {
+        const uint32_t* h = s.h_head(i);
+        if (h[1]) { st[i] = F3DS_ERR_ARG; continue; }      // (a label >= n_regions: d_comp_write wrote nothing)
+        const size_t cnt = h[0];
+        if (cnt > n) return F3DS_ERR_LOGIC;
+        if (host_out) memcpy(comp_labels[i], s.o->h_li + s.slot[i].at, image_bytes);
+        n_out[i] = cnt;
+        if (results) {
+            results[i].n_regions = n_regions[i]; results[i].n_components = h[0]; results[i].n_dropped = h[2]; results[i].reserved = 0u;
+            memcpy(&results[i].n_labelled, h + 4, 8); memcpy(&results[i].n_kept, h + 6, 8);
+        }
+        if (!rows || !rows[i]) continue;
+        if (caps[i] < cnt) { st[i] = F3DS_ERR_CAPACITY; continue; }
+        if (host_out) { count[i] = cnt; dst[i] = rows[i]; }
+    }
+    if (const int rc = li_rows_behind(s, b, nctx, sizeof(f3ds_region_component), count.data(), dst.data())) return rc;
+    return li_statuses(st, status);
+}
+extern "C" int f3ds_region_components(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, const f3ds_component_params* params,
+                                      int inputs_on_device, uint32_t* comp_labels, f3ds_region_component* rows, size_t cap, int outputs_on_device, size_t* n_out,
+                                      f3ds_region_components_result* result) {
+    return f3ds_region_components_batch(&c, 1, fmt_, &depth, &labels, &n_regions, params, inputs_on_device, &comp_labels, rows ? &rows : nullptr, &cap, outputs_on_device, n_out, result,
+                                        nullptr);
 }

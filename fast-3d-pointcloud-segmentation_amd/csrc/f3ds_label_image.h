@@ -41,6 +41,33 @@ inline bool li_labels_in_range(const uint32_t* labels, size_t n, uint32_t n_regi
     return true;
 }
 
+// The staging of a region call over nctx frames, a pure function of the frames' byte counts.  The nctx heads come first, contiguous;
+// behind them, at 8-byte aligned offsets, every frame's payload: `fixed[i]` bytes whose size the host knows beforehand (the rows of a table, the image of the
+// components) and, for the calls whose row count the device decides, room for `stage_rows[i]` rows of `row_bytes` (stage_rows == NULL: no such rows).  A
+// row array of at most `first_rows` rows sits right behind its frame's fixed bytes; the longer ones follow behind ALL of those, so that ONE download of
+// *first_bytes from offset 0 brings every head, every fixed payload, every short row array whole and the first `first_rows` rows of the first long one (with
+// one frame that is the lone call's download: the head, what is fixed, the first rows).  slot[i].first = the rows of frame i's array that this download
+// brings.  Returns the bytes in all.
+struct LiSlot { size_t at, rows_at, first; };
+inline size_t li_align8(size_t x) { return (x + 7u) & ~(size_t)7u; }
+inline size_t li_stage_layout(size_t nctx, const size_t* fixed, const size_t* stage_rows, size_t row_bytes, size_t first_rows, LiSlot* slot, size_t* first_bytes) {
+    size_t off = nctx * LI_HEAD_BYTES;
+    for (size_t i = 0; i < nctx; ++i) {
+        slot[i].at = off; off += li_align8(fixed[i]);
+        slot[i].rows_at = off; slot[i].first = 0;
+        if (stage_rows && stage_rows[i] <= first_rows) { slot[i].first = stage_rows[i]; off += li_align8(stage_rows[i] * row_bytes); }
+    }
+    *first_bytes = off;
+    bool first_long = true;
+    for (size_t i = 0; stage_rows && i < nctx; ++i) {
+        if (stage_rows[i] <= first_rows) continue;
+        slot[i].rows_at = off;
+        if (first_long) { slot[i].first = first_rows; *first_bytes = off + first_rows * row_bytes; first_long = false; }
+        off += li_align8(stage_rows[i] * row_bytes);
+    }
+    return off;
+}
+
 // depth pixel (u, v) on the host, read with memcpy: an image row may start anywhere its pitch puts it
 inline bool li_read_depth(const f3ds_rgbd_format& fmt, const RgbdLayout& lay, const void* depth, uint32_t u, uint32_t v, float& z) {
     const unsigned char* drow = static_cast<const unsigned char*>(depth) + (size_t)v * lay.depth_pitch;

@@ -520,6 +520,46 @@ int f3ds_region_components_tiled(const f3ds_rgbd_format* fmt, const void* depth,
                                  const f3ds_component_params* params, uint32_t tile_w, uint32_t tile_h, uint32_t* comp_labels,
                                  f3ds_region_component* rows, size_t cap, size_t* n_out, f3ds_region_components_result* result);
 
+/* ---- batch forms of the five region calls: nctx frames of ONE format, one dispatch per kernel, one wait --------------------------
+ * Shaped like f3ds_segment_rgbd_batch: one context per frame (all on one device, none twice), one f3ds_rgbd_format for the batch, arrays of nctx per-frame
+ * pointers and counts.  Nothing new is defined numerically:
+ *   frame i    every output of frame i (rows[i], shapes[i], comp_labels[i], n_out[i], results[i]) holds the bits the lone call on ctxs[i] with frame i's
+ *              arguments writes, which are the bits of the f3ds_*_host definition.
+ *   refusals   of the call as a whole; nothing is written then, `status` included: F3DS_ERR_ARG for NULL ctxs, nctx < 1, a NULL or repeated context or contexts
+ *              on different devices; F3DS_ERR_ARG for a NULL pointer array the call needs (depth, labels, n_regions; rows of the table, shapes and boxes;
+ *              comp_labels; n_out; caps beside rows); then whatever the lone call refuses before it looks at a pixel, frame by frame in order -- the first
+ *              refusing frame's code is returned.  `color` (table) and `shapes` (boxes) are for every frame or for none: a NULL array means none, and a NULL
+ *              entry of a non-NULL array is F3DS_ERR_ARG (a NULL shapes[i] is allowed where n_regions[i] is 0).  rows[i] may be NULL where the lone call
+ *              allows it (n_regions[i] == 0; contacts and components: that frame is only counted).
+ *   status     status[i] (status may be NULL) = what the lone call returns once it has looked at pixels: F3DS_OK, F3DS_ERR_ARG for a label >= n_regions[i]
+ *              other than F3DS_NO_LABEL (nothing of frame i is written), F3DS_ERR_CAPACITY for contacts and components (n_out[i] and results[i] are
+ *              written, no row is; the image of the components is).  A failing frame does not disturb the others.  The call returns F3DS_OK if every frame
+ *              is, else the status of the lowest failing frame.  A HIP failure fails the whole call.
+ *   contexts   every context's state is as if the call never happened, as for the lone calls.  The call runs on ctxs[0]'s stream (a context with another
+ *              stream is waited for first) and is synchronous: the uploads of host inputs are queued together and awaited once, everything that comes down
+ *              comes in ONE download -- with device outputs the nctx heads of 32 bytes alone -- and the call waits once.  Frames beyond the ordinary case cost
+ *              further downloads: host row arrays of contacts / components longer than 2048 rows, and a contacts frame with more than 32768 contact
+ *              records, which runs once more on its own after the batch (the same bits).
+ * Each lone call is its batch form with nctx = 1. */
+int f3ds_region_table_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format* fmt, const void* const* depth,
+                            const void* const* color /* NULL: no colour image for any frame; else every entry non-NULL */, const uint32_t* const* labels,
+                            const uint32_t* n_regions /* nctx */, int inputs_on_device, f3ds_region_row* const* rows, int rows_on_device,
+                            f3ds_region_table_result* results /* nctx, may be NULL */, int* status /* nctx, may be NULL */);
+int f3ds_region_shapes_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format* fmt, const void* const* depth, const uint32_t* const* labels,
+                             const uint32_t* n_regions, int inputs_on_device, f3ds_region_shape* const* rows, int rows_on_device,
+                             f3ds_region_shapes_result* results, int* status);
+int f3ds_region_boxes_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format* fmt, const void* const* depth, const uint32_t* const* labels,
+                            const uint32_t* n_regions, float plane_tol, int inputs_on_device, f3ds_region_box* const* rows,
+                            f3ds_region_shape* const* shapes /* NULL: none; else every entry non-NULL */, int rows_on_device,
+                            f3ds_region_boxes_result* results, int* status);
+int f3ds_region_contacts_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format* fmt, const void* const* depth, const uint32_t* const* labels,
+                               const uint32_t* n_regions, float depth_tol, int inputs_on_device, f3ds_region_contact* const* rows /* NULL: counts only */,
+                               const size_t* caps /* nctx */, int rows_on_device, size_t* n_out /* nctx */, f3ds_region_contacts_result* results, int* status);
+int f3ds_region_components_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format* fmt, const void* const* depth, const uint32_t* const* labels,
+                                 const uint32_t* n_regions, const f3ds_component_params* params, int inputs_on_device, uint32_t* const* comp_labels,
+                                 f3ds_region_component* const* rows /* NULL: no rows */, const size_t* caps /* nctx */, int outputs_on_device,
+                                 size_t* n_out /* nctx */, f3ds_region_components_result* results, int* status);
+
 /* Clustering::cluster(threshold) again on the supervoxels of the last f3ds_segment call, with
  * possibly different metric / merging settings (src/clustering.cpp:670-679).  Only the merge
  * fields of `params` are read. */
