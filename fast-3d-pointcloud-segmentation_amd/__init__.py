@@ -189,6 +189,32 @@ REGION_BOX_DTYPE = np.dtype([("n_pixels", np.uint32), ("n_inliers", np.uint32)] 
 assert REGION_BOX_DTYPE.itemsize == ctypes.sizeof(RegionBox) == 96
 
 
+class JointParams(ctypes.Structure):
+    """f3ds_joint_params (include/f3ds.h): the contacts' depth tolerance, and the plane distance and the cosine below which two regions count as coplanar."""
+    _fields_ = [("depth_tol", ctypes.c_float), ("plane_tol", ctypes.c_float), ("cos_coplanar", ctypes.c_float)]
+
+
+class RegionJoint(ctypes.Structure):
+    """f3ds_region_joint (include/f3ds.h): the border of two touching regions in space and the relation of their planes, 80 bytes."""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("a", "b", "n_pairs", "n_close")] + [(k, ctypes.c_float * 3) for k in ("centroid", "direction", "spread")] + \
+               [(k, ctypes.c_float) for k in ("cos_angle", "delta_g", "h_ab", "h_ba", "e_a", "e_b")] + [("kind", ctypes.c_uint32)]
+
+
+class RegionJointsResult(ctypes.Structure):
+    """f3ds_region_joints_result (include/f3ds.h): the counts of one call for the region joints."""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("n_regions", "n_joints", "n_surface", "reserved")] + [("n_pairs", ctypes.c_uint64), ("n_close", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+# the same 80 bytes as a numpy structured dtype: what region_joints_host and Context.region_joints return their rows in
+REGION_JOINT_DTYPE = np.dtype([(k, np.uint32) for k in ("a", "b", "n_pairs", "n_close")] + [(k, np.float32, (3,)) for k in ("centroid", "direction", "spread")] +
+                              [(k, np.float32) for k in ("cos_angle", "delta_g", "h_ab", "h_ba", "e_a", "e_b")] + [("kind", np.uint32)])
+assert REGION_JOINT_DTYPE.itemsize == ctypes.sizeof(RegionJoint) == 80
+JOINT_OCCLUSION, JOINT_COPLANAR, JOINT_CONVEX, JOINT_CONCAVE, JOINT_KIND_MASK, JOINT_REF_CONVEX = 0, 1, 2, 3, 0xFF, 0x100      # the values and the flag of `kind`
+
+
 class ComponentParams(ctypes.Structure):
     """f3ds_component_params (include/f3ds.h): the depth tolerance of a link and the smallest component that is kept."""
     _fields_ = [("depth_tol", ctypes.c_float), ("min_pixels", ctypes.c_uint32)]
@@ -307,6 +333,15 @@ def load_library(path=None):
         lib.f3ds_region_components_tiled.restype = ctypes.c_int
         lib.f3ds_region_components.argtypes = [vp, ctypes.POINTER(RgbdFormat), vp, vp, ctypes.c_uint32, ckp, ctypes.c_int, vp, vp, sz, ctypes.c_int, ctypes.POINTER(sz), rkp]
         lib.f3ds_region_components.restype = ctypes.c_int
+    if hasattr(lib, "f3ds_region_joints"):
+        rjp, jpp, fp = ctypes.POINTER(RegionJointsResult), ctypes.POINTER(JointParams), ctypes.POINTER(RgbdFormat)
+        lib.f3ds_default_joint_params.argtypes = [jpp]; lib.f3ds_default_joint_params.restype = None
+        lib.f3ds_region_joints_host.argtypes = [fp, vp, vp, ctypes.c_uint32, jpp, vp, sz, ctypes.POINTER(sz), vp, rjp]; lib.f3ds_region_joints_host.restype = ctypes.c_int
+        lib.f3ds_region_joints.argtypes = [vp, fp, vp, vp, ctypes.c_uint32, jpp, ctypes.c_int, vp, sz, vp, ctypes.c_int, ctypes.POINTER(sz), rjp]
+        lib.f3ds_region_joints.restype = ctypes.c_int
+        lib.f3ds_region_joints_batch.argtypes = [ctypes.POINTER(vp), ctypes.c_int, fp, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, jpp, ctypes.c_int, ctypes.POINTER(vp), vp,
+                                                 ctypes.POINTER(vp), ctypes.c_int, vp, vp, vp]
+        lib.f3ds_region_joints_batch.restype = ctypes.c_int
     if hasattr(lib, "f3ds_region_table_batch"):      # the batch forms: arrays of per-frame pointers (void**), counts and results
         pp, fp, i32 = ctypes.POINTER(vp), ctypes.POINTER(RgbdFormat), ctypes.c_int
         lib.f3ds_region_table_batch.argtypes = [pp, i32, fp, pp, pp, pp, vp, i32, pp, i32, vp, vp]
@@ -821,6 +856,34 @@ def region_boxes_host(depth, labels, n_regions, fmt, plane_tol=0.01, want_shapes
     return (rows, shapes, res) if want_shapes else (rows, res)
 
 
+# ---- region joints ---------------------------------------------------------------------------------
+def default_joint_params(**overrides):
+    p = JointParams()
+    load_library().f3ds_default_joint_params(ctypes.byref(p))
+    for k, v in overrides.items():
+        setattr(p, k, v)
+    return p
+
+
+def region_joints_host(depth, labels, n_regions, fmt, params=None, want_shapes=False, rows_out=None):
+    """f3ds_region_joints_host: (rows, RegionJointsResult), or (rows, shapes, RegionJointsResult) with ``want_shapes`` -- one REGION_JOINT_DTYPE row per pair of
+    regions (a < b) of the label image that touch, by a and then b: the contacts' n_pairs and n_close, centroid, direction and spread of the border's samples
+    (both points of every close pair), the cosine between the two regions' planes, the reference's delta_g, the distances of each centroid from the other
+    region's plane and of the border centroid from both, and ``kind`` (JOINT_OCCLUSION / _COPLANAR / _CONVEX / _CONCAVE, | JOINT_REF_CONVEX).  ``params``: a
+    JointParams (None: the defaults); shapes: the REGION_SHAPE_DTYPE rows of region_shapes_host, the same bits.  Host arithmetic only: what
+    Context.region_joints computes on the device, bit for bit."""
+    lib = load_library()
+    f, d, _, lab = _region_inputs(fmt, depth, labels, None)
+    res = RegionJointsResult()
+    shapes = _shape_rows(None, n_regions) if want_shapes else None
+    sp = shapes.ctypes.data if want_shapes and len(shapes) else None
+    pp = ctypes.byref(params) if params is not None else None
+    rc, rows = _contact_rows(lambda ptr, cap, n_out: lib.f3ds_region_joints_host(ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), pp, ptr, cap, n_out, sp,
+                                                                                  ctypes.byref(res)), rows_out, REGION_JOINT_DTYPE)
+    _check(lib, rc)
+    return (rows, shapes, res) if want_shapes else (rows, res)
+
+
 # ---- region components -----------------------------------------------------------------------------
 def default_component_params(**overrides):
     p = ComponentParams()
@@ -975,6 +1038,31 @@ class Context(_Handle):
         shapes = _shape_rows(None if shapes_out is True else shapes_out, n_regions) if want else None
         _check(self.lib, self.lib.f3ds_region_boxes(self.handle, ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), float(plane_tol), 0,
                                                     rows.ctypes.data if len(rows) else None, shapes.ctypes.data if want and len(shapes) else None, 0, ctypes.byref(res)))
+        return (rows, shapes, res) if want else (rows, res)
+
+    def region_joints(self, depth, labels, n_regions, fmt, params=None, rows_out=None, shapes_out=None, on_device=False):
+        """f3ds_region_joints: (rows, RegionJointsResult) -- what region_joints_host returns, computed on the device with one wait; a and b index the rows of
+        region_table and region_shapes.  With ``shapes_out`` the shape rows come too and the answer is (rows, shapes, RegionJointsResult): ``True`` for a new
+        REGION_SHAPE_DTYPE array, or such an array to fill.  depth and labels as in region_table, or device pointers (ints, the depth pitch of ``fmt`` applies)
+        with ``on_device=True``: ``rows_out`` is then ``(device pointer, capacity in rows)`` or None (count only), ``shapes_out`` a device pointer to n_regions
+        rows or None, the rows returned are None and ``result.n_joints`` says how many were written (CapacityError, and none written, when there are more than
+        the capacity).  With host arrays ``rows_out`` may be a REGION_JOINT_DTYPE array to fill; without it a buffer that turns out too small is grown from the
+        count and the call repeated.  Leaves the context's frame as it is."""
+        res = RegionJointsResult()
+        pp = ctypes.byref(params) if params is not None else None
+        if on_device:
+            ptr, cap = (None, 0) if rows_out is None else (ctypes.c_void_p(int(rows_out[0])), int(rows_out[1]))
+            n_out = ctypes.c_size_t(0)
+            _check(self.lib, self.lib.f3ds_region_joints(self.handle, ctypes.byref(fmt), ctypes.c_void_p(int(depth)), ctypes.c_void_p(int(labels)), int(n_regions), pp, 1, ptr, cap,
+                                                         ctypes.c_void_p(int(shapes_out)) if shapes_out is not None else None, 1, ctypes.byref(n_out), ctypes.byref(res)))
+            return (None, res) if shapes_out is None else (None, None, res)
+        f, d, _, lab = _region_inputs(fmt, depth, labels, None)
+        want = shapes_out is not None and shapes_out is not False
+        shapes = _shape_rows(None if shapes_out is True else shapes_out, n_regions) if want else None
+        sp = shapes.ctypes.data if want and len(shapes) else None
+        rc, rows = _contact_rows(lambda ptr, cap, n_out: self.lib.f3ds_region_joints(self.handle, ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), pp, 0, ptr, cap,
+                                                                                     sp, 0, n_out, ctypes.byref(res)), rows_out, REGION_JOINT_DTYPE)
+        _check(self.lib, rc)
         return (rows, shapes, res) if want else (rows, res)
 
     def region_components(self, depth, labels, n_regions, fmt, depth_tol=0.05, min_pixels=1, rows_out=None, comp_out=None, on_device=False):
@@ -1627,6 +1715,48 @@ def region_contacts_batch(ctxs, depths, labels, n_regions, fmt, depth_tol=0.05, 
     rc, bufs, n_out = _capped_rows_batch(call, k, rows_out, on_device, REGION_CONTACT_DTYPE)
     rows = _capped_deliver(lib, call, rc, status, bufs, n_out, rows_out, REGION_CONTACT_DTYPE, on_device)
     return [(rows[i], results[i] if status[i] != ERR_ARG else None) for i in range(k)], status
+
+
+def region_joints_batch(ctxs, depths, labels, n_regions, fmt, params=None, rows_out=None, shapes_out=None, on_device=False):
+    """f3ds_region_joints_batch: Context.region_joints for every frame at once (lists as in region_contacts_batch).  ``shapes_out``: None, ``True`` (host form: new
+    arrays) or a list of buffers, for every frame or for none.  Returns ([(rows, RegionJointsResult)], status), or ([(rows, shapes, RegionJointsResult)], status)
+    with shapes."""
+    lib = load_library()
+    k, handles, f, dp, _, lp, nr, status, keep = _region_batch_inputs(ctxs, depths, labels, n_regions, fmt, None, on_device)
+    vp = ctypes.c_void_p
+    results = (RegionJointsResult * k)()
+    where = 1 if on_device else 0
+    pp = ctypes.byref(params) if params is not None else None
+    want = shapes_out is not None and shapes_out is not False
+    souts = [None] * k if (shapes_out is True or not want) else _outs(shapes_out, k, "shapes_out")
+    if want and shapes_out is not True and any(s is None for s in souts):
+        raise ValueError("shapes_out: a buffer for every frame or None (one command sequence for the batch)")
+    if on_device:
+        if shapes_out is True:
+            raise ValueError("on_device needs device buffers for the shape rows")
+        shapes = [None] * k
+        sp = (vp * k)(*[_opt_ptr(o) for o in souts]) if want else None
+    else:
+        shapes = [_shape_rows(o, nr[i]) for i, o in enumerate(souts)] if want else [None] * k
+        sp = (vp * k)(*[vp(s.ctypes.data) if len(s) else None for s in shapes]) if want else None
+
+    def call(rp, caps, n_out, frames, st=status):
+        m = len(frames)
+        pick = lambda arr, ty: (ty * m)(*[arr[i] for i in frames])
+        sub_res = (RegionJointsResult * m)()
+        rc = lib.f3ds_region_joints_batch(pick(handles, vp), m, ctypes.byref(f), pick(dp, vp), pick(lp, vp), pick(nr, ctypes.c_uint32), pp, where, rp, caps,
+                                          pick(sp, vp) if want else None, where, n_out, sub_res, st.ctypes.data)
+        for j, i in enumerate(frames):
+            if st[j] != _STATUS_UNSET:
+                results[i] = sub_res[j]
+        return rc
+
+    rc, bufs, n_out = _capped_rows_batch(call, k, rows_out, on_device, REGION_JOINT_DTYPE)
+    rows = _capped_deliver(lib, call, rc, status, bufs, n_out, rows_out, REGION_JOINT_DTYPE, on_device)
+    ok = [status[i] != ERR_ARG for i in range(k)]
+    if want:
+        return [(rows[i], shapes[i] if ok[i] else None, results[i] if ok[i] else None) for i in range(k)], status
+    return [(rows[i], results[i] if ok[i] else None) for i in range(k)], status
 
 
 def region_components_batch(ctxs, depths, labels, n_regions, fmt, depth_tol=0.05, min_pixels=1, rows_out=None, comp_out=None, on_device=False):

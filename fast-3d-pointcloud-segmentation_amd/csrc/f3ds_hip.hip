@@ -54,6 +54,7 @@
 #include "f3ds_contacts.h"
 #include "f3ds_shapes.h"
 #include "f3ds_boxes.h"
+#include "f3ds_joints.h"
 #include "f3ds_components.h"
 
 using namespace f3ds;
@@ -66,6 +67,7 @@ using namespace f3ds;
 #include "f3ds_contacts.inc"
 #include "f3ds_shapes.inc"
 #include "f3ds_boxes.inc"
+#include "f3ds_joints.inc"
 #include "f3ds_components.inc"
 
 // ================================================================================================
@@ -142,7 +144,7 @@ const int g_inc_shift = [] { const char* e = dev_getenv("F3DS_INC_SHIFT"); retur
 // where hundreds of getenv() scans per call would also race with a setenv from another thread.  Tests still see per-call values.
 struct Switches {
     bool direct_labels = false, copy_stream = true, copy_duplex = false, split_voxel_accum = false, sweep_tiles = true, merge_spec = true, force_global_merge = false, no_stream_pool = false, sort_pairs = false, host_prof = false, trace_err = false, vox_hash = true, vox_tiles_forced = false, levels_global = false;
-    int normals_threads = 0, merge_nw = 0, merge_keys = -1; uint32_t tile_holes = 0, ilist_slack = 32, r_rounds = F3DS_R_ROUNDS, grid_cap = 0, rgc_first_cap = 0; long relabel_lds_cap = -1;
+    int normals_threads = 0, merge_nw = 0, merge_keys = -1; uint32_t tile_holes = 0, ilist_slack = 32, r_rounds = F3DS_R_ROUNDS, grid_cap = 0, rgc_first_cap = 0, rgj_first_cap = 0; long relabel_lds_cap = -1;
     void read() {
         auto on = [](const char* n) { return dev_getenv(n) != nullptr; };
         auto num = [](const char* n, long dflt) { const char* e = dev_getenv(n); return e ? atol(e) : dflt; };
@@ -160,6 +162,7 @@ struct Switches {
         { const long v = num("F3DS_ILIST_SLACK", 32); ilist_slack = v >= 1 && v <= 32 ? (uint32_t)v : 32u; }      // tests: a short incident-list pool (the merge stage then reruns with a larger one)
         { const long v = num("F3DS_GRID_CAP", 0); grid_cap = v >= 1 && v <= 2048 ? (uint32_t)v : 0u; }      // tests: 1 ... 2048 workgroups per frame, exactly, for grid_for() and grid_wide(): the grid-stride loops make several trips on small frames (0: unset)
         { const long v = num("F3DS_RGC_FIRST_CAP", 0); rgc_first_cap = v >= 1 && v <= 0x7fffffffl ? (uint32_t)v : 0u; }      // tests: a short first record buffer of f3ds_region_contacts (the frame then runs again with room for all; 0: unset)
+        { const long v = num("F3DS_RGJ_FIRST_CAP", 0); rgj_first_cap = v >= 1 && v <= 0x7fffffffl ? (uint32_t)v : 0u; }      // tests: likewise the first record buffer of f3ds_region_joints
     }
 };
 thread_local Switches g_sw;
@@ -198,6 +201,8 @@ const int g_merge_shared_res = [] { const char* e = dev_getenv("F3DS_MERGE_SHARE
     X(ShAcc, rgs_acc) \
     /* region boxes (f3ds_boxes.inc; pass one adds into rgs_acc): the frames, the accumulators of pass two, its head, the shape rows of a caller who wants none */ \
     X(BxFrame, rgx_frame) X(BxAcc, rgx_acc) X(uint32_t, rgx_head) X(f3ds_region_shape, rgx_shape) \
+    /* region joints (f3ds_joints.inc): the shapes' accumulators and head, the shape rows of a caller who wants none, then as the contacts: the records' keys and indices (twice: the sort), the records, the runs' flags, keys, starts and ends, the run count */ \
+    X(ShAcc, rgj_sacc) X(uint32_t, rgj_shead) X(f3ds_region_shape, rgj_shape) X(uint64_t, rgj_k0) X(uint64_t, rgj_k1) X(uint32_t, rgj_v0) X(uint32_t, rgj_v1) X(uint32_t, rgj_rec) X(uint32_t, rgj_flag) X(uint64_t, rgj_ukey) X(uint32_t, rgj_ustart) X(uint32_t, rgj_uend) X(uint32_t, rgj_cnt) \
     /* region components (f3ds_components.inc): a parent, a size and a flag word per pixel */ \
     X(uint32_t, rgk_parent) X(uint32_t, rgk_cnt) X(uint32_t, rgk_flag)
 template <class T> struct Scratch { T* p = nullptr; size_t cap = 0; int slot = -1; };      // cap: bytes allocated; slot: position in F3DS_SCRATCH
@@ -2792,7 +2797,7 @@ extern "C" int f3ds_region_contacts(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, c
 // ------------------------------------------------------------------------------------------------
 // region shapes (f3ds_shapes.h / .inc): one row per region of a label image over a depth image -- covariance, eigenvalues, plane and long
 // axis.  The call has the region table's shape: d_shape_init, d_shape_accum (the one read of the image and the labels), d_shape_finish; behind the heads the
-// rows of a host caller (84 B per region).  sh_record is also pass one of the boxes.
+// rows of a host caller (84 B per region).  sh_record is also pass one of the boxes and the first step of the joints.
 // ------------------------------------------------------------------------------------------------
 namespace {
 ShapeArgs sh_args(const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, uint32_t K) {
@@ -2803,11 +2808,12 @@ ShapeArgs sh_args(const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, uint
     a.depth_scale = fmt.depth_scale; a.fx = fmt.fx; a.fy = fmt.fy; a.cx = fmt.cx; a.cy = fmt.cy;
     return a;
 }
-int sh_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, const LiImages& im, uint32_t K, uint32_t* head, f3ds_region_shape* d_rows) {
+// accs: the accumulators' scratch -- rgs_acc for the shapes and the boxes, the joints' own for the joints
+int sh_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, const LiImages& im, uint32_t K, uint32_t* head, f3ds_region_shape* d_rows, Scratch<ShAcc>& accs) {
     const ShapeArgs a = sh_args(fmt, lay, K);
     const uint32_t n = a.n;
     ShAcc* acc;
-    ENSURE(c->rgs_acc, K ? (size_t)K * a.copies : 1u, acc);
+    ENSURE(accs, K ? (size_t)K * a.copies : 1u, acc);
     rec<d_shape_init>(c, grid_for((size_t)K * a.copies * SH_WORDS, 256), 0u, reinterpret_cast<uint32_t*>(acc), K * a.copies, head);
     rec<d_shape_accum>(c, grid_for((n + LI_TRIPS - 1u) / LI_TRIPS, 256), 0u, im.depth, im.labels, a, acc, head);
     rec<d_shape_finish>(c, grid_for(K, 256), 0u, acc, K, a.copies, head, d_rows);
@@ -2829,7 +2835,7 @@ extern "C" int f3ds_region_shapes_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rg
     if (const int rc = li_upload(ctxs, nctx, b, lay, depth, nullptr, labels, inputs_on_device, im.data())) return rc;
     for (int i = 0; i < nctx; ++i) {
         f3ds_region_shape* d_rows = rows_on_device ? rows[i] : reinterpret_cast<f3ds_region_shape*>(s.out + s.slot[i].at);
-        if (const int rc = sh_record(ctxs[i], fmt, lay, im[i], n_regions[i], s.head(i), d_rows)) return rc;
+        if (const int rc = sh_record(ctxs[i], fmt, lay, im[i], n_regions[i], s.head(i), d_rows, ctxs[i]->rgs_acc)) return rc;
     }
     if (const int rc = flush(b)) return rc;
     if (const int rc = li_download_heads(s, b)) return rc;
@@ -2868,7 +2874,7 @@ int bx_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& 
     ENSURE(c->rgx_frame, K ? K : 1u, frames);
     ENSURE(c->rgx_head, LI_HEAD_WORDS, head2);
     if (!d_shapes) ENSURE(c->rgx_shape, K ? K : 1u, d_shapes);
-    if (const int rc = sh_record(c, fmt, lay, im, K, head, d_shapes)) return rc;      // (rgs_acc is ensured before its first rec<>, and nothing recorded refers to it yet)
+    if (const int rc = sh_record(c, fmt, lay, im, K, head, d_shapes, c->rgs_acc)) return rc;      // (rgs_acc is ensured before its first rec<>, and nothing recorded refers to it yet)
     rec<d_box_frame>(c, grid_for(K, 256), 0u, d_shapes, K, a.copies, plane_tol, head, frames, acc2, head2);
     rec<d_box_accum>(c, accum_grid, 0u, im.depth, im.labels, a, frames, acc2, head, head2);
     rec<d_box_finish>(c, grid_for(K, 256), 0u, acc2, frames, K, a.copies, head, d_rows);
@@ -2919,6 +2925,122 @@ extern "C" int f3ds_region_boxes_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgb
 extern "C" int f3ds_region_boxes(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, float plane_tol, int inputs_on_device,
                                  f3ds_region_box* rows, f3ds_region_shape* shapes, int rows_on_device, f3ds_region_boxes_result* result) {
     return f3ds_region_boxes_batch(&c, 1, fmt_, &depth, &labels, &n_regions, plane_tol, inputs_on_device, &rows, shapes ? &shapes : nullptr, rows_on_device, result, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------
+// region joints (f3ds_joints.h / .inc): one row per pair of regions of a label image that touch -- the border in space and the join of the
+// two regions' shape rows.  One flush: the three kernels of the shapes as they are (sh_record, into the joints' own accumulators and a head of their own: the
+// call's head is the contacts'), d_joint_init, d_joint_accum (the pass over the borders: records of (pair, 34 words)), the radix sort of the record keys,
+// d_evl_heads / scan, d_track_runs, d_joint_finish.  Behind the head the shape rows of a host caller who asked for them (84 B per region), then the first
+// RGJ_FIRST_ROWS rows.  Records that do not fit, long row arrays and the frames of a batch: as the contacts (ct_run).  Beside rgj_* the call uses the sort's
+// histogram and the scan's tile sums, which hold nothing between calls.
+// ------------------------------------------------------------------------------------------------
+namespace {
+int jt_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, const LiImages& im, uint32_t K, const f3ds_joint_params& prm, uint32_t rec_cap, int sort_bits,
+              uint32_t* head, f3ds_region_joint* d_rows, size_t cap, f3ds_region_shape* d_shapes /* NULL: the context's scratch */) {
+    const uint32_t n = (uint32_t)lay.n;
+    uint64_t *k0, *k1, *ukey; uint32_t *v0, *v1, *rec_words, *flag, *ustart, *uend, *cnt, *hist, *tiles, *shead;
+    ENSURE(c->rgj_k0, rec_cap, k0); ENSURE(c->rgj_k1, rec_cap, k1); ENSURE(c->rgj_v0, rec_cap, v0); ENSURE(c->rgj_v1, rec_cap, v1);
+    ENSURE(c->rgj_rec, (size_t)rec_cap * JT_WORDS, rec_words); ENSURE(c->rgj_flag, rec_cap, flag); ENSURE(c->rgj_ukey, rec_cap, ukey);
+    ENSURE(c->rgj_ustart, rec_cap, ustart); ENSURE(c->rgj_uend, rec_cap, uend); ENSURE(c->rgj_cnt, 4, cnt); ENSURE(c->rgj_shead, LI_HEAD_WORDS, shead);
+    ENSURE(c->hist, (size_t)RS_BINS * ((rec_cap + RS_TILE - 1) / RS_TILE + 1), hist); ENSURE(c->tiles, (rec_cap + SCAN_TILE - 1) / SCAN_TILE + 1, tiles);
+    if (!d_shapes) ENSURE(c->rgj_shape, K ? K : 1u, d_shapes);
+    if (const int rc = sh_record(c, fmt, lay, im, K, shead, d_shapes, c->rgj_sacc)) return rc;      // (rgj_sacc is ensured before its first rec<>, and nothing recorded refers to it yet)
+    JointArgs a;
+    memset(&a, 0, sizeof a);
+    a.width = fmt.width; a.height = fmt.height; a.n = n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
+    a.K = K; a.kb = ct_bits(K); a.rec_cap = rec_cap; a.depth_scale = fmt.depth_scale; a.depth_tol = prm.depth_tol; a.fx = fmt.fx; a.fy = fmt.fy; a.cx = fmt.cx; a.cy = fmt.cy;
+    const uint64_t hole = ct_hole(K, a.kb);
+    int rc;
+    rec<d_joint_init>(c, grid_for(rec_cap, 256), 0u, k0, v0, rec_cap, head);
+    rec<d_joint_accum>(c, grid_for((n + RGJ_TRIPS - 1u) / RGJ_TRIPS, RGJ_BLOCK), 0u, im.depth, im.labels, a, k0, rec_words, head);
+    uint64_t* ks; uint32_t* vs;
+    if ((rc = radix_sort(c, k0, v0, k1, v1, rec_cap, sort_bits, &ks, &vs))) return rc;
+    rec<d_evl_heads>(c, grid_for(rec_cap, 256), 0u, ks, rec_cap, hole, flag);
+    if ((rc = scan_u32(c, flag, flag, rec_cap))) return rc;
+    rec<d_track_runs>(c, grid_for(rec_cap, 256), 0u, ks, rec_cap, hole, flag, ukey, ustart, uend, cnt);
+    rec<d_joint_finish>(c, grid_for((size_t)(rec_cap < 8192u ? rec_cap : 8192u) * 64u, 256), 0u, ukey, ustart, uend, cnt, vs, rec_words, d_shapes, prm, a.kb, rec_cap, head, d_rows,
+                        (uint64_t)cap);
+    return F3DS_OK;
+}
+// the call after its checks, with room for first_cap records (at most 2n) per frame: st[i] = frame i's status; the result is a failure of the call as a whole
+int jt_run(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, const void* const* depth, const uint32_t* const* labels, const uint32_t* n_regions,
+           const f3ds_joint_params& prm, int inputs_on_device, f3ds_region_joint* const* rows, const size_t* caps, f3ds_region_shape* const* shapes, int rows_on_device, size_t* n_out,
+           f3ds_region_joints_result* results, uint32_t first_cap, int* st) {
+    Batch b;
+    if (const int rc = li_begin(ctxs, nctx, &b)) return rc;
+    const uint32_t n = (uint32_t)lay.n;
+    const uint32_t rec_all = 2u * n;      // (n < 2^29: jt_check)  every contact pair a record of its own is fewer than this
+    const uint32_t rec_cap = first_cap < rec_all ? first_cap : rec_all;
+    int sort_bits = 0;
+    for (int i = 0; i < nctx; ++i) sort_bits = std::max(sort_bits, ct_sort_bits(n_regions[i]));
+    std::vector<size_t> fixed((size_t)nctx, 0u), stage_rows((size_t)nctx, 0u), count((size_t)nctx, 0u);
+    std::vector<void*> dst((size_t)nctx, nullptr);
+    for (int i = 0; i < nctx; ++i) {
+        if (shapes && shapes[i] && !rows_on_device) fixed[i] = (size_t)n_regions[i] * sizeof(f3ds_region_shape);      // (84 B a row: li_stage_layout aligns what follows)
+        if (rows && rows[i] && !rows_on_device) stage_rows[i] = caps[i] < rec_cap ? caps[i] : (size_t)rec_cap;      // (rows <= records <= rec_cap)
+    }
+    LiStage s; std::vector<LiImages> im((size_t)nctx);
+    if (const int rc = li_out_buffers(ctxs[0], nctx, fixed.data(), stage_rows.data(), sizeof(f3ds_region_joint), RGJ_FIRST_ROWS, &s)) return rc;
+    if (const int rc = li_upload(ctxs, nctx, b, lay, depth, nullptr, labels, inputs_on_device, im.data())) return rc;
+    for (int i = 0; i < nctx; ++i) {
+        f3ds_region_joint* const r = rows ? rows[i] : nullptr;
+        f3ds_region_joint* d_rows = !r ? nullptr : (rows_on_device ? r : reinterpret_cast<f3ds_region_joint*>(s.out + s.slot[i].rows_at));
+        f3ds_region_shape* d_shapes = !shapes || !shapes[i] ? nullptr : (rows_on_device ? shapes[i] : reinterpret_cast<f3ds_region_shape*>(s.out + s.slot[i].at));
+        if (const int rc = jt_record(ctxs[i], fmt, lay, im[i], n_regions[i], prm, rec_cap, sort_bits, s.head(i), d_rows, r ? caps[i] : 0u, d_shapes)) return rc;
+    }
+    if (const int rc = flush(b)) return rc;
+    if (const int rc = li_download_heads(s, b)) return rc;
+    std::vector<int> again;
+    for (int i = 0; i < nctx; ++i) {
+        const uint32_t* h = s.h_head(i);
+        st[i] = F3DS_OK;
+        if (h[1]) { st[i] = F3DS_ERR_ARG; continue; }      // (a label >= n_regions: neither finish kernel wrote a row)
+        if (h[2] > rec_cap) {      // (rare: more records than the first buffer holds)
+            if (rec_cap >= rec_all) return F3DS_ERR_LOGIC;
+            again.push_back(i); continue;
+        }
+        const size_t cnt = h[0];
+        if (cnt > rec_cap) return F3DS_ERR_LOGIC;
+        n_out[i] = cnt;
+        if (fixed[i]) memcpy(shapes[i], s.o->h_li + s.slot[i].at, fixed[i]);
+        if (results) {
+            results[i].n_regions = n_regions[i]; results[i].n_joints = h[0]; results[i].n_surface = h[3]; results[i].reserved = 0u;
+            memcpy(&results[i].n_pairs, h + 4, 8); memcpy(&results[i].n_close, h + 6, 8);
+        }
+        if (!rows || !rows[i]) continue;
+        if (caps[i] < cnt) { st[i] = F3DS_ERR_CAPACITY; continue; }
+        if (!rows_on_device) { count[i] = cnt; dst[i] = rows[i]; }
+    }
+    if (const int rc = li_rows_behind(s, b, nctx, sizeof(f3ds_region_joint), count.data(), dst.data())) return rc;
+    for (const int i : again) {      // (the owner's staging is free again: everything else has been delivered)
+        if (const int rc = jt_run(ctxs + i, 1, fmt, lay, depth + i, labels + i, n_regions + i, prm, inputs_on_device, rows ? rows + i : nullptr, caps ? caps + i : nullptr,
+                                  shapes ? shapes + i : nullptr, rows_on_device, n_out + i, results ? results + i : nullptr, rec_all, &st[i])) return rc;
+    }
+    return F3DS_OK;
+}
+}  // namespace
+
+extern "C" int f3ds_region_joints_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format* fmt_, const void* const* depth, const uint32_t* const* labels, const uint32_t* n_regions,
+                                        const f3ds_joint_params* params, int inputs_on_device, f3ds_region_joint* const* rows, const size_t* caps, f3ds_region_shape* const* shapes,
+                                        int rows_on_device, size_t* n_out, f3ds_region_joints_result* results, int* status) {
+    if (!li_batch_ctxs(ctxs, nctx) || !depth || !labels || !n_regions || (rows && !caps)) return F3DS_ERR_ARG;
+    f3ds_rgbd_format fmt; f3ds::RgbdLayout lay; f3ds_joint_params prm;
+    for (int i = 0; i < nctx; ++i) {
+        if (shapes && !shapes[i] && n_regions[i]) return F3DS_ERR_ARG;      // (shape rows for every frame or for none)
+        if (const int rc = jt_check(fmt_, depth[i], labels[i], n_regions[i], params, n_out, &fmt, &lay, &prm)) return rc;
+    }
+    std::vector<int> st((size_t)nctx, F3DS_OK);
+    g_sw.read();
+    const uint32_t first = g_sw.rgj_first_cap ? g_sw.rgj_first_cap : RGJ_FIRST_CAP;
+    if (const int rc = jt_run(ctxs, nctx, fmt, lay, depth, labels, n_regions, prm, inputs_on_device, rows, caps, shapes, rows_on_device, n_out, results, first, st.data())) return rc;
+    return li_statuses(st, status);
+}
+extern "C" int f3ds_region_joints(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, const f3ds_joint_params* params,
+                                  int inputs_on_device, f3ds_region_joint* rows, size_t cap, f3ds_region_shape* shapes, int rows_on_device, size_t* n_out,
+                                  f3ds_region_joints_result* result) {
+    return f3ds_region_joints_batch(&c, 1, fmt_, &depth, &labels, &n_regions, params, inputs_on_device, rows ? &rows : nullptr, &cap, shapes ? &shapes : nullptr, rows_on_device, n_out,
+                                    result, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -24,6 +24,7 @@
 #include "f3ds_contacts.h"
 #include "f3ds_shapes.h"
 #include "f3ds_boxes.h"
+#include "f3ds_joints.h"
 #include "f3ds_components.h"
 
 extern "C" {
@@ -322,6 +323,61 @@ int f3ds_region_boxes_host(const f3ds_rgbd_format* fmt_, const void* depth, cons
     if (result) {
         result->n_regions = n_regions; result->n_nonempty = sres.n_nonempty; result->n_labelled = sres.n_labelled; result->n_clamped = sres.n_clamped;
         result->n_inliers = n_inliers;
+    }
+    return F3DS_OK;
+}
+
+// ---- region joints: the definition (the rules are in f3ds_joints.h, which d_joint_accum and d_joint_finish call too) ----
+void f3ds_default_joint_params(f3ds_joint_params* p) { if (p) { p->depth_tol = 0.05f; p->plane_tol = 0.01f; p->cos_coplanar = 0.9659258f; } }
+
+// The shapes' host function first (it checks the labels before it writes a row), then the contacts' loop over the pixel pairs with one ordered map from the
+// pair's key to its accumulator, then the same finish as the device: the rows come out by a, then b.
+int f3ds_region_joints_host(const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, const f3ds_joint_params* params,
+                            f3ds_region_joint* rows, size_t cap, size_t* n_out, f3ds_region_shape* shapes, f3ds_region_joints_result* result) {
+    f3ds_rgbd_format fmt; f3ds::RgbdLayout l; f3ds_joint_params prm;
+    if (const int rc = f3ds::jt_check(fmt_, depth, labels, n_regions, params, n_out, &fmt, &l, &prm)) return rc;
+    if (!f3ds::li_labels_in_range(labels, l.n, n_regions)) return F3DS_ERR_ARG;
+    std::vector<f3ds_region_shape> own(shapes ? 0u : n_regions);
+    f3ds_region_shape* S = shapes ? shapes : own.data();
+    if (const int rc = f3ds_region_shapes_host(fmt_, depth, labels, n_regions, n_regions ? S : nullptr, nullptr)) return rc;
+    auto pixel = [&](uint32_t u, uint32_t v, float& z) {      // labelled?
+        return f3ds::li_read_depth(fmt, l, depth, u, v, z) && labels[(size_t)v * fmt.width + u] != F3DS_NO_LABEL;
+    };
+    const int kb = f3ds::ct_bits(n_regions);
+    std::map<uint64_t, f3ds::JtAcc> acc;
+    auto contact = [&](uint32_t u, uint32_t v, bool horizontal, float zp, float zq) {
+        const uint32_t p = v * fmt.width + u, q = horizontal ? p + 1u : p + fmt.width;
+        if (labels[p] == labels[q]) return;
+        float P[3], Q[3];
+        f3ds::n_deproject(u, v, true, zp, fmt.fx, fmt.fy, fmt.cx, fmt.cy, P[0], P[1], P[2]);
+        f3ds::n_deproject(horizontal ? u + 1u : u, horizontal ? v : v + 1u, true, zq, fmt.fx, fmt.fy, fmt.cx, fmt.cy, Q[0], Q[1], Q[2]);
+        uint32_t a, b; f3ds::JtAcc one;
+        f3ds::jt_pair(p, horizontal, labels[p], zp, labels[q], zq, prm.depth_tol, P, Q, a, b, one);
+        auto it = acc.find(f3ds::ct_key(a, b, kb));
+        if (it == acc.end()) acc.emplace(f3ds::ct_key(a, b, kb), one); else f3ds::jt_merge(it->second, one);
+    };
+    for (uint32_t v = 0; v < fmt.height; ++v)
+        for (uint32_t u = 0; u < fmt.width; ++u) {
+            float zp = 0.0f, zq = 0.0f;
+            if (!pixel(u, v, zp)) continue;
+            if (u + 1u < fmt.width && pixel(u + 1u, v, zq)) contact(u, v, true, zp, zq);
+            if (v + 1u < fmt.height && pixel(u, v + 1u, zq)) contact(u, v, false, zp, zq);
+        }
+    const size_t count = acc.size();
+    uint64_t n_pairs = 0, n_close = 0; uint32_t n_surface = 0;
+    for (const auto& kv : acc) { n_pairs += kv.second.n_pairs; n_close += kv.second.n_close; if (kv.second.n_close) ++n_surface; }
+    *n_out = count;
+    if (result) {
+        result->n_regions = n_regions; result->n_joints = (uint32_t)count; result->n_surface = n_surface; result->reserved = 0u;
+        result->n_pairs = n_pairs; result->n_close = n_close;
+    }
+    if (!rows) return F3DS_OK;
+    if (cap < count) return F3DS_ERR_CAPACITY;
+    size_t e = 0;
+    const uint64_t bmask = (1ull << kb) - 1ull;
+    for (const auto& kv : acc) {
+        const uint32_t a = (uint32_t)(kv.first >> kb), b = (uint32_t)(kv.first & bmask);
+        f3ds::jt_finish(a, b, kv.second, S[a], S[b], prm, &rows[e++]);
     }
     return F3DS_OK;
 }

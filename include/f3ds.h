@@ -520,6 +520,80 @@ int f3ds_region_components_tiled(const f3ds_rgbd_format* fmt, const void* depth,
                                  const f3ds_component_params* params, uint32_t tile_w, uint32_t tile_h, uint32_t* comp_labels,
                                  f3ds_region_component* rows, size_t cap, size_t* n_out, f3ds_region_components_result* result);
 
+/* ---- region joints: one fixed-size row per pair of touching regions: the border in space and the dihedral relation of the two planes -----
+ * The sixth member of the family joins the contacts with the shapes: a contact row (a, b) and the two shape rows S_a, S_b become one row that says where
+ * in space the border runs, which way, and whether the two planes meet in a convex edge, a concave corner, lie in one plane, or merely hide one another.
+ * labels, n_regions and the region ids are the region table's.  The definition, bit for bit (csrc/f3ds_joints.h):
+ *   point, pairs, contact, close   the contacts', word for word.  The rows are the rows of f3ds_region_contacts at the same depth_tol: the pairs (a, b),
+ *              their order and count, n_pairs and n_close are the same bits, and so are *n_out and the result's n_joints (the contacts' n_contacts),
+ *              n_pairs and n_close.  n_surface = the number of rows with n_close > 0.
+ *   samples    every CLOSE pair contributes both of its pixels' points (x, y, z by the rule of f3ds_deproject) as two samples of (a, b); a pixel in
+ *              two close pairs of the same (a, b) counts twice.  The samples' moments are the shapes': every coordinate through the table's fix, then
+ *              n, S_a and M_ab as exact integer sums.  The finish of the shapes on these moments gives centroid (its centroid), direction (its axis) and
+ *              spread (its eigenvalue); nothing else of that shape row is looked at.  A frame has at most 4 * width * height samples and the shapes'
+ *              finish wants n < 2^31: width * height > 0x1FFFFFFF is F3DS_ERR_UNSUPPORTED, after the family's checks.
+ *   regions    S_a, S_b = the rows f3ds_region_shapes defines for a and b (both non-empty: each has a labelled pixel in a contact).  Only their public
+ *              floats are used: c = centroid, n = normal, d = plane_d.  Every operation below is one rounded f32 operation, nothing fused, in this order:
+ *                cos_angle = (n_a.x * n_b.x + n_a.y * n_b.y) + n_a.z * n_b.z
+ *                h_ab = ((n_a.x * c_b.x + n_a.y * c_b.y) + n_a.z * c_b.z) + d_a;  h_ba likewise with a and b swapped
+ *                e_a, e_b: the same form with the border centroid (the row's `centroid`) in place of the other region's centroid
+ *                delta_g = the reference's normals_diff (src/clustering.cpp:53-96) on (n_a, c_a, n_b, c_b); F3DS_JOINT_REF_CONVEX iff its is_convex
+ *              Every float of the row is canonicalised as in the boxes (t != t ? 0x7FC00000 : bits).  Two identical centroids give a NaN delta_g and no flag.
+ *   kind       n_close == 0: F3DS_JOINT_OCCLUSION; centroid, direction, spread, e_a and e_b are the quiet NaN 0x7FC00000, the other fields as above.
+ *              Otherwise F3DS_JOINT_COPLANAR iff cos_angle >= cos_coplanar && fabsf(h_ab) <= plane_tol && fabsf(h_ba) <= plane_tol (comparisons fail on
+ *              NaN); otherwise F3DS_JOINT_CONVEX iff h_ab + h_ba < 0 (one f32 add); otherwise F3DS_JOINT_CONCAVE.  Normals face the camera, so the far
+ *              face of a box edge lies below the near face's plane (convex) and a wall stands above the floor's plane (concave).
+ *   shapes     a non-NULL `shapes` receives the n_regions rows of f3ds_region_shapes, the same bits, as in f3ds_region_boxes.
+ *   capacity   the contacts': *n_out receives the row count on F3DS_OK and on F3DS_ERR_CAPACITY.  rows == NULL: count only, cap is ignored.  cap smaller
+ *              than the count: F3DS_ERR_CAPACITY, no row is written; shapes and result are.
+ * A region of one point or of points on a line has a plane that is defined but MEANINGLESS, as in the shapes: look at eigenvalue[1] of S_a and S_b before
+ * believing kind, cos_angle or the h and e fields, and at spread[2] before believing direction (a border of one close pair has two samples).
+ * Everything that meets more than one pixel is an integer sum or a count, and the finish is one function for host and device: the device gives the bits
+ * of the host function under any schedule.  Not built: samples of occlusion borders, 8-connected pairs, joints of clouds without an image grid.
+ * Errors (both functions alike): the contacts' (a NULL fmt, depth, labels or n_out, a refused format, a depth_tol that is negative or not finite:
+ * F3DS_ERR_ARG), F3DS_ERR_ARG for a plane_tol that is negative or NaN and for a cos_coplanar that is NaN or outside [-1, 1], then F3DS_ERR_UNSUPPORTED for
+ * n_regions > 0x00FFFFFF or width * height > 0x1FFFFFFF, then F3DS_ERR_ARG for a label >= n_regions other than F3DS_NO_LABEL (the device function finds
+ * it on the device and reports it at the call's one wait).  params == NULL: the defaults.  After an error nothing is written: no row, no shape row, no
+ * n_out, no result. */
+enum { F3DS_JOINT_OCCLUSION = 0, F3DS_JOINT_COPLANAR = 1, F3DS_JOINT_CONVEX = 2, F3DS_JOINT_CONCAVE = 3 };
+#define F3DS_JOINT_REF_CONVEX 0x100u   /* flag in `kind`: the reference's is_convex on the two regions */
+typedef struct f3ds_joint_params { float depth_tol, plane_tol, cos_coplanar; } f3ds_joint_params;   /* defaults 0.05f, 0.01f, 0.9659258f (15 degrees) */
+typedef struct f3ds_region_joint {      /* 80 bytes, 20 words */
+    uint32_t a, b;            /* region ids, a < b: the contact row's                                   */
+    uint32_t n_pairs, n_close;/* the bits of f3ds_region_contacts at the same depth_tol                 */
+    float centroid[3];        /* of the border samples                                                  */
+    float direction[3];       /* the direction the border runs in (the shapes' `axis` rule)             */
+    float spread[3];          /* eigenvalues of the samples' covariance, ascending                      */
+    float cos_angle;          /* n_a . n_b                                                              */
+    float delta_g;            /* the reference's normals_diff on the two regions                        */
+    float h_ab, h_ba;         /* signed distance of b's centroid from a's plane, and of a's from b's    */
+    float e_a, e_b;           /* signed distance of the border centroid from a's and from b's plane     */
+    uint32_t kind;            /* F3DS_JOINT_* | F3DS_JOINT_REF_CONVEX                                   */
+} f3ds_region_joint;
+typedef struct f3ds_region_joints_result { uint32_t n_regions, n_joints, n_surface, reserved; uint64_t n_pairs, n_close; } f3ds_region_joints_result;
+void f3ds_default_joint_params(f3ds_joint_params* params);
+/* host arithmetic only, no device needed: the definition.  shapes: n_regions rows or NULL */
+int f3ds_region_joints_host(const f3ds_rgbd_format* fmt, const void* depth, const uint32_t* labels, uint32_t n_regions, const f3ds_joint_params* params,
+                            f3ds_region_joint* rows, size_t cap, size_t* n_out, f3ds_region_shape* shapes /* may be NULL */,
+                            f3ds_region_joints_result* result /* may be NULL */);
+/* the same rows from the device: the kernels of f3ds_region_shapes, one pass over the borders, the sort of its records and one finish per row, recorded
+ * back to back with ONE wait (csrc/f3ds_joints.inc).  inputs_on_device: depth and labels are device memory and read where they are; host inputs go
+ * through the device's copy stream like those of f3ds_region_table.  rows_on_device covers both outputs: rows (cap rows of it), and shapes unless it is
+ * NULL, are device memory; host rows arrive with the call's one download (a second one only for more than 2048 rows).  Synchronous.  Runs on ctx's stream
+ * and uses scratch of its own (and the sort's histogram and scan buffers, which hold nothing between calls): every other call on the context behaves as
+ * if this one never happened.  Also F3DS_ERR_ARG for a NULL ctx.  result may be NULL.  A frame with more than 32768 border records runs once more with
+ * room for all (the same bits). */
+int f3ds_region_joints(f3ds_ctx* ctx, const f3ds_rgbd_format* fmt, const void* depth, const uint32_t* labels, uint32_t n_regions,
+                       const f3ds_joint_params* params, int inputs_on_device, f3ds_region_joint* rows, size_t cap,
+                       f3ds_region_shape* shapes /* may be NULL */, int rows_on_device, size_t* n_out, f3ds_region_joints_result* result);
+/* the batch form, by the rules of the batch forms below (rows as the contacts': NULL or a NULL entry counts only, caps beside rows; shapes as the boxes':
+ * for every frame or for none; status[i] may be F3DS_ERR_CAPACITY: n_out[i], results[i] and shapes[i] are written, no row is) */
+int f3ds_region_joints_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format* fmt, const void* const* depth, const uint32_t* const* labels,
+                             const uint32_t* n_regions, const f3ds_joint_params* params, int inputs_on_device,
+                             f3ds_region_joint* const* rows /* NULL: counts only */, const size_t* caps /* nctx */,
+                             f3ds_region_shape* const* shapes /* NULL: none; else every entry non-NULL */, int rows_on_device, size_t* n_out /* nctx */,
+                             f3ds_region_joints_result* results, int* status);
+
 /* ---- batch forms of the five region calls: nctx frames of ONE format, one dispatch per kernel, one wait --------------------------
  * Shaped like f3ds_segment_rgbd_batch: one context per frame (all on one device, none twice), one f3ds_rgbd_format for the batch, arrays of nctx per-frame
  * pointers and counts.  Nothing new is defined numerically:
