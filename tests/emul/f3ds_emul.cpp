@@ -63,6 +63,10 @@ struct f3ds_emul {
     // memoised.  r_deep_cold (only with F3DS_EMUL_R_COLD set: a copy of the memo per voxel): voxels whose a_eval_R_mask overflows when it starts from the memo as the
     // pre-pass left it -- what a device thread meets that runs before any other has settled part of its chain; the device evaluates a work list in no particular order.
     uint32_t r_deep = 0u, r_deep_cold = 0u;
+    // The last f3ds_emul_refine, per iteration (tests/refine_clouds_common.py): helpers with ghost_active set when the iteration starts, and the seed d_reseed gives every
+    // helper (-1: erased earlier)
+    std::vector<uint32_t> refine_ghosts, refine_ghosts_above;      // (above: ... whose label is higher than the owner's of the voxel they hold: the ones d_refine_ghost_L writes for)
+    std::vector<std::vector<int>> refine_seeds;
     f3ds_result res;
 };
 
@@ -688,7 +692,11 @@ int f3ds_emul_refine(f3ds_emul* Ep, int num_itr, uint32_t* voxel_sv_label, float
     const std::vector<uint32_t> owner0 = E.owner, hcount0 = E.hcount;
     const std::vector<int> gv0 = E.ghost_vox; const std::vector<uint8_t> ga0 = E.ghost_active;
     const f3ds_result res0 = E.res;
+    E.refine_ghosts.clear(); E.refine_ghosts_above.clear(); E.refine_seeds.clear();
     for (int it = 0; it < num_itr; ++it) {
+        uint32_t alive = 0, above = 0;
+        for (int h = 1; h <= S0; ++h) if (E.ghost_active[h]) { alive++; if (E.ghost_vox[h] >= 0 && (uint32_t)h > E.owner[E.ghost_vox[h]]) above++; }
+        E.refine_ghosts.push_back(alive); E.refine_ghosts_above.push_back(above);
         std::vector<uint32_t> L = E.owner;                                   // d_refine_ghost_L
         for (int h = 1; h <= S0; ++h) if (E.ghost_active[h] && E.ghost_vox[h] >= 0 && (uint32_t)h > L[E.ghost_vox[h]]) L[E.ghost_vox[h]] = (uint32_t)h;
         for (int v = 0; v < V; ++v) {                                        // d_refine_normals (reads xyz only, writes normals)
@@ -714,16 +722,31 @@ int f3ds_emul_refine(f3ds_emul* Ep, int num_itr, uint32_t* voxel_sv_label, float
             n_plane_normal(acc, cnt, &E.vf[(size_t)v * 12], n4);
             E.vf[(size_t)v * 12 + 6] = n4[0]; E.vf[(size_t)v * 12 + 7] = n4[1]; E.vf[(size_t)v * 12 + 8] = n4[2];
         }
-        std::vector<int> seeds(S0, -1);                                      // d_reseed
+        // d_reseed, thread for thread: BLOCK threads scan the voxels BLOCK apart in ascending order (the first minimum stays), then the tree reduction over the
+        // threads' minima, in which an exact tie goes to the lower ordinal
+        constexpr int BLOCK = 256;
+        std::vector<int> seeds(S0, -1);
+        std::vector<float> xyz((size_t)V * 3);
+        for (int v = 0; v < V; ++v) for (int a = 0; a < 3; ++a) xyz[(size_t)v * 3 + a] = E.vf[(size_t)v * 12 + a];
         for (int h = 1; h <= S0; ++h) {
             if (!E.hcount[h]) continue;
-            int best = -1; float bd = 0.0f;
-            for (int v = 0; v < V; ++v) {
-                const float d = a_sqdist(&E.hc[(size_t)h * 12], &E.vf[(size_t)v * 12]);
-                if (best < 0 || d < bd) { best = v; bd = d; }
+            float sd[BLOCK]; int sv[BLOCK];
+            for (int t = 0; t < BLOCK; ++t) {
+                int best = -1; float bd = 0.0f;
+                for (int v = t; v < V; v += BLOCK) {
+                    const float d = a_sqdist(&E.hc[(size_t)h * 12], &xyz[(size_t)v * 3]);
+                    if (best < 0 || d < bd) { best = v; bd = d; }
+                }
+                sd[t] = bd; sv[t] = best;
             }
-            seeds[h - 1] = best;
+            for (int w = BLOCK / 2; w > 0; w >>= 1)
+                for (int t = 0; t < w; ++t) {
+                    const int ob = sv[t + w], mb = sv[t]; const float od = sd[t + w], md = sd[t];
+                    if (ob >= 0 && (mb < 0 || od < md || (od == md && ob < mb))) { sv[t] = ob; sd[t] = od; }
+                }
+            seeds[h - 1] = sv[0];
         }
+        E.refine_seeds.push_back(seeds);
         int rc = stage_sweeps(E, seeds, true);
         if (rc) return rc;
     }
@@ -744,6 +767,21 @@ int f3ds_emul_refine(f3ds_emul* Ep, int num_itr, uint32_t* voxel_sv_label, float
     if (n_sv_out) *n_sv_out = k;
     E.vf = vf0; E.dist = dist0; E.hc = hc0; E.owner = owner0; E.hcount = hcount0; E.ghost_vox = gv0; E.ghost_active = ga0; E.res = res0;
     return k > cap_sv && (sv_label || sv_feat || sv_count) ? F3DS_ERR_CAPACITY : F3DS_OK;
+}
+
+// What the last f3ds_emul_refine met (tests/refine_clouds_common.py).  Iteration it = 0 .. num_itr - 1; both return -1 for an iteration that call did not run.
+// ghosts: helpers with ghost_active set when the iteration starts (it = 0: ghost leaves of the seed stage that outlived the frame's own sweeps); above != 0: only those
+// with a higher label than the owner of the voxel they hold -- refineNormals of such a helper is the last to write that voxel's normal
+int f3ds_emul_refine_ghosts(const f3ds_emul* E, int it, int above) {
+    if (!E || it < 0 || (size_t)it >= E->refine_ghosts.size()) return -1;
+    return (int)(above ? E->refine_ghosts_above[it] : E->refine_ghosts[it]);
+}
+// seeds: the voxel d_reseed gives helper 1 .. S0 in that iteration (-1: the helper was empty); returns S0
+int f3ds_emul_refine_seeds(const f3ds_emul* E, int it, int* seeds, size_t cap) {
+    if (!E || it < 0 || (size_t)it >= E->refine_seeds.size()) return -1;
+    const std::vector<int>& s = E->refine_seeds[it];
+    if (seeds) for (size_t i = 0; i < s.size() && i < cap; ++i) seeds[i] = s[i];
+    return (int)s.size();
 }
 
 // the sweep-control protocol of the device kernels (a_sweep_begin, a_sweep_thr in csrc/f3ds_algo.h) for tests/test_sweep_control_cpu.py.  words: n_changed, sweep_full,
