@@ -47,10 +47,11 @@ def test_every_stage_matches_oracle_and_golden(P, oracle, gpu_ctx, name, stage0,
 
 
 def test_tile_voxelisation_falls_back_where_it_must_and_agrees_everywhere(P, oracle, monkeypatch):
-    """Stage 0's tile path refuses, per context and for good, what it is not made for -- an unorganised cloud (no locality: a tile holds more distinct voxels than its
-    LDS table), voxels of more than 256 points (the per-leaf order check would go quadratic) -- and the frame takes the sort path in the same call; either way the arrays
-    are the oracle's.  Also: a 1000-wide frame with many holes (runs of one voxel meet inside one 256-point step: the leaf lists are sorted in place), both leaf orders,
-    and a batch that mixes frames of both kinds."""
+    """Stage 0's tile path refuses, per context, what it is not made for -- an unorganised cloud (no locality: a tile holds more distinct voxels than its LDS table),
+    voxels of more than 256 points (the per-leaf order check would go quadratic) -- and the frame takes the sort path in the same call; either way the arrays are the
+    oracle's.  The context then stays off the tile path for 8 calls that would have taken it, tries it again, and waits twice as long after every further refusal (16,
+    32, ... 1024 calls): tests/test_batch_mix_gpu.py walks through the first penalty.  Also: a 1000-wide frame with many holes (runs of one voxel meet inside one
+    256-point step: the leaf lists are sorted in place), both leaf orders, and a batch that mixes frames of both kinds."""
     monkeypatch.setenv("F3DS_VOX_TILES", "2")
     cases = [("organised, holes", P.synth_frame(0, 21, 1000, 120, 150), dict(voxel_res=0.008, seed_res=0.08)),
              ("organised, descending leaves", P.synth_frame(0, 22, 640, 200, 30), dict(voxel_res=0.01, seed_res=0.1, leaf_order=1)),
@@ -880,9 +881,10 @@ def test_cli_gpus_and_dump(P, oracle, tmp_path):
 
 
 @pytest.mark.gpu
-def test_adjacency_list_regrows_instead_of_failing(P, monkeypatch):
+def test_adjacency_list_regrows_instead_of_failing(P, oracle, monkeypatch):
     """More adjacencies than the list holds (S0 * 32 + 1024 by default) used to be F3DS_ERR_UNSUPPORTED; now the pass runs again with
-    four times the room.  Forced here by starting with S0 * 1 + 1024 (F3DS_EDGE_MULT, read when a context is created)."""
+    four times the room.  Forced here by starting with S0 * 1 + 1024 (F3DS_EDGE_MULT, read when a context is created).  In a batch the
+    pass of every frame runs again as long as one frame overflows: the second frame is the oracle's too."""
     monkeypatch.setenv("F3DS_EDGE_MULT", "1")
     gold = json.load(open(os.path.join(ROOT, "tests", "golden", "oracle_golden.json")))
     big = json.load(open(os.path.join(ROOT, "tests", "golden", "oracle_golden_big.json")))
@@ -895,6 +897,10 @@ def test_adjacency_list_regrows_instead_of_failing(P, monkeypatch):
     ctxs = [P.Context(0), P.Context(0)]
     labs = P.segment_batch(ctxs, frames, P.launch_params(**e["params"]))       # a batch in which only one frame overflows
     assert ctxs[0].result.n_edges > ctxs[0].result.n_seeds + 1024 and sha_of(labs[0]) == e["labels_sha256"]
+    rc, olab, ores, oh = oracle.segment(frames[1], P.launch_params(**e["params"]))
+    assert rc == 0      # (the second frame's pass runs again whenever the first one's does, whether it still needs room or not)
+    assert np.array_equal(labs[1], olab) and ctxs[1].result.n_edges == ores.n_edges
+    assert first_mismatch("EDGES", oh.get("EDGES"), ctxs[1].debug("EDGES")) is None
     for c in ctxs + [ctx]:
         c.close()
 
@@ -1253,8 +1259,10 @@ def test_incident_list_pool_regrows_instead_of_failing(P, oracle, monkeypatch):
     frames = [case_points(P, n) for n in ("rgbd_160x120", "rgbd_320x240_ghosts", "fixture_launch_flags")]
     prm = case_params(P, "rgbd_320x240_ghosts")
     labs = P.segment_batch(ctxs, frames, prm)
-    for f, l in zip(frames, labs):
-        assert np.array_equal(l, oracle.segment(f, prm)[1])
+    for f, l, c in zip(frames, labs, ctxs):
+        rc, olab, ores, oh = oracle.segment(f, prm)
+        assert rc == 0 and np.array_equal(l, olab)
+        assert c.result.n_merges == ores.n_merges and first_mismatch("MERGES", oh.get("MERGES"), c.debug("MERGES")) is None
     for c in ctxs + [ctx]:
         c.close()
 
