@@ -230,10 +230,11 @@ int stage_seeds(f3ds_emul& E) {
     return 0;
 }
 
+// A run of sweeps, split in two (the kernel probe's kp_sweeps and f3ds_emul_sweeps_from below enter the loop from a caller's state, not from seeds):
+// sweeps_init = createSupervoxelHelpers / reseedSupervoxels, sweeps_run = expandSupervoxels' iterations the way the device runs them.
 // seeds: one voxel per helper label 1..S0 (-1: a helper erased earlier, refineSupervoxels only); reseed: the centroids
 // stay what the last updateCentroid left (d_reseed_own / d_reseed_init on the device) instead of zeros
-int stage_sweeps(f3ds_emul& E, const std::vector<int>& seeds, bool reseed) {
-    const f3ds_params& prm = E.prm;
+void sweeps_init(f3ds_emul& E, const std::vector<int>& seeds, bool reseed) {
     const int V = E.V;
     const int S0 = (int)seeds.size();
     E.owner.assign(V, 0u); E.dist.assign(V, F3DS_FLT_MAX);
@@ -247,21 +248,30 @@ int stage_sweeps(f3ds_emul& E, const std::vector<int>& seeds, bool reseed) {
         E.owner[v] = (uint32_t)(i + 1);
         E.hcount[i + 1] = 1;
     }
-    int max_depth = (int)(1.8f * prm.seed_res / prm.voxel_res);
-    E.res.sweeps = max_depth > 1 ? (uint32_t)(max_depth - 1) : 0u;
+}
+// What sweeps_run leaves per sweep when asked to (f3ds_emul_sweeps_from): the state after every sweep, and the census of the paths the device takes on it.  The helper
+// books the emulation has no use for itself -- the raw tile lists d_sweep_claim appends to and d_centroid rewrites -- are followed here as sets, to say which path of
+// d_centroid a helper takes: the constants are the kernels' (HT_CAP, the row path's 16 list entries and 64 leaves, V > 48 S0; tests/test_sweep_states_cpu.py reads them
+// from their defining lines).
+constexpr uint32_t EM_HT_CAP = 256, EM_ROW_LIST = 16, EM_ROW_LEAVES = 64, EM_WAVE_RATIO = 48, EM_LIST_TILES = 64;
+enum { EM_BOOK_ROW = 0, EM_BOOK_WAVE = 1, EM_BOOK_RAW_OVERFLOW = 2, EM_BOOK_WINDOW = 3, EM_BOOK_MAX_GAIN = 4, EM_BOOK_MAX_RAW = 5, EM_BOOK_MAX_TILES = 6, EM_BOOK_TAIL = 7, EM_BOOKS = 8 };
+struct SweepLog {
+    uint32_t* owner; float* dist; float* hc; uint32_t* hcount; uint8_t *gact, *gdone; uint32_t *tcnt, *n_changed, *rounds, *books;
+    std::vector<std::set<uint32_t>> list;      // per helper: the distinct tiles of its list
+    std::vector<uint32_t> raw;                 // per helper: tcnt as the device holds it (HT_CAP + 1: overflowed)
+};
+int sweeps_run(f3ds_emul& E, uint32_t nsweeps, int shift, int ROUNDS, bool cold_probe, SweepLog* log) {
+    const f3ds_params& prm = E.prm;
+    const int V = E.V;
+    const int S0 = (int)E.hcount.size() - 1;
     std::vector<unsigned char> R(V), Rchk(V), done(S0 + 1);      // R: the walkers' memo, as on the device; Rchk: the memo of the cross-check of a mask sweep
     std::vector<uint32_t> ghost_head(V, 0u), ghost_next(S0 + 1, 0u), ownR(V, 0u), tmask(V, 0u);
     std::vector<int> nbrT((size_t)V * 27);
     for (int v = 0; v < V; ++v) for (int k = 0; k < 27; ++k) nbrT[(size_t)k * V + v] = E.nbr[(size_t)v * 27 + k];
     // Sweep control and dirty-tile bookkeeping: the protocol of the device kernels (a_sweep_begin and its predicates in f3ds_algo.h; the same events and stamps as
-    // f3ds_kernels.inc, SweepFrame).  F3DS_EMUL_INC_SHIFT is the device's F3DS_INC_SHIFT; F3DS_EMUL_R_ROUNDS (1 .. F3DS_R_ROUNDS) its F3DS_R_ROUNDS_RUN: fewer
-    // rounds, so that tests reach the sweeps that turn full because their last round still changed a word.
-    const char* env = getenv("F3DS_EMUL_INC_SHIFT");
-    const int shift = env ? atoi(env) : 6;
+    // f3ds_kernels.inc, SweepFrame).  shift is the device's F3DS_INC_SHIFT, ROUNDS (1 .. F3DS_R_ROUNDS) its F3DS_R_ROUNDS_RUN.
     const uint32_t T = (uint32_t)(V + 63) / 64u;
     const uint32_t thr = a_sweep_thr((uint32_t)V, shift);
-    env = getenv("F3DS_EMUL_R_ROUNDS");
-    const int ROUNDS = env && atoi(env) >= 1 && atoi(env) <= F3DS_R_ROUNDS ? atoi(env) : F3DS_R_ROUNDS;
     std::vector<uint32_t> tR[2] = {std::vector<uint32_t>(T, 0u), std::vector<uint32_t>(T, 0u)}, tC[2] = {std::vector<uint32_t>(T, 0u), std::vector<uint32_t>(T, 0u)};
     std::vector<std::vector<uint32_t>> tRr(ROUNDS, std::vector<uint32_t>(T, 0u));
     std::vector<uint32_t> hD(S0 + 1, 0u);
@@ -269,8 +279,9 @@ int stage_sweeps(f3ds_emul& E, const std::vector<int>& seeds, bool reseed) {
     const SweepCtl ctl{&n_changed, &sweep_full, &sweep_pre, &sweep_marks, &sweep_idle};
     for (uint32_t& n : E.sweep_stats) n = 0u;
     E.r_deep = 0u; E.r_deep_cold = 0u;
-    const bool cold_probe = getenv("F3DS_EMUL_R_COLD") != nullptr;
     long stat_r_evals = 0, stat_c_evals = 0, stat_h_evals = 0;
+    std::map<uint32_t, std::set<uint32_t>> gained_tiles;      // (log only) per helper: the tiles it gained a voxel in during this sweep's claim pass
+    std::map<uint32_t, uint32_t> gained;                      //            and how many voxels
     auto mark = [&](int v, std::vector<uint32_t>& a, std::vector<uint32_t>& b, uint32_t stamp) {
         for (int k = 0; k < 27; ++k) { int u = nbrT[(size_t)k * V + v]; if (u >= 0) { a[u >> 6] = stamp; b[u >> 6] = stamp; } }
     };
@@ -290,13 +301,27 @@ int stage_sweeps(f3ds_emul& E, const std::vector<int>& seeds, bool reseed) {
         }
         return true;
     };
-    for (uint32_t t = 0; t < E.res.sweeps; ++t) {
+    for (uint32_t t = 0; t < nsweeps; ++t) {
         if (a_sweep_needs_clear(t)) std::fill(R.begin(), R.end(), (unsigned char)0);
         for (int h = 1; h <= S0; ++h) if (E.ghost_vox[h] >= 0) ghost_head[E.ghost_vox[h]] = 0u;
         for (int h = 1; h <= S0; ++h) if (E.ghost_active[h]) { ghost_next[h] = ghost_head[E.ghost_vox[h]]; ghost_head[E.ghost_vox[h]] = (uint32_t)h; }
         uint32_t n_ghosts = 0;
         for (int h = 1; h <= S0; ++h) n_ghosts += E.ghost_active[h];
-        if (!a_sweep_begin(ctl, t, n_ghosts, thr)) { E.sweep_stats[F3DS_SWEEP_IDLE]++; continue; }
+        uint32_t rounds_changed = 0u;
+        uint32_t books[EM_BOOKS] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+        const uint32_t deep_before = E.r_deep;
+        auto snapshot = [&]() {
+            if (!log) return;
+            const size_t L = (size_t)S0 + 1;
+            memcpy(log->owner + (size_t)t * V, E.owner.data(), (size_t)V * 4); memcpy(log->dist + (size_t)t * V, E.dist.data(), (size_t)V * 4);
+            memcpy(log->hc + (size_t)t * L * 12, E.hc.data(), L * 48); memcpy(log->hcount + (size_t)t * L, E.hcount.data(), L * 4);
+            memcpy(log->gact + (size_t)t * L, E.ghost_active.data(), L); memset(log->gdone + (size_t)t * L, 0, L);      // (d_centroid clears ghost_done of every helper it had been set for)
+            memcpy(log->tcnt + (size_t)t * L, log->raw.data(), L * 4);
+            log->n_changed[t] = n_changed; log->rounds[t] = rounds_changed;
+            books[EM_BOOK_TAIL] = E.r_deep - deep_before;
+            memcpy(log->books + (size_t)t * EM_BOOKS, books, sizeof books);
+        };
+        if (!a_sweep_begin(ctl, t, n_ghosts, thr)) { E.sweep_stats[F3DS_SWEEP_IDLE]++; snapshot(); continue; }
         SweepView s{V, nbrT.data(), E.vf.data(), E.owner.data(), E.dist.data(), E.hc.data(), ghost_head.data(), ghost_next.data(), &n_ghosts,
                     prm.seed_res, prm.w_normal, prm.w_color, prm.w_spatial};
         const uint32_t stamp = t + 1u;
@@ -314,6 +339,7 @@ int stage_sweeps(f3ds_emul& E, const std::vector<int>& seeds, bool reseed) {
                     const uint32_t nw = E.owner[v] | (a_eval_R_step(s, snap.data(), v) ? F3DS_OWNR_RTRUE : 0u);
                     if (nw != snap[v]) writes.push_back({v, nw});
                 }
+                if (!writes.empty()) rounds_changed++;
                 for (auto& w : writes) {
                     ownR[w.first] = w.second;
                     mark(w.first, last ? tC[t & 1u] : tRr[r], tC[t & 1u], stamp);
@@ -357,6 +383,7 @@ int stage_sweeps(f3ds_emul& E, const std::vector<int>& seeds, bool reseed) {
         {
             const bool full = a_sweep_is_full(ctl, t), marks = a_sweep_marks(ctl, t);
             std::vector<std::pair<int, std::pair<uint32_t, float>>> writes;
+            gained_tiles.clear(); gained.clear();
             for (int v = 0; v < V; ++v) {
                 if (!full && tC[t & 1u][v >> 6] != stamp) continue;
                 stat_c_evals++;
@@ -369,6 +396,7 @@ int stage_sweeps(f3ds_emul& E, const std::vector<int>& seeds, bool reseed) {
                 const int v = w.first; const uint32_t o0 = E.owner[v], o = w.second.first;
                 E.owner[v] = o; E.dist[v] = w.second.second;
                 if (o != o0) { if (o) hD[o] = stamp; if (o0) hD[o0] = stamp; }
+                if (log && o != o0 && o) { gained_tiles[o].insert((uint32_t)v >> 6); gained[o]++; }      // (d_sweep_claim appends one list entry per helper and wave, i.e. per 64-voxel tile it gained in)
                 if (marks) mark(v, tR[(t + 1u) & 1u], tC[(t + 1u) & 1u], t + 2u);
                 n_changed++;
             }
@@ -381,6 +409,7 @@ int stage_sweeps(f3ds_emul& E, const std::vector<int>& seeds, bool reseed) {
         for (int h = 1; h <= S0; ++h) proc[h] = !(t != 0u && hD[h] != stamp && !E.ghost_active[h]);
         std::vector<float> sum((size_t)(S0 + 1) * 9, 0.0f);
         std::vector<uint32_t> cnt(S0 + 1, 0u);
+        std::vector<std::set<uint32_t>> own_tiles(log ? S0 + 1 : 0);
         auto add = [&](uint32_t h, int v) {
             if (!proc[h]) return;
             const float* f = &E.vf[(size_t)v * 12];
@@ -392,21 +421,56 @@ int stage_sweeps(f3ds_emul& E, const std::vector<int>& seeds, bool reseed) {
         for (int v = 0; v < V; ++v) {       // ascending ordinal = SupervoxelHelper leaf order
             uint32_t h = E.owner[v];
             if (h) add(h, v);
+            if (log && h) own_tiles[h].insert((uint32_t)v >> 6);
             if (!gmap.empty()) { auto it = gmap.find(v); if (it != gmap.end()) for (int g : it->second) add((uint32_t)g, v); }
         }
         for (int h = 1; h <= S0; ++h) {
             if (!proc[h]) continue;
             stat_h_evals++;
+            if (log) {
+                // the books as d_centroid meets them: the list d_sweep_claim appended to (raw length, distinct tiles with the ghost leaf's), and the path that follows
+                const bool gact = E.ghost_active[h] && !done[h];
+                const uint32_t raw = log->raw[h] > EM_HT_CAP ? log->raw[h] : log->raw[h] + (uint32_t)gained_tiles[(uint32_t)h].size();
+                std::set<uint32_t> tiles = log->list[h];
+                for (uint32_t x : gained_tiles[(uint32_t)h]) tiles.insert(x);
+                if (gact) tiles.insert((uint32_t)E.ghost_vox[h] >> 6);
+                const bool by_wave = marks || (uint32_t)V > EM_WAVE_RATIO * (uint32_t)S0;
+                int path;
+                if (raw > EM_HT_CAP) path = EM_BOOK_RAW_OVERFLOW;
+                else if (raw + (gact ? 1u : 0u) > EM_LIST_TILES && tiles.size() > EM_LIST_TILES) path = EM_BOOK_WINDOW;
+                else if (by_wave || raw + (gact ? 1u : 0u) > EM_ROW_LIST || cnt[h] > EM_ROW_LEAVES) path = EM_BOOK_WAVE;
+                else path = EM_BOOK_ROW;
+                books[path]++;
+                books[EM_BOOK_MAX_GAIN] = std::max(books[EM_BOOK_MAX_GAIN], gained[(uint32_t)h]);
+                books[EM_BOOK_MAX_RAW] = std::max(books[EM_BOOK_MAX_RAW], raw);
+                books[EM_BOOK_MAX_TILES] = std::max(books[EM_BOOK_MAX_TILES], (uint32_t)tiles.size());
+                // ... and as it leaves them: exactly the tiles that hold a leaf the helper owns
+                log->list[h].swap(own_tiles[h]);
+                log->raw[h] = log->list[h].size() <= EM_HT_CAP ? (uint32_t)log->list[h].size() : EM_HT_CAP + 1u;
+            }
             if (done[h]) E.ghost_active[h] = 0;
             E.hcount[h] = cnt[h];
             if (cnt[h]) a_centroid_finish(&sum[(size_t)h * 9], cnt[h], &E.hc[(size_t)h * 12]);
         }
+        snapshot();
     }
     if (getenv("F3DS_EMUL_SWEEP_STATS"))
         fprintf(stderr, "%u sweeps: %u full from their start, %u incremental, %u fallbacks, %u idle; R evals %ld, claim evals %ld, centroid evals %ld (evaluating everything: %ld / %ld / %ld)\n",
-                E.res.sweeps, E.sweep_stats[F3DS_SWEEP_FULL], E.sweep_stats[F3DS_SWEEP_INCREMENTAL], E.sweep_stats[F3DS_SWEEP_FALLBACK], E.sweep_stats[F3DS_SWEEP_IDLE],
-                stat_r_evals, stat_c_evals, stat_h_evals, (long)V * E.res.sweeps, (long)V * E.res.sweeps, (long)S0 * E.res.sweeps);
+                nsweeps, E.sweep_stats[F3DS_SWEEP_FULL], E.sweep_stats[F3DS_SWEEP_INCREMENTAL], E.sweep_stats[F3DS_SWEEP_FALLBACK], E.sweep_stats[F3DS_SWEEP_IDLE],
+                stat_r_evals, stat_c_evals, stat_h_evals, (long)V * nsweeps, (long)V * nsweeps, (long)S0 * nsweeps);
     return 0;
+}
+// F3DS_EMUL_INC_SHIFT is the device's F3DS_INC_SHIFT; F3DS_EMUL_R_ROUNDS (1 .. F3DS_R_ROUNDS) its F3DS_R_ROUNDS_RUN: fewer rounds, so that tests reach the sweeps
+// that turn full because their last round still changed a word.
+int stage_sweeps(f3ds_emul& E, const std::vector<int>& seeds, bool reseed) {
+    sweeps_init(E, seeds, reseed);
+    int max_depth = (int)(1.8f * E.prm.seed_res / E.prm.voxel_res);
+    E.res.sweeps = max_depth > 1 ? (uint32_t)(max_depth - 1) : 0u;
+    const char* env = getenv("F3DS_EMUL_INC_SHIFT");
+    const int shift = env ? atoi(env) : 6;
+    env = getenv("F3DS_EMUL_R_ROUNDS");
+    const int ROUNDS = env && atoi(env) >= 1 && atoi(env) <= F3DS_R_ROUNDS ? atoi(env) : F3DS_R_ROUNDS;
+    return sweeps_run(E, E.res.sweeps, shift, ROUNDS, getenv("F3DS_EMUL_R_COLD") != nullptr, nullptr);
 }
 
 int stage_merge(f3ds_emul& E) {
@@ -786,6 +850,36 @@ int f3ds_emul_refine_seeds(const f3ds_emul* E, int it, int* seeds, size_t cap) {
 
 // the sweep-control protocol of the device kernels (a_sweep_begin, a_sweep_thr in csrc/f3ds_algo.h) for tests/test_sweep_control_cpu.py.  words: n_changed, sweep_full,
 // sweep_pre, sweep_marks, sweep_idle, updated in place; returns 0 for an idle sweep
+// n sweeps from a caller's start-of-run state (the arguments of the kernel probe's kp_sweeps, tests/kernprobe: the caller keeps its contract, nothing is checked here).
+// in[12] = nbr[V x 27], vf[V x 12], owner[V], dist[V], hc[(S0 + 1) x 12], hcount, hlo, hhi (not used: the emulation keeps no ordinal windows), tl[(S0 + 1) x 256], tcnt,
+// ghost_vox, ghost_active (S0 + 1 each);  w[4] = seed_res, w_normal, w_color, w_spatial;  inc_shift as F3DS_INC_SHIFT (< 0: every sweep full), r_rounds 1 .. F3DS_R_ROUNDS.
+// out[12], per sweep: owner, dist, hc, hcount, ghost_active, ghost_done, tcnt, n_changed, the R rounds that still changed a word, books[8] (helpers d_centroid takes on the
+// row path / a wave each through their list / the ordinal window because the raw list overflowed / the window because of more than 64 distinct tiles; the most voxels one
+// helper gained, its longest raw list, its most distinct tiles; voxels the walkers put off);  at the end: sweep_stats[4], (r_deep, r_deep_cold).
+int f3ds_emul_sweeps_from(uint32_t V, uint32_t S0, uint32_t n, const void* const* in, const float* w, int inc_shift, int r_rounds, void* const* out) {
+    if (!in || !w || !out || V < 1u || r_rounds < 1 || r_rounds > F3DS_R_ROUNDS) return F3DS_ERR_ARG;
+    for (int i = 0; i < 12; ++i) if (!in[i] || !out[i]) return F3DS_ERR_ARG;
+    std::unique_ptr<f3ds_emul> Ep(new f3ds_emul);
+    f3ds_emul& E = *Ep;
+    memset(&E.prm, 0, sizeof E.prm); memset(&E.res, 0, sizeof E.res);
+    E.prm.seed_res = w[0]; E.prm.w_normal = w[1]; E.prm.w_color = w[2]; E.prm.w_spatial = w[3];
+    const size_t L = (size_t)S0 + 1;
+    E.V = (int)V;
+    E.nbr.assign((const int*)in[0], (const int*)in[0] + (size_t)V * 27); E.vf.assign((const float*)in[1], (const float*)in[1] + (size_t)V * 12);
+    E.owner.assign((const uint32_t*)in[2], (const uint32_t*)in[2] + V); E.dist.assign((const float*)in[3], (const float*)in[3] + V);
+    E.hc.assign((const float*)in[4], (const float*)in[4] + L * 12); E.hcount.assign((const uint32_t*)in[5], (const uint32_t*)in[5] + L);
+    E.ghost_vox.assign((const int*)in[10], (const int*)in[10] + L); E.ghost_active.assign((const uint8_t*)in[11], (const uint8_t*)in[11] + L);
+    SweepLog log{(uint32_t*)out[0], (float*)out[1], (float*)out[2], (uint32_t*)out[3], (uint8_t*)out[4], (uint8_t*)out[5], (uint32_t*)out[6], (uint32_t*)out[7], (uint32_t*)out[8], (uint32_t*)out[9], {}, {}};
+    const uint32_t *tl = (const uint32_t*)in[8], *tcnt = (const uint32_t*)in[9];
+    log.list.resize(L); log.raw.assign(tcnt, tcnt + L);
+    for (size_t h = 0; h < L; ++h) for (uint32_t i = 0; i < tcnt[h] && i < EM_HT_CAP; ++i) log.list[h].insert(tl[h * EM_HT_CAP + i]);
+    const int rc = sweeps_run(E, n, inc_shift, r_rounds, true, &log);
+    if (rc) return rc;
+    memcpy(out[10], E.sweep_stats, sizeof E.sweep_stats);
+    ((uint32_t*)out[11])[0] = E.r_deep; ((uint32_t*)out[11])[1] = E.r_deep_cold;
+    return 0;
+}
+
 int f3ds_emul_sweep_begin(uint32_t* words, uint32_t t, uint32_t n_ghosts, uint32_t thr) {
     return a_sweep_begin(SweepCtl{&words[0], &words[1], &words[2], &words[3], &words[4]}, t, n_ghosts, thr) ? 1 : 0;
 }

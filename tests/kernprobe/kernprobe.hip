@@ -41,6 +41,12 @@ constexpr int KP_EARG = -2;      // a precondition does not hold: nothing was la
 template <class K, class... A>
 __global__ __launch_bounds__(K::BLOCK) void kp_call(A... a) { K{}(a...); }
 
+// the same with the register budget the host layer's launcher gives a kernel that asks for one (f3ds_hip.hip: waves_per_simd, k_batched): kp_sweeps
+template <class K, class = void> struct kp_wps { static constexpr int v = 1; };
+template <class K> struct kp_wps<K, std::void_t<decltype(K::WAVES_PER_SIMD)>> { static constexpr int v = K::WAVES_PER_SIMD; };
+template <class K, class... A>
+__global__ __launch_bounds__(K::BLOCK, kp_wps<K>::v) void kp_call_w(A... a) { K{}(a...); }
+
 // ---- wave primitives: one wave per workgroup, one case (64 words) per workgroup -------------------------------------------------------
 enum { KP_WAVE_SCAN = 0, KP_WAVE_SCAN_DPP = 1, KP_WAVE_MIN = 2, KP_ROW_MIN = 3, KP_ROW_SORT16 = 4 };
 __global__ __launch_bounds__(64) void kp_wave_k(int op, const uint32_t* in, uint32_t* out) {
@@ -641,6 +647,157 @@ int kp_seed_filter(const float* vf, uint32_t V, const uint32_t* ckey, const uint
                        dim3((C + 3u) / 4u + extra, 1), dim3(d_seed_filter::BLOCK), 0, 0, t.vf, t.ckey, t.sorted_vox, t.cell_start, t.dc, t.grid, t.hkeys, t.hvals, t.hmask, dso, r2, min_points, dk);
     B.sync(); B.back(keep, (const uint32_t*)dk, init.size());
     return (int)B.err;
+}
+}  // extern "C"
+namespace {
+constexpr uint32_t KP_MAX_SWEEPS = 140;
+// The start-of-run contract of kp_sweeps: the state createSupervoxelHelpers / reseedSupervoxels / a finished run of sweeps could have left, as far as the sweep kernels
+// read it.  Arrays by voxel have V entries, by label S0 + 1 (row 0 is nobody's: no leaf, no ghost, empty books).
+//   owner <= S0;  dist = FLT_MAX where owner is 0, finite and >= 0 elsewhere;  hc and the nine feature words of every voxel finite;
+//   nbr[v][k] is -1 or a voxel, slot 13 is v itself, and u = nbr[v][k] has v in its slot 26 - k (the marks of the dirty-tile scheme go to N(v) and are meant for the
+//   voxels that have v in theirs: the table of a lattice, and of d_neighbors);
+//   a helper has at most one ghost leaf (ghost_active 0 | 1; ghost_vox a voxel whose owner has a HIGHER label -- createSupervoxelHelpers' last seed owns -- or -1);
+//   hcount = voxels owned + the ghost leaf;  hlo <= every leaf <= hhi < V (0, 0 for a helper without leaves);  tcnt <= HT_CAP lists tiles below T, among them every tile
+//   the helper owns a voxel in (d_helper_init: the seed's tile, nothing for a ghost seed; d_centroid: exactly those tiles), or tcnt = HT_CAP + 1: the ordinal window.
+bool sweep_state_ok(uint32_t V, uint32_t S0, const int* nbr, const float* vf, const uint32_t* owner, const float* dist, const float* hc, const uint32_t* hcount, const uint32_t* hlo,
+                    const uint32_t* hhi, const uint32_t* tl, const uint32_t* tcnt, const int* ghost_vox, const unsigned char* ghost_active) {
+    const size_t L = (size_t)S0 + 1;
+    const uint32_t T = (V + 63u) / 64u;
+    for (uint32_t v = 0; v < V; ++v) {
+        for (int k = 0; k < 27; ++k) {
+            const int u = nbr[(size_t)v * 27 + k];
+            if (u < -1 || (u >= 0 && (uint32_t)u >= V)) return false;
+            if (u >= 0 && nbr[(size_t)u * 27 + (26 - k)] != (int)v) return false;
+        }
+        if (nbr[(size_t)v * 27 + 13] != (int)v) return false;
+        for (int k = 0; k < 9; ++k) if (!std::isfinite(vf[(size_t)v * 12 + k])) return false;
+        if (owner[v] > S0) return false;
+        if (owner[v] == 0u) { const float fmax = F3DS_FLT_MAX; if (memcmp(&dist[v], &fmax, 4) != 0) return false; }
+        else if (!std::isfinite(dist[v]) || !(dist[v] >= 0.0f)) return false;
+    }
+    for (size_t i = 0; i < L * 12; ++i) if (!std::isfinite(hc[i])) return false;
+    std::vector<uint32_t> cnt(L, 0u), lo(L, 0xFFFFFFFFu), hi(L, 0u);
+    auto leaf = [&](uint32_t h, uint32_t v) { cnt[h]++; if (v < lo[h]) lo[h] = v; if (v > hi[h]) hi[h] = v; };
+    for (uint32_t v = 0; v < V; ++v) if (owner[v]) leaf(owner[v], v);
+    for (uint32_t h = 0; h <= S0; ++h) {
+        if (ghost_active[h] > 1) return false;
+        if (!ghost_active[h]) { if (ghost_vox[h] != -1) return false; continue; }
+        if (h == 0u || ghost_vox[h] < 0 || (uint32_t)ghost_vox[h] >= V || owner[ghost_vox[h]] <= h) return false;
+        leaf(h, (uint32_t)ghost_vox[h]);
+    }
+    if (cnt[0] != 0u) return false;
+    std::vector<std::vector<uint32_t>> listed(L);
+    for (uint32_t h = 0; h <= S0; ++h) {
+        if (hcount[h] != cnt[h]) return false;
+        if (cnt[h] ? !(hlo[h] <= lo[h] && hi[h] <= hhi[h] && hhi[h] < V) : (hlo[h] != 0u || hhi[h] != 0u)) return false;
+        if (tcnt[h] > HT_CAP + 1u) return false;
+        if (tcnt[h] > HT_CAP) continue;
+        for (uint32_t i = 0; i < tcnt[h]; ++i) { if (tl[(size_t)h * HT_CAP + i] >= T) return false; listed[h].push_back(tl[(size_t)h * HT_CAP + i]); }
+        std::sort(listed[h].begin(), listed[h].end());
+    }
+    for (uint32_t v = 0; v < V; ++v) {
+        const uint32_t h = owner[v];
+        if (h && tcnt[h] <= HT_CAP && !std::binary_search(listed[h].begin(), listed[h].end(), v >> 6)) return false;
+    }
+    return true;
+}
+}  // namespace
+extern "C" {
+// The sweep kernels of sweeps 0 .. n - 1 in the order seg_sweeps_on (f3ds_hip.hip) records them, from the caller's start-of-run state (sweep_state_ok above; anything
+// else is refused before a device is touched), with the state copied back after every sweep.  Everything private to the device -- stamps, hD, ownR, the memo R, work
+// lists, thief masks, ghost chains, the counters -- starts zeroed, as seg_sweeps_on fills it or as sweeps 0 and 1, which are full by construction, rebuild it.
+//   in[12] = nbr[V x 27] (row-major; nbrT is derived here), vf[V x 12], owner, dist, hc[(S0 + 1) x 12], hcount, hlo, hhi, tl[(S0 + 1) x HT_CAP], tcnt, ghost_vox, ghost_active
+//   w[4] = seed_res, w_normal, w_color, w_spatial
+//   ctl[5] = n (<= 140), inc_shift + 1 (0: every sweep full; thr = a_sweep_thr(V, inc_shift), the library's F3DS_INC_SHIFT), r_rounds (1 .. F3DS_R_ROUNDS, its
+//            F3DS_R_ROUNDS_RUN), tiles (0: tile_n1 = nullptr, the global-gather path; 1: the tables d_normals_t<384> builds from vf and nbr, as seg_normals launches it --
+//            the caller's normals are put back afterwards), gx_cap (0: the widths of grid_for; 1 or 3: every launch wider than that is that wide, as F3DS_GRID_CAP)
+//   out[10], per sweep: owner[n x V], dist, hc[n x (S0 + 1) x 12], hcount, ghost_active, ghost_done, tcnt, n_changed[n] (as the claim pass left it);  at the end:
+//            sweep_stats[4], tile_n1[(V + 127) / 128] (0xFFFFFFFF: a tile on the global path; all of them with tiles = 0)
+int kp_sweeps(uint32_t V, uint32_t S0, const void* const* in, const float* w, const uint32_t* ctl, void* const* out) {
+    if (!in || !w || !ctl || !out) return KP_EARG;
+    for (int i = 0; i < 12; ++i) if (!in[i]) return KP_EARG;
+    for (int i = 0; i < 10; ++i) if (!out[i]) return KP_EARG;
+    const uint32_t n = ctl[0], r_rounds = ctl[2], tiles = ctl[3], gx_cap = ctl[4];
+    const int inc_shift = (int)ctl[1] - 1;
+    if (V < 1 || V > (1u << 20) || S0 > 65536 || n > KP_MAX_SWEEPS || ctl[1] > 33u || r_rounds < 1 || r_rounds > (uint32_t)F3DS_R_ROUNDS || tiles > 1 || (gx_cap != 0 && gx_cap != 1 && gx_cap != 3)) return KP_EARG;
+    for (int i = 0; i < 4; ++i) if (!std::isfinite(w[i]) || w[i] < 0.0f) return KP_EARG;
+    if (!(w[0] > 0.0f)) return KP_EARG;
+    const int* nbr = (const int*)in[0]; const float* vf = (const float*)in[1]; const uint32_t* owner = (const uint32_t*)in[2]; const float* dist = (const float*)in[3];
+    const float* hc = (const float*)in[4]; const uint32_t *hcount = (const uint32_t*)in[5], *hlo = (const uint32_t*)in[6], *hhi = (const uint32_t*)in[7], *tl = (const uint32_t*)in[8],
+                                          *tcnt = (const uint32_t*)in[9];
+    const int* ghost_vox = (const int*)in[10]; const unsigned char* ghost_active = (const unsigned char*)in[11];
+    if (!sweep_state_ok(V, S0, nbr, vf, owner, dist, hc, hcount, hlo, hhi, tl, tcnt, ghost_vox, ghost_active)) return KP_EARG;
+    const size_t L = (size_t)S0 + 1;
+    const uint32_t T = (V + 63u) / 64u, NT = (V + NT_TILE - 1) / NT_TILE;
+    std::vector<int> nbrT((size_t)27 * V);
+    for (uint32_t v = 0; v < V; ++v) for (int k = 0; k < 27; ++k) nbrT[(size_t)k * V + v] = nbr[(size_t)v * 27 + k];
+    auto width = [&](size_t work, int block) { const uint32_t g = kp_grid_for(work, block); return gx_cap && g > gx_cap ? gx_cap : g; };
+    Bufs B;
+    float* dvf = B.mk<float>((size_t)V * 12, vf);
+    const int* dnbr = B.mk<int>((size_t)27 * V, nbr);
+    const int* dnbrT = B.mk<int>((size_t)27 * V, nbrT.data());
+    uint32_t* down = B.mk<uint32_t>(V, owner);
+    float* ddist = B.mk<float>(V, dist);
+    float* dhc = B.mk<float>(L * 12, hc);
+    uint32_t *dghead = B.mk<uint32_t>(V), *dgnext = B.mk<uint32_t>(L);
+    DevCounters hdc;
+    memset(&hdc, 0, sizeof hdc);
+    hdc.n_voxels = V;
+    DevCounters* ddc = B.mk<DevCounters>(1, &hdc);
+    SweepFrame a;
+    a.sv = SweepView{(int)V, dnbrT, dvf, down, ddist, dhc, dghead, dgnext, ddc ? &ddc->n_ghosts : nullptr, w[0], w[1], w[2], w[3], dnbr};
+    a.R = B.mk<unsigned char>(V); a.ownR = B.mk<uint32_t>(V); a.owner_out = down; a.dist_out = ddist;
+    a.ghost_done = B.mk<unsigned char>(L); a.ghost_active = B.mk<unsigned char>(L, ghost_active); a.ghost_vox = B.mk<int>(L, ghost_vox);
+    a.ghost_head = dghead; a.ghost_next = dgnext;
+    a.hlo = B.mk<uint32_t>(L, hlo); a.hhi = B.mk<uint32_t>(L, hhi); a.hcount = B.mk<uint32_t>(L, hcount); a.hc = dhc; a.dc = ddc; a.S0 = S0;
+    uint32_t* tiles4 = B.mk<uint32_t>((size_t)4 * T);
+    a.tR0 = tiles4; a.tR1 = tiles4 + T; a.tC0 = tiles4 + 2 * (size_t)T; a.tC1 = tiles4 + 3 * (size_t)T;
+    a.tRr = B.mk<uint32_t>((size_t)(F3DS_R_ROUNDS > 1 ? F3DS_R_ROUNDS - 1 : 1) * T); a.hD = B.mk<uint32_t>(L); a.T = T;
+    a.tl = B.mk<uint32_t>(L * HT_CAP, tl); a.tcnt = B.mk<uint32_t>(L, tcnt);
+    a.wl = B.mk<uint32_t>(V); a.wl2 = B.mk<uint32_t>(V); a.tmask = B.mk<uint32_t>(V);
+    a.thr = a_sweep_thr(V, inc_shift);
+    std::vector<uint32_t> none(NT, SW_TILE_NONE);
+    uint32_t* dtn1 = B.mk<uint32_t>(NT, none.data());
+    uint32_t* dtord = B.mk<uint32_t>((size_t)NT * NT_RING1);
+    uint32_t* dtslots = B.mk<uint32_t>((size_t)NT * SW_SLOT_WORDS * NT_TILE);
+    a.tile_n1 = tiles ? dtn1 : nullptr; a.tile_ord = dtord; a.tile_slots = dtslots;
+    if (B.err != hipSuccess) return (int)B.err;
+    if (tiles) {
+        hipLaunchKernelGGL((kp_call_w<d_normals_t<384>, float*, const int*, const DevCounters*, uint32_t*, uint32_t*, uint32_t*, uint32_t>), dim3(NT, 1), dim3(384), 0, 0,
+                           dvf, dnbr, (const DevCounters*)ddc, dtn1, dtord, dtslots, 0u);
+        B.sync();
+        if (B.err == hipSuccess) B.err = hipMemcpy(dvf, vf, (size_t)V * 48, hipMemcpyHostToDevice);      // the caller's normals, not the ones the kernel computed on the way
+        if (B.err != hipSuccess) return (int)B.err;
+    }
+    for (uint32_t t = 0; t < n; ++t) {
+        if (a_sweep_needs_clear(t)) B.err = hipMemset(a.R, 0, V);
+        if (B.err != hipSuccess) return (int)B.err;
+        const unsigned char tag = a_sweep_tag(t);
+        hipLaunchKernelGGL((kp_call_w<d_sweep_begin, SweepFrame, uint32_t>), dim3(1, 1), dim3(d_sweep_begin::BLOCK), 0, 0, a, t);
+        const uint32_t nrounds = inc_shift >= 0 && t >= 2u ? r_rounds : 0u;      // (as seg_sweeps_on: sweeps 0 and 1 are full by construction)
+        hipLaunchKernelGGL((kp_call_w<d_sweep_R_first, SweepFrame, unsigned char, uint32_t, uint32_t>), dim3(width(V, 256), 1), dim3(d_sweep_R_first::BLOCK), 0, 0, a, tag, t, nrounds);
+        for (uint32_t r = 1; r < nrounds; ++r)
+            hipLaunchKernelGGL((kp_call_w<d_sweep_R_round, SweepFrame, uint32_t, uint32_t, uint32_t>), dim3(width(V, 256), 1), dim3(d_sweep_R_round::BLOCK), 0, 0, a, t, r, nrounds);
+        for (uint32_t pass = 0; pass < F3DS_R_PASSES; ++pass)
+            hipLaunchKernelGGL((kp_call_w<d_sweep_R, SweepFrame, unsigned char, uint32_t, uint32_t>), dim3(pass == 0 ? width(V, 256) : (gx_cap ? gx_cap : 64u), 1), dim3(d_sweep_R::BLOCK), 0, 0, a, tag, t, pass);
+        hipLaunchKernelGGL((kp_call_w<d_sweep_R_tail, SweepFrame, unsigned char, uint32_t>), dim3(1, 1), dim3(d_sweep_R_tail::BLOCK), 0, 0, a, tag, t);
+        hipLaunchKernelGGL((kp_call_w<d_sweep_claim, SweepFrame, uint32_t>), dim3(width(V, 256), 1), dim3(d_sweep_claim::BLOCK), 0, 0, a, t);
+        hipLaunchKernelGGL((kp_call_w<d_centroid, SweepFrame, uint32_t>), dim3(width((size_t)S0 * 64u, 256), 1), dim3(d_centroid::BLOCK), 0, 0, a, t);
+        B.sync();
+        B.back((uint32_t*)out[0] + (size_t)t * V, (const uint32_t*)down, V); B.back((float*)out[1] + (size_t)t * V, (const float*)ddist, V);
+        B.back((float*)out[2] + (size_t)t * L * 12, (const float*)dhc, L * 12); B.back((uint32_t*)out[3] + (size_t)t * L, (const uint32_t*)a.hcount, L);
+        B.back((unsigned char*)out[4] + (size_t)t * L, (const unsigned char*)a.ghost_active, L); B.back((unsigned char*)out[5] + (size_t)t * L, (const unsigned char*)a.ghost_done, L);
+        B.back((uint32_t*)out[6] + (size_t)t * L, (const uint32_t*)a.tcnt, L);
+        B.back(&hdc, (const DevCounters*)ddc, 1);
+        if (B.err != hipSuccess) return (int)B.err;      // (nothing more is launched after an error)
+        ((uint32_t*)out[7])[t] = hdc.n_changed;
+        if (hdc.r_overflow) return KP_EARG - 1;          // the tail made no progress: cannot happen
+    }
+    B.back(&hdc, (const DevCounters*)ddc, 1); B.back((uint32_t*)out[9], (const uint32_t*)dtn1, NT);
+    if (B.err != hipSuccess) return (int)B.err;
+    memcpy(out[8], hdc.sweep_stats, sizeof hdc.sweep_stats);
+    if (!tiles) for (uint32_t i = 0; i < NT; ++i) ((uint32_t*)out[9])[i] = SW_TILE_NONE;
+    return 0;
 }
 
 }  // extern "C"

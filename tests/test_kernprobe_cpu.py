@@ -35,7 +35,7 @@ class KernProbe:
     def __init__(self, path):
         self.lib = ctypes.CDLL(path)
         for nm in ("const", "wave", "run_of_lane", "block", "scan_single", "scan_u32", "radix_hist", "radix_scatter", "radix_sort", "seg_table", "relabel", "tile_list",
-                   "row_leaves", "vblock", "centroid", "sv_fill"):
+                   "row_leaves", "vblock", "centroid", "sv_fill", "sweeps"):
             getattr(self.lib, "kp_" + nm).restype = ctypes.c_int
 
     def const(self, i):
@@ -131,6 +131,21 @@ class KernProbe:
         rc = self.lib.kp_sv_fill(C32(S0), C32(V), _p(st.owner), _p(st.vf), _p(st.ghost_active), _p(st.ghost_vox), _p(st.hlo), _p(st.hhi), _p(st.hcount), _p(loff), _p(st.hc),
                                  _p(st.tl), _p(st.tcnt), _p(rows), _p(rv), _p(racc), _p(rcnt), _p(rrec), _p(ral), _p(na))
         return rc, rows, rv, racc, rcnt, rrec, ral, int(na[0])
+
+    def sweeps(self, st, n, inc_shift=6, r_rounds=4, tiles=1, gx_cap=0):
+        """kp_sweeps on a start-of-run state (tests/sweep_states_common.py: State) -> rc, dict of the per-sweep arrays, sweep_stats[4], tile_n1"""
+        V, L = st.V, st.S0 + 1
+        ins = [_c(st.nbr, np.int32), _c(st.vf, F), _c(st.owner, U32), _c(st.dist, F), _c(st.hc, F), _c(st.hcount, U32), _c(st.hlo, U32), _c(st.hhi, U32), _c(st.tl, U32),
+               _c(st.tcnt, U32), _c(st.ghost_vox, np.int32), _c(st.ghost_active, np.uint8)]
+        m = max(n, 1)
+        out = dict(owner=np.zeros((m, V), U32), dist=np.zeros((m, V), F), hc=np.zeros((m, L, 12), F), hcount=np.zeros((m, L), U32), ghost_active=np.zeros((m, L), np.uint8),
+                   ghost_done=np.zeros((m, L), np.uint8), tcnt=np.zeros((m, L), U32), n_changed=np.zeros(m, U32))
+        stats = np.zeros(4, U32); tn1 = np.zeros((V + 127) // 128, U32)
+        outs = list(out.values()) + [stats, tn1]
+        w = np.array([st.seed_res, st.w_normal, st.w_color, st.w_spatial], F)
+        ctl = np.array([n, inc_shift + 1, r_rounds, tiles, gx_cap], np.int64).astype(U32)
+        rc = self.lib.kp_sweeps(C32(V), C32(st.S0), (VP * 12)(*[a.ctypes.data for a in ins]), _p(w), _p(ctl), (VP * 10)(*[a.ctypes.data for a in outs]))
+        return rc, {k: v[:n] for k, v in out.items()}, stats, tn1
 
 
 class HostRef:
