@@ -41,6 +41,7 @@ DBG = dict(GRID=0, VOXEL_KEYS=1, VOXEL_COUNT=2, VOXEL_XYZ=3, VOXEL_RGB=4, VOXEL_
            EDGES=14, EDGE_DELTAS=15, EDGE_WEIGHTS=16, MERGES=17, VOXEL_REGION=18, SV_REGION=19)
 # ... and the selectors of diagnostics (a few words about the last call, not an array of the frame): Context.merge_layout() etc.
 DBG_INFO = dict(MERGE_LAYOUT=20, TILE_LIST_LEN=21, SWEEP_STATS=22, STAGE0_PATH=23, LAUNCH_SHAPE=24)
+DBG_CLOUD_PATH = 25      # F3DS_DBG_CLOUD_PATH (include/f3ds.h): a selector of the region family, outside the enum of the frame's hooks
 DBG_DTYPE = dict(GRID=np.float64, VOXEL_KEYS=np.uint32, VOXEL_COUNT=np.uint32, VOXEL_XYZ=np.float32, VOXEL_RGB=np.float32,
                  VOXEL_NORMAL=np.float32, VOXEL_NEIGHBORS=np.int32, POINT_VOXEL=np.int32, SEED_ORIG=np.int32, SEED_KEPT=np.int32,
                  VOXEL_SVLABEL=np.uint32, VOXEL_DIST=np.float32, SV_LABELS=np.uint32, SV_CENTROID=np.float32, EDGES=np.uint32,
@@ -187,6 +188,34 @@ class RegionBoxesResult(ctypes.Structure):
 REGION_BOX_DTYPE = np.dtype([("n_pixels", np.uint32), ("n_inliers", np.uint32)] +
                             [(k, np.float32, (3,)) for k in ("center", "axis_n", "axis_m", "axis_l", "lo", "hi", "half")] + [("mean_abs_residual", np.float32)])
 assert REGION_BOX_DTYPE.itemsize == ctypes.sizeof(RegionBox) == 96
+
+
+class CloudParams(ctypes.Structure):
+    """f3ds_cloud_params (include/f3ds.h): the boxes' inlier distance and the segmenter's fold of negative z."""
+    _fields_ = [("plane_tol", ctypes.c_float), ("fold_negative_z", ctypes.c_int32)]
+
+
+class CloudRegion(ctypes.Structure):
+    """f3ds_cloud_region (include/f3ds.h): one region of a labelled point cloud -- the table's and the shapes' fields in one row, 128 bytes."""
+    _fields_ = [("n_points", ctypes.c_uint32), ("first_point", ctypes.c_uint32)] + \
+               [(k, ctypes.c_float * 3) for k in ("lo", "hi", "centroid", "mean_rgb")] + [("cov", ctypes.c_float * 6)] + \
+               [(k, ctypes.c_float * 3) for k in ("eigenvalue", "normal", "axis")] + [("plane_d", ctypes.c_float), ("curvature", ctypes.c_float), ("reserved", ctypes.c_uint32)]
+
+
+class CloudRegionsResult(ctypes.Structure):
+    """f3ds_cloud_regions_result (include/f3ds.h): the counts of one call for the region rows of a cloud."""
+    _fields_ = [("n_regions", ctypes.c_uint32), ("n_nonempty", ctypes.c_uint32), ("n_labelled", ctypes.c_uint64), ("n_clamped", ctypes.c_uint64),
+                ("n_inliers", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+# the same 128 bytes as a numpy structured dtype: what cloud_regions_host and Context.cloud_regions return their rows in
+CLOUD_REGION_DTYPE = np.dtype([("n_points", np.uint32), ("first_point", np.uint32)] + [(k, np.float32, (3,)) for k in ("lo", "hi", "centroid", "mean_rgb")] +
+                              [("cov", np.float32, (6,))] + [(k, np.float32, (3,)) for k in ("eigenvalue", "normal", "axis")] +
+                              [("plane_d", np.float32), ("curvature", np.float32), ("reserved", np.uint32)])
+assert CLOUD_REGION_DTYPE.itemsize == ctypes.sizeof(CloudRegion) == 128
 
 
 class JointParams(ctypes.Structure):
@@ -342,6 +371,13 @@ def load_library(path=None):
         lib.f3ds_region_joints_batch.argtypes = [ctypes.POINTER(vp), ctypes.c_int, fp, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, jpp, ctypes.c_int, ctypes.POINTER(vp), vp,
                                                  ctypes.POINTER(vp), ctypes.c_int, vp, vp, vp]
         lib.f3ds_region_joints_batch.restype = ctypes.c_int
+    if hasattr(lib, "f3ds_cloud_regions"):
+        crp, cpp, pp = ctypes.POINTER(CloudRegionsResult), ctypes.POINTER(CloudParams), ctypes.POINTER(vp)
+        lib.f3ds_default_cloud_params.argtypes = [cpp]; lib.f3ds_default_cloud_params.restype = None
+        lib.f3ds_cloud_regions_host.argtypes = [vp, sz, vp, ctypes.c_uint32, cpp, vp, vp, crp]; lib.f3ds_cloud_regions_host.restype = ctypes.c_int
+        lib.f3ds_cloud_regions.argtypes = [vp, vp, sz, vp, ctypes.c_uint32, cpp, ctypes.c_int, vp, vp, ctypes.c_int, crp]; lib.f3ds_cloud_regions.restype = ctypes.c_int
+        lib.f3ds_cloud_regions_batch.argtypes = [pp, ctypes.c_int, pp, vp, pp, vp, cpp, ctypes.c_int, pp, pp, ctypes.c_int, vp, vp]
+        lib.f3ds_cloud_regions_batch.restype = ctypes.c_int
     if hasattr(lib, "f3ds_region_table_batch"):      # the batch forms: arrays of per-frame pointers (void**), counts and results
         pp, fp, i32 = ctypes.POINTER(vp), ctypes.POINTER(RgbdFormat), ctypes.c_int
         lib.f3ds_region_table_batch.argtypes = [pp, i32, fp, pp, pp, pp, vp, i32, pp, i32, vp, vp]
@@ -856,6 +892,53 @@ def region_boxes_host(depth, labels, n_regions, fmt, plane_tol=0.01, want_shapes
     return (rows, shapes, res) if want_shapes else (rows, res)
 
 
+# ---- region rows of a point cloud --------------------------------------------------------------------
+def default_cloud_params(**overrides):
+    p = CloudParams()
+    load_library().f3ds_default_cloud_params(ctypes.byref(p))
+    for k, v in overrides.items():
+        setattr(p, k, v)
+    return p
+
+
+def _cloud_rows(buf, n_regions):
+    if buf is None:
+        return np.empty(int(n_regions), CLOUD_REGION_DTYPE)
+    if not (isinstance(buf, np.ndarray) and buf.dtype == CLOUD_REGION_DTYPE and buf.flags.c_contiguous and buf.size == int(n_regions)):
+        raise ValueError("rows_out must be a contiguous CLOUD_REGION_DTYPE array with one entry per region")
+    return buf
+
+
+def _cloud_inputs(points, labels):
+    """(records as (n, 4) f32 or None, labels as (n,) u32) of a host caller; points: (n, 4) float32 records (the colour word's bits in column 3), or None"""
+    lab = np.ascontiguousarray(labels, np.uint32).reshape(-1)
+    if points is None:
+        return None, lab
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+    if len(pts) != len(lab):
+        raise ValueError("one label per point is required")
+    return pts, lab
+
+
+def _ptr(a):
+    return None if a is None or not a.size else a.ctypes.data
+
+
+def cloud_regions_host(points, labels, n_regions, params=None, want_boxes=False):
+    """f3ds_cloud_regions_host: (rows, CloudRegionsResult), or (rows, boxes, CloudRegionsResult) with ``want_boxes`` -- one CLOUD_REGION_DTYPE row per region
+    of a labelled cloud: points (n, 4) float32 records as Context.segment takes them, labels n uint32 (< n_regions or NO_LABEL); boxes: REGION_BOX_DTYPE rows
+    by the definition of region_boxes_host with the cloud rows' shape fields.  params: CloudParams (None: the defaults).  Host arithmetic only: what
+    Context.cloud_regions computes on the device, bit for bit."""
+    lib = load_library()
+    pts, lab = _cloud_inputs(points, labels)
+    rows, res = _cloud_rows(None, n_regions), CloudRegionsResult()
+    boxes = _box_rows(None, n_regions) if want_boxes else None
+    keep = np.zeros(4, np.float32)      # (an empty cloud still has an address)
+    _check(lib, lib.f3ds_cloud_regions_host(_ptr(pts) or keep.ctypes.data, len(lab), _ptr(lab) or keep.ctypes.data, int(n_regions), ctypes.byref(params) if params is not None else None,
+                                            _ptr(rows), _ptr(boxes) if want_boxes else None, ctypes.byref(res)))
+    return (rows, boxes, res) if want_boxes else (rows, res)
+
+
 # ---- region joints ---------------------------------------------------------------------------------
 def default_joint_params(**overrides):
     p = JointParams()
@@ -1039,6 +1122,35 @@ class Context(_Handle):
         _check(self.lib, self.lib.f3ds_region_boxes(self.handle, ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), float(plane_tol), 0,
                                                     rows.ctypes.data if len(rows) else None, shapes.ctypes.data if want and len(shapes) else None, 0, ctypes.byref(res)))
         return (rows, shapes, res) if want else (rows, res)
+
+    def cloud_regions(self, points, labels, n_regions, params=None, rows_out=None, boxes_out=None, n=None, on_device=False):
+        """f3ds_cloud_regions: (rows, CloudRegionsResult) -- what cloud_regions_host returns, computed on the device with one wait.  points: (n, 4) float32
+        records, or None for the records the context's last segment call ran on (LogicError when they were the caller's device buffer).  With ``boxes_out`` the
+        boxes come too and the answer is (rows, boxes, CloudRegionsResult): ``True`` for a new REGION_BOX_DTYPE array, or such an array to fill.  With
+        ``on_device=True`` points (or None) and labels are device pointers (ints or torch tensors), ``n`` the point count, ``rows_out`` and ``boxes_out`` device
+        pointers to n_regions rows each (``boxes_out`` may be None) and the rows returned are None.  Leaves the context's frame as it is."""
+        res = CloudRegionsResult()
+        prm = ctypes.byref(params) if params is not None else None
+        if on_device:
+            if n is None:
+                raise ValueError("on_device needs the point count n")
+            _check(self.lib, self.lib.f3ds_cloud_regions(self.handle, _opt_ptr(points), int(n), _device_ptr(labels), int(n_regions), prm, 1, _opt_ptr(rows_out), _opt_ptr(boxes_out), 1,
+                                                         ctypes.byref(res)))
+            return (None, res) if boxes_out is None else (None, None, res)
+        pts, lab = _cloud_inputs(points, labels)
+        rows = _cloud_rows(rows_out, n_regions)
+        want = boxes_out is not None and boxes_out is not False
+        boxes = _box_rows(None if boxes_out is True else boxes_out, n_regions) if want else None
+        keep = np.zeros(4, np.float32)      # (an empty cloud still has an address)
+        _check(self.lib, self.lib.f3ds_cloud_regions(self.handle, None if pts is None else (_ptr(pts) or keep.ctypes.data), len(lab), _ptr(lab) or keep.ctypes.data, int(n_regions), prm, 0,
+                                                     _ptr(rows), (_ptr(boxes) or keep.ctypes.data) if want else None, 0, ctypes.byref(res)))
+        return (rows, boxes, res) if want else (rows, res)
+
+    def cloud_path(self):
+        """F3DS_DBG_CLOUD_PATH: how the context's last cloud_regions call walked its points -- "direct", "ordered", or None before any."""
+        w = np.zeros(1, np.uint32)
+        _check(self.lib, self.lib.f3ds_get_debug(self.handle, DBG_CLOUD_PATH, w.ctypes.data, 4, None))
+        return {1: "direct", 2: "ordered"}.get(int(w[0]))
 
     def region_joints(self, depth, labels, n_regions, fmt, params=None, rows_out=None, shapes_out=None, on_device=False):
         """f3ds_region_joints: (rows, RegionJointsResult) -- what region_joints_host returns, computed on the device with one wait; a and b index the rows of
@@ -1646,6 +1758,54 @@ def region_boxes_batch(ctxs, depths, labels, n_regions, fmt, plane_tol=0.01, row
     ok = status == 0
     if want:
         return [(rows[i] if ok[i] else None, shapes[i] if ok[i] else None, results[i] if ok[i] else None) for i in range(k)], status
+    return [(rows[i] if ok[i] else None, results[i] if ok[i] else None) for i in range(k)], status
+
+
+def cloud_regions_batch(ctxs, points, labels, n_regions, params=None, rows_out=None, boxes_out=None, counts=None, on_device=False):
+    """f3ds_cloud_regions_batch: Context.cloud_regions for every frame at once; every frame has its own point count (0 is legal).  points / labels: lists of
+    arrays (a points entry may be None: the context's own records), or of device pointers / torch tensors with ``on_device`` (``counts`` then gives the point
+    counts, ``rows_out`` / ``boxes_out`` are lists of device buffers).  ``boxes_out``: None, ``True`` (host form: new arrays) or a list of buffers, for every
+    frame or for none.  Returns ([(rows, CloudRegionsResult)], status), or ([(rows, boxes, CloudRegionsResult)], status) with boxes."""
+    lib = load_library()
+    k = len(ctxs)
+    if k < 1:
+        raise ValueError("a batch needs at least one context")
+    for name, seq in (("points", points), ("labels", labels), ("n_regions", n_regions)):
+        if len(seq) != k:
+            raise ValueError("%s must hold one entry per context" % name)
+    vp = ctypes.c_void_p
+    handles = (vp * k)(*[c.handle for c in ctxs])
+    nr = (ctypes.c_uint32 * k)(*[int(x) for x in n_regions])
+    status = np.full(k, _STATUS_UNSET, np.int32)
+    outs, results = _outs(rows_out, k, "rows_out"), (CloudRegionsResult * k)()
+    want = boxes_out is not None and boxes_out is not False
+    bouts = [None] * k if (boxes_out is True or not want) else _outs(boxes_out, k, "boxes_out")
+    if want and boxes_out is not True and any(b is None for b in bouts):
+        raise ValueError("boxes_out: a buffer for every frame or None (one command sequence for the batch)")
+    spare = np.zeros(24, np.float32)      # (an empty cloud, and the boxes of a frame without regions, still have an address)
+    if on_device:
+        if boxes_out is True or counts is None or len(counts) != k:
+            raise ValueError("on_device needs the point counts, and device buffers for the boxes")
+        keep, cnt = None, (ctypes.c_size_t * k)(*[int(x) for x in counts])
+        pp = (vp * k)(*[_opt_ptr(x) for x in points]); lp = (vp * k)(*[_device_ptr(x) for x in labels])
+        rows, boxes = [None] * k, [None] * k
+        rp = (vp * k)(*[_opt_ptr(o) for o in outs])
+        bp = (vp * k)(*[_opt_ptr(o) for o in bouts]) if want else None
+    else:
+        keep = [_cloud_inputs(p, lab) for p, lab in zip(points, labels)]
+        cnt = (ctypes.c_size_t * k)(*[len(x[1]) for x in keep])
+        pp = (vp * k)(*[None if x[0] is None else vp(_ptr(x[0]) or spare.ctypes.data) for x in keep])
+        lp = (vp * k)(*[vp(_ptr(x[1]) or spare.ctypes.data) for x in keep])
+        rows = [_cloud_rows(o, nr[i]) for i, o in enumerate(outs)]
+        boxes = [_box_rows(o, nr[i]) for i, o in enumerate(bouts)] if want else [None] * k
+        rp = (vp * k)(*[vp(r.ctypes.data) if len(r) else None for r in rows])
+        bp = (vp * k)(*[vp(_ptr(x) or spare.ctypes.data) for x in boxes]) if want else None
+    where = 1 if on_device else 0
+    rc = lib.f3ds_cloud_regions_batch(handles, k, pp, cnt, lp, nr, ctypes.byref(params) if params is not None else None, where, rp, bp, where, results, status.ctypes.data)
+    _batch_done(lib, rc, status)
+    ok = status == 0
+    if want:
+        return [(rows[i] if ok[i] else None, boxes[i] if ok[i] else None, results[i] if ok[i] else None) for i in range(k)], status
     return [(rows[i] if ok[i] else None, results[i] if ok[i] else None) for i in range(k)], status
 
 

@@ -56,6 +56,7 @@
 #include "f3ds_boxes.h"
 #include "f3ds_joints.h"
 #include "f3ds_components.h"
+#include "f3ds_cloud.h"
 
 using namespace f3ds;
 
@@ -69,6 +70,7 @@ using namespace f3ds;
 #include "f3ds_boxes.inc"
 #include "f3ds_joints.inc"
 #include "f3ds_components.inc"
+#include "f3ds_cloud.inc"
 
 // ================================================================================================
 // batched launch machinery
@@ -144,7 +146,7 @@ const int g_inc_shift = [] { const char* e = dev_getenv("F3DS_INC_SHIFT"); retur
 // where hundreds of getenv() scans per call would also race with a setenv from another thread.  Tests still see per-call values.
 struct Switches {
     bool direct_labels = false, copy_stream = true, copy_duplex = false, split_voxel_accum = false, sweep_tiles = true, merge_spec = true, force_global_merge = false, no_stream_pool = false, sort_pairs = false, host_prof = false, trace_err = false, vox_hash = true, vox_tiles_forced = false, levels_global = false;
-    int normals_threads = 0, merge_nw = 0, merge_keys = -1; uint32_t tile_holes = 0, ilist_slack = 32, r_rounds = F3DS_R_ROUNDS, grid_cap = 0, rgc_first_cap = 0, rgj_first_cap = 0; long relabel_lds_cap = -1;
+    int normals_threads = 0, merge_nw = 0, merge_keys = -1; uint32_t tile_holes = 0, ilist_slack = 32, r_rounds = F3DS_R_ROUNDS, grid_cap = 0, rgc_first_cap = 0, rgj_first_cap = 0, cloud_path = 0; long relabel_lds_cap = -1;
     void read() {
         auto on = [](const char* n) { return dev_getenv(n) != nullptr; };
         auto num = [](const char* n, long dflt) { const char* e = dev_getenv(n); return e ? atol(e) : dflt; };
@@ -162,6 +164,7 @@ struct Switches {
         { const long v = num("F3DS_ILIST_SLACK", 32); ilist_slack = v >= 1 && v <= 32 ? (uint32_t)v : 32u; }      // tests: a short incident-list pool (the merge stage then reruns with a larger one)
         { const long v = num("F3DS_GRID_CAP", 0); grid_cap = v >= 1 && v <= 2048 ? (uint32_t)v : 0u; }      // tests: 1 ... 2048 workgroups per frame, exactly, for grid_for() and grid_wide(): the grid-stride loops make several trips on small frames (0: unset)
         { const long v = num("F3DS_RGC_FIRST_CAP", 0); rgc_first_cap = v >= 1 && v <= 0x7fffffffl ? (uint32_t)v : 0u; }      // tests: a short first record buffer of f3ds_region_contacts (the frame then runs again with room for all; 0: unset)
+        { const char* e = dev_getenv("F3DS_CLOUD_PATH"); cloud_path = !e ? 0u : (!strcmp(e, "direct") ? CD_PATH_DIRECT : (!strcmp(e, "ordered") ? CD_PATH_ORDERED : 0u)); }      // tests: how f3ds_cloud_regions walks its points, whatever K says (0: unset)
         { const long v = num("F3DS_RGJ_FIRST_CAP", 0); rgj_first_cap = v >= 1 && v <= 0x7fffffffl ? (uint32_t)v : 0u; }      // tests: likewise the first record buffer of f3ds_region_joints
     }
 };
@@ -204,7 +207,9 @@ const int g_merge_shared_res = [] { const char* e = dev_getenv("F3DS_MERGE_SHARE
     /* region joints (f3ds_joints.inc): the shapes' accumulators and head, the shape rows of a caller who wants none, then as the contacts: the records' keys and indices (twice: the sort), the records, the runs' flags, keys, starts and ends, the run count */ \
     X(ShAcc, rgj_sacc) X(uint32_t, rgj_shead) X(f3ds_region_shape, rgj_shape) X(uint64_t, rgj_k0) X(uint64_t, rgj_k1) X(uint32_t, rgj_v0) X(uint32_t, rgj_v1) X(uint32_t, rgj_rec) X(uint32_t, rgj_flag) X(uint64_t, rgj_ukey) X(uint32_t, rgj_ustart) X(uint32_t, rgj_uend) X(uint32_t, rgj_cnt) \
     /* region components (f3ds_components.inc): a parent, a size and a flag word per pixel */ \
-    X(uint32_t, rgk_parent) X(uint32_t, rgk_cnt) X(uint32_t, rgk_flag)
+    X(uint32_t, rgk_parent) X(uint32_t, rgk_cnt) X(uint32_t, rgk_flag) \
+    /* region rows of a cloud (f3ds_cloud.inc): the records of a host caller as uploaded (its labels ride in li_lab), the accumulators, the keys (twice: the sort), then the box pass: the shape rows, the frames, the accumulators of pass two and its head */ \
+    X(P16, rgp_pts) X(CdAcc, rgp_acc) X(uint64_t, rgp_k0) X(uint64_t, rgp_k1) X(f3ds_region_shape, rgp_shape) X(BxFrame, rgp_frame) X(BxAcc, rgp_bacc) X(uint32_t, rgp_head)
 template <class T> struct Scratch { T* p = nullptr; size_t cap = 0; int slot = -1; };      // cap: bytes allocated; slot: position in F3DS_SCRATCH
 #define F3DS_SCRATCH_SLOT(T, name) S_##name,
 #define F3DS_SCRATCH_MEMBER(T, name) Scratch<T> name{nullptr, 0, S_##name};
@@ -265,6 +270,7 @@ struct f3ds_ctx {
     // device scratch (grow-only): one typed member per entry of F3DS_SCRATCH; each_scratch(f) calls f on every one of them until one returns non-zero
     F3DS_SCRATCH(F3DS_SCRATCH_MEMBER)
     template <class F> int each_scratch(F&& f) { F3DS_SCRATCH(F3DS_SCRATCH_VISIT) return 0; }
+    uint32_t cloud_path = 0;           // how the last f3ds_cloud_regions call of this context walked its points (CD_PATH_*; F3DS_DBG_CLOUD_PATH)
     uint32_t launch_shape[3] = {0, 0, 0};      // cap of grid_for(), cap of grid_wide(), frames of the last entry call that recorded kernels for this context (F3DS_DBG_LAUNCH_SHAPE)
     std::vector<uint32_t> tsize;       // voxels per truth label (evaluation)
     float cluster_T = 0.0f;            // threshold of the last cluster run: f3ds_labels_at_thresholds serves levels t <= cluster_T from its merge log
@@ -1941,11 +1947,12 @@ extern "C" int f3ds_get_debug(f3ds_ctx* c, int what, void* dst, size_t cap_bytes
     auto put = [&](const void* src, size_t nb) { const uint8_t* b = static_cast<const uint8_t*>(src); buf.insert(buf.end(), b, b + nb); };
     int rc = F3DS_OK;
     std::vector<float> f; std::vector<uint32_t> u, u2, u3; std::vector<int> iv; std::vector<unsigned char> uc;
-    if (what != F3DS_DBG_GRID && what != F3DS_DBG_LAUNCH_SHAPE && !c->have_frame) return F3DS_ERR_LOGIC;      // (the launch shape describes the call: an empty frame of a batch has one too)
+    if (what != F3DS_DBG_GRID && what != F3DS_DBG_LAUNCH_SHAPE && what != F3DS_DBG_CLOUD_PATH && !c->have_frame) return F3DS_ERR_LOGIC;      // (the launch shape describes the call: an empty frame of a batch has one too)
     switch (what) {
         case F3DS_DBG_GRID: { HIPCHECK(hipMemcpy(c->h_grid, c->d_grid, sizeof(GridInfo), hipMemcpyDeviceToHost)); double g[5] = {c->h_grid->min[0], c->h_grid->min[1], c->h_grid->min[2], c->h_grid->res, (double)c->h_grid->depth}; put(g, sizeof g); break; }
         case F3DS_DBG_TILE_LIST_LEN: if ((rc = fetch(c, c->tile_n1, (size_t)(V + NT_TILE - 1) / NT_TILE, u))) return rc; put(u.data(), u.size() * 4); break;
         case F3DS_DBG_LAUNCH_SHAPE: put(c->launch_shape, 12); break;
+        case F3DS_DBG_CLOUD_PATH: put(&c->cloud_path, 4); break;
         case F3DS_DBG_STAGE0_PATH: { const uint32_t w = c->vox_hashed ? 1u : 0u; put(&w, 4); break; }
         case F3DS_DBG_SWEEP_STATS: {
             DevCounters dcs;
@@ -3121,4 +3128,125 @@ extern "C" int f3ds_region_components(f3ds_ctx* c, const f3ds_rgbd_format* fmt_,
                                       f3ds_region_components_result* result) {
     return f3ds_region_components_batch(&c, 1, fmt_, &depth, &labels, &n_regions, params, inputs_on_device, &comp_labels, rows ? &rows : nullptr, &cap, outputs_on_device, n_out, result,
                                         nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------
+// region rows of a point cloud (f3ds_cloud.h / .inc): one row per region of n labelled records, and optionally the region boxes.  The
+// call has the shape of the family's batch forms -- checks, staging, uploads, one record per frame, one flush, one download, one wait -- over points, not
+// images: every frame has its own n.  What every frame of a batch must agree on is decided for the batch: the walk (ordered if any frame's K asks for it, or
+// what F3DS_CLOUD_PATH says), the key layout (index bits of the longest frame, label bits of the largest K: the same sort passes for all) and whether there
+// are boxes.  Kernels: d_cloud_init, [d_cloud_keys, the stage-0 radix sort on the label bits,] d_cloud_accum, d_cloud_finish, [d_box_frame, d_cloud_box_accum,
+// d_box_finish].  Behind the heads the rows of a host caller (128 B per region) and behind them its boxes (96 B).  Beside rgp_* the call uses the sort's
+// histogram, which holds nothing between calls, and li_lab for a host caller's labels.
+// ------------------------------------------------------------------------------------------------
+namespace {
+int cd_record(f3ds_ctx* c, const P16* pts, const uint32_t* labels, uint32_t n, uint32_t K, const f3ds_cloud_params& prm, bool ordered, uint32_t idx_bits, int label_bits, uint32_t* head,
+              f3ds_cloud_region* d_rows, f3ds_region_box* d_boxes /* NULL: none */) {
+    CloudArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = n; a.K = K; a.copies = rgt_copies(K); a.idx_bits = idx_bits; a.fold_negative_z = prm.fold_negative_z; a.ordered = ordered ? 1 : 0;
+    const uint32_t walk_grid = grid_for(((size_t)n + LI_TRIPS - 1u) / LI_TRIPS, 256);      // (both walks, both passes: LI_TRIPS trips a workgroup, as the image family)
+    CdAcc* acc; uint64_t *k0 = nullptr, *k1 = nullptr, *ks = nullptr;
+    f3ds_region_shape* shapes = nullptr; BxFrame* frames = nullptr; BxAcc* acc2 = nullptr; uint32_t* head2 = nullptr;
+    ENSURE(c->rgp_acc, K ? (size_t)K * a.copies : 1u, acc);
+    if (ordered) { ENSURE(c->rgp_k0, n ? n : 1u, k0); ENSURE(c->rgp_k1, n ? n : 1u, k1); }
+    if (d_boxes) {
+        ENSURE(c->rgp_shape, K ? K : 1u, shapes); ENSURE(c->rgp_frame, K ? K : 1u, frames);
+        ENSURE(c->rgp_bacc, K ? (size_t)K * a.copies : 1u, acc2); ENSURE(c->rgp_head, LI_HEAD_WORDS, head2);
+    }
+    rec<d_cloud_init>(c, grid_for((size_t)K * a.copies * CD_WORDS, 256), 0u, reinterpret_cast<uint32_t*>(acc), K * a.copies, head);
+    if (ordered) {
+        rec<d_cloud_keys>(c, grid_for(n, 256), 0u, labels, a, k0, head);
+        if (const int rc = radix_sort(c, k0, nullptr, k1, nullptr, n, label_bits, &ks, nullptr, (int)idx_bits)) return rc;
+    }
+    rec<d_cloud_accum>(c, walk_grid, 0u, pts, labels, ks, a, acc, head);
+    rec<d_cloud_finish>(c, grid_for(K, 256), 0u, acc, K, a.copies, head, d_rows, shapes);
+    if (d_boxes) {
+        rec<d_box_frame>(c, grid_for(K, 256), 0u, shapes, K, a.copies, prm.plane_tol, head, frames, acc2, head2);
+        rec<d_cloud_box_accum>(c, walk_grid, 0u, pts, labels, ks, a, frames, acc2, head, head2);
+        rec<d_box_finish>(c, grid_for(K, 256), 0u, acc2, frames, K, a.copies, head, d_boxes);
+    }
+    c->cloud_path = ordered ? CD_PATH_ORDERED : CD_PATH_DIRECT;
+    return F3DS_OK;
+}
+}  // namespace
+
+extern "C" int f3ds_cloud_regions_batch(f3ds_ctx** ctxs, int nctx, const void* const* points, const size_t* counts, const uint32_t* const* labels, const uint32_t* n_regions,
+                                        const f3ds_cloud_params* params, int inputs_on_device, f3ds_cloud_region* const* rows, f3ds_region_box* const* boxes, int rows_on_device,
+                                        f3ds_cloud_regions_result* results, int* status) {
+    if (!li_batch_ctxs(ctxs, nctx) || !points || !counts || !labels || !n_regions || !rows) return F3DS_ERR_ARG;
+    f3ds_cloud_params prm;
+    for (int i = 0; i < nctx; ++i) {
+        if (boxes && !boxes[i] && n_regions[i]) return F3DS_ERR_ARG;      // (boxes for every frame or for none)
+        if (const int rc = cd_check(points[i], counts[i], labels[i], n_regions[i], params, rows[i], true, &prm)) return rc;
+    }
+    for (int i = 0; i < nctx; ++i) {      // the context's own records, by the rule of f3ds_get_points
+        if (points[i]) continue;
+        if (!ctxs[i]->d_pts || ctxs[i]->d_pts != ctxs[i]->pts.p) return F3DS_ERR_LOGIC;
+        if (counts[i] != ctxs[i]->n) return F3DS_ERR_ARG;
+    }
+    Batch b;
+    if (const int rc = li_begin(ctxs, nctx, &b)) return rc;
+    // the batch-wide decisions
+    uint32_t maxn = 1, maxk = 0;
+    bool ordered = false;
+    for (int i = 0; i < nctx; ++i) {
+        maxn = std::max(maxn, (uint32_t)counts[i]); maxk = std::max(maxk, n_regions[i]);
+        ordered = ordered || cd_choose_path(n_regions[i]) == CD_PATH_ORDERED;
+    }
+    if (g_sw.cloud_path) ordered = g_sw.cloud_path == CD_PATH_ORDERED;
+    const uint32_t idx_bits = (uint32_t)bits_for((uint64_t)maxn - 1u);
+    const int label_bits = bits_for(maxk);      // (the key of a point without a label carries K itself)
+    std::vector<size_t> fixed((size_t)nctx), row_bytes((size_t)nctx), box_bytes((size_t)nctx);
+    for (int i = 0; i < nctx; ++i) {
+        row_bytes[i] = rows_on_device ? 0u : (size_t)n_regions[i] * sizeof(f3ds_cloud_region);      // (a multiple of 8: the boxes behind them are aligned)
+        box_bytes[i] = rows_on_device || !boxes ? 0u : (size_t)n_regions[i] * sizeof(f3ds_region_box);
+        fixed[i] = row_bytes[i] + box_bytes[i];
+    }
+    LiStage s;
+    if (const int rc = li_out_buffers(ctxs[0], nctx, fixed.data(), nullptr, 0u, 0u, &s)) return rc;
+    // the inputs as the kernels read them: host records and labels go up through the device's copy stream, all frames' copies awaited once
+    std::vector<const P16*> d_pts((size_t)nctx); std::vector<const uint32_t*> d_lab((size_t)nctx);
+    hipStream_t up = (!inputs_on_device && g_sw.copy_stream) ? copy_stream_of(b.owner->device) : nullptr;
+    for (int i = 0; i < nctx; ++i) {
+        f3ds_ctx* c = ctxs[i];
+        const size_t n = counts[i];
+        d_pts[i] = points[i] ? static_cast<const P16*>(points[i]) : c->d_pts;
+        d_lab[i] = labels[i];
+        if (inputs_on_device) continue;
+        uint32_t* ul;
+        ENSURE(c->li_lab, n ? n : 1u, ul);
+        if (n) HIPCHECK(hipMemcpyAsync(ul, labels[i], n * 4, hipMemcpyHostToDevice, up ? up : b.st));
+        d_lab[i] = ul;
+        if (points[i]) {
+            P16* upts;
+            ENSURE(c->rgp_pts, n ? n : 1u, upts);
+            if (n) HIPCHECK(hipMemcpyAsync(upts, points[i], n * 16, hipMemcpyHostToDevice, up ? up : b.st));
+            d_pts[i] = upts;
+        }
+    }
+    if (up) { if (const int urc = await_uploads(b, up)) return urc; }
+    for (int i = 0; i < nctx; ++i) {
+        f3ds_cloud_region* d_rows = rows_on_device ? rows[i] : reinterpret_cast<f3ds_cloud_region*>(s.out + s.slot[i].at);
+        f3ds_region_box* d_boxes = !boxes ? nullptr : (rows_on_device && boxes[i] ? boxes[i] : reinterpret_cast<f3ds_region_box*>(s.out + s.slot[i].at + row_bytes[i]));
+        if (const int rc = cd_record(ctxs[i], d_pts[i], d_lab[i], (uint32_t)counts[i], n_regions[i], prm, ordered, idx_bits, label_bits, s.head(i), d_rows, d_boxes)) return rc;
+    }
+    if (const int rc = flush(b)) return rc;
+    if (const int rc = li_download_heads(s, b)) return rc;
+    std::vector<int> st((size_t)nctx, F3DS_OK);
+    for (int i = 0; i < nctx; ++i) {
+        const uint32_t* h = s.h_head(i);
+        if (h[1]) { st[i] = F3DS_ERR_ARG; continue; }      // (a label >= n_regions: no finish kernel wrote a row)
+        if (row_bytes[i]) memcpy(rows[i], s.o->h_li + s.slot[i].at, row_bytes[i]);
+        if (box_bytes[i]) memcpy(boxes[i], s.o->h_li + s.slot[i].at + row_bytes[i], box_bytes[i]);
+        if (results) {
+            results[i].n_regions = n_regions[i]; results[i].n_nonempty = h[0];
+            memcpy(&results[i].n_labelled, h + 2, 8); memcpy(&results[i].n_clamped, h + 4, 8); memcpy(&results[i].n_inliers, h + 6, 8);
+        }
+    }
+    return li_statuses(st, status);
+}
+extern "C" int f3ds_cloud_regions(f3ds_ctx* c, const void* points16, size_t n, const uint32_t* labels, uint32_t n_regions, const f3ds_cloud_params* params, int inputs_on_device,
+                                  f3ds_cloud_region* rows, f3ds_region_box* boxes, int rows_on_device, f3ds_cloud_regions_result* result) {
+    return f3ds_cloud_regions_batch(&c, 1, &points16, &n, &labels, &n_regions, params, inputs_on_device, &rows, boxes ? &boxes : nullptr, rows_on_device, result, nullptr);
 }

@@ -24,6 +24,7 @@
 #include "f3ds_contacts.h"
 #include "f3ds_shapes.h"
 #include "f3ds_boxes.h"
+#include "f3ds_cloud.h"
 #include "f3ds_joints.h"
 #include "f3ds_components.h"
 
@@ -324,6 +325,53 @@ int f3ds_region_boxes_host(const f3ds_rgbd_format* fmt_, const void* depth, cons
         result->n_regions = n_regions; result->n_nonempty = sres.n_nonempty; result->n_labelled = sres.n_labelled; result->n_clamped = sres.n_clamped;
         result->n_inliers = n_inliers;
     }
+    return F3DS_OK;
+}
+
+// ---- region rows of a point cloud: the definition (the rules are in f3ds_cloud.h, which d_cloud_accum and d_cloud_finish call too; the boxes' in f3ds_boxes.h) ----
+// The labels are checked before a row is written; the box pass measures every labelled point in the frame made of its region's row.
+void f3ds_default_cloud_params(f3ds_cloud_params* p) { if (p) { p->plane_tol = 0.01f; p->fold_negative_z = 0; } }
+
+int f3ds_cloud_regions_host(const void* points16, size_t n, const uint32_t* labels, uint32_t n_regions, const f3ds_cloud_params* params, f3ds_cloud_region* rows,
+                            f3ds_region_box* boxes, f3ds_cloud_regions_result* result) {
+    f3ds_cloud_params prm;
+    if (const int rc = f3ds::cd_check(points16, n, labels, n_regions, params, rows, false, &prm)) return rc;
+    if (!f3ds::li_labels_in_range(labels, n, n_regions)) return F3DS_ERR_ARG;
+    const unsigned char* rec = static_cast<const unsigned char*>(points16);
+    auto point = [&](size_t i, float& x, float& y, float& z, uint32_t& rgba) {      // (a record may start anywhere: memcpy)
+        float f[3]; memcpy(f, rec + 16u * i, 12); memcpy(&rgba, rec + 16u * i + 12u, 4);
+        x = f[0]; y = f[1]; z = f[2];
+        return f3ds::cd_finite(x, y, z, prm.fold_negative_z);
+    };
+    std::vector<f3ds::CdAcc> acc(n_regions);
+    for (f3ds::CdAcc& a : acc) f3ds::cd_empty(a);
+    uint64_t n_labelled = 0, n_clamped = 0, n_inliers = 0;
+    for (size_t i = 0; i < n; ++i) {
+        float x, y, z; uint32_t rgba;
+        if (labels[i] == F3DS_NO_LABEL || !point(i, x, y, z, rgba)) continue;
+        f3ds::CdAcc one;
+        if (f3ds::cd_point((uint32_t)i, x, y, z, rgba, one)) ++n_clamped;
+        f3ds::cd_merge(acc[labels[i]], one);
+        ++n_labelled;
+    }
+    uint32_t n_nonempty = 0;
+    std::vector<f3ds_region_shape> shapes(n_regions);
+    for (uint32_t r = 0; r < n_regions; ++r) { f3ds::cd_finish(acc[r], &rows[r], &shapes[r]); if (acc[r].w[0]) ++n_nonempty; }
+    if (boxes) {
+        std::vector<f3ds::BxFrame> frames(n_regions);
+        std::vector<f3ds::BxAcc> bacc(n_regions);
+        for (uint32_t r = 0; r < n_regions; ++r) { f3ds::bx_frame(shapes[r], prm.plane_tol, frames[r]); f3ds::bx_empty(bacc[r]); }
+        for (size_t i = 0; i < n; ++i) {
+            float x, y, z; uint32_t rgba;
+            if (labels[i] == F3DS_NO_LABEL || !point(i, x, y, z, rgba)) continue;
+            f3ds::BxAcc one;
+            f3ds::bx_empty(one);
+            f3ds::bx_pixel(x, y, z, frames[labels[i]], one);
+            f3ds::bx_merge(bacc[labels[i]], one);
+        }
+        for (uint32_t r = 0; r < n_regions; ++r) { f3ds::bx_finish(bacc[r], frames[r], &boxes[r]); n_inliers += bacc[r].w[1]; }
+    }
+    if (result) { result->n_regions = n_regions; result->n_nonempty = n_nonempty; result->n_labelled = n_labelled; result->n_clamped = n_clamped; result->n_inliers = n_inliers; }
     return F3DS_OK;
 }
 

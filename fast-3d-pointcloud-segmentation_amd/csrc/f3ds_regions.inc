@@ -83,6 +83,8 @@ __device__ __forceinline__ void label_init(uint32_t* acc_words, uint32_t n_acc, 
 
 // Span of workgroup b: [b * span, min(n, (b + 1) * span)), span = ceil(n / gridDim.x) rounded up to a multiple of the block: every lane of the workgroup makes
 // the same number of trips (the ballots and barriers below are uniform), a lane past the end contributes nothing.
+// This loop has a TWIN: cloud_accum_span (f3ds_cloud.inc) walks points instead of pixels with the same span arithmetic, one-label ballot, send logic, counts
+// and final flush.  A fix to one of the two belongs in the other.
 template <class Rule, bool DEPTH_F32>
 __device__ __forceinline__ void label_accum_span(const Rule& rule, const unsigned char* depth, const uint32_t* label, const typename Rule::Args& a, typename Rule::Acc* acc,
                                                  uint32_t* head, typename Rule::Table& tab, rg_u64* s_count) {

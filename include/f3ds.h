@@ -634,6 +634,79 @@ int f3ds_region_components_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_form
                                  f3ds_region_component* const* rows /* NULL: no rows */, const size_t* caps /* nctx */, int outputs_on_device,
                                  size_t* n_out /* nctx */, f3ds_region_components_result* results, int* status);
 
+/* ---- region rows of a point cloud: what the table, the shapes and the boxes say of a region, for labels WITHOUT an image grid -----
+ * The segmenter's first input is a cloud (f3ds_segment, the fused scenes, a lidar sweep); the region family above needs a depth image.  This call describes
+ * the regions of n labelled RECORDS: points16 is what f3ds_segment takes, n records {float x, y, z; uint32 rgba}; labels is one u32 per record, < n_regions
+ * or F3DS_NO_LABEL -- what f3ds_segment wrote, a level of f3ds_labels_at_thresholds, track ids, any relabelling.  Row i is region i.  Nothing is defined
+ * numerically anew; the definition, bit for bit (csrc/f3ds_cloud.h):
+ *   point      with params->fold_negative_z != 0 a z below 0 is replaced by fabsf(z): the segmenter's prelude rule (f3ds_params.fold_negative_z, main()'s
+ *              z < 0 -> |z|, which f3ds_segment applies to every point it reads).  Point i is LABELLED iff x, y and z are all finite after the fold and
+ *              labels[i] != F3DS_NO_LABEL.  A label over a non-finite point contributes nothing.  Only labelled points contribute.
+ *   fixed      the table's, word for word: fix(a) = (int64)rint(clamp((double)a, -32768, 32768) * 65536), units of 2^-16 m clamped to +-32768; a labelled
+ *              point is CLAMPED iff the clamp changed one of its coordinates.
+ *   order      minima and maxima of floats in the total order of key(bits) = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000): -0 below +0.
+ *   row        n_points, first_point (the smallest index i of a labelled point of the region), lo, hi, centroid and mean_rgb follow the rules that
+ *              f3ds_region_row gives n_pixels, first_pixel, lo, hi, centroid and mean_rgb, with "point i" read for "pixel p" (mean_rgb: r = bits 16-23,
+ *              g = bits 8-15, b = bits 0-7 of the colour word).  cov, eigenvalue, normal, axis, plane_d and curvature are those of f3ds_region_shape on the
+ *              same moments (n, S_a, M_ab as exact integers, the 128-bit scatter, the eight Jacobi sweeps): one call of the shapes' finish.
+ *              "Towards the camera" remains "towards the origin": normal . centroid <= 0.  For a fused cloud the origin is a convention of whoever fused
+ *              it, not a viewpoint; (normal, plane_d) is the same plane either way.
+ *   empty      a region without a labelled point has n_points = 0, first_point = 0xFFFFFFFF, lo = +inf, hi = -inf, the quiet NaN 0x7FC00000 in every other
+ *              float, reserved = 0.
+ *   boxes      optional (NULL: none): n_regions rows of the existing f3ds_region_box, by the definition of f3ds_region_boxes with "pixel" read as "point"
+ *              and S_i taken as the shape fields of cloud row i -- the frame from the public floats (c = centroid, n = normal, l = axis, m = n x l), q
+ *              from the fixed coordinates, t, lo / hi / half, inliers at params->plane_tol, mean_abs_residual.  A second pass over the points, which
+ *              depends on the finish of the first.
+ *   result     n_nonempty regions with a labelled point, n_labelled and n_clamped points, n_inliers the sum of the boxes' n_inliers (0 without boxes).
+ * Everything that meets more than one point is a count, a minimum, a maximum or a sum of integers: the result does not depend on the order of the points
+ * (first_point apart, which names an index) nor on the order of evaluation, and the device gives the bits of the host function.
+ * Errors (host and device alike, in this order): F3DS_ERR_ARG for a NULL labels, for a NULL points16 with n > 0 (the device form excepted, below), for NULL
+ * rows unless n_regions == 0, and for a plane_tol that is negative or NaN (+inf is a tolerance; it is checked without boxes too); F3DS_ERR_UNSUPPORTED for
+ * n_regions > 0x00FFFFFF or n > 0x7FFFFFFF; F3DS_ERR_ARG for a label >= n_regions other than F3DS_NO_LABEL on any point, a non-finite one included (the
+ * device function finds it on the device and reports it at the call's one wait).  After an error nothing is written.  n == 0, or no labelled point, is
+ * F3DS_OK with all rows empty.  params may be NULL: the defaults.  Joints, contacts, components and the tracker of clouds are not built. */
+typedef struct f3ds_cloud_params {
+    float plane_tol;            /* the boxes' inlier distance, metres; default 0.01         */
+    int32_t fold_negative_z;    /* f3ds_params.fold_negative_z; default 0                   */
+} f3ds_cloud_params;
+void f3ds_default_cloud_params(f3ds_cloud_params* p);
+typedef struct f3ds_cloud_region {      /* 128 bytes, 32 words */
+    uint32_t n_points;        /* labelled points of the region                                           */
+    uint32_t first_point;     /* the smallest index of one of them; 0xFFFFFFFF if there is none          */
+    float lo[3], hi[3];       /* box of the points, the cloud's axes                                     */
+    float centroid[3];
+    float mean_rgb[3];        /* 0 ... 255                                                               */
+    float cov[6];             /* xx, xy, xz, yy, yz, zz, square metres                                   */
+    float eigenvalue[3];      /* ascending                                                               */
+    float normal[3];          /* eigenvector of eigenvalue[0], turned towards the origin                 */
+    float axis[3];            /* eigenvector of eigenvalue[2], largest component non-negative            */
+    float plane_d;            /* normal . x + plane_d = 0 through the centroid                           */
+    float curvature;          /* eigenvalue[0] / (sum of the three), 0 if the sum is 0                   */
+    uint32_t reserved;        /* 0                                                                       */
+} f3ds_cloud_region;
+typedef struct f3ds_cloud_regions_result { uint32_t n_regions, n_nonempty; uint64_t n_labelled, n_clamped, n_inliers; } f3ds_cloud_regions_result;
+/* host arithmetic only, no device needed: the definition */
+int f3ds_cloud_regions_host(const void* points16, size_t n, const uint32_t* labels, uint32_t n_regions, const f3ds_cloud_params* params /* may be NULL */,
+                            f3ds_cloud_region* rows, f3ds_region_box* boxes /* may be NULL */, f3ds_cloud_regions_result* result /* may be NULL */);
+/* the same rows from the device (csrc/f3ds_cloud.inc).  inputs_on_device: points16 and labels are device memory and read where they are; host inputs go
+ * through the device's copy stream like those of f3ds_region_table.  points16 == NULL means the records the context's last segment call ran on, by the
+ * rule of f3ds_get_points: F3DS_ERR_LOGIC when the context does not own them (the caller's device buffer), F3DS_ERR_ARG if n differs from their count
+ * -- an rgbd frame, or a frame segmented from host points, is described without a second upload (labels are then host or device memory as
+ * inputs_on_device says).  These two come after the refusals above.  rows_on_device covers rows and boxes; host rows arrive with the call's one download.
+ * Synchronous.  Runs on ctx's stream and uses scratch of its own only: every other call on the context behaves as if this one never happened.  The box pass
+ * is recorded back to back with the first: the call waits once.  The points are walked in input order when n_regions <= 96 and in the order of
+ * (label, index) -- a radix sort first -- beyond; the bits are the same (F3DS_DBG_CLOUD_PATH tells which).  Also F3DS_ERR_ARG for a NULL ctx. */
+int f3ds_cloud_regions(f3ds_ctx* ctx, const void* points16, size_t n, const uint32_t* labels, uint32_t n_regions, const f3ds_cloud_params* params,
+                       int inputs_on_device, f3ds_cloud_region* rows, f3ds_region_box* boxes /* may be NULL */, int rows_on_device,
+                       f3ds_cloud_regions_result* result /* may be NULL */);
+/* nctx frames at once, by the rules of the batch forms of the region calls above (whole-call refusals, per-frame status, one dispatch per kernel with
+ * grid.y = frame, one download, one wait), with one difference: every frame has its own point count counts[i], and a frame with counts[i] == 0 is legal.
+ * Also refused as a whole: NULL points, counts, labels, n_regions or rows arrays.  points[i] may be NULL as in the lone call. */
+int f3ds_cloud_regions_batch(f3ds_ctx** ctxs, int nctx, const void* const* points, const size_t* counts, const uint32_t* const* labels,
+                             const uint32_t* n_regions, const f3ds_cloud_params* params, int inputs_on_device, f3ds_cloud_region* const* rows,
+                             f3ds_region_box* const* boxes /* NULL: none; else every entry non-NULL */, int rows_on_device,
+                             f3ds_cloud_regions_result* results, int* status);
+
 /* Clustering::cluster(threshold) again on the supervoxels of the last f3ds_segment call, with
  * possibly different metric / merging settings (src/clustering.cpp:670-679).  Only the merge
  * fields of `params` are read. */
@@ -686,6 +759,10 @@ enum {
                                      everything in global memory) and where it kept the per-edge arrays (2 = order keys + endpoints in
                                      LDS, 0 = in global memory).  Diagnostics (bench.py names the kernel it timed): results do not depend on it */
 };
+/* One more selector, outside the enum of the segment path's hooks because it describes a call of the region family and needs no frame: 1 u32, how the
+ * last f3ds_cloud_regions[_batch] call that ran kernels for this context walked its points -- 1 = direct (input order), 2 = ordered (sorted by label
+ * first), 0 = no such call yet.  Diagnostics and tests: the development switch F3DS_CLOUD_PATH=direct|ordered forces one, and the two give the same bits. */
+#define F3DS_DBG_CLOUD_PATH 25
 int f3ds_get_debug(f3ds_ctx* ctx, int what, void* dst, size_t cap_bytes, size_t* bytes_out);
 /* Diagnostics, host arithmetic only (no device needed): the LDS carve-up of the merge kernel d_merge_il_t<waves, keys_in_lds> for a frame with n_edges
  * adjacencies -- the same function the launch and the kernel use (csrc/f3ds_kernels.inc, merge_il_offsets).  out[0] = dynamic LDS bytes, out[1] = voxel rows the
