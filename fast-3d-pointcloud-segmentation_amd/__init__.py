@@ -993,6 +993,22 @@ def region_components_host(depth, labels, n_regions, fmt, depth_tol=0.05, min_pi
 
 
 # ---- device context ------------------------------------------------------------------------------
+def _lone(lib, answer, rows_out=None, count=None):
+    """What a lone region call answers, from its batch of one frame (the C entry points are that too): the frame's status raised as the lone call's return
+    code, else the frame's tuple.  count: the result field with the row count of a call whose rows the device counts."""
+    frames, status = answer
+    rc = int(status[0])
+    if rc == 0 and count and isinstance(rows_out, np.ndarray) and getattr(frames[0][-1], count) > len(rows_out):      # (an empty buffer is a NULL pointer: the call only counted)
+        rc = ERR_CAPACITY
+    _check(lib, rc)
+    return frames[0]
+
+
+def _one_second(out):
+    """the optional second output of a lone call (None / False, True, or a buffer) as its batch of one takes it"""
+    return out if out is None or out is True or out is False else [out]
+
+
 class Context(_Handle):
     """One (device, stream) pair with its grow-only scratch.  Not thread-safe; one per GPU/stream."""
 
@@ -1054,17 +1070,7 @@ class Context(_Handle):
         of labels_at_thresholds, ...), computed on the device in one read of the images; row i is region i, so its track id is ``Tracker.ids()[i]``.  depth,
         color, labels as in segment_rgbd / Tracker.update (color may be None: mean_rgb is then 0), or device pointers (ints, the pitches of ``fmt`` apply) with
         ``on_device=True``: ``rows_out`` is then a device pointer to n_regions rows and the rows returned are None.  Leaves the context's frame as it is."""
-        res = RegionTableResult()
-        if on_device:
-            _check(self.lib, self.lib.f3ds_region_table(self.handle, ctypes.byref(fmt), ctypes.c_void_p(int(depth)), ctypes.c_void_p(int(color)) if color is not None else None,
-                                                        ctypes.c_void_p(int(labels)), int(n_regions), 1, ctypes.c_void_p(int(rows_out)) if rows_out is not None else None, 1,
-                                                        ctypes.byref(res)))
-            return None, res
-        f, d, c, lab = _region_inputs(fmt, depth, labels, color)
-        rows = _region_rows(rows_out, n_regions)
-        _check(self.lib, self.lib.f3ds_region_table(self.handle, ctypes.byref(f), d.ctypes.data, None if c is None else c.ctypes.data, lab.ctypes.data, int(n_regions), 0,
-                                                    rows.ctypes.data if len(rows) else None, 0, ctypes.byref(res)))
-        return rows, res
+        return _lone(self.lib, region_table_batch([self], [depth], [labels], [n_regions], fmt, [color], [rows_out], on_device))
 
     def region_contacts(self, depth, labels, n_regions, fmt, depth_tol=0.05, rows_out=None, on_device=False):
         """f3ds_region_contacts: (rows, RegionContactsResult) -- what region_contacts_host returns, computed on the device; a and b index the rows of
@@ -1073,34 +1079,14 @@ class Context(_Handle):
         ``result.n_contacts`` says how many were written (CapacityError, and none written, when there are more than the capacity).  With host arrays
         ``rows_out`` may be a REGION_CONTACT_DTYPE array to fill (the rows returned are a view of it); without it a buffer that turns out too small is grown
         from the count and the call repeated: one device pass when it suffices.  Leaves the context's frame as it is."""
-        res = RegionContactsResult()
-        if on_device:
-            ptr, cap = (None, 0) if rows_out is None else (ctypes.c_void_p(int(rows_out[0])), int(rows_out[1]))
-            n_out = ctypes.c_size_t(0)
-            _check(self.lib, self.lib.f3ds_region_contacts(self.handle, ctypes.byref(fmt), ctypes.c_void_p(int(depth)), ctypes.c_void_p(int(labels)), int(n_regions),
-                                                           float(depth_tol), 1, ptr, cap, 1, ctypes.byref(n_out), ctypes.byref(res)))
-            return None, res
-        f, d, _, lab = _region_inputs(fmt, depth, labels, None)
-        rc, rows = _contact_rows(lambda ptr, cap, n_out: self.lib.f3ds_region_contacts(self.handle, ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions),
-                                                                                       float(depth_tol), 0, ptr, cap, 0, n_out, ctypes.byref(res)), rows_out)
-        _check(self.lib, rc)
-        return rows, res
+        return _lone(self.lib, region_contacts_batch([self], [depth], [labels], [n_regions], fmt, depth_tol, [rows_out], on_device), rows_out, "n_contacts")
 
     def region_shapes(self, depth, labels, n_regions, fmt, rows_out=None, on_device=False):
         """f3ds_region_shapes: (rows, RegionShapesResult) -- what region_shapes_host returns, computed on the device in one read of the depth image and the
         labels; row i is region i, the row i of region_table and ``Tracker.ids()[i]``.  depth and labels as in region_table, or device pointers (ints, the depth
         pitch of ``fmt`` applies) with ``on_device=True``: ``rows_out`` is then a device pointer to n_regions rows and the rows returned are None.  With host
         arrays ``rows_out`` may be a REGION_SHAPE_DTYPE array to fill.  Leaves the context's frame as it is."""
-        res = RegionShapesResult()
-        if on_device:
-            _check(self.lib, self.lib.f3ds_region_shapes(self.handle, ctypes.byref(fmt), ctypes.c_void_p(int(depth)), ctypes.c_void_p(int(labels)), int(n_regions), 1,
-                                                         ctypes.c_void_p(int(rows_out)) if rows_out is not None else None, 1, ctypes.byref(res)))
-            return None, res
-        f, d, _, lab = _region_inputs(fmt, depth, labels, None)
-        rows = _shape_rows(rows_out, n_regions)
-        _check(self.lib, self.lib.f3ds_region_shapes(self.handle, ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), 0,
-                                                     rows.ctypes.data if len(rows) else None, 0, ctypes.byref(res)))
-        return rows, res
+        return _lone(self.lib, region_shapes_batch([self], [depth], [labels], [n_regions], fmt, [rows_out], on_device))
 
     def region_boxes(self, depth, labels, n_regions, fmt, plane_tol=0.01, rows_out=None, shapes_out=None, on_device=False):
         """f3ds_region_boxes: (rows, RegionBoxesResult) -- what region_boxes_host returns, computed on the device in two reads of the depth image and the
@@ -1109,19 +1095,7 @@ class Context(_Handle):
         device pointers (ints, the depth pitch of ``fmt`` applies) with ``on_device=True``: ``rows_out`` and ``shapes_out`` are then device pointers to
         n_regions rows each (``shapes_out`` may be None) and the rows returned are None.  With host arrays ``rows_out`` may be a REGION_BOX_DTYPE array to
         fill.  Leaves the context's frame as it is."""
-        res = RegionBoxesResult()
-        if on_device:
-            _check(self.lib, self.lib.f3ds_region_boxes(self.handle, ctypes.byref(fmt), ctypes.c_void_p(int(depth)), ctypes.c_void_p(int(labels)), int(n_regions), float(plane_tol),
-                                                        1, ctypes.c_void_p(int(rows_out)) if rows_out is not None else None,
-                                                        ctypes.c_void_p(int(shapes_out)) if shapes_out is not None else None, 1, ctypes.byref(res)))
-            return (None, res) if shapes_out is None else (None, None, res)
-        f, d, _, lab = _region_inputs(fmt, depth, labels, None)
-        rows = _box_rows(rows_out, n_regions)
-        want = shapes_out is not None and shapes_out is not False
-        shapes = _shape_rows(None if shapes_out is True else shapes_out, n_regions) if want else None
-        _check(self.lib, self.lib.f3ds_region_boxes(self.handle, ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), float(plane_tol), 0,
-                                                    rows.ctypes.data if len(rows) else None, shapes.ctypes.data if want and len(shapes) else None, 0, ctypes.byref(res)))
-        return (rows, shapes, res) if want else (rows, res)
+        return _lone(self.lib, region_boxes_batch([self], [depth], [labels], [n_regions], fmt, plane_tol, [rows_out], _one_second(shapes_out), on_device))
 
     def cloud_regions(self, points, labels, n_regions, params=None, rows_out=None, boxes_out=None, n=None, on_device=False):
         """f3ds_cloud_regions: (rows, CloudRegionsResult) -- what cloud_regions_host returns, computed on the device with one wait.  points: (n, 4) float32
@@ -1129,22 +1103,9 @@ class Context(_Handle):
         boxes come too and the answer is (rows, boxes, CloudRegionsResult): ``True`` for a new REGION_BOX_DTYPE array, or such an array to fill.  With
         ``on_device=True`` points (or None) and labels are device pointers (ints or torch tensors), ``n`` the point count, ``rows_out`` and ``boxes_out`` device
         pointers to n_regions rows each (``boxes_out`` may be None) and the rows returned are None.  Leaves the context's frame as it is."""
-        res = CloudRegionsResult()
-        prm = ctypes.byref(params) if params is not None else None
-        if on_device:
-            if n is None:
-                raise ValueError("on_device needs the point count n")
-            _check(self.lib, self.lib.f3ds_cloud_regions(self.handle, _opt_ptr(points), int(n), _device_ptr(labels), int(n_regions), prm, 1, _opt_ptr(rows_out), _opt_ptr(boxes_out), 1,
-                                                         ctypes.byref(res)))
-            return (None, res) if boxes_out is None else (None, None, res)
-        pts, lab = _cloud_inputs(points, labels)
-        rows = _cloud_rows(rows_out, n_regions)
-        want = boxes_out is not None and boxes_out is not False
-        boxes = _box_rows(None if boxes_out is True else boxes_out, n_regions) if want else None
-        keep = np.zeros(4, np.float32)      # (an empty cloud still has an address)
-        _check(self.lib, self.lib.f3ds_cloud_regions(self.handle, None if pts is None else (_ptr(pts) or keep.ctypes.data), len(lab), _ptr(lab) or keep.ctypes.data, int(n_regions), prm, 0,
-                                                     _ptr(rows), (_ptr(boxes) or keep.ctypes.data) if want else None, 0, ctypes.byref(res)))
-        return (rows, boxes, res) if want else (rows, res)
+        if on_device and n is None:
+            raise ValueError("on_device needs the point count n")
+        return _lone(self.lib, cloud_regions_batch([self], [points], [labels], [n_regions], params, [rows_out], _one_second(boxes_out), None if n is None else [n], on_device))
 
     def cloud_path(self):
         """F3DS_DBG_CLOUD_PATH: how the context's last cloud_regions call walked its points -- "direct", "ordered", or None before any."""
@@ -1160,22 +1121,7 @@ class Context(_Handle):
         rows or None, the rows returned are None and ``result.n_joints`` says how many were written (CapacityError, and none written, when there are more than
         the capacity).  With host arrays ``rows_out`` may be a REGION_JOINT_DTYPE array to fill; without it a buffer that turns out too small is grown from the
         count and the call repeated.  Leaves the context's frame as it is."""
-        res = RegionJointsResult()
-        pp = ctypes.byref(params) if params is not None else None
-        if on_device:
-            ptr, cap = (None, 0) if rows_out is None else (ctypes.c_void_p(int(rows_out[0])), int(rows_out[1]))
-            n_out = ctypes.c_size_t(0)
-            _check(self.lib, self.lib.f3ds_region_joints(self.handle, ctypes.byref(fmt), ctypes.c_void_p(int(depth)), ctypes.c_void_p(int(labels)), int(n_regions), pp, 1, ptr, cap,
-                                                         ctypes.c_void_p(int(shapes_out)) if shapes_out is not None else None, 1, ctypes.byref(n_out), ctypes.byref(res)))
-            return (None, res) if shapes_out is None else (None, None, res)
-        f, d, _, lab = _region_inputs(fmt, depth, labels, None)
-        want = shapes_out is not None and shapes_out is not False
-        shapes = _shape_rows(None if shapes_out is True else shapes_out, n_regions) if want else None
-        sp = shapes.ctypes.data if want and len(shapes) else None
-        rc, rows = _contact_rows(lambda ptr, cap, n_out: self.lib.f3ds_region_joints(self.handle, ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions), pp, 0, ptr, cap,
-                                                                                     sp, 0, n_out, ctypes.byref(res)), rows_out, REGION_JOINT_DTYPE)
-        _check(self.lib, rc)
-        return (rows, shapes, res) if want else (rows, res)
+        return _lone(self.lib, region_joints_batch([self], [depth], [labels], [n_regions], fmt, params, [rows_out], _one_second(shapes_out), on_device), rows_out, "n_joints")
 
     def region_components(self, depth, labels, n_regions, fmt, depth_tol=0.05, min_pixels=1, rows_out=None, comp_out=None, on_device=False):
         """f3ds_region_components: (comp_labels, rows, RegionComponentsResult) -- what region_components_host returns, computed on the device.  The image is a
@@ -1185,21 +1131,8 @@ class Context(_Handle):
         ``result.n_components`` says how many rows were written (CapacityError, and none written, when there are more than the capacity).  With host arrays
         ``rows_out`` may be a REGION_COMPONENT_DTYPE array to fill; without it a buffer that turns out too small is grown from the count and the call
         repeated: one device pass when it suffices.  Leaves the context's frame as it is."""
-        prm, res = ComponentParams(float(depth_tol), int(min_pixels)), RegionComponentsResult()
-        if on_device:
-            ptr, cap = (None, 0) if rows_out is None else (ctypes.c_void_p(int(rows_out[0])), int(rows_out[1]))
-            n_out = ctypes.c_size_t(0)
-            _check(self.lib, self.lib.f3ds_region_components(self.handle, ctypes.byref(fmt), ctypes.c_void_p(int(depth)), ctypes.c_void_p(int(labels)), int(n_regions),
-                                                             ctypes.byref(prm), 1, ctypes.c_void_p(int(comp_out)) if comp_out is not None else None, ptr, cap, 1,
-                                                             ctypes.byref(n_out), ctypes.byref(res)))
-            return None, None, res
-        f, d, _, lab = _region_inputs(fmt, depth, labels, None)
-        comp = np.empty((int(fmt.height), int(fmt.width)), np.uint32)
-        rc, rows = _contact_rows(lambda ptr, cap, n_out: self.lib.f3ds_region_components(self.handle, ctypes.byref(f), d.ctypes.data, lab.ctypes.data, int(n_regions),
-                                                                                         ctypes.byref(prm), 0, comp.ctypes.data, ptr, cap, 0, n_out, ctypes.byref(res)),
-                                 rows_out, REGION_COMPONENT_DTYPE)
-        _check(self.lib, rc)
-        return comp, rows, res
+        return _lone(self.lib, region_components_batch([self], [depth], [labels], [n_regions], fmt, depth_tol, min_pixels, [rows_out], [comp_out], on_device), rows_out,
+                     "n_components")
 
     def points(self):
         """f3ds_get_points: the (N, 4) float32 records the last segment call ran on, when the context holds them (segment_rgbd, or segment
@@ -1698,6 +1631,25 @@ def _batch_done(lib, rc, status):
     return status
 
 
+def _second_out(out, k, name, what, on_device, make_rows, nr, spare=None):
+    """The optional second output of a batch call (the shape rows of the boxes and the joints, the boxes of the cloud rows).  ``out``: None / False, ``True``
+    (host form: new arrays) or a list of buffers, for every frame or for none.  Returns (wanted?, the k arrays -- None without, or on the device --, the pointer
+    array or None); the pointer of an array without rows is ``spare``'s, or NULL."""
+    if out is None or out is False:
+        return False, [None] * k, None
+    outs = [None] * k if out is True else _outs(out, k, name)
+    if out is not True and any(o is None for o in outs):
+        raise ValueError("%s: a buffer for every frame or None (one command sequence for the batch)" % name)
+    vp = ctypes.c_void_p
+    if on_device:
+        if out is True:
+            raise ValueError("on_device needs device buffers for " + what)
+        return True, [None] * k, (vp * k)(*[_opt_ptr(o) for o in outs])
+    arrays = [make_rows(o, nr[i]) for i, o in enumerate(outs)]
+    empty = None if spare is None else vp(spare.ctypes.data)
+    return True, arrays, (vp * k)(*[vp(a.ctypes.data) if len(a) else empty for a in arrays])
+
+
 def _fixed_rows_batch(fn, make_rows, res_type, ctxs, depths, labels, n_regions, fmt, colors, rows_out, on_device, lead=(), with_color=False):
     """the batch calls with one row per region (table, shapes): fn(handles, k, fmt, depth[, color], labels, n_regions, *lead, on_device, rows, on_device, results, status)"""
     lib = load_library()
@@ -1737,21 +1689,13 @@ def region_boxes_batch(ctxs, depths, labels, n_regions, fmt, plane_tol=0.01, row
     k, handles, f, dp, _, lp, nr, status, keep = _region_batch_inputs(ctxs, depths, labels, n_regions, fmt, None, on_device)
     vp = ctypes.c_void_p
     outs, results = _outs(rows_out, k, "rows_out"), (RegionBoxesResult * k)()
-    want = shapes_out is not None and shapes_out is not False
-    souts = [None] * k if (shapes_out is True or not want) else _outs(shapes_out, k, "shapes_out")
-    if want and shapes_out is not True and any(s is None for s in souts):
-        raise ValueError("shapes_out: a buffer for every frame or None (one command sequence for the batch)")
+    want, shapes, sp = _second_out(shapes_out, k, "shapes_out", "the shape rows", on_device, _shape_rows, nr)
     if on_device:
-        if shapes_out is True:
-            raise ValueError("on_device needs device buffers for the shape rows")
-        rows, shapes = [None] * k, [None] * k
+        rows = [None] * k
         rp = (vp * k)(*[_opt_ptr(o) for o in outs])
-        sp = (vp * k)(*[_opt_ptr(o) for o in souts]) if want else None
     else:
         rows = [_box_rows(o, nr[i]) for i, o in enumerate(outs)]
-        shapes = [_shape_rows(o, nr[i]) for i, o in enumerate(souts)] if want else [None] * k
         rp = (vp * k)(*[vp(r.ctypes.data) if len(r) else None for r in rows])
-        sp = (vp * k)(*[vp(s.ctypes.data) if len(s) else None for s in shapes]) if want else None
     where = 1 if on_device else 0
     rc = lib.f3ds_region_boxes_batch(handles, k, ctypes.byref(f), dp, lp, nr, float(plane_tol), where, rp, sp, where, results, status.ctypes.data)
     _batch_done(lib, rc, status)
@@ -1778,28 +1722,22 @@ def cloud_regions_batch(ctxs, points, labels, n_regions, params=None, rows_out=N
     nr = (ctypes.c_uint32 * k)(*[int(x) for x in n_regions])
     status = np.full(k, _STATUS_UNSET, np.int32)
     outs, results = _outs(rows_out, k, "rows_out"), (CloudRegionsResult * k)()
-    want = boxes_out is not None and boxes_out is not False
-    bouts = [None] * k if (boxes_out is True or not want) else _outs(boxes_out, k, "boxes_out")
-    if want and boxes_out is not True and any(b is None for b in bouts):
-        raise ValueError("boxes_out: a buffer for every frame or None (one command sequence for the batch)")
     spare = np.zeros(24, np.float32)      # (an empty cloud, and the boxes of a frame without regions, still have an address)
+    want, boxes, bp = _second_out(boxes_out, k, "boxes_out", "the boxes", on_device, _box_rows, nr, spare)
     if on_device:
-        if boxes_out is True or counts is None or len(counts) != k:
-            raise ValueError("on_device needs the point counts, and device buffers for the boxes")
+        if counts is None or len(counts) != k:
+            raise ValueError("on_device needs the point counts")
         keep, cnt = None, (ctypes.c_size_t * k)(*[int(x) for x in counts])
         pp = (vp * k)(*[_opt_ptr(x) for x in points]); lp = (vp * k)(*[_device_ptr(x) for x in labels])
-        rows, boxes = [None] * k, [None] * k
+        rows = [None] * k
         rp = (vp * k)(*[_opt_ptr(o) for o in outs])
-        bp = (vp * k)(*[_opt_ptr(o) for o in bouts]) if want else None
     else:
         keep = [_cloud_inputs(p, lab) for p, lab in zip(points, labels)]
         cnt = (ctypes.c_size_t * k)(*[len(x[1]) for x in keep])
         pp = (vp * k)(*[None if x[0] is None else vp(_ptr(x[0]) or spare.ctypes.data) for x in keep])
         lp = (vp * k)(*[vp(_ptr(x[1]) or spare.ctypes.data) for x in keep])
         rows = [_cloud_rows(o, nr[i]) for i, o in enumerate(outs)]
-        boxes = [_box_rows(o, nr[i]) for i, o in enumerate(bouts)] if want else [None] * k
         rp = (vp * k)(*[vp(r.ctypes.data) if len(r) else None for r in rows])
-        bp = (vp * k)(*[vp(_ptr(x) or spare.ctypes.data) for x in boxes]) if want else None
     where = 1 if on_device else 0
     rc = lib.f3ds_cloud_regions_batch(handles, k, pp, cnt, lp, nr, ctypes.byref(params) if params is not None else None, where, rp, bp, where, results, status.ctypes.data)
     _batch_done(lib, rc, status)
@@ -1807,6 +1745,27 @@ def cloud_regions_batch(ctxs, points, labels, n_regions, params=None, rows_out=N
     if want:
         return [(rows[i] if ok[i] else None, boxes[i] if ok[i] else None, results[i] if ok[i] else None) for i in range(k)], status
     return [(rows[i] if ok[i] else None, results[i] if ok[i] else None) for i in range(k)], status
+
+
+def _capped_call(fn, results, status, batch, param, on_device, before=(), after=()):
+    """call(rows pointer array or None, caps, n_out, frames[, status]) -> rc of a batch function whose row counts the device decides: it runs the listed frames
+    of ``batch`` = (handles, format, depth pointers, label pointers, region counts) through fn(handles, m, format, depths, labels, n_regions, param, on_device,
+    *before, rows, caps, *after, on_device, n_out, results, status) and keeps the results of the frames it reached.  before / after: per-frame pointer arrays
+    (or None) of the whole batch."""
+    handles, f, dp, lp, nr = batch
+    where = 1 if on_device else 0
+
+    def call(rp, caps, n_out, frames, st=status):
+        m = len(frames)
+        pick = lambda arr, ty=ctypes.c_void_p: None if arr is None else (ty * m)(*[arr[i] for i in frames])
+        sub_res = (results._type_ * m)()
+        rc = fn(pick(handles), m, ctypes.byref(f), pick(dp), pick(lp), pick(nr, ctypes.c_uint32), param, where, *[pick(a) for a in before], rp, caps, *[pick(a) for a in after],
+                where, n_out, sub_res, st.ctypes.data)
+        for j, i in enumerate(frames):
+            if st[j] != _STATUS_UNSET:
+                results[i] = sub_res[j]
+        return rc
+    return call
 
 
 def _capped_rows_batch(call, k, rows_out, on_device, dtype):
@@ -1857,21 +1816,8 @@ def region_contacts_batch(ctxs, depths, labels, n_regions, fmt, depth_tol=0.05, 
     ``on_device`` of ``(device pointer, capacity in rows)`` / None).  Returns ([(rows, RegionContactsResult)], status)."""
     lib = load_library()
     k, handles, f, dp, _, lp, nr, status, keep = _region_batch_inputs(ctxs, depths, labels, n_regions, fmt, None, on_device)
-    vp = ctypes.c_void_p
     results = (RegionContactsResult * k)()
-    where = 1 if on_device else 0
-
-    def call(rp, caps, n_out, frames, st=status):
-        m = len(frames)
-        pick = lambda arr, ty: (ty * m)(*[arr[i] for i in frames])
-        sub_res = (RegionContactsResult * m)()
-        rc = lib.f3ds_region_contacts_batch(pick(handles, vp), m, ctypes.byref(f), pick(dp, vp), pick(lp, vp), pick(nr, ctypes.c_uint32), float(depth_tol), where, rp, caps, where,
-                                            n_out, sub_res, st.ctypes.data)
-        for j, i in enumerate(frames):
-            if st[j] != _STATUS_UNSET:
-                results[i] = sub_res[j]
-        return rc
-
+    call = _capped_call(lib.f3ds_region_contacts_batch, results, status, (handles, f, dp, lp, nr), float(depth_tol), on_device)
     rc, bufs, n_out = _capped_rows_batch(call, k, rows_out, on_device, REGION_CONTACT_DTYPE)
     rows = _capped_deliver(lib, call, rc, status, bufs, n_out, rows_out, REGION_CONTACT_DTYPE, on_device)
     return [(rows[i], results[i] if status[i] != ERR_ARG else None) for i in range(k)], status
@@ -1883,34 +1829,9 @@ def region_joints_batch(ctxs, depths, labels, n_regions, fmt, params=None, rows_
     with shapes."""
     lib = load_library()
     k, handles, f, dp, _, lp, nr, status, keep = _region_batch_inputs(ctxs, depths, labels, n_regions, fmt, None, on_device)
-    vp = ctypes.c_void_p
     results = (RegionJointsResult * k)()
-    where = 1 if on_device else 0
-    pp = ctypes.byref(params) if params is not None else None
-    want = shapes_out is not None and shapes_out is not False
-    souts = [None] * k if (shapes_out is True or not want) else _outs(shapes_out, k, "shapes_out")
-    if want and shapes_out is not True and any(s is None for s in souts):
-        raise ValueError("shapes_out: a buffer for every frame or None (one command sequence for the batch)")
-    if on_device:
-        if shapes_out is True:
-            raise ValueError("on_device needs device buffers for the shape rows")
-        shapes = [None] * k
-        sp = (vp * k)(*[_opt_ptr(o) for o in souts]) if want else None
-    else:
-        shapes = [_shape_rows(o, nr[i]) for i, o in enumerate(souts)] if want else [None] * k
-        sp = (vp * k)(*[vp(s.ctypes.data) if len(s) else None for s in shapes]) if want else None
-
-    def call(rp, caps, n_out, frames, st=status):
-        m = len(frames)
-        pick = lambda arr, ty: (ty * m)(*[arr[i] for i in frames])
-        sub_res = (RegionJointsResult * m)()
-        rc = lib.f3ds_region_joints_batch(pick(handles, vp), m, ctypes.byref(f), pick(dp, vp), pick(lp, vp), pick(nr, ctypes.c_uint32), pp, where, rp, caps,
-                                          pick(sp, vp) if want else None, where, n_out, sub_res, st.ctypes.data)
-        for j, i in enumerate(frames):
-            if st[j] != _STATUS_UNSET:
-                results[i] = sub_res[j]
-        return rc
-
+    want, shapes, sp = _second_out(shapes_out, k, "shapes_out", "the shape rows", on_device, _shape_rows, nr)
+    call = _capped_call(lib.f3ds_region_joints_batch, results, status, (handles, f, dp, lp, nr), ctypes.byref(params) if params is not None else None, on_device, after=(sp,))
     rc, bufs, n_out = _capped_rows_batch(call, k, rows_out, on_device, REGION_JOINT_DTYPE)
     rows = _capped_deliver(lib, call, rc, status, bufs, n_out, rows_out, REGION_JOINT_DTYPE, on_device)
     ok = [status[i] != ERR_ARG for i in range(k)]
@@ -1926,7 +1847,6 @@ def region_components_batch(ctxs, depths, labels, n_regions, fmt, depth_tol=0.05
     k, handles, f, dp, _, lp, nr, status, keep = _region_batch_inputs(ctxs, depths, labels, n_regions, fmt, None, on_device)
     vp = ctypes.c_void_p
     prm, results = ComponentParams(float(depth_tol), int(min_pixels)), (RegionComponentsResult * k)()
-    where = 1 if on_device else 0
     if on_device:
         if comp_out is None or len(comp_out) != k:
             raise ValueError("on_device needs one device image per context in comp_out")
@@ -1935,18 +1855,7 @@ def region_components_batch(ctxs, depths, labels, n_regions, fmt, depth_tol=0.05
     else:
         comps = [np.empty((int(fmt.height), int(fmt.width)), np.uint32) for _ in range(k)]
         kp = (vp * k)(*[vp(c.ctypes.data) for c in comps])
-
-    def call(rp, caps, n_out, frames, st=status):
-        m = len(frames)
-        pick = lambda arr, ty: (ty * m)(*[arr[i] for i in frames])
-        sub_res = (RegionComponentsResult * m)()
-        rc = lib.f3ds_region_components_batch(pick(handles, vp), m, ctypes.byref(f), pick(dp, vp), pick(lp, vp), pick(nr, ctypes.c_uint32), ctypes.byref(prm), where, pick(kp, vp),
-                                              rp, caps, where, n_out, sub_res, st.ctypes.data)
-        for j, i in enumerate(frames):
-            if st[j] != _STATUS_UNSET:
-                results[i] = sub_res[j]
-        return rc
-
+    call = _capped_call(lib.f3ds_region_components_batch, results, status, (handles, f, dp, lp, nr), ctypes.byref(prm), on_device, before=(kp,))
     rc, bufs, n_out = _capped_rows_batch(call, k, rows_out, on_device, REGION_COMPONENT_DTYPE)
     rows = _capped_deliver(lib, call, rc, status, bufs, n_out, rows_out, REGION_COMPONENT_DTYPE, on_device)
     return [(comps[i] if status[i] != ERR_ARG else None, rows[i], results[i] if status[i] != ERR_ARG else None) for i in range(k)], status

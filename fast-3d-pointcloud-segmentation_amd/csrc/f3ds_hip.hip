@@ -65,6 +65,7 @@ using namespace f3ds;
 #include "f3ds_eval_levels.inc"
 #include "f3ds_track.inc"
 #include "f3ds_regions.inc"
+#include "f3ds_pairs.inc"
 #include "f3ds_contacts.inc"
 #include "f3ds_shapes.inc"
 #include "f3ds_boxes.inc"
@@ -1159,6 +1160,33 @@ int li_rows_behind(const LiStage& s, Batch& b, int nctx, size_t row_bytes, const
     if (more) HIPCHECK(timed_sync(b.st));
     for (int i = 0; i < nctx; ++i) if (count[i]) memcpy(rows[i], s.o->h_li + s.slot[(size_t)i].rows_at, count[i] * row_bytes);
     return F3DS_OK;
+}
+// Where the kernels write an output of frame i that has a fixed size: the caller's device array, or `off` bytes into the frame's slot of the staging
+template <class T>
+T* li_out_ptr(int on_device, T* caller, const LiStage& s, int i, size_t off = 0u) { return on_device ? caller : reinterpret_cast<T*>(s.out + s.slot[(size_t)i].at + off); }
+// the end of a batch form: the frames' statuses to the caller, the lowest failing frame's as the call's
+int li_statuses(const std::vector<int>& st, int* status) {
+    int ret = F3DS_OK;
+    for (size_t i = 0; i < st.size(); ++i) { if (status) status[i] = st[i]; if (st[i] && !ret) ret = st[i]; }
+    return ret;
+}
+// The end of a call whose rows have a fixed size (one per region): the flush, the ONE download, and per frame its status -- F3DS_ERR_ARG where a label was
+// >= n_regions: no finish kernel wrote a row --, its payloads out of the staging (bytes0[i] bytes at the start of the slot into out0[i], bytes1[i] behind
+// them into out1[i]; 0 bytes: a device caller, or no such output; bytes1 may be NULL) and its result fields, fill(i, head).
+template <class R0, class R1, class Fill>
+int li_deliver_fixed(const LiStage& s, Batch& b, int nctx, const size_t* bytes0, R0* const* out0, const size_t* bytes1, R1* const* out1, int* status, const Fill& fill) {
+    if (const int rc = flush(b)) return rc;
+    if (const int rc = li_download_heads(s, b)) return rc;
+    std::vector<int> st((size_t)nctx, F3DS_OK);
+    for (int i = 0; i < nctx; ++i) {
+        const uint32_t* h = s.h_head(i);
+        if (h[1]) { st[i] = F3DS_ERR_ARG; continue; }
+        const unsigned char* src = s.o->h_li + s.slot[(size_t)i].at;
+        if (bytes0[i]) memcpy(out0[i], src, bytes0[i]);
+        if (bytes1 && bytes1[i]) memcpy(out1[i], src + bytes0[i], bytes1[i]);
+        fill(i, h);
+    }
+    return li_statuses(st, status);
 }
 // Start of every accessor: ARG for no context, LOGIC for a context that does not hold what the call needs -- both before any HIP call --, then the
 // context's device and everything queued on its stream.
@@ -2636,12 +2664,6 @@ extern "C" int f3ds_tracker_update(f3ds_tracker* t, const f3ds_rgbd_format* fmt_
 namespace {
 // what every batch form refuses first: no contexts, a NULL or repeated one, contexts on different devices
 inline bool li_batch_ctxs(f3ds_ctx* const* ctxs, int nctx) { return ctxs && nctx >= 1 && distinct_contexts_on_one_device(ctxs, nctx); }
-// the end of a batch form: the frames' statuses to the caller, the lowest failing frame's as the call's
-int li_statuses(const std::vector<int>& st, int* status) {
-    int ret = F3DS_OK;
-    for (size_t i = 0; i < st.size(); ++i) { if (status) status[i] = st[i]; if (st[i] && !ret) ret = st[i]; }
-    return ret;
-}
 
 // region table (f3ds_regions.h / .inc): one row per region of a label image over an RGB-D frame.  Three kernels -- d_region_init,
 // d_region_accum (the one read of the images), d_region_finish; behind the heads the rows of a host caller (72 B per region).
@@ -2677,23 +2699,12 @@ extern "C" int f3ds_region_table_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgb
     LiStage s; std::vector<LiImages> im((size_t)nctx);
     if (const int rc = li_out_buffers(ctxs[0], nctx, fixed.data(), nullptr, 0u, 0u, &s)) return rc;
     if (const int rc = li_upload(ctxs, nctx, b, lay, depth, color, labels, inputs_on_device, im.data())) return rc;
-    for (int i = 0; i < nctx; ++i) {
-        f3ds_region_row* d_rows = rows_on_device ? rows[i] : reinterpret_cast<f3ds_region_row*>(s.out + s.slot[i].at);
-        if (const int rc = rg_record(ctxs[i], fmt, lay, im[i], n_regions[i], s.head(i), d_rows)) return rc;
-    }
-    if (const int rc = flush(b)) return rc;
-    if (const int rc = li_download_heads(s, b)) return rc;
-    std::vector<int> st((size_t)nctx, F3DS_OK);
-    for (int i = 0; i < nctx; ++i) {
-        const uint32_t* h = s.h_head(i);
-        if (h[1]) { st[i] = F3DS_ERR_ARG; continue; }      // (a label >= n_regions: d_region_finish wrote no row)
-        if (fixed[i]) memcpy(rows[i], s.o->h_li + s.slot[i].at, fixed[i]);
-        if (results) {
-            results[i].n_regions = n_regions[i]; results[i].n_nonempty = h[0];
-            memcpy(&results[i].n_labelled, h + 2, 8); memcpy(&results[i].n_clamped, h + 4, 8);
-        }
-    }
-    return li_statuses(st, status);
+    for (int i = 0; i < nctx; ++i) if (const int rc = rg_record(ctxs[i], fmt, lay, im[i], n_regions[i], s.head(i), li_out_ptr(rows_on_device, rows[i], s, i))) return rc;
+    return li_deliver_fixed(s, b, nctx, fixed.data(), rows, nullptr, static_cast<void* const*>(nullptr), status, [&](int i, const uint32_t* h) {
+        if (!results) return;
+        results[i].n_regions = n_regions[i]; results[i].n_nonempty = h[0];
+        memcpy(&results[i].n_labelled, h + 2, 8); memcpy(&results[i].n_clamped, h + 4, 8);
+    });
 }
 extern "C" int f3ds_region_table(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const void* color, const uint32_t* labels, uint32_t n_regions, int inputs_on_device,
                                  f3ds_region_row* rows, int rows_on_device, f3ds_region_table_result* result) {
@@ -2701,43 +2712,61 @@ extern "C" int f3ds_region_table(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, cons
 }
 
 // ------------------------------------------------------------------------------------------------
-// region contacts (f3ds_contacts.h / .inc): one row per pair of regions of a label image that touch.  d_contact_init, d_contact_accum
+// region contacts (f3ds_contacts.h / .inc): one row per pair of regions of a label image that touch.  d_pair_init, d_contact_accum
 // (the one pass over the images: records of (pair, seven words)), the radix sort of the record keys, d_evl_heads / scan, d_track_runs, d_contact_finish; behind
 // the head (row count, the bad-label flag, the records asked for, the sums) the first RGC_FIRST_ROWS rows of a host caller.  A frame with more records than the
 // first buffer holds says so in the head and runs once more, alone, with room for all (every contact pair a record of its own: fewer than 2n) once the others
 // have been delivered; a host caller with more rows gets the rest in a second download.  The frames of a batch share the record room (one n) and the sort
 // width, the largest any frame needs (zero key bits above a frame's own sort to nothing).  Beside rgc_* the call uses the sort's histogram and the scan's
-// tile sums, which hold nothing between calls.
+// tile sums, which hold nothing between calls.  All of this is the pair call's (pair_record, pair_run), which the joints share: a call is its scratch, its two
+// kernels, its row and its result.
 // ------------------------------------------------------------------------------------------------
 namespace {
-int ct_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, const LiImages& im, uint32_t K, float depth_tol, uint32_t rec_cap, int sort_bits, uint32_t* head,
-              f3ds_region_contact* d_rows, size_t cap) {
-    const uint32_t n = (uint32_t)lay.n;
-    uint64_t *k0, *k1, *ukey; uint32_t *v0, *v1, *rec_words, *flag, *ustart, *uend, *cnt, *hist, *tiles;
-    ENSURE(c->rgc_k0, rec_cap, k0); ENSURE(c->rgc_k1, rec_cap, k1); ENSURE(c->rgc_v0, rec_cap, v0); ENSURE(c->rgc_v1, rec_cap, v1);
-    ENSURE(c->rgc_rec, (size_t)rec_cap * CT_WORDS, rec_words); ENSURE(c->rgc_flag, rec_cap, flag); ENSURE(c->rgc_ukey, rec_cap, ukey);
-    ENSURE(c->rgc_ustart, rec_cap, ustart); ENSURE(c->rgc_uend, rec_cap, uend); ENSURE(c->rgc_cnt, 4, cnt);
-    ENSURE(c->hist, (size_t)RS_BINS * ((rec_cap + RS_TILE - 1) / RS_TILE + 1), hist); ENSURE(c->tiles, (rec_cap + SCAN_TILE - 1) / SCAN_TILE + 1, tiles);
-    ContactArgs a;
+// The scratch of a pair call (the contacts over rgc_*, the joints over rgj_*): the records' keys and indices (twice: the sort), the records, the runs' flags,
+// keys, starts and ends, the run count.
+struct PairScratch {
+    Scratch<uint64_t>&k0, &k1; Scratch<uint32_t>&v0, &v1, &rec, &flag; Scratch<uint64_t>& ukey; Scratch<uint32_t>&ustart, &uend, &cnt;
+};
+inline PairScratch rgc_scratch(f3ds_ctx* c) { return {c->rgc_k0, c->rgc_k1, c->rgc_v0, c->rgc_v1, c->rgc_rec, c->rgc_flag, c->rgc_ukey, c->rgc_ustart, c->rgc_uend, c->rgc_cnt}; }
+inline PairScratch rgj_scratch(f3ds_ctx* c) { return {c->rgj_k0, c->rgj_k1, c->rgj_v0, c->rgj_v1, c->rgj_rec, c->rgj_flag, c->rgj_ukey, c->rgj_ustart, c->rgj_uend, c->rgj_cnt}; }
+PairArgs pair_args(const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, uint32_t K, float depth_tol, uint32_t rec_cap) {
+    PairArgs a;
     memset(&a, 0, sizeof a);
-    a.width = fmt.width; a.height = fmt.height; a.n = n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
-    a.K = K; a.kb = ct_bits(K); a.depth_scale = fmt.depth_scale; a.depth_tol = depth_tol; a.rec_cap = rec_cap;
-    const uint64_t hole = ct_hole(K, a.kb);
+    a.width = fmt.width; a.height = fmt.height; a.n = (uint32_t)lay.n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
+    a.K = K; a.kb = ct_bits(K); a.rec_cap = rec_cap; a.depth_scale = fmt.depth_scale; a.depth_tol = depth_tol; a.fx = fmt.fx; a.fy = fmt.fy; a.cx = fmt.cx; a.cy = fmt.cy;
+    return a;
+}
+// One frame of a pair call: its scratch, d_pair_init, accum(keys, records) -- the call's own pass over the images --, the runs of equal keys (the radix sort of
+// the record keys with the record index as value, d_evl_heads, the scan, d_track_runs), finish(run keys, starts, ends, run count, sorted indices, records) -- the
+// call's own kernel that writes the rows.  Everything is ensured before the first of these kernels is recorded.
+template <class Accum, class Finish>
+int pair_record(f3ds_ctx* c, const PairScratch& s, size_t words, const PairArgs& a, int sort_bits, uint32_t* head, const Accum& accum, const Finish& finish) {
+    const uint32_t rec_cap = a.rec_cap;
+    uint64_t *k0, *k1, *ukey; uint32_t *v0, *v1, *rec_words, *flag, *ustart, *uend, *cnt, *hist, *tiles;
+    ENSURE(s.k0, rec_cap, k0); ENSURE(s.k1, rec_cap, k1); ENSURE(s.v0, rec_cap, v0); ENSURE(s.v1, rec_cap, v1);
+    ENSURE(s.rec, (size_t)rec_cap * words, rec_words); ENSURE(s.flag, rec_cap, flag); ENSURE(s.ukey, rec_cap, ukey);
+    ENSURE(s.ustart, rec_cap, ustart); ENSURE(s.uend, rec_cap, uend); ENSURE(s.cnt, 4, cnt);
+    ENSURE(c->hist, (size_t)RS_BINS * ((rec_cap + RS_TILE - 1) / RS_TILE + 1), hist); ENSURE(c->tiles, (rec_cap + SCAN_TILE - 1) / SCAN_TILE + 1, tiles);
+    const uint64_t hole = ct_hole(a.K, a.kb);
     int rc;
-    rec<d_contact_init>(c, grid_for(rec_cap, 256), 0u, k0, v0, rec_cap, head);
-    rec<d_contact_accum>(c, grid_for((n + RGC_TRIPS - 1u) / RGC_TRIPS, 256), 0u, im.depth, im.labels, a, k0, rec_words, head);
+    rec<d_pair_init>(c, grid_for(rec_cap, 256), 0u, k0, v0, rec_cap, head);
+    accum(k0, rec_words);
     uint64_t* ks; uint32_t* vs;
     if ((rc = radix_sort(c, k0, v0, k1, v1, rec_cap, sort_bits, &ks, &vs))) return rc;
     rec<d_evl_heads>(c, grid_for(rec_cap, 256), 0u, ks, rec_cap, hole, flag);
     if ((rc = scan_u32(c, flag, flag, rec_cap))) return rc;
     rec<d_track_runs>(c, grid_for(rec_cap, 256), 0u, ks, rec_cap, hole, flag, ukey, ustart, uend, cnt);
-    rec<d_contact_finish>(c, grid_for((size_t)(rec_cap < 8192u ? rec_cap : 8192u) * 64u, 256), 0u, ukey, ustart, uend, cnt, vs, rec_words, a.kb, rec_cap, head, d_rows, (uint64_t)cap);
+    finish(ukey, ustart, uend, cnt, vs, rec_words);
     return F3DS_OK;
 }
-// the call after its checks, with room for first_cap records (at most 2n) per frame: st[i] = frame i's status; the result is a failure of the call as a whole
-int ct_run(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, const void* const* depth, const uint32_t* const* labels, const uint32_t* n_regions,
-           float depth_tol, int inputs_on_device, f3ds_region_contact* const* rows, const size_t* caps, int rows_on_device, size_t* n_out, f3ds_region_contacts_result* results,
-           uint32_t first_cap, int* st) {
+// A pair call after its checks, with room for first_cap records (at most 2n) per frame: st[i] = frame i's status; the result is a failure of the call as a
+// whole.  The call is its row and result types, first_rows (the rows of a host caller that ride with the head), record(context, images, K, rec_cap, sort_bits,
+// head, device rows, row cap, device shapes) for one frame, and fill(head, K, result).  shapes: the joints' second output, a fixed payload in front of the rows
+// (NULL: none, and always for the contacts).
+template <class Row, class Result, class Record, class Fill>
+int pair_run(f3ds_ctx** ctxs, int nctx, const f3ds::RgbdLayout& lay, const void* const* depth, const uint32_t* const* labels, const uint32_t* n_regions, int inputs_on_device,
+             Row* const* rows, const size_t* caps, f3ds_region_shape* const* shapes, int rows_on_device, size_t* n_out, Result* results, size_t first_rows, uint32_t first_cap, int* st,
+             const Record& record, const Fill& fill) {
     Batch b;
     if (const int rc = li_begin(ctxs, nctx, &b)) return rc;
     const uint32_t n = (uint32_t)lay.n;
@@ -2747,14 +2776,18 @@ int ct_run(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format& fmt, const f3ds::R
     for (int i = 0; i < nctx; ++i) sort_bits = std::max(sort_bits, ct_sort_bits(n_regions[i]));
     std::vector<size_t> fixed((size_t)nctx, 0u), stage_rows((size_t)nctx, 0u), count((size_t)nctx, 0u);
     std::vector<void*> dst((size_t)nctx, nullptr);
-    for (int i = 0; i < nctx; ++i) if (rows && rows[i] && !rows_on_device) stage_rows[i] = caps[i] < rec_cap ? caps[i] : (size_t)rec_cap;      // (rows <= records <= rec_cap)
+    for (int i = 0; i < nctx; ++i) {
+        if (shapes && shapes[i] && !rows_on_device) fixed[i] = (size_t)n_regions[i] * sizeof(f3ds_region_shape);      // (84 B a row: li_stage_layout aligns what follows)
+        if (rows && rows[i] && !rows_on_device) stage_rows[i] = caps[i] < rec_cap ? caps[i] : (size_t)rec_cap;      // (rows <= records <= rec_cap)
+    }
     LiStage s; std::vector<LiImages> im((size_t)nctx);
-    if (const int rc = li_out_buffers(ctxs[0], nctx, fixed.data(), stage_rows.data(), sizeof(f3ds_region_contact), RGC_FIRST_ROWS, &s)) return rc;
+    if (const int rc = li_out_buffers(ctxs[0], nctx, fixed.data(), stage_rows.data(), sizeof(Row), first_rows, &s)) return rc;
     if (const int rc = li_upload(ctxs, nctx, b, lay, depth, nullptr, labels, inputs_on_device, im.data())) return rc;
     for (int i = 0; i < nctx; ++i) {
-        f3ds_region_contact* const r = rows ? rows[i] : nullptr;
-        f3ds_region_contact* d_rows = !r ? nullptr : (rows_on_device ? r : reinterpret_cast<f3ds_region_contact*>(s.out + s.slot[i].rows_at));
-        if (const int rc = ct_record(ctxs[i], fmt, lay, im[i], n_regions[i], depth_tol, rec_cap, sort_bits, s.head(i), d_rows, r ? caps[i] : 0u)) return rc;
+        Row* const r = rows ? rows[i] : nullptr;
+        Row* d_rows = !r ? nullptr : (rows_on_device ? r : reinterpret_cast<Row*>(s.out + s.slot[i].rows_at));
+        f3ds_region_shape* d_shapes = !shapes || !shapes[i] ? nullptr : li_out_ptr(rows_on_device, shapes[i], s, i);
+        if (const int rc = record(ctxs[i], im[i], n_regions[i], rec_cap, sort_bits, s.head(i), d_rows, r ? caps[i] : 0u, d_shapes)) return rc;
     }
     if (const int rc = flush(b)) return rc;
     if (const int rc = li_download_heads(s, b)) return rc;
@@ -2762,7 +2795,7 @@ int ct_run(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format& fmt, const f3ds::R
     for (int i = 0; i < nctx; ++i) {
         const uint32_t* h = s.h_head(i);
         st[i] = F3DS_OK;
-        if (h[1]) { st[i] = F3DS_ERR_ARG; continue; }      // (a label >= n_regions: d_contact_finish wrote no row)
+        if (h[1]) { st[i] = F3DS_ERR_ARG; continue; }      // (a label >= n_regions: no finish kernel wrote a row)
         if (h[2] > rec_cap) {      // (rare: more records than the first buffer holds)
             if (rec_cap >= rec_all) return F3DS_ERR_LOGIC;
             again.push_back(i); continue;
@@ -2770,17 +2803,28 @@ int ct_run(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format& fmt, const f3ds::R
         const size_t cnt = h[0];
         if (cnt > rec_cap) return F3DS_ERR_LOGIC;
         n_out[i] = cnt;
-        if (results) { results[i].n_regions = n_regions[i]; results[i].n_contacts = h[0]; memcpy(&results[i].n_pairs, h + 4, 8); memcpy(&results[i].n_close, h + 6, 8); }
+        if (fixed[i]) memcpy(shapes[i], s.o->h_li + s.slot[i].at, fixed[i]);
+        if (results) fill(h, n_regions[i], results[i]);
         if (!rows || !rows[i]) continue;
         if (caps[i] < cnt) { st[i] = F3DS_ERR_CAPACITY; continue; }
         if (!rows_on_device) { count[i] = cnt; dst[i] = rows[i]; }
     }
-    if (const int rc = li_rows_behind(s, b, nctx, sizeof(f3ds_region_contact), count.data(), dst.data())) return rc;
+    if (const int rc = li_rows_behind(s, b, nctx, sizeof(Row), count.data(), dst.data())) return rc;
     for (const int i : again) {      // (the owner's staging is free again: everything else has been delivered)
-        if (const int rc = ct_run(ctxs + i, 1, fmt, lay, depth + i, labels + i, n_regions + i, depth_tol, inputs_on_device, rows ? rows + i : nullptr, caps ? caps + i : nullptr,
-                                  rows_on_device, n_out + i, results ? results + i : nullptr, rec_all, &st[i])) return rc;
+        if (const int rc = pair_run(ctxs + i, 1, lay, depth + i, labels + i, n_regions + i, inputs_on_device, rows ? rows + i : nullptr, caps ? caps + i : nullptr,
+                                    shapes ? shapes + i : nullptr, rows_on_device, n_out + i, results ? results + i : nullptr, first_rows, rec_all, &st[i], record, fill)) return rc;
     }
     return F3DS_OK;
+}
+int ct_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, const LiImages& im, uint32_t K, float depth_tol, uint32_t rec_cap, int sort_bits, uint32_t* head,
+              f3ds_region_contact* d_rows, size_t cap) {
+    const PairArgs a = pair_args(fmt, lay, K, depth_tol, rec_cap);
+    const uint32_t n = a.n;
+    return pair_record(c, rgc_scratch(c), CT_WORDS, a, sort_bits, head,
+        [&](uint64_t* k0, uint32_t* rec_words) { rec<d_contact_accum>(c, grid_for((n + RGC_TRIPS - 1u) / RGC_TRIPS, 256), 0u, im.depth, im.labels, a, k0, rec_words, head); },
+        [&](uint64_t* ukey, uint32_t* ustart, uint32_t* uend, uint32_t* cnt, uint32_t* vs, uint32_t* rec_words) {
+            rec<d_contact_finish>(c, grid_for((size_t)(rec_cap < 8192u ? rec_cap : 8192u) * 64u, 256), 0u, ukey, ustart, uend, cnt, vs, rec_words, a.kb, rec_cap, head, d_rows, (uint64_t)cap);
+        });
 }
 }  // namespace
 
@@ -2793,7 +2837,12 @@ extern "C" int f3ds_region_contacts_batch(f3ds_ctx** ctxs, int nctx, const f3ds_
     std::vector<int> st((size_t)nctx, F3DS_OK);
     g_sw.read();
     const uint32_t first = g_sw.rgc_first_cap ? g_sw.rgc_first_cap : RGC_FIRST_CAP;
-    if (const int rc = ct_run(ctxs, nctx, fmt, lay, depth, labels, n_regions, depth_tol, inputs_on_device, rows, caps, rows_on_device, n_out, results, first, st.data())) return rc;
+    const auto record = [&](f3ds_ctx* c, const LiImages& im, uint32_t K, uint32_t rec_cap, int sort_bits, uint32_t* head, f3ds_region_contact* d_rows, size_t cap, f3ds_region_shape*) {
+        return ct_record(c, fmt, lay, im, K, depth_tol, rec_cap, sort_bits, head, d_rows, cap);
+    };
+    const auto fill = [](const uint32_t* h, uint32_t K, f3ds_region_contacts_result& r) { r.n_regions = K; r.n_contacts = h[0]; memcpy(&r.n_pairs, h + 4, 8); memcpy(&r.n_close, h + 6, 8); };
+    if (const int rc = pair_run(ctxs, nctx, lay, depth, labels, n_regions, inputs_on_device, rows, caps, nullptr, rows_on_device, n_out, results, RGC_FIRST_ROWS, first, st.data(), record,
+                                fill)) return rc;
     return li_statuses(st, status);
 }
 extern "C" int f3ds_region_contacts(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, float depth_tol,
@@ -2841,22 +2890,13 @@ extern "C" int f3ds_region_shapes_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rg
     if (const int rc = li_out_buffers(ctxs[0], nctx, fixed.data(), nullptr, 0u, 0u, &s)) return rc;
     if (const int rc = li_upload(ctxs, nctx, b, lay, depth, nullptr, labels, inputs_on_device, im.data())) return rc;
     for (int i = 0; i < nctx; ++i) {
-        f3ds_region_shape* d_rows = rows_on_device ? rows[i] : reinterpret_cast<f3ds_region_shape*>(s.out + s.slot[i].at);
-        if (const int rc = sh_record(ctxs[i], fmt, lay, im[i], n_regions[i], s.head(i), d_rows, ctxs[i]->rgs_acc)) return rc;
+        if (const int rc = sh_record(ctxs[i], fmt, lay, im[i], n_regions[i], s.head(i), li_out_ptr(rows_on_device, rows[i], s, i), ctxs[i]->rgs_acc)) return rc;
     }
-    if (const int rc = flush(b)) return rc;
-    if (const int rc = li_download_heads(s, b)) return rc;
-    std::vector<int> st((size_t)nctx, F3DS_OK);
-    for (int i = 0; i < nctx; ++i) {
-        const uint32_t* h = s.h_head(i);
-        if (h[1]) { st[i] = F3DS_ERR_ARG; continue; }      // (a label >= n_regions: d_shape_finish wrote no row)
-        if (fixed[i]) memcpy(rows[i], s.o->h_li + s.slot[i].at, fixed[i]);
-        if (results) {
-            results[i].n_regions = n_regions[i]; results[i].n_nonempty = h[0];
-            memcpy(&results[i].n_labelled, h + 2, 8); memcpy(&results[i].n_clamped, h + 4, 8);
-        }
-    }
-    return li_statuses(st, status);
+    return li_deliver_fixed(s, b, nctx, fixed.data(), rows, nullptr, static_cast<void* const*>(nullptr), status, [&](int i, const uint32_t* h) {
+        if (!results) return;
+        results[i].n_regions = n_regions[i]; results[i].n_nonempty = h[0];
+        memcpy(&results[i].n_labelled, h + 2, 8); memcpy(&results[i].n_clamped, h + 4, 8);
+    });
 }
 extern "C" int f3ds_region_shapes(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, int inputs_on_device,
                                   f3ds_region_shape* rows, int rows_on_device, f3ds_region_shapes_result* result) {
@@ -2910,24 +2950,14 @@ extern "C" int f3ds_region_boxes_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgb
     if (const int rc = li_out_buffers(ctxs[0], nctx, fixed.data(), nullptr, 0u, 0u, &s)) return rc;
     if (const int rc = li_upload(ctxs, nctx, b, lay, depth, nullptr, labels, inputs_on_device, im.data())) return rc;
     for (int i = 0; i < nctx; ++i) {
-        f3ds_region_box* d_rows = rows_on_device ? rows[i] : reinterpret_cast<f3ds_region_box*>(s.out + s.slot[i].at);
-        f3ds_region_shape* d_shapes = !shapes || !shapes[i] ? nullptr : (rows_on_device ? shapes[i] : reinterpret_cast<f3ds_region_shape*>(s.out + s.slot[i].at + box_bytes[i]));
-        if (const int rc = bx_record(ctxs[i], fmt, lay, im[i], n_regions[i], plane_tol, s.head(i), d_rows, d_shapes)) return rc;
+        f3ds_region_shape* d_shapes = !shapes || !shapes[i] ? nullptr : li_out_ptr(rows_on_device, shapes[i], s, i, box_bytes[i]);
+        if (const int rc = bx_record(ctxs[i], fmt, lay, im[i], n_regions[i], plane_tol, s.head(i), li_out_ptr(rows_on_device, rows[i], s, i), d_shapes)) return rc;
     }
-    if (const int rc = flush(b)) return rc;
-    if (const int rc = li_download_heads(s, b)) return rc;
-    std::vector<int> st((size_t)nctx, F3DS_OK);
-    for (int i = 0; i < nctx; ++i) {
-        const uint32_t* h = s.h_head(i);
-        if (h[1]) { st[i] = F3DS_ERR_ARG; continue; }      // (a label >= n_regions: no finish kernel wrote a row)
-        if (box_bytes[i]) memcpy(rows[i], s.o->h_li + s.slot[i].at, box_bytes[i]);
-        if (shape_bytes[i]) memcpy(shapes[i], s.o->h_li + s.slot[i].at + box_bytes[i], shape_bytes[i]);
-        if (results) {
-            results[i].n_regions = n_regions[i]; results[i].n_nonempty = h[0];
-            memcpy(&results[i].n_labelled, h + 2, 8); memcpy(&results[i].n_clamped, h + 4, 8); memcpy(&results[i].n_inliers, h + 6, 8);
-        }
-    }
-    return li_statuses(st, status);
+    return li_deliver_fixed(s, b, nctx, box_bytes.data(), rows, shape_bytes.data(), shapes, status, [&](int i, const uint32_t* h) {
+        if (!results) return;
+        results[i].n_regions = n_regions[i]; results[i].n_nonempty = h[0];
+        memcpy(&results[i].n_labelled, h + 2, 8); memcpy(&results[i].n_clamped, h + 4, 8); memcpy(&results[i].n_inliers, h + 6, 8);
+    });
 }
 extern "C" int f3ds_region_boxes(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, float plane_tol, int inputs_on_device,
                                  f3ds_region_box* rows, f3ds_region_shape* shapes, int rows_on_device, f3ds_region_boxes_result* result) {
@@ -2937,94 +2967,27 @@ extern "C" int f3ds_region_boxes(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, cons
 // ------------------------------------------------------------------------------------------------
 // region joints (f3ds_joints.h / .inc): one row per pair of regions of a label image that touch -- the border in space and the join of the
 // two regions' shape rows.  One flush: the three kernels of the shapes as they are (sh_record, into the joints' own accumulators and a head of their own: the
-// call's head is the contacts'), d_joint_init, d_joint_accum (the pass over the borders: records of (pair, 34 words)), the radix sort of the record keys,
+// call's head is the contacts'), d_pair_init, d_joint_accum (the pass over the borders: records of (pair, 34 words)), the radix sort of the record keys,
 // d_evl_heads / scan, d_track_runs, d_joint_finish.  Behind the head the shape rows of a host caller who asked for them (84 B per region), then the first
-// RGJ_FIRST_ROWS rows.  Records that do not fit, long row arrays and the frames of a batch: as the contacts (ct_run).  Beside rgj_* the call uses the sort's
+// RGJ_FIRST_ROWS rows.  Records that do not fit, long row arrays and the frames of a batch: as the contacts (pair_run).  Beside rgj_* the call uses the sort's
 // histogram and the scan's tile sums, which hold nothing between calls.
 // ------------------------------------------------------------------------------------------------
 namespace {
 int jt_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, const LiImages& im, uint32_t K, const f3ds_joint_params& prm, uint32_t rec_cap, int sort_bits,
               uint32_t* head, f3ds_region_joint* d_rows, size_t cap, f3ds_region_shape* d_shapes /* NULL: the context's scratch */) {
-    const uint32_t n = (uint32_t)lay.n;
-    uint64_t *k0, *k1, *ukey; uint32_t *v0, *v1, *rec_words, *flag, *ustart, *uend, *cnt, *hist, *tiles, *shead;
-    ENSURE(c->rgj_k0, rec_cap, k0); ENSURE(c->rgj_k1, rec_cap, k1); ENSURE(c->rgj_v0, rec_cap, v0); ENSURE(c->rgj_v1, rec_cap, v1);
-    ENSURE(c->rgj_rec, (size_t)rec_cap * JT_WORDS, rec_words); ENSURE(c->rgj_flag, rec_cap, flag); ENSURE(c->rgj_ukey, rec_cap, ukey);
-    ENSURE(c->rgj_ustart, rec_cap, ustart); ENSURE(c->rgj_uend, rec_cap, uend); ENSURE(c->rgj_cnt, 4, cnt); ENSURE(c->rgj_shead, LI_HEAD_WORDS, shead);
-    ENSURE(c->hist, (size_t)RS_BINS * ((rec_cap + RS_TILE - 1) / RS_TILE + 1), hist); ENSURE(c->tiles, (rec_cap + SCAN_TILE - 1) / SCAN_TILE + 1, tiles);
+    const PairArgs a = pair_args(fmt, lay, K, prm.depth_tol, rec_cap);
+    const uint32_t n = a.n;
+    uint32_t* shead;
+    ENSURE(c->rgj_shead, LI_HEAD_WORDS, shead);
     if (!d_shapes) ENSURE(c->rgj_shape, K ? K : 1u, d_shapes);
+    // (the scratch of the pair kernels is ensured behind the shapes' kernels: none of them refers to it, nor to the sort's histogram or the scan's tile sums)
     if (const int rc = sh_record(c, fmt, lay, im, K, shead, d_shapes, c->rgj_sacc)) return rc;      // (rgj_sacc is ensured before its first rec<>, and nothing recorded refers to it yet)
-    JointArgs a;
-    memset(&a, 0, sizeof a);
-    a.width = fmt.width; a.height = fmt.height; a.n = n; a.depth_pitch = lay.depth_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
-    a.K = K; a.kb = ct_bits(K); a.rec_cap = rec_cap; a.depth_scale = fmt.depth_scale; a.depth_tol = prm.depth_tol; a.fx = fmt.fx; a.fy = fmt.fy; a.cx = fmt.cx; a.cy = fmt.cy;
-    const uint64_t hole = ct_hole(K, a.kb);
-    int rc;
-    rec<d_joint_init>(c, grid_for(rec_cap, 256), 0u, k0, v0, rec_cap, head);
-    rec<d_joint_accum>(c, grid_for((n + RGJ_TRIPS - 1u) / RGJ_TRIPS, RGJ_BLOCK), 0u, im.depth, im.labels, a, k0, rec_words, head);
-    uint64_t* ks; uint32_t* vs;
-    if ((rc = radix_sort(c, k0, v0, k1, v1, rec_cap, sort_bits, &ks, &vs))) return rc;
-    rec<d_evl_heads>(c, grid_for(rec_cap, 256), 0u, ks, rec_cap, hole, flag);
-    if ((rc = scan_u32(c, flag, flag, rec_cap))) return rc;
-    rec<d_track_runs>(c, grid_for(rec_cap, 256), 0u, ks, rec_cap, hole, flag, ukey, ustart, uend, cnt);
-    rec<d_joint_finish>(c, grid_for((size_t)(rec_cap < 8192u ? rec_cap : 8192u) * 64u, 256), 0u, ukey, ustart, uend, cnt, vs, rec_words, d_shapes, prm, a.kb, rec_cap, head, d_rows,
-                        (uint64_t)cap);
-    return F3DS_OK;
-}
-// the call after its checks, with room for first_cap records (at most 2n) per frame: st[i] = frame i's status; the result is a failure of the call as a whole
-int jt_run(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& lay, const void* const* depth, const uint32_t* const* labels, const uint32_t* n_regions,
-           const f3ds_joint_params& prm, int inputs_on_device, f3ds_region_joint* const* rows, const size_t* caps, f3ds_region_shape* const* shapes, int rows_on_device, size_t* n_out,
-           f3ds_region_joints_result* results, uint32_t first_cap, int* st) {
-    Batch b;
-    if (const int rc = li_begin(ctxs, nctx, &b)) return rc;
-    const uint32_t n = (uint32_t)lay.n;
-    const uint32_t rec_all = 2u * n;      // (n < 2^29: jt_check)  every contact pair a record of its own is fewer than this
-    const uint32_t rec_cap = first_cap < rec_all ? first_cap : rec_all;
-    int sort_bits = 0;
-    for (int i = 0; i < nctx; ++i) sort_bits = std::max(sort_bits, ct_sort_bits(n_regions[i]));
-    std::vector<size_t> fixed((size_t)nctx, 0u), stage_rows((size_t)nctx, 0u), count((size_t)nctx, 0u);
-    std::vector<void*> dst((size_t)nctx, nullptr);
-    for (int i = 0; i < nctx; ++i) {
-        if (shapes && shapes[i] && !rows_on_device) fixed[i] = (size_t)n_regions[i] * sizeof(f3ds_region_shape);      // (84 B a row: li_stage_layout aligns what follows)
-        if (rows && rows[i] && !rows_on_device) stage_rows[i] = caps[i] < rec_cap ? caps[i] : (size_t)rec_cap;      // (rows <= records <= rec_cap)
-    }
-    LiStage s; std::vector<LiImages> im((size_t)nctx);
-    if (const int rc = li_out_buffers(ctxs[0], nctx, fixed.data(), stage_rows.data(), sizeof(f3ds_region_joint), RGJ_FIRST_ROWS, &s)) return rc;
-    if (const int rc = li_upload(ctxs, nctx, b, lay, depth, nullptr, labels, inputs_on_device, im.data())) return rc;
-    for (int i = 0; i < nctx; ++i) {
-        f3ds_region_joint* const r = rows ? rows[i] : nullptr;
-        f3ds_region_joint* d_rows = !r ? nullptr : (rows_on_device ? r : reinterpret_cast<f3ds_region_joint*>(s.out + s.slot[i].rows_at));
-        f3ds_region_shape* d_shapes = !shapes || !shapes[i] ? nullptr : (rows_on_device ? shapes[i] : reinterpret_cast<f3ds_region_shape*>(s.out + s.slot[i].at));
-        if (const int rc = jt_record(ctxs[i], fmt, lay, im[i], n_regions[i], prm, rec_cap, sort_bits, s.head(i), d_rows, r ? caps[i] : 0u, d_shapes)) return rc;
-    }
-    if (const int rc = flush(b)) return rc;
-    if (const int rc = li_download_heads(s, b)) return rc;
-    std::vector<int> again;
-    for (int i = 0; i < nctx; ++i) {
-        const uint32_t* h = s.h_head(i);
-        st[i] = F3DS_OK;
-        if (h[1]) { st[i] = F3DS_ERR_ARG; continue; }      // (a label >= n_regions: neither finish kernel wrote a row)
-        if (h[2] > rec_cap) {      // (rare: more records than the first buffer holds)
-            if (rec_cap >= rec_all) return F3DS_ERR_LOGIC;
-            again.push_back(i); continue;
-        }
-        const size_t cnt = h[0];
-        if (cnt > rec_cap) return F3DS_ERR_LOGIC;
-        n_out[i] = cnt;
-        if (fixed[i]) memcpy(shapes[i], s.o->h_li + s.slot[i].at, fixed[i]);
-        if (results) {
-            results[i].n_regions = n_regions[i]; results[i].n_joints = h[0]; results[i].n_surface = h[3]; results[i].reserved = 0u;
-            memcpy(&results[i].n_pairs, h + 4, 8); memcpy(&results[i].n_close, h + 6, 8);
-        }
-        if (!rows || !rows[i]) continue;
-        if (caps[i] < cnt) { st[i] = F3DS_ERR_CAPACITY; continue; }
-        if (!rows_on_device) { count[i] = cnt; dst[i] = rows[i]; }
-    }
-    if (const int rc = li_rows_behind(s, b, nctx, sizeof(f3ds_region_joint), count.data(), dst.data())) return rc;
-    for (const int i : again) {      // (the owner's staging is free again: everything else has been delivered)
-        if (const int rc = jt_run(ctxs + i, 1, fmt, lay, depth + i, labels + i, n_regions + i, prm, inputs_on_device, rows ? rows + i : nullptr, caps ? caps + i : nullptr,
-                                  shapes ? shapes + i : nullptr, rows_on_device, n_out + i, results ? results + i : nullptr, rec_all, &st[i])) return rc;
-    }
-    return F3DS_OK;
+    return pair_record(c, rgj_scratch(c), JT_WORDS, a, sort_bits, head,
+        [&](uint64_t* k0, uint32_t* rec_words) { rec<d_joint_accum>(c, grid_for((n + RGJ_TRIPS - 1u) / RGJ_TRIPS, RGJ_BLOCK), 0u, im.depth, im.labels, a, k0, rec_words, head); },
+        [&](uint64_t* ukey, uint32_t* ustart, uint32_t* uend, uint32_t* cnt, uint32_t* vs, uint32_t* rec_words) {
+            rec<d_joint_finish>(c, grid_for((size_t)(rec_cap < 8192u ? rec_cap : 8192u) * 64u, 256), 0u, ukey, ustart, uend, cnt, vs, rec_words, d_shapes, prm, a.kb, rec_cap, head, d_rows,
+                                (uint64_t)cap);
+        });
 }
 }  // namespace
 
@@ -3040,7 +3003,15 @@ extern "C" int f3ds_region_joints_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rg
     std::vector<int> st((size_t)nctx, F3DS_OK);
     g_sw.read();
     const uint32_t first = g_sw.rgj_first_cap ? g_sw.rgj_first_cap : RGJ_FIRST_CAP;
-    if (const int rc = jt_run(ctxs, nctx, fmt, lay, depth, labels, n_regions, prm, inputs_on_device, rows, caps, shapes, rows_on_device, n_out, results, first, st.data())) return rc;
+    const auto record = [&](f3ds_ctx* c, const LiImages& im, uint32_t K, uint32_t rec_cap, int sort_bits, uint32_t* head, f3ds_region_joint* d_rows, size_t cap, f3ds_region_shape* d_shapes) {
+        return jt_record(c, fmt, lay, im, K, prm, rec_cap, sort_bits, head, d_rows, cap, d_shapes);
+    };
+    const auto fill = [](const uint32_t* h, uint32_t K, f3ds_region_joints_result& r) {
+        r.n_regions = K; r.n_joints = h[0]; r.n_surface = h[3]; r.reserved = 0u;
+        memcpy(&r.n_pairs, h + 4, 8); memcpy(&r.n_close, h + 6, 8);
+    };
+    if (const int rc = pair_run(ctxs, nctx, lay, depth, labels, n_regions, inputs_on_device, rows, caps, shapes, rows_on_device, n_out, results, RGJ_FIRST_ROWS, first, st.data(), record,
+                                fill)) return rc;
     return li_statuses(st, status);
 }
 extern "C" int f3ds_region_joints(f3ds_ctx* c, const f3ds_rgbd_format* fmt_, const void* depth, const uint32_t* labels, uint32_t n_regions, const f3ds_joint_params* params,
@@ -3098,7 +3069,7 @@ extern "C" int f3ds_region_components_batch(f3ds_ctx** ctxs, int nctx, const f3d
     if (const int rc = li_upload(ctxs, nctx, b, lay, depth, nullptr, labels, inputs_on_device, im.data())) return rc;
     for (int i = 0; i < nctx; ++i) {
         f3ds_region_component* const r = rows ? rows[i] : nullptr;
-        uint32_t* d_comp = host_out ? reinterpret_cast<uint32_t*>(s.out + s.slot[i].at) : comp_labels[i];
+        uint32_t* d_comp = li_out_ptr(outputs_on_device, comp_labels[i], s, i);
         f3ds_region_component* d_rows = !r ? nullptr : (host_out ? reinterpret_cast<f3ds_region_component*>(s.out + s.slot[i].rows_at) : r);
         if (const int rc = cc_record(ctxs[i], fmt, lay, prm, im[i], n_regions[i], s.head(i), d_comp, d_rows, r ? caps[i] : 0u)) return rc;
     }
@@ -3227,24 +3198,16 @@ extern "C" int f3ds_cloud_regions_batch(f3ds_ctx** ctxs, int nctx, const void* c
     }
     if (up) { if (const int urc = await_uploads(b, up)) return urc; }
     for (int i = 0; i < nctx; ++i) {
-        f3ds_cloud_region* d_rows = rows_on_device ? rows[i] : reinterpret_cast<f3ds_cloud_region*>(s.out + s.slot[i].at);
-        f3ds_region_box* d_boxes = !boxes ? nullptr : (rows_on_device && boxes[i] ? boxes[i] : reinterpret_cast<f3ds_region_box*>(s.out + s.slot[i].at + row_bytes[i]));
-        if (const int rc = cd_record(ctxs[i], d_pts[i], d_lab[i], (uint32_t)counts[i], n_regions[i], prm, ordered, idx_bits, label_bits, s.head(i), d_rows, d_boxes)) return rc;
+        // (boxes for every frame: a frame without regions may come without an array and then has nothing to write, wherever its pointer goes)
+        f3ds_region_box* d_boxes = !boxes ? nullptr : li_out_ptr(rows_on_device && boxes[i], boxes[i], s, i, row_bytes[i]);
+        if (const int rc = cd_record(ctxs[i], d_pts[i], d_lab[i], (uint32_t)counts[i], n_regions[i], prm, ordered, idx_bits, label_bits, s.head(i),
+                                     li_out_ptr(rows_on_device, rows[i], s, i), d_boxes)) return rc;
     }
-    if (const int rc = flush(b)) return rc;
-    if (const int rc = li_download_heads(s, b)) return rc;
-    std::vector<int> st((size_t)nctx, F3DS_OK);
-    for (int i = 0; i < nctx; ++i) {
-        const uint32_t* h = s.h_head(i);
-        if (h[1]) { st[i] = F3DS_ERR_ARG; continue; }      // (a label >= n_regions: no finish kernel wrote a row)
-        if (row_bytes[i]) memcpy(rows[i], s.o->h_li + s.slot[i].at, row_bytes[i]);
-        if (box_bytes[i]) memcpy(boxes[i], s.o->h_li + s.slot[i].at + row_bytes[i], box_bytes[i]);
-        if (results) {
-            results[i].n_regions = n_regions[i]; results[i].n_nonempty = h[0];
-            memcpy(&results[i].n_labelled, h + 2, 8); memcpy(&results[i].n_clamped, h + 4, 8); memcpy(&results[i].n_inliers, h + 6, 8);
-        }
-    }
-    return li_statuses(st, status);
+    return li_deliver_fixed(s, b, nctx, row_bytes.data(), rows, box_bytes.data(), boxes, status, [&](int i, const uint32_t* h) {
+        if (!results) return;
+        results[i].n_regions = n_regions[i]; results[i].n_nonempty = h[0];
+        memcpy(&results[i].n_labelled, h + 2, 8); memcpy(&results[i].n_clamped, h + 4, 8); memcpy(&results[i].n_inliers, h + 6, 8);
+    });
 }
 extern "C" int f3ds_cloud_regions(f3ds_ctx* c, const void* points16, size_t n, const uint32_t* labels, uint32_t n_regions, const f3ds_cloud_params* params, int inputs_on_device,
                                   f3ds_cloud_region* rows, f3ds_region_box* boxes, int rows_on_device, f3ds_cloud_regions_result* result) {

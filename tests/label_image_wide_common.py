@@ -2,7 +2,7 @@
 _contacts, _shapes, _boxes, _components) at frames WIDER than a workgroup.  Nothing here is a new reference: the references are those of
 region_table_common, region_contacts_common, region_shapes_common, region_boxes_common, region_components_common and track_common, and the scenes are their
 generators at new sizes.  What this file adds is the list of cases, each with the classes of control flow it is for, and a CENSUS: the launch arithmetic of
-csrc/f3ds_hip.hip and the span arithmetic of label_accum_span / contact_accum_span restated in plain Python from the kernels' constants (read from their
+csrc/f3ds_hip.hip and the span arithmetic of label_accum_span / pair_accum_span restated in plain Python from the kernels' constants (read from their
 defining lines, KERNEL_CONSTANT_PATTERNS), so that a CPU test can assert that every case reaches what it claims.
 
 Shapes (width x height, depth, layout) and what they reach -- a trip of a 256-thread workgroup moves a lane sv = 256 // width rows and su = 256 - sv * width

@@ -1,4 +1,4 @@
-"""The region contacts on the device (f3ds_region_contacts: d_contact_init, d_contact_accum, the record sort, d_contact_finish in csrc/f3ds_contacts.inc)
+"""The region contacts on the device (f3ds_region_contacts: d_pair_init, d_contact_accum, the record sort, d_contact_finish: ContactRule of csrc/f3ds_contacts.inc over csrc/f3ds_pairs.inc)
 against the numpy reference of tests/region_contacts_common.py, bit for bit: the scenes and shapes of tests/test_region_contacts_cpu.py, host buffers and
 all-device buffers, at the default launch width and at F3DS_GRID_CAP = 1 and 3.  At one workgroup the 5917 pixels of 97 x 61 are one span of 23 full trips and
 a ragged one; at three the spans end ragged and straddle rows, so lower neighbours fall into another workgroup's span.  Scene 3 (every pixel its own region)

@@ -1,5 +1,5 @@
-"""The region joints on the device (f3ds_region_joints: the shapes' kernels, d_joint_init, d_joint_accum, the record sort, d_joint_finish in
-csrc/f3ds_joints.inc) against f3ds_region_joints_host, bit for bit.  The frames are the smallest at which the kernels can go wrong: 300 x 7 and 257 x 5 are
+"""The region joints on the device (f3ds_region_joints: the shapes' kernels, d_pair_init, d_joint_accum, the record sort, d_joint_finish: JointRule of
+csrc/f3ds_joints.inc over the pair skeleton of csrc/f3ds_pairs.inc) against f3ds_region_joints_host, bit for bit.  The frames are the smallest at which the kernels can go wrong: 300 x 7 and 257 x 5 are
 wider than a workgroup (spans straddle rows; at 300 x 7 the accumulate launch has two workgroups, so a pair's two pixels lie in different spans), 64 x 48 are
 the analytic scenes, 33 x 31 with every pixel its own region has some 1400 pairs in one span: eleven times the 128 slots of the LDS table, so pairs become
 records of their own.  The rerun with room for all records (F3DS_RGJ_FIRST_CAP = 16) and the narrow launches (F3DS_GRID_CAP = 1, 3, 8) run in fresh child
@@ -266,6 +266,40 @@ def test_batch_statuses_and_bits(P, three):
             b.view(np.uint32)[:] = PREFILL
         rc = P.load_library().f3ds_region_joints_batch(hs, 3, ctypes.byref(f), dp, lp, nr, None, 0, rp, caps, None, 0, n_out, None, st.ctypes.data)
         assert rc == P.ERR_ARG and st.tolist() == [1, 1, 1] and list(n_out) == [777] * 3 and all((b.view(np.uint32) == PREFILL).all() for b in bufs)
+
+
+@pytest.mark.parametrize("where", ["host", "device"])
+def test_batch_overflow_reruns_the_frames_that_need_it(P, three, monkeypatch, where):
+    """The rerun with room for all records inside a batch (the contacts' twin: test_region_batch_gpu.py): with room for 64 records the checker frame --
+    thousands of rows, and a row needs at least one record -- runs again alone; the frame of one region has no pair, hence no record, and runs with the batch
+    only."""
+    monkeypatch.setenv("F3DS_RGJ_FIRST_CAP", "64")
+    w, h = 67, 45
+    s7 = J.scene(P, 7, w, h, "f32")
+    fmt = s7["fmt"]
+    frames = [s7, dict(J.checker_scene(P, w, h), fmt=fmt), dict(s7, labels=np.zeros((h, w), np.uint32), n_regions=1)]      # (one format for the batch: scene 7's, f32 metres)
+    want = [P.region_joints_host(f["depth"], f["labels"], f["n_regions"], fmt, want_shapes=True) for f in frames]
+    assert len(want[1][0]) > 64 and len(want[2][0]) == 0      # (by the host function alone: the checker frame cannot fit, the last one has nothing to fit)
+    depths, labels, K = [f["depth"] for f in frames], [f["labels"] for f in frames], [f["n_regions"] for f in frames]
+    if where == "host":
+        got, status = P.region_joints_batch(three, depths, labels, K, fmt, shapes_out=True)
+    else:
+        import torch
+        dd = [to_device(np.ascontiguousarray(d, np.float32)) for d in depths]
+        dl = [to_device(np.ascontiguousarray(x, np.uint32).view(np.int32)) for x in labels]
+        caps = [len(wrows) + 1 for wrows, _, _ in want]
+        dr = [torch.zeros(20 * c, dtype=torch.int32, device="cuda") for c in caps]
+        ds = [torch.zeros(21 * k, dtype=torch.int32, device="cuda") for k in K]
+        out, status = P.region_joints_batch(three, dd, dl, K, fmt, rows_out=[(r.data_ptr(), c) for r, c in zip(dr, caps)], shapes_out=ds, on_device=True)
+        torch.cuda.synchronize()
+        assert all(o[0] is None and o[1] is None for o in out)
+        got = [(r.cpu().numpy().view(P.REGION_JOINT_DTYPE)[:o[2].n_joints], s.cpu().numpy().view(P.REGION_SHAPE_DTYPE), o[2]) for r, s, o in zip(dr, ds, out)]
+    assert status.tolist() == [0, 0, 0]
+    for (rows, shapes, res), (wrows, wshapes, wres) in zip(got, want):
+        J.assert_rows_equal(rows, wrows)
+        S.assert_rows_equal(P, shapes, wshapes)
+        assert res.as_dict() == wres.as_dict()
+    assert three[2].launch_shape()[2] == 3 and three[1].launch_shape()[2] == 1      # (a rerun is a launch of one frame)
 
 
 # ---- 5. end to end: the context is untouched ------------------------------------------------------------------------------------------------------------------

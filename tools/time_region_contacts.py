@@ -12,7 +12,7 @@ along borders, and sort only the records of border spans).  No margin.  The host
 the link.
 usage: tools/time_region_contacts.py [--reps R] [--warmup W]
        tools/time_region_contacts.py --trace   one warm-up and one timed frame, device form only: the program of the rocprofv3 --kernel-trace --stats run
-                                               (d_contact_init, d_contact_accum, the record sort, d_evl_heads, the scan, d_track_runs and d_contact_finish)"""
+                                               (d_pair_init, d_contact_accum, the record sort, d_evl_heads, the scan, d_track_runs and d_contact_finish)"""
 import argparse, ctypes, importlib, json, os, sys, time
 import numpy as np
 import torch        # (first: libf3ds binds to the HIP runtime torch has mapped, INTEGRATION.md section 3)

@@ -11,7 +11,7 @@ f3ds_region_shapes in the same run (the joints do everything those two do and sa
 and for one Jacobi finish per row).  The host form is reported beside it with no condition.
 usage: tools/time_region_joints.py [--reps R] [--warmup W]
        tools/time_region_joints.py --trace   one warm-up and one timed frame, device form only: the program of the rocprofv3 --kernel-trace --stats run
-                                             (the shapes' three kernels, d_joint_init, d_joint_accum, the record sort, d_evl_heads, the scan, d_track_runs
+                                             (the shapes' three kernels, d_pair_init, d_joint_accum, the record sort, d_evl_heads, the scan, d_track_runs
                                              and d_joint_finish)"""
 import argparse, ctypes, importlib, json, os, sys, time
 import numpy as np
