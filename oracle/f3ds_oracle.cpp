@@ -176,8 +176,10 @@ void eigen33(const float cov[3][3], float* eigenvalue, float* evec) {
 // pcl::computePointNormal on a sequence of points given in order (is_dense path) followed by
 // flipNormalTowardsViewpoint(point, 0,0,0), normal[3]=0, normalize()  [PCL-recall A5]
 struct XYZ { float x, y, z; };
+// the two halves (plane_params = computePointNormal, flip_towards_origin = the sign test of flipNormalTowardsViewpoint) are also
+// exported on their own: the build of the reference's merge half (oracle/ref_shim) calls them where the reference calls PCL
 template <class It, class Get>
-void point_normal(It begin, It end, size_t count, Get get, const float vp_point[3], float normal[4], float* curvature) {
+void plane_params(It begin, It end, size_t count, Get get, float normal[4], float* curvature) {
     if (count < 3) {
         normal[0] = normal[1] = normal[2] = normal[3] = std::numeric_limits<float>::quiet_NaN();
         *curvature = normal[0];
@@ -208,15 +210,30 @@ void point_normal(It begin, It end, size_t count, Get get, const float vp_point[
         normal[3] = 0.0f;
         normal[3] = -1.0f * dot4(normal, cen);
     }
-    // flipNormalTowardsViewpoint
-    float vp[4] = {0.0f - vp_point[0], 0.0f - vp_point[1], 0.0f - vp_point[2], 0.0f};
+}
+// flipNormalTowardsViewpoint
+inline void flip_towards(const float point[3], float vp_x, float vp_y, float vp_z, float normal[4]) {
+    float vp[4] = {vp_x - point[0], vp_y - point[1], vp_z - point[2], 0.0f};
     float cos_theta = dot4(vp, normal);
     if (cos_theta < 0.0f) {
         normal[0] *= -1.0f; normal[1] *= -1.0f; normal[2] *= -1.0f; normal[3] *= -1.0f;
         // (Hessian component recomputed in PCL; the caller overwrites it with 0 next)
     }
+}
+template <class It, class Get>
+void point_normal(It begin, It end, size_t count, Get get, const float vp_point[3], float normal[4], float* curvature) {
+    plane_params(begin, end, count, get, normal, curvature);
+    flip_towards(vp_point, 0.0f, 0.0f, 0.0f, normal);
     normal[3] = 0.0f;
     normalize4(normal);
+}
+// pcl::computeCentroid -> CentroidPoint: xyz = sum / n  [PCL-recall A9]
+template <class It, class Get>
+void centroid_of(It begin, It end, size_t count, Get get, float centroid[3]) {
+    float sx = 0, sy = 0, sz = 0;
+    for (It it = begin; it != end; ++it) { XYZ p = get(*it); sx += p.x; sy += p.y; sz += p.z; }
+    float nf = (float)count;
+    centroid[0] = sx / nf; centroid[1] = sy / nf; centroid[2] = sz / nf;
 }
 
 // ---- colour [src/color_utilities.cpp] ----------------------------------------------------------
@@ -224,10 +241,11 @@ const float RGB_RANGE = 441.672943f;   // include/supervoxel_clustering/color_ut
 const float LAB_RANGE = 137.3607f;     // include/supervoxel_clustering/color_utilities.h:63
 
 // cv::cvtColor(COLOR_RGB2Lab) on CV_32FC3, restated analytically -- unpinned
-void rgb2lab(const float rgb[3], float lab[3]) {
+// (unit_rgb2lab is cvtColor's part, on channels in [0, 1]; exported on its own for oracle/ref_shim)
+void unit_rgb2lab(const float unit[3], float lab[3]) {
     float c[3];
     for (int i = 0; i < 3; ++i) {
-        float v = rgb[i] / 255;                       // src/color_utilities.cpp:153-155
+        float v = unit[i];
         v = v <= 0.04045f ? v / 12.92f : o_gamma(v);
         c[i] = v;
     }
@@ -240,6 +258,10 @@ void rgb2lab(const float rgb[3], float lab[3]) {
     lab[0] = Y > 0.008856f ? 116.0f * fy - 16.0f : 903.3f * Y;
     lab[1] = 500.0f * (fx - fy);
     lab[2] = 200.0f * (fy - fz);
+}
+void rgb2lab(const float rgb[3], float lab[3]) {
+    float unit[3] = {rgb[0] / 255, rgb[1] / 255, rgb[2] / 255};       // src/color_utilities.cpp:153-155
+    unit_rgb2lab(unit, lab);
 }
 
 // OpenCV-distance estimate (tests/test_pins.py): OpenCV 4's float RGB -> Lab goes through a trilinearly interpolated LUT by default and
@@ -895,11 +917,7 @@ int run_clustering(f3ds_oracle& o) {
         sn->voxels = sup1->voxels; sn->voxels.insert(sn->voxels.end(), sup2->voxels.begin(), sup2->voxels.end());
         sn->voxel_idx = sup1->voxel_idx; sn->voxel_idx.insert(sn->voxel_idx.end(), sup2->voxel_idx.begin(), sup2->voxel_idx.end());
         sn->leaves = sup1->leaves; sn->leaves.insert(sn->leaves.end(), sup2->leaves.begin(), sup2->leaves.end());
-        // pcl::computeCentroid -> CentroidPoint: xyz = sum / n  [PCL-recall A9]
-        float sx = 0, sy = 0, sz = 0;
-        for (const SvPoint& v : sn->voxels) { sx += v.x; sy += v.y; sz += v.z; }
-        float nf = (float)sn->voxels.size();
-        sn->centroid[0] = sx / nf; sn->centroid[1] = sy / nf; sn->centroid[2] = sz / nf;
+        centroid_of(sn->voxels.begin(), sn->voxels.end(), sn->voxels.size(), [](const SvPoint& v) { return XYZ{v.x, v.y, v.z}; }, sn->centroid);
         float n4[4], curv;
         point_normal(sn->voxels.begin(), sn->voxels.end(), sn->voxels.size(),
                      [](const SvPoint& v) { return XYZ{v.x, v.y, v.z}; }, sn->centroid, n4, &curv);
@@ -1258,6 +1276,30 @@ void f3ds_oracle_normal(const float* xyz, size_t n, const float* view_point, flo
     for (size_t i = 0; i < n; ++i) pts[i] = XYZ{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
     point_normal(pts.begin(), pts.end(), n, [](const XYZ& p) { return p; }, view_point, normal4, &curv);
 }
+// the PCL / OpenCV primitives one by one, for the build of the reference's own merge half and scorer (oracle/ref_shim forwards to them,
+// oracle/ref_driver.cpp): computePointNormal's unflipped plane parameters + curvature, the sign test of flipNormalTowardsViewpoint,
+// computeCentroid, cvtColor(COLOR_RGB2Lab) on one pixel with channels in [0, 1]; and array forms of the per-element entries
+void f3ds_oracle_plane_params(const float* xyz, size_t n, float* plane4, float* curvature) {
+    const XYZ* p = (const XYZ*)xyz;
+    plane_params(p, p + n, n, [](const XYZ& q) { return q; }, plane4, curvature);
+}
+void f3ds_oracle_flip_normal(const float* point3, float vp_x, float vp_y, float vp_z, float* normal4) { flip_towards(point3, vp_x, vp_y, vp_z, normal4); }
+void f3ds_oracle_centroid(const float* xyz, size_t n, float* centroid3) {
+    const XYZ* p = (const XYZ*)xyz;
+    centroid_of(p, p + n, n, [](const XYZ& q) { return q; }, centroid3);
+}
+void f3ds_oracle_unit_rgb2lab(const float* unit_rgb, float* lab) { unit_rgb2lab(unit_rgb, lab); }
+void f3ds_oracle_ciede00_rows(const float* lab_pairs, size_t n, float* out) { for (size_t i = 0; i < n; ++i) out[i] = lab_ciede00(lab_pairs + 6 * i, lab_pairs + 6 * i + 3); }
+void f3ds_oracle_rgb_eucl_rows(const float* rgb_pairs, size_t n, float* out) { for (size_t i = 0; i < n; ++i) out[i] = rgb_eucl(rgb_pairs + 6 * i, rgb_pairs + 6 * i + 3); }
+// mean_color of n_rows voxel lists: row i holds the packed 0x00RRGGBB colours [offset[i], offset[i + 1])
+void f3ds_oracle_mean_color_rows(const uint32_t* rgba, const uint32_t* offset, size_t n_rows, float* out3) {
+    for (size_t i = 0; i < n_rows; ++i) {
+        Supervoxel s;
+        for (uint32_t v = offset[i]; v < offset[i + 1]; ++v) s.voxels.push_back(SvPoint{0, 0, 0, (uint8_t)((rgba[v] >> 16) & 255), (uint8_t)((rgba[v] >> 8) & 255), (uint8_t)(rgba[v] & 255)});
+        const float* m = mean_color(s);
+        for (int a = 0; a < 3; ++a) out3[3 * i + a] = m[a];
+    }
+}
 // fn: 0 exp 1 log 2 sin 3 cos 4 atan2 5 cbrt 6 pow(a,b) 7 logf 8 atan2f 9 cosf 10 sinf   (shared-math probes);
 // 100 + fn: the same function with its f64 constants read from a copy of the table (f3ds::m_tab, the provider the merge kernel uses with an LDS copy)
 double f3ds_oracle_math(int fn, double a, double b) {
@@ -1448,6 +1490,17 @@ extern "C" int f3ds_oracle_evaluate(f3ds_oracle* o, const uint32_t* truth_point_
     if (segm.empty() || truth.empty()) return F3DS_ERR_ARG;      // std::invalid_argument (testing.cpp:414,431)
     *out = eval_performance(segm, truth);
     return 0;
+}
+// the truth cloud main() hands to Testing / all_thresh (src/supervoxel_clustering.cpp:387-400): one labelled point per voxel, leaf order
+extern "C" int f3ds_oracle_truth_cloud(f3ds_oracle* o, const uint32_t* truth_point_labels, float* xyz, uint32_t* label, size_t cap, size_t* n_out) {
+    if (!o || !truth_point_labels) return F3DS_ERR_ARG;
+    std::vector<LPoint> truth = truth_cloud(*o, truth_point_labels);
+    for (size_t i = 0; i < truth.size() && i < cap; ++i) {
+        if (xyz) { xyz[3 * i] = truth[i].x; xyz[3 * i + 1] = truth[i].y; xyz[3 * i + 2] = truth[i].z; }
+        if (label) label[i] = truth[i].label;
+    }
+    if (n_out) *n_out = truth.size();
+    return truth.size() > cap && (xyz || label) ? F3DS_ERR_CAPACITY : 0;
 }
 // Testing on two hand-made labelled clouds (known-answer probe for tests/test_oracle.py)
 extern "C" int f3ds_oracle_eval_clouds(const float* sxyz, const uint32_t* slab, size_t ns, const float* txyz, const uint32_t* tlab, size_t nt, f3ds_performance* out) {
