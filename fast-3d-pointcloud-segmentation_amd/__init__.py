@@ -17,6 +17,7 @@ can be passed with ``on_device=True``.
 """
 import ctypes
 import os
+import struct
 
 import numpy as np
 
@@ -479,6 +480,85 @@ def merge_layout_info(n_edges, waves=8, keys_in_lds=2):
     lib = load_library()
     _check(lib, lib.f3ds_merge_layout_info(ctypes.c_uint32(int(n_edges)), int(waves), int(keys_in_lds), out))
     return int(out[0]), int(out[1]), int(out[2]), bool(out[3])
+
+
+def constant(name):
+    """f3ds_constant: a limit of the kernels or of the host's batch-wide decisions by name ("NT_RING1", "EDGE_MULT", "d_reseed::BLOCK", ...), from the constant
+    the code itself uses.  Host arithmetic only.  The seed kernels' floating margins come back as floats."""
+    out = ctypes.c_uint64()
+    lib = load_library()
+    _check(lib, lib.f3ds_constant(str(name).encode(), ctypes.byref(out)))
+    if name in ("SEED_NN_MARGIN", "SEED_NN_ULP", "SEED_PRUNE_MARGIN"):
+        return struct.unpack("<d", struct.pack("<Q", out.value))[0]
+    return int(out.value)
+
+
+def constants():
+    """Every name f3ds_constant knows, with its value."""
+    lib = load_library()
+    lib.f3ds_constant_name.restype = ctypes.c_char_p
+    names, i = [], 0
+    while True:
+        n = lib.f3ds_constant_name(ctypes.c_size_t(i))
+        if n is None:
+            return {k: constant(k) for k in names}
+        names.append(n.decode()); i += 1
+
+
+def stage0_plan(max_depth, max_points, n_contexts, vox_tiles=1, sort_pairs=0):
+    """f3ds_stage0_plan: (tile path?, tile bits, index bits of a one-word sort key or -1 for (key, index) pairs, sort key bits without the index) of a batch
+    call with fresh contexts.  vox_tiles: F3DS_VOX_TILES (1: unset).  Host arithmetic only."""
+    out = (ctypes.c_int32 * 4)()
+    lib = load_library()
+    _check(lib, lib.f3ds_stage0_plan(int(max_depth), ctypes.c_uint32(int(max_points)), int(n_contexts), int(vox_tiles), int(sort_pairs), out))
+    return bool(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+
+CAP_EDGES, CAP_EVENTS, CAP_LEAF_POOL, CAP_ILIST = 0, 1, 2, 3
+
+
+def policy_capacity(what, count, mult, n_seeds=0, slack=32):
+    """f3ds_policy_capacity: entries of the adjacency list (CAP_EDGES: count seeds), the weight history (CAP_EVENTS: count edges), the leaf pool (CAP_LEAF_POOL:
+    count seeds) or the incident-list pool (CAP_ILIST: count edges, n_seeds, F3DS_ILIST_SLACK = slack) at the multiplier `mult`."""
+    out = ctypes.c_uint32()
+    lib = load_library()
+    _check(lib, lib.f3ds_policy_capacity(int(what), ctypes.c_uint32(int(count)), ctypes.c_uint32(int(n_seeds)), ctypes.c_uint32(int(mult)), ctypes.c_uint32(int(slack)), ctypes.byref(out)))
+    return int(out.value)
+
+
+def policy_grow(mult, cap):
+    """f3ds_policy_grow: a buffer's multiplier after an overflow (unchanged once it has reached `cap`)."""
+    out = ctypes.c_uint32()
+    lib = load_library()
+    _check(lib, lib.f3ds_policy_grow(ctypes.c_uint32(int(mult)), ctypes.c_uint32(int(cap)), ctypes.byref(out)))
+    return int(out.value)
+
+
+def policy_dense_penalty(penalty):
+    """f3ds_policy_dense_penalty: the calls a context stays off the tile path after its next refusal."""
+    lib = load_library()
+    lib.f3ds_policy_dense_penalty.restype = ctypes.c_uint32
+    return int(lib.f3ds_policy_dense_penalty(ctypes.c_uint32(int(penalty))))
+
+
+def policy_launch(frames, normals_forced=0, grid_target=None, grid_cap_forced=0):
+    """f3ds_policy_launch: (threads of the normals kernel, workgroups per frame of a streaming kernel, of a gathering kernel) in a call of `frames` frames."""
+    out = (ctypes.c_uint32 * 3)()
+    lib = load_library()
+    target = constant("GRID_TARGET") if grid_target is None else grid_target
+    _check(lib, lib.f3ds_policy_launch(int(frames), int(normals_forced), ctypes.c_uint32(int(target)), ctypes.c_uint32(int(grid_cap_forced)), out))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def policy_stage_layout(fixed_bytes, stage_rows, row_bytes, first_rows):
+    """f3ds_policy_stage_layout: ([[at, rows_at, first] per frame], first_bytes, total) of a label-image batch call's staging.  stage_rows: None for a call without rows."""
+    n = len(fixed_bytes)
+    arr = ctypes.c_size_t * n
+    slots = (ctypes.c_size_t * (3 * n))(); first, total = ctypes.c_size_t(), ctypes.c_size_t()
+    lib = load_library()
+    _check(lib, lib.f3ds_policy_stage_layout(ctypes.c_size_t(n), arr(*fixed_bytes), None if stage_rows is None else arr(*stage_rows), ctypes.c_size_t(int(row_bytes)),
+                                             ctypes.c_size_t(int(first_rows)), slots, ctypes.byref(first), ctypes.byref(total)))
+    return [[int(slots[3 * i]), int(slots[3 * i + 1]), int(slots[3 * i + 2])] for i in range(n)], int(first.value), int(total.value)
 
 
 def check_library_is_current(lib=None):

@@ -178,8 +178,20 @@ F3DS_HD float a_helper_dist_row(const SweepView& s, uint32_t g, const float vrow
 #define F3DS_OWNR_RTRUE 0x80000000u
 // memo byte = (tag << 2) | value; tag = (sweep % 63) + 1 so that entries written in an earlier sweep
 // read as "unknown" without clearing the array (it is zeroed before sweep 0, 63, 126, ...)
-F3DS_HD unsigned char a_sweep_tag(unsigned sweep) { return (unsigned char)((sweep % 63u) + 1u); }
-F3DS_HD bool a_sweep_needs_clear(unsigned sweep) { return sweep % 63u == 0u; }
+constexpr unsigned A_TAG_PERIOD = 63u;
+F3DS_HD unsigned char a_sweep_tag(unsigned sweep) { return (unsigned char)((sweep % A_TAG_PERIOD) + 1u); }
+F3DS_HD bool a_sweep_needs_clear(unsigned sweep) { return sweep % A_TAG_PERIOD == 0u; }
+// ---- Why a stage wants to run again: DevCounters::ev_overflow (f3ds_kernels.inc), stored by the kernel that ran out of room beside error = F3DS_ERR_UNSUPPORTED and
+// compared by the host (run_cluster, segment_batch_from), which grows the room named and runs the stage again.  The numbers are part of the F3DS_TRACE_ERR output.
+enum F3dsOverflow : int {
+    F3DS_OVF_NONE = 0,
+    F3DS_OVF_EVENTS = 1,          // merge loop: more weight-history events than ev_cap (grows ev_mult)
+    F3DS_OVF_LEAF_POOL = 2,       // merge loop: the leaf pool is full (grows pool_mult)
+    F3DS_OVF_EDGE_LIST = 3,       // adjacency pass: more adjacencies than the list holds (grows edge_mult)
+    F3DS_OVF_ILIST_POOL = 4,      // merge loop: the incident-list pool is full (grows ilist_mult)
+    F3DS_OVF_DENSE_VOXEL = 6,     // stage 0, tile path: a voxel of more than VL_MAX_RUN points (the batch runs again on the sort path)
+    F3DS_OVF_TILE_VOXELS = 7,     // stage 0, tile path: a tile of more than VT_ENT_MAX voxels, or more leaves than the tables hold (as 6)
+};
 // ---- Sweep control: the five words that steer sweep t, decided once per sweep by a_sweep_begin and read by every other sweep kernel -- and by the
 // CPU emulation of the sweeps (tests/emul) -- through the predicates below.  A word holds t + 1 while its statement is true of sweep t; no clearing between sweeps.
 struct SweepCtl {

@@ -126,6 +126,7 @@ __device__ __forceinline__ void comp_local_tiles(const unsigned char* depth, con
     }
     if (bad) head[1] = 1u;      // (every writer stores the same word)
 }
+constexpr int CC_TILES_PER_WG = 1;      // tiles a workgroup of d_comp_local takes per trip: what its launch divides the tile count by
 struct d_comp_local {
     static constexpr int BLOCK = 256;
     __device__ void operator()(const unsigned char* depth, const uint32_t* label, CompArgs a, uint32_t* parent, uint32_t* cnt, uint32_t* head) const {

@@ -57,6 +57,7 @@
 #include "f3ds_joints.h"
 #include "f3ds_components.h"
 #include "f3ds_cloud.h"
+#include "f3ds_batch_policy.h"
 
 using namespace f3ds;
 
@@ -147,7 +148,7 @@ const int g_inc_shift = [] { const char* e = dev_getenv("F3DS_INC_SHIFT"); retur
 // where hundreds of getenv() scans per call would also race with a setenv from another thread.  Tests still see per-call values.
 struct Switches {
     bool direct_labels = false, copy_stream = true, copy_duplex = false, split_voxel_accum = false, sweep_tiles = true, merge_spec = true, force_global_merge = false, no_stream_pool = false, sort_pairs = false, host_prof = false, trace_err = false, vox_hash = true, vox_tiles_forced = false, levels_global = false;
-    int normals_threads = 0, merge_nw = 0, merge_keys = -1; uint32_t tile_holes = 0, ilist_slack = 32, r_rounds = F3DS_R_ROUNDS, grid_cap = 0, rgc_first_cap = 0, rgj_first_cap = 0, cloud_path = 0; long relabel_lds_cap = -1;
+    int normals_threads = 0, merge_nw = 0, merge_keys = -1; uint32_t tile_holes = 0, ilist_slack = f3ds_policy::ILIST_SLACK, r_rounds = F3DS_R_ROUNDS, grid_cap = 0, rgc_first_cap = 0, rgj_first_cap = 0, cloud_path = 0; long relabel_lds_cap = -1;
     void read() {
         auto on = [](const char* n) { return dev_getenv(n) != nullptr; };
         auto num = [](const char* n, long dflt) { const char* e = dev_getenv(n); return e ? atol(e) : dflt; };
@@ -162,8 +163,8 @@ struct Switches {
         relabel_lds_cap = num("F3DS_RELABEL_LDS_CAP", -1);
         levels_global = num("F3DS_LEVELS_GLOBAL", 0) != 0;      // (tests: the hierarchy levels take the global-table form on small frames too)
         { const long v = num("F3DS_R_ROUNDS_RUN", F3DS_R_ROUNDS); r_rounds = v >= 1 && v <= F3DS_R_ROUNDS ? (uint32_t)v : (uint32_t)F3DS_R_ROUNDS; }
-        { const long v = num("F3DS_ILIST_SLACK", 32); ilist_slack = v >= 1 && v <= 32 ? (uint32_t)v : 32u; }      // tests: a short incident-list pool (the merge stage then reruns with a larger one)
-        { const long v = num("F3DS_GRID_CAP", 0); grid_cap = v >= 1 && v <= 2048 ? (uint32_t)v : 0u; }      // tests: 1 ... 2048 workgroups per frame, exactly, for grid_for() and grid_wide(): the grid-stride loops make several trips on small frames (0: unset)
+        { const long v = num("F3DS_ILIST_SLACK", f3ds_policy::ILIST_SLACK); ilist_slack = v >= 1 && v <= (long)f3ds_policy::ILIST_SLACK ? (uint32_t)v : f3ds_policy::ILIST_SLACK; }      // tests: a short incident-list pool (the merge stage then reruns with a larger one)
+        { const long v = num("F3DS_GRID_CAP", 0); grid_cap = v >= 1 && v <= (long)f3ds_policy::WIDE_CAP ? (uint32_t)v : 0u; }      // tests: 1 ... 2048 workgroups per frame, exactly, for grid_for() and grid_wide(): the grid-stride loops make several trips on small frames (0: unset)
         { const long v = num("F3DS_RGC_FIRST_CAP", 0); rgc_first_cap = v >= 1 && v <= 0x7fffffffl ? (uint32_t)v : 0u; }      // tests: a short first record buffer of f3ds_region_contacts (the frame then runs again with room for all; 0: unset)
         { const char* e = dev_getenv("F3DS_CLOUD_PATH"); cloud_path = !e ? 0u : (!strcmp(e, "direct") ? CD_PATH_DIRECT : (!strcmp(e, "ordered") ? CD_PATH_ORDERED : 0u)); }      // tests: how f3ds_cloud_regions walks its points, whatever K says (0: unset)
         { const long v = num("F3DS_RGJ_FIRST_CAP", 0); rgj_first_cap = v >= 1 && v <= 0x7fffffffl ? (uint32_t)v : 0u; }      // tests: likewise the first record buffer of f3ds_region_joints
@@ -254,15 +255,15 @@ struct f3ds_ctx {
     f3ds_result res;
     bool merge_in_lds = false;
     int merge_kind = 0;                // which merge kernel the last cluster stage ran (MergeKind)
-    uint32_t ev_mult = 64;             // weight-history events per initial edge the merge loop may write
+    uint32_t ev_mult = f3ds_policy::EV_MULT;             // weight-history events per initial edge the merge loop may write
     uint32_t pool_mult = 1;            // leaf pool size factor (grown on demand like ev_mult)
     uint32_t vox_cap = 0;              // bound on the leaves of the current frame that stage 0's tile path sized its buffers by
     bool vox_hashed = false;           // stage 0 of the current frame took the tile path (seg_vox_tiles)
     bool vox_dense = false;            // this context met a frame the tile path refuses (an unorganised cloud, a voxel of more than VL_MAX_RUN points): its frames take the sort path ...
-    uint32_t vox_dense_wait = 0, vox_dense_penalty = 8;      // ... for this many calls, then the tile path is tried again (8, 16, ... 1024 calls after every further refusal): one odd frame
+    uint32_t vox_dense_wait = 0, vox_dense_penalty = f3ds_policy::DENSE_PENALTY;      // ... for this many calls, then the tile path is tried again (8, 16, ... 1024 calls after every further refusal): one odd frame
                                                              // does not cost a long-lived context the faster stage 0 for good
     uint32_t ilist_mult = 1;           // incident-list pool size factor (its own: a leaf-pool overflow must not grow the list pool too)
-    uint32_t edge_mult = 32;           // adjacency list room per seed (S0 * edge_mult + 1024), grown on demand
+    uint32_t edge_mult = f3ds_policy::EDGE_MULT;           // adjacency list room per seed (S0 * edge_mult + 1024), grown on demand
     bool relabel_lds = true;           // stage 6 as one kernel (the region-id table fits LDS for every frame of the batch)
     int refined_itr = -1;              // >= 0: the r_* buffers hold the state after that many refinement iterations of this frame
     int idxbits = -1;                  // >= 0: the sorted point keys carry the point index in their low bits
@@ -361,23 +362,21 @@ int pregrow_scratch(f3ds_ctx* c) {
 // 192 frames per launch the streaming kernels of the sweeps run 1.5-2x faster on 32 fat workgroups per frame than on
 // 300 thin ones (per-workgroup prologue: argument pack, counters, stamps), see DESIGN.md 4b.  The hash-probing /
 // gathering kernels want every wave they can get and keep the old cap (grid_wide).  Set per batch call (one host thread).
-thread_local size_t g_grid_cap = 2048;
-thread_local size_t g_wide_cap = 2048;    // cap of grid_wide(): 2048 unless F3DS_GRID_CAP narrows every launch
+thread_local size_t g_grid_cap = f3ds_policy::WIDE_CAP;
+thread_local size_t g_wide_cap = f3ds_policy::WIDE_CAP;    // cap of grid_wide(): 2048 unless F3DS_GRID_CAP narrows every launch
 thread_local int g_batch_frames = 1;      // frames of the batch call this thread is running
 // batch calls inside f3ds_segment_batch right now, per device: a call whose merge dispatch shares the chip with other calls takes the 4-wave merge kernel (choose_merge_kind)
 std::atomic<int> g_batch_calls[16];
 struct BatchCallCount { int d; explicit BatchCallCount(int dev) : d(dev & 15) { g_batch_calls[d].fetch_add(1, std::memory_order_relaxed); } ~BatchCallCount() { g_batch_calls[d].fetch_sub(1, std::memory_order_relaxed); } };
 size_t grid_cap_for_batch(int frames) {
-    static const size_t target = dev_getenv("F3DS_GRID_TARGET") ? (size_t)atol(dev_getenv("F3DS_GRID_TARGET")) : 3072;      // with six calls in flight: 24 576: 2 150, 12 288: 2 250, 6 144: 2 280, 3 072 ... 1 024: 2 340 Mpoints/s
-    if (!target) return 2048;
-    size_t cap = target / (size_t)(frames > 0 ? frames : 1);
-    return cap < 8 ? 8 : (cap > 2048 ? 2048 : cap);
+    static const size_t target = dev_getenv("F3DS_GRID_TARGET") ? (size_t)atol(dev_getenv("F3DS_GRID_TARGET")) : f3ds_policy::GRID_TARGET;      // with six calls in flight: 24 576: 2 150, 12 288: 2 250, 6 144: 2 280, 3 072 ... 1 024: 2 340 Mpoints/s
+    return f3ds_policy::grid_cap_for_batch(frames, target, g_sw.grid_cap);
 }
 // Start of every entry call that records kernels, after g_sw.read(): the launch widths of this call, noted in its frames (F3DS_DBG_LAUNCH_SHAPE).
 // F3DS_GRID_CAP (development) replaces both caps by the given one; unset, grid_for() gets the batch's share and grid_wide() 2048 as ever.
 inline void set_launch_shape(f3ds_ctx* const* frames, int nframes) {
-    g_grid_cap = g_sw.grid_cap ? (size_t)g_sw.grid_cap : grid_cap_for_batch(nframes);
-    g_wide_cap = g_sw.grid_cap ? (size_t)g_sw.grid_cap : 2048;
+    g_grid_cap = grid_cap_for_batch(nframes);
+    g_wide_cap = f3ds_policy::wide_cap(g_sw.grid_cap);
     g_batch_frames = nframes;
     for (int i = 0; i < nframes; ++i) { frames[i]->launch_shape[0] = (uint32_t)g_grid_cap; frames[i]->launch_shape[1] = (uint32_t)g_wide_cap; frames[i]->launch_shape[2] = (uint32_t)nframes; }
 }
@@ -392,7 +391,9 @@ inline uint32_t grid_for(size_t work, int block) {
     return (uint32_t)g;
 }
 inline uint32_t pow2_ge(size_t x) { uint32_t p = 1; while (p < x) p <<= 1; return p; }
-int bits_for(uint64_t max_value) { int b = 0; while (b < 64 && (max_value >> b)) ++b; return b; }
+using f3ds_policy::bits_for;
+constexpr f3ds_policy::TileLimits VT_LIMITS = {VT_TILE, (uint32_t)VT_CNT_BITS, VT_ENT_MAX, VT_TAB};
+inline uint32_t seed_cell_grid(uint32_t C) { return (C + SEED_CELLS_PER_WG - 1u) / SEED_CELLS_PER_WG; }      // d_seed_nn / d_seed_filter: a wave per seed cell
 
 // record one kernel call of frame `c` (nothing is launched here)
 template <class K, class... As> void rec(f3ds_ctx* c, uint32_t gx, uint32_t lds, As... as);
@@ -423,7 +424,7 @@ inline void rec_op(f3ds_ctx* c, void* dst, const void* src, uint32_t value, size
     MultiOp& m = c->ops;
     if (m.n == 0) memset(&m, 0, sizeof m);
     m.dst[m.n] = static_cast<uint32_t*>(dst); m.src[m.n] = static_cast<const uint32_t*>(src); m.val[m.n] = value; m.words[m.n] = words; m.n++;      // (d_multi_op fills / copies any buffer word by word)
-    const uint32_t g = grid_for(words, 256);
+    const uint32_t g = grid_for(words, d_multi_op::BLOCK);
     if (g > c->ops_grid) c->ops_grid = g;
 }
 inline void rec_fill(f3ds_ctx* c, void* dst, uint32_t value, size_t bytes) { rec_op(c, dst, nullptr, value, bytes); }
@@ -603,15 +604,15 @@ int seg_sort(f3ds_ctx* c, int sort_bits, int idxbits) {      // idxbits >= 0: (c
     ENSURE(c->pt_voxel, n, pt_voxel);
     c->idxbits = idxbits;
     const int ks = idxbits < 0 ? 0 : idxbits;
-    rec<d_keys>(c, grid_for(n, 256), 0u, c->d_pts, n, c->fa, c->d_grid, k0, v0, ks);
+    rec<d_keys>(c, grid_for(n, d_keys::BLOCK), 0u, c->d_pts, n, c->fa, c->d_grid, k0, v0, ks);
     c->vs = nullptr;
     int rc = radix_sort(c, k0, v0, k1, v1, n, sort_bits, &c->ks, &c->vs, ks);
     if (rc) return rc;
     const uint64_t invalid = 1ull << (3 * c->h_dc->depth);
     if (g_sw.split_voxel_accum) {      // development: round 2's chain (d_point_gather reads the rank array)
-        rec<d_heads>(c, grid_for(n, 256), 0u, c->ks, n, invalid, flags, ks);
+        rec<d_heads>(c, grid_for(n, d_heads::BLOCK), 0u, c->ks, n, invalid, flags, ks);
         if ((rc = scan_u32(c, flags, incl, n))) return rc;
-        rec<d_segstart>(c, grid_for(n, 256), 0u, c->ks, flags, incl, n, invalid, seg_start, &c->d_dc->n_voxels, &c->d_dc->n_valid, ks);
+        rec<d_segstart>(c, grid_for(n, d_segstart::BLOCK), 0u, c->ks, flags, incl, n, invalid, seg_start, &c->d_dc->n_voxels, &c->d_dc->n_valid, ks);
         return F3DS_OK;
     }
     const uint32_t nt = n ? (n + SCAN_TILE - 1) / SCAN_TILE : 1u;
@@ -627,7 +628,7 @@ int seg_vox_tiles(f3ds_ctx* c, int code_bits, int tile_bits) {      // (code_bit
     const uint32_t n = c->n;
     const uint32_t ntiles = (n + VT_TILE - 1u) / VT_TILE;
     const uint64_t dcap64 = (uint64_t)ntiles * VT_ENT_MAX;
-    if (code_bits + tile_bits + VT_CNT_BITS > 64 || dcap64 > 0x7fffffffull || (uint64_t)ntiles * VT_TAB > 0x7fffffffull) return F3DS_ERR_UNSUPPORTED;      // (the caller takes the sort path)
+    if (!f3ds_policy::tile_path_fits(code_bits, tile_bits, n, VT_LIMITS)) return F3DS_ERR_UNSUPPORTED;      // (the caller takes the sort path: segment_batch_from asks the same question first)
     const uint32_t dcap = (uint32_t)dcap64;
     const uint64_t fin = c->h_dc->n_finite;
     const uint32_t capV = (uint32_t)std::max<uint64_t>(256u, std::min<uint64_t>(fin, dcap));
@@ -648,7 +649,7 @@ int seg_vox_tiles(f3ds_ctx* c, int code_bits, int tile_bits) {      // (code_bit
     rec<d_desc_offsets>(c, 1u, 0u, part, dcap, capV, seg_start, c->d_dc);
     rec<d_desc_apply>(c, nchunks, 0u, ks, vs, dcap, capV, tile_bits, c->fa, c->d_grid, part, bo_te, seg_start, vkey, c->d_dc);
     rec<d_tile_place>(c, std::min<uint32_t>(ntiles, (uint32_t)g_grid_cap * 16u), 0u, ploc, n, bo_te, list, pt_voxel, c->d_dc);
-    rec<d_voxel_list_accum>(c, std::min<uint32_t>(grid_wide(capV, 256), std::max<uint32_t>(64u, grid_wide(n / 8u, 256))), 0u, c->d_pts, list, seg_start, c->fa, vf, vcount, c->d_dc, capV);
+    rec<d_voxel_list_accum>(c, std::min<uint32_t>(grid_wide(capV, d_voxel_list_accum::BLOCK), std::max<uint32_t>(64u, grid_wide(n / 8u, d_voxel_list_accum::BLOCK))), 0u, c->d_pts, list, seg_start, c->fa, vf, vcount, c->d_dc, capV);
     c->vox_hashed = true;
     return F3DS_OK;
 }
@@ -666,7 +667,7 @@ int seg_neighbors(f3ds_ctx* c, uint32_t wgs) {
     if (!blocks) ENSURE(c->hvals, cap, hvals);
     rec_fill(c, hkeys, 0xFFFFFFFFu, words * 8);
     rec<d_vox_table>(c, wgs, 0u, c->vkey.p, V, c->d_grid, hkeys, hvals, c->hmask);
-    rec<d_neighbors>(c, grid_wide((size_t)V * 27, 256), 0u, c->vkey.p, c->d_dc, c->d_grid, c->fa.leaf_order, hkeys, hvals, c->hmask, nbr, nbrT);
+    rec<d_neighbors>(c, grid_wide((size_t)V * 27, d_neighbors::BLOCK), 0u, c->vkey.p, c->d_dc, c->d_grid, c->fa.leaf_order, hkeys, hvals, c->hmask, nbr, nbrT);
     return F3DS_OK;
 }
 // stage 0c + 1 + 2a: voxel sums, neighbour tables, normals, seed grid growth
@@ -677,10 +678,10 @@ int seg_voxels(f3ds_ctx* c) {
     ENSURE(c->vkey, (size_t)V * 3, vkey); ENSURE(c->vcount, V, vcount); ENSURE(c->vf, (size_t)V * 12, vf);
     if (g_sw.split_voxel_accum) {      // development: round 2's two kernels (a sorted copy of the frame in between)
         P16* spts; ENSURE(c->spts, n, spts);
-        rec<d_point_gather>(c, grid_wide(n, 256), 0u, c->d_pts, c->vs, c->ks, c->idxbits < 0 ? 0 : c->idxbits, c->incl.p, n, c->d_dc, spts, c->pt_voxel.p);
-        rec<d_voxel_accum>(c, grid_wide(V, 256), 0u, spts, c->ks, c->idxbits < 0 ? 0 : c->idxbits, c->seg_start.p, c->d_dc, c->fa, c->d_grid, vkey, vcount, vf);
+        rec<d_point_gather>(c, grid_wide(n, d_point_gather::BLOCK), 0u, c->d_pts, c->vs, c->ks, c->idxbits < 0 ? 0 : c->idxbits, c->incl.p, n, c->d_dc, spts, c->pt_voxel.p);
+        rec<d_voxel_accum>(c, grid_wide(V, d_voxel_accum::BLOCK), 0u, spts, c->ks, c->idxbits < 0 ? 0 : c->idxbits, c->seg_start.p, c->d_dc, c->fa, c->d_grid, vkey, vcount, vf);
     } else
-        rec<d_voxel_gather_accum>(c, grid_wide(V, 256), 0u, c->d_pts, c->vs, c->ks, c->idxbits < 0 ? 0 : c->idxbits, c->seg_start.p, n, c->d_dc, c->fa, c->d_grid, vkey, vcount, vf, c->pt_voxel.p);
+        rec<d_voxel_gather_accum>(c, grid_wide(V, d_voxel_gather_accum::BLOCK), 0u, c->d_pts, c->vs, c->ks, c->idxbits < 0 ? 0 : c->idxbits, c->seg_start.p, n, c->d_dc, c->fa, c->d_grid, vkey, vcount, vf, c->pt_voxel.p);
     return seg_neighbors(c, grid_for(V, 4096));
 }
 // stage 1b: voxel normals -- ONE launch per batch call, bracketed by its own pair of events (f3ds_result.ms_stage[7]: besides the merge
@@ -702,7 +703,7 @@ int seg_normals(f3ds_ctx* c) {
     // 256 threads per tile for the calls of a batch pipeline (their workgroups fit beside the 4-wave merge loops of the other calls), 384 otherwise (kernels.inc)
     const int nthr_env = g_sw.normals_threads;
     const uint32_t holes = g_sw.tile_holes;
-    if (nthr_env ? nthr_env == 256 : g_batch_frames >= 16)
+    if (f3ds_policy::normals_threads(g_batch_frames, nthr_env) == 256)
         rec<d_normals_t<256>>(c, std::min(nt, share), 0u, c->vf.p, c->nbr.p, c->d_dc, tn1, tord, tslots, holes);
     else
         rec<d_normals_t<384>>(c, std::min(nt, share), 0u, c->vf.p, c->nbr.p, c->d_dc, tn1, tord, tslots, holes);
@@ -724,13 +725,13 @@ int seg_seed_cells(f3ds_ctx* c, int sort_bits, int max_sdepth) {
     uint32_t *ckey, *cell_start, *v0, *v1; uint64_t *k0 = c->keys0.p, *k1 = c->keys1.p;
     ENSURE(c->vals0, V, v0); ENSURE(c->vals1, V, v1);
     ENSURE(c->ckey, (size_t)V * 3, ckey); ENSURE(c->cell_start, (size_t)V + 1, cell_start);
-    rec<d_seed_keys>(c, grid_for(V, 256), 0u, c->vf.p, c->d_dc, c->d_sgrid, ckey, k0, v0);
+    rec<d_seed_keys>(c, grid_for(V, d_seed_keys::BLOCK), 0u, c->vf.p, c->d_dc, c->d_sgrid, ckey, k0, v0);
     int rc = radix_sort(c, k0, v0, k1, v1, V, sort_bits, &c->cks, &c->cvs);
     if (rc) return rc;
     const uint64_t climit = max_sdepth >= 21 ? 0xFFFFFFFFFFFFFFFFull : (1ull << (3 * max_sdepth));
-    rec<d_heads>(c, grid_for(V, 256), 0u, c->cks, V, climit, c->flags.p, 0);
+    rec<d_heads>(c, grid_for(V, d_heads::BLOCK), 0u, c->cks, V, climit, c->flags.p, 0);
     if ((rc = scan_u32(c, c->flags.p, c->incl.p, V))) return rc;
-    rec<d_segstart>(c, grid_for(V, 256), 0u, c->cks, c->flags.p, c->incl.p, V, climit, cell_start, &c->d_dc->n_cells, &c->d_dc->seg_count, 0);
+    rec<d_segstart>(c, grid_for(V, d_segstart::BLOCK), 0u, c->cks, c->flags.p, c->incl.p, V, climit, cell_start, &c->d_dc->n_cells, &c->d_dc->seg_count, 0);
     return F3DS_OK;
 }
 // stage 2c: nearest voxel per cell, radius filter, kept seeds
@@ -743,12 +744,12 @@ int seg_seeds(f3ds_ctx* c) {
     rec_copy(c, sorted_vox, c->cvs, (size_t)V * 4);      // the sort buffers are reused later
     rec_fill(c, chk, 0xFFFFFFFFu, (size_t)ccap * 8);
     const uint32_t* ckey = c->ckey.p; const uint32_t* cell_start = c->cell_start.p; const float* vf = c->vf.p;
-    rec<d_cell_hash>(c, grid_for(C, 256), 0u, ckey, sorted_vox, cell_start, c->d_dc, chk, chvals, ccap - 1);
-    rec<d_seed_nn>(c, (C + 3u) / 4u, 0u, vf, ckey, sorted_vox, cell_start, c->d_dc, c->d_sgrid, chk, chvals, ccap - 1, seed_orig);
-    rec<d_seed_filter>(c, (C + 3u) / 4u, 0u, vf, ckey, sorted_vox, cell_start, c->d_dc, c->d_sgrid, chk, chvals, ccap - 1, seed_orig, a_radius_sq(c->prm.seed_res), a_min_points(c->prm.seed_res, c->prm.voxel_res), keep);
+    rec<d_cell_hash>(c, grid_for(C, d_cell_hash::BLOCK), 0u, ckey, sorted_vox, cell_start, c->d_dc, chk, chvals, ccap - 1);
+    rec<d_seed_nn>(c, seed_cell_grid(C), 0u, vf, ckey, sorted_vox, cell_start, c->d_dc, c->d_sgrid, chk, chvals, ccap - 1, seed_orig);
+    rec<d_seed_filter>(c, seed_cell_grid(C), 0u, vf, ckey, sorted_vox, cell_start, c->d_dc, c->d_sgrid, chk, chvals, ccap - 1, seed_orig, a_radius_sq(c->prm.seed_res), a_min_points(c->prm.seed_res, c->prm.voxel_res), keep);
     int rc = scan_u32(c, keep, c->incl.p, C);
     if (rc) return rc;
-    rec<d_seed_compact>(c, grid_for(C, 256), 0u, seed_orig, keep, c->incl.p, c->d_dc, seed_kept);
+    rec<d_seed_compact>(c, grid_for(C, d_seed_compact::BLOCK), 0u, seed_orig, keep, c->incl.p, c->d_dc, seed_kept);
     return F3DS_OK;
 }
 // stage 3: helpers and all label-propagation sweeps
@@ -781,11 +782,11 @@ int seg_sweeps_on(f3ds_ctx* c, const SweepBufs& sb) {
     rec_fill(c, ghost_next, 0u, (size_t)(S0 + 1) * 4);
     { const float fmax = F3DS_FLT_MAX; uint32_t bits; memcpy(&bits, &fmax, 4); rec_fill(c, dist0, bits, (size_t)V * 4); }
     if (sb.reseed) {
-        rec<d_reseed_own>(c, grid_for(S0, 256), 0u, sb.seeds, S0, owner0);
-        rec<d_reseed_init>(c, grid_for(S0 + 1, 256), 0u, sb.seeds, S0, owner0, ghost_vox, ghost_active, ghost_done, hlo, hhi, hcount, tl, tcnt);
+        rec<d_reseed_own>(c, grid_for(S0, d_reseed_own::BLOCK), 0u, sb.seeds, S0, owner0);
+        rec<d_reseed_init>(c, grid_for(S0 + 1, d_reseed_init::BLOCK), 0u, sb.seeds, S0, owner0, ghost_vox, ghost_active, ghost_done, hlo, hhi, hcount, tl, tcnt);
     } else {
-        rec<d_helper_own>(c, grid_for(S0, 256), 0u, sb.seeds, S0, owner0);
-        rec<d_helper_init>(c, grid_for(S0 + 1, 256), 0u, sb.seeds, S0, owner0, ghost_vox, ghost_active, ghost_done, hlo, hhi, hcount, hc, tl, tcnt);
+        rec<d_helper_own>(c, grid_for(S0, d_helper_own::BLOCK), 0u, sb.seeds, S0, owner0);
+        rec<d_helper_init>(c, grid_for(S0 + 1, d_helper_init::BLOCK), 0u, sb.seeds, S0, owner0, ghost_vox, ghost_active, ghost_done, hlo, hhi, hcount, hc, tl, tcnt);
     }
     const int* nbrT = c->nbrT.p; const float* vf = sb.vf;
     SweepFrame a;
@@ -806,12 +807,12 @@ int seg_sweeps_on(f3ds_ctx* c, const SweepBufs& sb) {
         const bool can_skip = t >= 2u;
         const bool rounds = g_inc_shift >= 0 && can_skip;
         const uint32_t nrounds = rounds ? g_sw.r_rounds : 0u;      // (F3DS_R_ROUNDS; F3DS_R_ROUNDS_RUN=1|2 lets tests reach the non-convergence fallback of d_sweep_R)
-        rec<d_sweep_R_first>(c, grid_for(V, 256), 0u, a, a_sweep_tag(t), t, nrounds);      // pre-pass of a full sweep | round 0 of an incremental one
-        for (uint32_t r = 1; r < nrounds; ++r) rec<d_sweep_R_round>(c, grid_for(V, 256), 0u, a, t, r, nrounds);
-        for (uint32_t pass = 0; pass < F3DS_R_PASSES; ++pass) rec<d_sweep_R>(c, pass == 0 ? grid_for(V, 256) : 64u, 0u, a, a_sweep_tag(t), t, pass);
+        rec<d_sweep_R_first>(c, grid_for(V, d_sweep_R_first::BLOCK), 0u, a, a_sweep_tag(t), t, nrounds);      // pre-pass of a full sweep | round 0 of an incremental one
+        for (uint32_t r = 1; r < nrounds; ++r) rec<d_sweep_R_round>(c, grid_for(V, d_sweep_R_round::BLOCK), 0u, a, t, r, nrounds);
+        for (uint32_t pass = 0; pass < F3DS_R_PASSES; ++pass) rec<d_sweep_R>(c, pass == 0 ? grid_for(V, d_sweep_R::BLOCK) : 64u, 0u, a, a_sweep_tag(t), t, pass);
         rec<d_sweep_R_tail>(c, 1u, 0u, a, a_sweep_tag(t), t);
-        rec<d_sweep_claim>(c, grid_for(V, 256), 0u, a, t);
-        rec<d_centroid>(c, grid_for((size_t)S0 * 64u, 256), 0u, a, t);
+        rec<d_sweep_claim>(c, grid_for(V, d_sweep_claim::BLOCK), 0u, a, t);
+        rec<d_centroid>(c, grid_for((size_t)S0 * 64u, d_centroid::BLOCK), 0u, a, t);
     }
     return F3DS_OK;
 }
@@ -834,13 +835,13 @@ int seg_supervoxels(f3ds_ctx* c) {
     rec_fill(c, rcnt0, 0u, (size_t)(S0 + 1) * 4);
     rec<d_sv_fill>(c, S0 ? (S0 + 3u) / 4u : 1u, 0u,      // (four helpers per workgroup, one per row of its wave)
                    c->vf.p, c->owner0.p, S0, c->hlo.p, c->hhi.p, c->ghost_vox.p, c->ghost_active.p, c->hcount.p, loff, c->hc.p, rows, row_voxel, racc0, rcnt0, rrec0, ralive0, c->d_dc, c->htiles.p, c->htcnt.p, V);
-    const uint32_t ecap = (uint32_t)std::min<uint64_t>((uint64_t)S0 * c->edge_mult + 1024u, 0x7fffffffu);
+    const uint32_t ecap = f3ds_policy::edge_capacity(S0, c->edge_mult);
     const uint32_t ehcap = pow2_ge((size_t)ecap * 2);
     ENSURE(c->ehk, ehcap, ehk);
     ENSURE(c->ekeys0, ecap, ek0); ENSURE(c->ekeys1, ecap, ek1); ENSURE(c->evals0, ecap, ev0); ENSURE(c->evals1, ecap, ev1);
     rec_fill(c, ehk, 0xFFFFFFFFu, (size_t)ehcap * 8);
-    rec<d_edges>(c, grid_for(V, 256), 0u, V, S0, c->nbrT.p, c->owner0.p, ehk, ehcap - 1, ek0, ecap, c->d_dc);
-    rec<d_edges_ghost>(c, grid_for(S0, 256), 0u, V, S0, c->ghost_vox.p, c->ghost_active.p, c->nbrT.p, c->owner0.p, ehk, ehcap - 1, ek0, ecap, c->d_dc);
+    rec<d_edges>(c, grid_for(V, d_edges::BLOCK), 0u, V, S0, c->nbrT.p, c->owner0.p, ehk, ehcap - 1, ek0, ecap, c->d_dc);
+    rec<d_edges_ghost>(c, grid_for(S0, d_edges_ghost::BLOCK), 0u, V, S0, c->ghost_vox.p, c->ghost_active.p, c->nbrT.p, c->owner0.p, ehk, ehcap - 1, ek0, ecap, c->d_dc);
     return F3DS_OK;
 }
 // stage 4b: sorted edge list
@@ -849,10 +850,10 @@ int seg_edge_sort(f3ds_ctx* c, int sort_bits) {
     uint32_t *ea0, *eb0; ENSURE(c->ea0, E, ea0); ENSURE(c->eb0, E, eb0);
     uint32_t* evs;
     { uint32_t* h; ENSURE(c->hist, (size_t)RS_BINS * (((size_t)E * 2 + RS_TILE - 1) / RS_TILE + 1), h); }      // also holds the 2E-delta sort of seg_cluster_front, recorded before this one is flushed
-    rec<d_iota>(c, grid_for(E, 256), 0u, c->evals0.p, E);
+    rec<d_iota>(c, grid_for(E, d_iota::BLOCK), 0u, c->evals0.p, E);
     int rc = radix_sort(c, c->ekeys0.p, c->evals0.p, c->ekeys1.p, c->evals1.p, E, sort_bits, &c->eks, &evs);
     if (rc) return rc;
-    rec<d_edge_init>(c, grid_for(E, 256), 0u, c->eks, E, S0, ea0, eb0);
+    rec<d_edge_init>(c, grid_for(E, d_edge_init::BLOCK), 0u, c->eks, E, S0, ea0, eb0);
     return F3DS_OK;
 }
 // d_merge_il_t<NW, RES>: LDS a frame with E adjacencies needs (merge_il_offsets, f3ds_kernels.inc) and whether the kernel can take it
@@ -898,7 +899,7 @@ int seg_cluster_front(f3ds_ctx* c, const f3ds_params* prm, int kind) {
     MergeDev m;
     memset(&m, 0, sizeof m);
     m.E = E; m.S0 = S0; m.threshold = prm->threshold; m.dc = c->d_dc;
-    { const uint64_t cap = (uint64_t)E * c->ev_mult + 4096u; m.ev_cap = cap > 0x7fffffffull ? 0x7fffffffu : (uint32_t)cap; }      // weight-history events: grown on demand (run_cluster)
+    m.ev_cap = f3ds_policy::event_capacity(E, c->ev_mult);      // weight-history events: grown on demand (run_cluster)
     ENSURE(c->ea, E, m.ea); ENSURE(c->eb, E, m.eb); ENSURE(c->ew, ((size_t)E + 2047) & ~(size_t)2047, m.ew); /* d_merge: weights; d_merge_cw_t<., 0>: endpoints */ ENSURE(c->eku, ((size_t)E + 2047) & ~(size_t)2047, m.eku);      // (Ecap of the widest merge kernel)
     ENSURE(c->ehist, E, m.ehist); ENSURE(c->ealive, E, m.ealive);
     ENSURE(c->ev_epoch, m.ev_cap, m.ev_epoch); ENSURE(c->ev_key, m.ev_cap, m.ev_key); ENSURE(c->ev_prev, m.ev_cap, m.ev_prev);
@@ -918,31 +919,26 @@ int seg_cluster_front(f3ds_ctx* c, const f3ds_params* prm, int kind) {
     rec_copy(c, m.eb, c->eb0.p, (size_t)E * 4);
     MergeLds xl;
     merge_il_layout(E, S0, use_lds ? mk_waves(kind) : 8, use_lds ? mk_res(kind) : 0, &xl);
-    uint32_t logS = 1; while ((1u << logS) < S0 + 2u) ++logS;
-    xl.pool_cap = (S0 + 1u) * (4u * logS + 8u) * c->pool_mult;
+    xl.pool_cap = f3ds_policy::leaf_pool_capacity(S0, c->pool_mult);
     ENSURE(c->pool, xl.pool_cap, xl.pool); ENSURE(c->rstart, S0 + 1, xl.rstart); ENSURE(c->rnleaf, S0 + 1, xl.rnleaf);
     ENSURE(c->rcap, S0 + 1, xl.rcap);
     // incident-edge lists of the regions (d_inc_build): the initial lists take 2 E entries, a merge whose touched list outgrows a's segment takes a fresh one
-    // (only the incident-list kernels have them: d_merge, the all-global fallback of the large-E scenes, scans the edge arrays.  What the loop can need is bounded: a
-    // merge that leaves its segment takes at most nt + nt / 2 + 4 fresh entries, nt <= MC_TL_CAP, and there are at most S0 - 1 merges)
+    // (only the incident-list kernels have them: d_merge, the all-global fallback of the large-E scenes, scans the edge arrays)
     if (use_lds) {
-        const uint64_t bound = 2ull * E + (uint64_t)(S0 ? S0 - 1u : 0u) * (MC_TL_CAP + MC_TL_CAP / 2u + 4u) + 1024u;
-        uint64_t cap = 2ull * E + (uint64_t)g_sw.ilist_slack * E * c->ilist_mult + (g_sw.ilist_slack < 32u ? 16u : 1024u);
-        if (cap > bound) cap = bound;
-        xl.ilist_cap = cap > 0x7fffffffull ? 0x7fffffffu : (uint32_t)cap;
+        xl.ilist_cap = f3ds_policy::ilist_capacity(E, S0, g_sw.ilist_slack, c->ilist_mult, MC_TL_CAP);
         ENSURE(c->ilist, xl.ilist_cap, xl.ilist); ENSURE(c->istart, S0 + 1, xl.istart); ENSURE(c->ilen, S0 + 1, xl.ilen); ENSURE(c->icap, S0 + 1, xl.icap);
     }
     if (use_lds) rec<d_inc_build>(c, 1u, 0u, E, S0, m.ea, m.eb, xl.istart, xl.ilen, xl.icap, xl.ilist);
     xl.stop_key = (prm->threshold != prm->threshold) ? 0u : n_weight_key(prm->threshold);
     c->merge_in_lds = use_lds; c->merge_kind = kind;
-    rec<d_region_reset>(c, grid_for(S0 + 1, 256), 0u, S0, c->hcount.p, m.rhead, m.rtail, m.lnext, m.parent, m.markA, m.markB, xl.pool, xl.rstart, xl.rnleaf, xl.rcap, c->loff.p);
+    rec<d_region_reset>(c, grid_for(S0 + 1, d_region_reset::BLOCK), 0u, S0, c->hcount.p, m.rhead, m.rtail, m.lnext, m.parent, m.markA, m.markB, xl.pool, xl.rstart, xl.rnleaf, xl.rcap, c->loff.p);
     m.mp.color_metric = prm->color_metric; m.mp.geom_metric = prm->geom_metric; m.mp.merging = prm->merging; m.mp.lambda = lambda; m.mp.bins = bins;
     uint64_t *sk0 = nullptr, *sk1 = nullptr; uint32_t *sv0 = nullptr, *sv1 = nullptr;
     if (prm->merging == F3DS_ADAPTIVE_LAMBDA) {
         ENSURE(c->skeys0, (size_t)E * 2, sk0); ENSURE(c->skeys1, (size_t)E * 2, sk1);
         ENSURE(c->svals0, (size_t)E * 2, sv0); ENSURE(c->svals1, (size_t)E * 2, sv1);
     }
-    rec<d_edge_deltas>(c, grid_for(E, 256), 0u, E, m.ea, m.eb, m.rrec, prm->color_metric, prm->geom_metric, deltas, sk0, sv0);
+    rec<d_edge_deltas>(c, grid_for(E, d_edge_deltas::BLOCK), 0u, E, m.ea, m.eb, m.rrec, prm->color_metric, prm->geom_metric, deltas, sk0, sv0);
     if (prm->merging == F3DS_ADAPTIVE_LAMBDA) {
         uint64_t* ks; uint32_t* vs;
         int rc = radix_sort(c, sk0, sv0, sk1, sv1, E * 2u, 33, &ks, &vs);
@@ -952,11 +948,11 @@ int seg_cluster_front(f3ds_ctx* c, const f3ds_params* prm, int kind) {
         uint32_t* hist; float* cdf;
         ENSURE(c->cdf_hist, (size_t)2 * (bins > 0 ? bins : 1), hist); ENSURE(c->cdf, (size_t)2 * (bins > 0 ? bins : 1), cdf);
         rec_fill(c, hist, 0u, (size_t)2 * (bins > 0 ? bins : 1) * 4);
-        rec<d_cdf_hist>(c, grid_for((size_t)E * 2, 256), 0u, E, deltas, bins, hist, c->d_dc);
+        rec<d_cdf_hist>(c, grid_for((size_t)E * 2, d_cdf_hist::BLOCK), 0u, E, deltas, bins, hist, c->d_dc);
         rec<d_cdf_scan>(c, 1u, 0u, E, bins, hist, cdf);
         m.mp.cdf_c = cdf; m.mp.cdf_g = cdf + bins;
     }
-    rec<d_edge_weights>(c, grid_for(E, 256), 0u, m, deltas);
+    rec<d_edge_weights>(c, grid_for(E, d_edge_weights::BLOCK), 0u, m, deltas);
     c->mdev = m; c->mlds = xl; c->host_lambda = lambda;
     return F3DS_OK;
 }
@@ -990,12 +986,12 @@ int seg_labels(f3ds_ctx* c) {
     else ENSURE(c->labels, n, d_labels);
     if (c->relabel_lds) {
         // (every workgroup builds the table: a lone frame does not get more workgroups than it has 4096-point slices)
-        const uint32_t gx = std::min(grid_for(n, 256), grid_wide(n, 4096));
+        const uint32_t gx = std::min(grid_for(n, d_relabel::BLOCK), grid_wide(n, 4096));
         rec<d_relabel>(c, gx, (S0 + 1u) * 4u, n, c->pt_voxel.p, c->owner0.p, S0, m.parent, m.ralive, root, rincl, d_labels, c->d_dc);
     } else {
         uint32_t* rank; ENSURE(c->rrank, S0 + 1, rank);
         rec<d_region_ids>(c, 1u, 0u, S0, m.parent, m.ralive, rank, root, rincl, c->d_dc);
-        rec<d_point_labels>(c, grid_for(n, 256), 0u, n, c->pt_voxel.p, c->owner0.p, rank, d_labels);
+        rec<d_point_labels>(c, grid_for(n, d_point_labels::BLOCK), 0u, n, c->pt_voxel.p, c->owner0.p, rank, d_labels);
     }
     return F3DS_OK;
 }
@@ -1225,69 +1221,76 @@ static uint32_t* pinned_device_alias(uint32_t* host) {
 }
 
 // cluster stage for the live frames (also the whole of f3ds_recluster)
+// The stage starts from the untouched supervoxel state, so a frame that ran out of room -- or whose merge did not fit the LDS kernel's lists -- makes it run again
+// for all frames: the loop below goes round until neither happens.
 int run_cluster(Batch& b, const f3ds_params* prm, uint32_t* const* labels_of, const std::vector<int>& index_of, int labels_on_device, bool force_global = false) {
-    const int kind = choose_merge_kind(b.fr, force_global);      // one kernel for the whole batch
-    const bool all_lds = kind != MK_GLOBAL;
-    int rc = for_frames(b, [&](f3ds_ctx* c) { return seg_cluster_front(c, prm, kind); });
-    if (rc || (rc = flush(b))) return rc;
-    stage_mark(b, 5);
-    if ((rc = for_frames(b, seg_merge)) || (rc = flush(b))) return rc;
-    stage_mark(b, 6);
-    for (size_t i = 0; i < b.fr.size(); ++i) {
-        uint32_t* out = labels_of ? labels_of[index_of[i]] : nullptr;
-        // F3DS_DIRECT_LABELS=1 (experiment, measured and not the default): a host label buffer that is pinned (hipHostMalloc / hipHostRegister) is written by the relabel kernel
-        // itself through its device address instead of a staging buffer + device-to-host copy.  With six calls in flight the pinned-host-in / host-out rate of bench.py
-        // drops from 2 060 to 1 830 Mpoints/s: the kernel holds its workgroups while its stores trickle up the link.
-        if (out && !labels_on_device && g_sw.direct_labels) out = pinned_device_alias(out);
-        else if (!labels_on_device) out = nullptr;
-        b.fr[i]->user_labels = out;
-    }
-    {
-        const uint32_t cap = g_sw.relabel_lds_cap >= 0 ? (uint32_t)g_sw.relabel_lds_cap : RL_LDS_CAP;      // (tests: 0 forces the two-kernel form)
-        bool fits = true;
-        for (f3ds_ctx* c : b.fr) if (c->S0 + 1u > cap) fits = false;
-        for (f3ds_ctx* c : b.fr) c->relabel_lds = fits;
-    }
-    if ((rc = for_frames(b, seg_labels)) || (rc = flush(b))) return rc;
-    stage_mark(b, 7);
-    {
-        bool want = false;
-        for (size_t i = 0; i < b.fr.size(); ++i) if (labels_of && labels_of[index_of[i]] && !b.fr[i]->user_labels && b.fr[i]->n) want = true;
-        hipStream_t dl = nullptr;
-        if (want && !labels_on_device && (rc = download_begin(b, &dl))) return rc;
+    int rc;
+    for (;;) {
+        const int kind = choose_merge_kind(b.fr, force_global);      // one kernel for the whole batch
+        const bool all_lds = kind != MK_GLOBAL;
+        rc = for_frames(b, [&](f3ds_ctx* c) { return seg_cluster_front(c, prm, kind); });
+        if (rc || (rc = flush(b))) return rc;
+        stage_mark(b, 5);
+        if ((rc = for_frames(b, seg_merge)) || (rc = flush(b))) return rc;
+        stage_mark(b, 6);
         for (size_t i = 0; i < b.fr.size(); ++i) {
-            f3ds_ctx* c = b.fr[i];
             uint32_t* out = labels_of ? labels_of[index_of[i]] : nullptr;
-            if (out && !c->user_labels && c->n) HIPCHECK(hipMemcpyAsync(out, c->labels.p, (size_t)c->n * 4, hipMemcpyDeviceToHost, dl ? dl : b.st));
-            c->user_labels = nullptr;
+            // F3DS_DIRECT_LABELS=1 (experiment, measured and not the default): a host label buffer that is pinned (hipHostMalloc / hipHostRegister) is written by the relabel kernel
+            // itself through its device address instead of a staging buffer + device-to-host copy.  With six calls in flight the pinned-host-in / host-out rate of bench.py
+            // drops from 2 060 to 1 830 Mpoints/s: the kernel holds its workgroups while its stores trickle up the link.
+            if (out && !labels_on_device && g_sw.direct_labels) out = pinned_device_alias(out);
+            else if (!labels_on_device) out = nullptr;
+            b.fr[i]->user_labels = out;
         }
-        if ((rc = download_queued(b, dl)) || (rc = flush_sync(b)) || (rc = download_wait(b, dl))) return rc;      // (the frames' counters come to the host while the labels travel)
-    }
-    {
-        // a frame whose merge loop re-weights more edges than its event arrays hold (huge regions of tiny supervoxels)
-        // runs the stage again -- it starts from the untouched supervoxel state -- with four times the room
-        bool again = false;
-        for (f3ds_ctx* c : b.fr) {
-            if (c->h_dc->ev_overflow == 1 && c->ev_mult < 16384u) { c->ev_mult *= 4u; again = true; }
-            if (c->h_dc->ev_overflow == 2 && c->pool_mult < 64u) { c->pool_mult *= 4u; again = true; }
-            if (c->h_dc->ev_overflow == 4 && c->ilist_mult < 4096u) { c->ilist_mult *= 4u; again = true; }
+        {
+            const uint32_t cap = g_sw.relabel_lds_cap >= 0 ? (uint32_t)g_sw.relabel_lds_cap : RL_LDS_CAP;      // (tests: 0 forces the two-kernel form)
+            bool fits = true;
+            for (f3ds_ctx* c : b.fr) if (c->S0 + 1u > cap) fits = false;
+            for (f3ds_ctx* c : b.fr) c->relabel_lds = fits;
         }
-        if (again) {
-            if (g_sw.trace_err) fprintf(stderr, "f3ds: merge stage of %zu frames runs again with more history / leaf-pool room\n", b.fr.size());
-            for (f3ds_ctx* c : b.fr) if ((rc = clear_counters(c, b.st, &DevCounters::error, &DevCounters::ev_overflow))) return rc;
-            return run_cluster(b, prm, labels_of, index_of, labels_on_device, force_global);
+        if ((rc = for_frames(b, seg_labels)) || (rc = flush(b))) return rc;
+        stage_mark(b, 7);
+        {
+            bool want = false;
+            for (size_t i = 0; i < b.fr.size(); ++i) if (labels_of && labels_of[index_of[i]] && !b.fr[i]->user_labels && b.fr[i]->n) want = true;
+            hipStream_t dl = nullptr;
+            if (want && !labels_on_device && (rc = download_begin(b, &dl))) return rc;
+            for (size_t i = 0; i < b.fr.size(); ++i) {
+                f3ds_ctx* c = b.fr[i];
+                uint32_t* out = labels_of ? labels_of[index_of[i]] : nullptr;
+                if (out && !c->user_labels && c->n) HIPCHECK(hipMemcpyAsync(out, c->labels.p, (size_t)c->n * 4, hipMemcpyDeviceToHost, dl ? dl : b.st));
+                c->user_labels = nullptr;
+            }
+            if ((rc = download_queued(b, dl)) || (rc = flush_sync(b)) || (rc = download_wait(b, dl))) return rc;      // (the frames' counters come to the host while the labels travel)
         }
-    }
-    if (all_lds) {
-        // a merge whose two regions touch more than ML_TL_CAP edges does not fit the LDS kernel's lists: the stage
-        // (it starts from the untouched supervoxel state) runs again with the global-memory kernel
-        bool again = false;
-        for (f3ds_ctx* c : b.fr) if (c->h_dc->error == F3DS_ERR_UNSUPPORTED) again = true;
-        if (again) {
-            if (g_sw.trace_err) fprintf(stderr, "f3ds: merge stage of %zu frames runs again with the global-memory kernel\n", b.fr.size());
-            for (f3ds_ctx* c : b.fr) if ((rc = clear_counters(c, b.st, &DevCounters::error))) return rc;
-            return run_cluster(b, prm, labels_of, index_of, labels_on_device, true);
+        {
+            // a frame whose merge loop re-weights more edges than its event arrays hold (huge regions of tiny supervoxels)
+            // runs the stage again -- it starts from the untouched supervoxel state -- with four times the room
+            bool again = false;
+            for (f3ds_ctx* c : b.fr) {
+                if (c->h_dc->ev_overflow == F3DS_OVF_EVENTS && f3ds_policy::grow(&c->ev_mult, f3ds_policy::EV_MULT_CAP)) again = true;
+                if (c->h_dc->ev_overflow == F3DS_OVF_LEAF_POOL && f3ds_policy::grow(&c->pool_mult, f3ds_policy::POOL_MULT_CAP)) again = true;
+                if (c->h_dc->ev_overflow == F3DS_OVF_ILIST_POOL && f3ds_policy::grow(&c->ilist_mult, f3ds_policy::ILIST_MULT_CAP)) again = true;
+            }
+            if (again) {
+                if (g_sw.trace_err) fprintf(stderr, "f3ds: merge stage of %zu frames runs again with more history / leaf-pool room\n", b.fr.size());
+                for (f3ds_ctx* c : b.fr) if ((rc = clear_counters(c, b.st, &DevCounters::error, &DevCounters::ev_overflow))) return rc;
+                continue;
+            }
         }
+        if (all_lds) {
+            // a merge whose two regions touch more than ML_TL_CAP edges does not fit the LDS kernel's lists: the stage
+            // (it starts from the untouched supervoxel state) runs again with the global-memory kernel
+            bool again = false;
+            for (f3ds_ctx* c : b.fr) if (c->h_dc->error == F3DS_ERR_UNSUPPORTED) again = true;
+            if (again) {
+                if (g_sw.trace_err) fprintf(stderr, "f3ds: merge stage of %zu frames runs again with the global-memory kernel\n", b.fr.size());
+                for (f3ds_ctx* c : b.fr) if ((rc = clear_counters(c, b.st, &DevCounters::error))) return rc;
+                force_global = true;
+                continue;
+            }
+        }
+        break;
     }
     for (f3ds_ctx* c : b.fr) {
         if (c->h_dc->error) return trace_err(c->h_dc->error, "merge", c);
@@ -1322,7 +1325,7 @@ int f3ds_create(int device, f3ds_ctx** out) {
     HIPCHECK(hipSetDevice(device));
     f3ds_ctx* c = new f3ds_ctx;
     c->device = device;
-    if (const char* e = dev_getenv("F3DS_EDGE_MULT")) { const int v = atoi(e); if (v >= 1 && v <= 32) c->edge_mult = (uint32_t)v; }      // tests: start with a short adjacency list
+    if (const char* e = dev_getenv("F3DS_EDGE_MULT")) { const int v = atoi(e); if (v >= 1 && v <= (int)f3ds_policy::EDGE_MULT) c->edge_mult = (uint32_t)v; }      // tests: start with a short adjacency list
     const int rc = [c]() -> int {
         HIPCHECK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
         c->stream = c->own_stream;
@@ -1439,25 +1442,25 @@ int segment_batch_from(f3ds_ctx** ctxs, int nctx, Source&& source, int sources_o
     // Stage 0b/0c.  Default: the hash path (only the voxels are sorted).  The sort path (every point's key through a three-pass radix sort) remains for frames with
     // very dense voxels, for lone frames (below) and behind F3DS_VOX_TILES=0.
     // (a lone frame takes the sort path: two of the tile path's kernels are one workgroup per frame -- 2.4 ms on a lone frame's critical path, nothing in a batch)
-    bool hashed = g_sw.vox_hash && (nctx >= 4 || g_sw.vox_tiles_forced);
+    bool hashed = f3ds_policy::tile_path_wanted(nctx, g_sw.vox_hash, g_sw.vox_tiles_forced);
     for (f3ds_ctx* c : b.fr) {
         c->vox_hashed = false;
         if (c->vox_dense && hashed) { if (c->vox_dense_wait) c->vox_dense_wait--; else c->vox_dense = false; }      // (counted in calls that would have taken the tile path)
     }
     for (f3ds_ctx* c : b.fr) if (c->vox_dense) hashed = false;
+    uint32_t maxn = 1;
+    for (f3ds_ctx* c : b.fr) if (c->n > maxn) maxn = c->n;
+    const f3ds_policy::Stage0Plan plan = f3ds_policy::stage0_plan(maxd, maxn, hashed, g_sw.sort_pairs, VT_LIMITS);
     if (hashed) {
-        uint32_t maxtiles = 1;
-        for (f3ds_ctx* c : b.fr) maxtiles = std::max(maxtiles, (c->n + VT_TILE - 1u) / VT_TILE);
-        const int tile_bits = bits_for((uint64_t)maxtiles - 1u);
-        rc = for_frames(b, [&](f3ds_ctx* c) { return seg_vox_tiles(c, 3 * maxd, tile_bits); });
+        rc = plan.tiles ? for_frames(b, [&](f3ds_ctx* c) { return seg_vox_tiles(c, plan.code_bits, plan.tile_bits); }) : F3DS_ERR_UNSUPPORTED;
         if (rc == F3DS_ERR_UNSUPPORTED) {      // (a grid too deep / a frame too long for this path: nothing was flushed)
             for (f3ds_ctx* c : b.fr) { reset_recording(c); c->vox_hashed = false; }
             hashed = false;
         } else if (rc || (rc = flush_sync(b))) return rc;
         if (hashed && g_sw.trace_err) for (f3ds_ctx* c : b.fr) fprintf(stderr, "f3ds: tile path: most voxels in a tile %u, descriptors %u, leaves %u, lists sorted %u\n", c->h_dc->vox_max_tile, c->h_dc->seg_count, c->h_dc->n_voxels, c->h_dc->vox_disorder);
-        if (hashed) for (f3ds_ctx* c : b.fr) if (c->h_dc->ev_overflow == 6 || c->h_dc->ev_overflow == 7) {
-            if (g_sw.trace_err) fprintf(stderr, "f3ds: tile path refused a frame: %s (descriptors %u, leaves %u)\n", c->h_dc->ev_overflow == 6 ? "a voxel with too many points" : "a tile with too many voxels", c->h_dc->seg_count, c->h_dc->n_voxels);
-            c->vox_dense = true; c->vox_dense_wait = c->vox_dense_penalty; c->vox_dense_penalty = std::min(2u * c->vox_dense_penalty, 1024u); hashed = false;
+        if (hashed) for (f3ds_ctx* c : b.fr) if (c->h_dc->ev_overflow == F3DS_OVF_DENSE_VOXEL || c->h_dc->ev_overflow == F3DS_OVF_TILE_VOXELS) {
+            if (g_sw.trace_err) fprintf(stderr, "f3ds: tile path refused a frame: %s (descriptors %u, leaves %u)\n", c->h_dc->ev_overflow == F3DS_OVF_DENSE_VOXEL ? "a voxel with too many points" : "a tile with too many voxels", c->h_dc->seg_count, c->h_dc->n_voxels);
+            c->vox_dense = true; c->vox_dense_wait = c->vox_dense_penalty; c->vox_dense_penalty = f3ds_policy::next_dense_penalty(c->vox_dense_penalty); hashed = false;
         }
         if (!hashed) {
             if (g_sw.trace_err) fprintf(stderr, "f3ds: voxelisation of %zu frames runs again on the sort path (an unorganised cloud or dense voxels)\n", b.fr.size());
@@ -1468,12 +1471,7 @@ int segment_batch_from(f3ds_ctx** ctxs, int nctx, Source&& source, int sources_o
         }
     }
     if (!hashed) {
-        // (Morton code << idxbits) | point index in one 64-bit word when both fit: the sort then moves 8 bytes per point and pass, not 12
-        uint32_t maxn = 1;
-        for (f3ds_ctx* c : b.fr) if (c->n > maxn) maxn = c->n;
-        int idxbits = bits_for((uint64_t)maxn - 1u);
-        if (3 * maxd + 1 + idxbits > 64 || g_sw.sort_pairs) idxbits = -1;
-        if ((rc = for_frames(b, [&](f3ds_ctx* c) { return seg_sort(c, 3 * maxd + 1, idxbits); })) || (rc = flush_sync(b))) return rc;
+        if ((rc = for_frames(b, [&](f3ds_ctx* c) { return seg_sort(c, plan.sort_bits, plan.idxbits); })) || (rc = flush_sync(b))) return rc;
     }
     for (f3ds_ctx* c : b.fr) { if (c->h_dc->error) return trace_err(c->h_dc->error, "voxelisation", c); c->V = c->h_dc->n_voxels; c->res.n_voxels = c->V; }
     if ((rc = drop_dead([](f3ds_ctx* c) { return c->V == 0; }))) return rc;
@@ -1500,7 +1498,7 @@ int segment_batch_from(f3ds_ctx** ctxs, int nctx, Source&& source, int sources_o
     for (int attempt = 0; attempt < 6; ++attempt) {
         // a frame with more adjacencies than its list holds (tiny supervoxels: 26 neighbours each and more) runs the pass again with four times the room
         bool again = false;
-        for (f3ds_ctx* c : b.fr) if (c->h_dc->ev_overflow == 3 && c->edge_mult < (1u << 14)) { c->edge_mult *= 4u; again = true; }
+        for (f3ds_ctx* c : b.fr) if (c->h_dc->ev_overflow == F3DS_OVF_EDGE_LIST && f3ds_policy::grow(&c->edge_mult, f3ds_policy::EDGE_MULT_CAP)) again = true;
         if (!again) break;
         if (g_sw.trace_err) fprintf(stderr, "f3ds: adjacency pass of %zu frames runs again with more list room\n", b.fr.size());
         for (f3ds_ctx* c : b.fr) if ((rc = clear_counters(c, b.st, &DevCounters::error, &DevCounters::ev_overflow, &DevCounters::n_edges, &DevCounters::n_alive))) return rc;
@@ -1576,7 +1574,7 @@ int f3ds_segment_rgbd_batch(f3ds_ctx** ctxs, int nctx, const f3ds_rgbd_format* f
             HIPCHECK(hipMemcpyAsync(uc, color[i], lay.color_bytes, hipMemcpyHostToDevice, copy));
             uploaded = true; d_depth = ud; d_color = uc;
         }
-        rec<d_deproject>(c, grid_for(c->n, 256), 0u, d_depth, d_color, args, records);
+        rec<d_deproject>(c, grid_for(c->n, d_deproject::BLOCK), 0u, d_depth, d_color, args, records);
         c->d_pts = records;
         return F3DS_OK;
     };
@@ -1711,7 +1709,7 @@ int f3ds_cluster_supervoxels(f3ds_ctx* c, const f3ds_supervoxel_set* sv, const u
     rec_fill(c, ralive0, 0u, S + 1u);
     rec_fill(c, rcnt0, 0u, (size_t)(S + 1) * 4);
     rec_fill(c, racc0, 0u, 48); rec_fill(c, rrec0, 0u, 64); rec_fill(c, hc, 0u, 48);
-    rec<d_iota>(c, grid_for(Vt, 256), 0u, reinterpret_cast<uint32_t*>(pt_voxel), Vt);      // (the caller's voxels are their own "points": ordinal v >= 0 as int, written through the kernel's uint32 view)
+    rec<d_iota>(c, grid_for(Vt, d_iota::BLOCK), 0u, reinterpret_cast<uint32_t*>(pt_voxel), Vt);      // (the caller's voxels are their own "points": ordinal v >= 0 as int, written through the kernel's uint32 view)
     rec<d_sv_user_fill>(c, S, 0u, S, d_src, d_voff, d_xyz, d_rgba, d_cent, d_nrm, rows, row_voxel, owner, racc0, rcnt0, rrec0, ralive0, hc, c->d_dc);
     int rc = flush(b);
     if (rc) return rc;
@@ -1872,8 +1870,8 @@ extern "C" int f3ds_refine_supervoxels(f3ds_ctx* c, int num_itr) {
     int rc;
     for (int it = 0; it < num_itr; ++it) {
         rec_copy(c, L, r_owner, (size_t)V * 4);
-        rec<d_refine_ghost_L>(c, grid_for(S0, 256), 0u, S0, r_gvox, r_gact, L);
-        rec<d_refine_normals>(c, grid_for(V, 256), 0u, r_vf, c->nbr.p, r_owner, L, V);
+        rec<d_refine_ghost_L>(c, grid_for(S0, d_refine_ghost_L::BLOCK), 0u, S0, r_gvox, r_gact, L);
+        rec<d_refine_normals>(c, grid_for(V, d_refine_normals::BLOCK), 0u, r_vf, c->nbr.p, r_owner, L, V);
         rec<d_reseed>(c, S0 ? S0 : 1u, 0u, r_vf, V, S0, r_hcount, r_hc, seed);
         if ((rc = seg_sweeps_on(c, sb)) || (rc = flush_sync(b))) return rc;
         if (c->h_dc->error) return trace_err(c->h_dc->error, "refine", c);
@@ -2078,8 +2076,8 @@ int eval_truth(f3ds_ctx* c, const uint32_t* truth_point_labels) {
     HIPCHECK(hipMemcpyAsync(tp, truth_point_labels, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipMemsetAsync(tsum, 0, (size_t)V * 12, c->stream));
     Batch b = batch_of(c);
-    rec<d_truth_accum>(c, grid_for(n, 256), 0u, n, c->pt_voxel.p, tp, lut, tsum);
-    rec<d_truth_color>(c, grid_for(V, 256), 0u, V, tsum, c->vcount.p, tcol);
+    rec<d_truth_accum>(c, grid_for(n, d_truth_accum::BLOCK), 0u, n, c->pt_voxel.p, tp, lut, tsum);
+    rec<d_truth_color>(c, grid_for(V, d_truth_color::BLOCK), 0u, V, tsum, c->vcount.p, tcol);
     int rc = flush_sync(b);
     if (rc) return rc;
     std::vector<uint32_t> col;
@@ -2098,8 +2096,8 @@ int eval_scores(f3ds_ctx* c, const uint32_t* d_root, const uint32_t* d_incl, uin
     HIPCHECK(hipMemsetAsync(tab, 0, (size_t)K * M * 4, c->stream));
     HIPCHECK(hipMemsetAsync(ssz, 0, (size_t)K * 4, c->stream));
     Batch b = batch_of(c);
-    rec<d_contingency>(c, grid_for(V, 256), 0u, V, M, c->owner0.p, d_root, d_incl, c->tlab.p, tab, ssz);
-    rec<d_contingency_ghost>(c, grid_for(c->S0, 256), 0u, c->S0, M, c->ghost_vox.p, c->ghost_active.p, c->owner0.p, d_root, d_incl, c->tlab.p, tab, ssz);
+    rec<d_contingency>(c, grid_for(V, d_contingency::BLOCK), 0u, V, M, c->owner0.p, d_root, d_incl, c->tlab.p, tab, ssz);
+    rec<d_contingency_ghost>(c, grid_for(c->S0, d_contingency_ghost::BLOCK), 0u, c->S0, M, c->ghost_vox.p, c->ghost_active.p, c->owner0.p, d_root, d_incl, c->tlab.p, tab, ssz);
     int rc = flush_sync(b);
     if (rc) return rc;
     std::vector<uint32_t> table, ssize;
@@ -2203,17 +2201,17 @@ int levels_record(f3ds_ctx* c, const float* d_thr, uint32_t K, bool lds_form, ui
     const uint32_t* ord = pfx + K;
     const uint32_t* merges = c->merges.p;
     rec_fill(c, at, LV_NOT_ABSORBED, (size_t)(S0 + 1) * 4);
-    rec<d_level_log>(c, grid_for(nm, 256), 0u, nm, S0, merges, into, at);
+    rec<d_level_log>(c, grid_for(nm, d_level_log::BLOCK), 0u, nm, S0, merges, into, at);
     rec<d_level_prefix>(c, 1u, 0u, nm, merges, K, d_thr, pfx, pfx + K);
     const unsigned char* alive0 = c->ralive0.p;
     const int* pt_voxel = c->pt_voxel.p; const uint32_t* owner = c->owner0.p;
     if (lds_form) {
-        const uint32_t gx = std::min(grid_for(n, 256), grid_wide(n, 4096));      // (every workgroup builds the tables: as d_relabel)
+        const uint32_t gx = std::min(grid_for(n, d_level_labels::BLOCK), grid_wide(n, 4096));      // (every workgroup builds the tables: as d_relabel)
         rec<d_level_labels>(c, gx, (S0 + 1u) * Kp * 4u, n, pt_voxel, owner, S0, K, Kp, alive0, into, at, pfx, ord, d_out, nreg);
     } else {
         uint32_t* tab; ENSURE(c->lv_tab, (size_t)(S0 + 1) * Kp, tab);
         rec<d_level_tables>(c, 1u, 0u, S0, K, Kp, alive0, into, at, pfx, ord, tab, nreg);
-        rec<d_level_points>(c, grid_for(n, 256), 0u, n, K, Kp, pt_voxel, owner, tab, d_out);
+        rec<d_level_points>(c, grid_for(n, d_level_points::BLOCK), 0u, n, K, Kp, pt_voxel, owner, tab, d_out);
     }
     return F3DS_OK;
 }
@@ -2284,9 +2282,9 @@ struct EvlTruth { std::vector<uint32_t> col, tsize, order; uint32_t M = 0, nvis 
 int evl_reduce_record(f3ds_ctx* c, const uint64_t* keys, const uint32_t* vals, uint32_t n, uint64_t limit, uint64_t* ukey, uint32_t* ucnt, uint32_t* total) {
     uint32_t* flag = c->evl_flag.p;
     rec_fill(c, ucnt, 0u, (size_t)n * 4);
-    rec<d_evl_heads>(c, grid_for(n, 256), 0u, keys, n, limit, flag);
+    rec<d_evl_heads>(c, grid_for(n, d_evl_heads::BLOCK), 0u, keys, n, limit, flag);
     if (const int rc = scan_u32(c, flag, flag, n)) return rc;
-    rec<d_evl_reduce>(c, grid_for(n, 256), 0u, keys, vals, n, limit, flag, ukey, ucnt, total);
+    rec<d_evl_reduce>(c, grid_for(n, d_evl_reduce::BLOCK), 0u, keys, vals, n, limit, flag, ukey, ucnt, total);
     return F3DS_OK;
 }
 int run_eval_levels(f3ds_ctx** ctxs, int nctx, const uint32_t* const* truth, int truth_on_device, const float* thr, int K_, f3ds_performance* scores, uint32_t* n_regions) {
@@ -2315,12 +2313,12 @@ int run_eval_levels(f3ds_ctx** ctxs, int nctx, const uint32_t* const* truth, int
         if (!truth_on_device) { ENSURE(c->truth_pts, n, tp); HIPCHECK(hipMemcpyAsync(tp, truth[i], (size_t)n * 4, hipMemcpyHostToDevice, b.st)); d_truth = tp; }
         rec_fill(c, tsum, 0u, (size_t)V * 12);
         rec_fill(c, at, LV_NOT_ABSORBED, (size_t)(S0 + 1) * 4);
-        rec<d_truth_accum>(c, grid_for(n, 256), 0u, n, c->pt_voxel.p, d_truth, lut, tsum);
-        rec<d_truth_color>(c, grid_for(V, 256), 0u, V, tsum, c->vcount.p, tcol);
-        rec<d_level_log>(c, grid_for(nm, 256), 0u, nm, S0, c->merges.p, into, at);
+        rec<d_truth_accum>(c, grid_for(n, d_truth_accum::BLOCK), 0u, n, c->pt_voxel.p, d_truth, lut, tsum);
+        rec<d_truth_color>(c, grid_for(V, d_truth_color::BLOCK), 0u, V, tsum, c->vcount.p, tcol);
+        rec<d_level_log>(c, grid_for(nm, d_level_log::BLOCK), 0u, nm, S0, c->merges.p, into, at);
         rec<d_level_prefix>(c, 1u, 0u, nm, c->merges.p, K, d_thr, pfx, pfx + K);
         rec<d_level_tables>(c, 1u, 0u, S0, K, Kp, c->ralive0.p, into, at, pfx, pfx + K, tab, d_nreg + (size_t)i * K);
-        rec<d_evl_ghosts>(c, grid_for(S0, 256), 0u, S0, c->ghost_active.p, glist, d_counts + (size_t)i * 4 + 1);
+        rec<d_evl_ghosts>(c, grid_for(S0, d_evl_ghosts::BLOCK), 0u, S0, c->ghost_active.p, glist, d_counts + (size_t)i * 4 + 1);
     }
     int rc = flush(b);
     if (rc) return rc;
@@ -2353,7 +2351,7 @@ int run_eval_levels(f3ds_ctx** ctxs, int nctx, const uint32_t* const* truth, int
         HIPCHECK(hipMemcpyAsync(tlab, t.col.data(), (size_t)V * 4, hipMemcpyHostToDevice, b.st));
         HIPCHECK(hipMemcpyAsync(tsz, t.tsize.data(), (size_t)t.M * 4, hipMemcpyHostToDevice, b.st));
         HIPCHECK(hipMemcpyAsync(ord, t.order.data(), t.order.size() * 4, hipMemcpyHostToDevice, b.st));
-        rec<d_evl_base_keys>(c, grid_for(V, 256), 0u, V, S0, t.M, c->owner0.p, tlab, jb, k0, v0);
+        rec<d_evl_base_keys>(c, grid_for(V, d_evl_base_keys::BLOCK), 0u, V, S0, t.M, c->owner0.p, tlab, jb, k0, v0);
         uint64_t* ks; uint32_t* vs;
         if ((rc = radix_sort(c, k0, v0, k1, v1, V, hb + jb, &ks, &vs))) return rc;
         if ((rc = evl_reduce_record(c, ks, vs, V, (uint64_t)(S0 + 1u) << jb, bkey, bcnt, d_counts + (size_t)i * 4))) return rc;
@@ -2380,11 +2378,11 @@ int run_eval_levels(f3ds_ctx** ctxs, int nctx, const uint32_t* const* truth, int
         const uint32_t* ord = c->evl_order.p;
         rec_fill(c, ssize, 0u, (size_t)K * (S0 + 1) * 4);
         rec_fill(c, used, 0u, (size_t)K * (S0 + 1));
-        rec<d_evl_level_keys>(c, grid_for(ne, 256), 0u, t.Eb, t.G, K, Kp, S0, t.M, V, c->evl_bkey.p, c->evl_bcnt.p, c->evl_glist.p, c->ghost_vox.p, c->owner0.p, c->tlab.p, c->lv_tab.p, ib, jb, k0, v0, ssize);
+        rec<d_evl_level_keys>(c, grid_for(ne, d_evl_level_keys::BLOCK), 0u, t.Eb, t.G, K, Kp, S0, t.M, V, c->evl_bkey.p, c->evl_bcnt.p, c->evl_glist.p, c->ghost_vox.p, c->owner0.p, c->tlab.p, c->lv_tab.p, ib, jb, k0, v0, ssize);
         uint64_t* ks; uint32_t* vs;
         if ((rc = radix_sort(c, k0, v0, k1, v1, n, lb + ib + jb, &ks, &vs))) return rc;
         if ((rc = evl_reduce_record(c, ks, vs, n, (uint64_t)K << (ib + jb), ukey, ucnt, d_total))) return rc;
-        rec<d_evl_col_keys>(c, grid_for(n, 256), 0u, ukey, ucnt, d_total, ib, jb, k0, v0);
+        rec<d_evl_col_keys>(c, grid_for(n, d_evl_col_keys::BLOCK), 0u, ukey, ucnt, d_total, ib, jb, k0, v0);
         if ((rc = radix_sort(c, k0, v0, k1, v1, n, lb + jb, &ks, &vs, ib, d_total))) return rc;
         rec<d_evl_ht>(c, 1u, 0u, t.M, c->evl_tsize.p, V, tterm, tterm + t.M);
         rec<d_evl_score>(c, K, 0u, K, S0, V, d_nreg + (size_t)i * K, ssize, c->evl_tsize.p, ukey, ucnt, ks, vs, d_total, ib, jb, ord, ord + t.nvis, ord + 2 * (size_t)t.nvis, t.nvis,
@@ -2593,13 +2591,13 @@ extern "C" int f3ds_tracker_update(f3ds_tracker* t, const f3ds_rgbd_format* fmt_
     const int nxt = t->cur ^ 1;
     int rc;
     HIPCHECK(hipMemsetAsync(cnt, 0, 16, b.st));      // [0] entries, [1] the bad-label flag
-    rec<d_track_keys>(c, grid_for(n, 256), 0u, d_depth, d_lab, t->have_prev ? t->slot[t->cur] : nullptr, t->have_prev ? t->z[t->cur] : nullptr, a, k0, t->slot[nxt], t->z[nxt], cnt + 1);
+    rec<d_track_keys>(c, grid_for(n, d_track_keys::BLOCK), 0u, d_depth, d_lab, t->have_prev ? t->slot[t->cur] : nullptr, t->have_prev ? t->z[t->cur] : nullptr, a, k0, t->slot[nxt], t->z[nxt], cnt + 1);
     uint64_t* ks;
     if ((rc = radix_sort(c, k0, nullptr, k1, nullptr, n, sort_bits, &ks, nullptr))) return rc;
-    rec<d_evl_heads>(c, grid_for(n, 256), 0u, ks, n, tk_hole(Kc, jb), flag);
+    rec<d_evl_heads>(c, grid_for(n, d_evl_heads::BLOCK), 0u, ks, n, tk_hole(Kc, jb), flag);
     if ((rc = scan_u32(c, flag, flag, n))) return rc;
-    rec<d_track_runs>(c, grid_for(n, 256), 0u, ks, n, tk_hole(Kc, jb), flag, ukey, ustart, uend, cnt);
-    rec<d_track_pack>(c, grid_for(cap, 256), 0u, ukey, ustart, uend, cnt, cnt + 1, jb, (uint32_t)cap, out);
+    rec<d_track_runs>(c, grid_for(n, d_track_runs::BLOCK), 0u, ks, n, tk_hole(Kc, jb), flag, ukey, ustart, uend, cnt);
+    rec<d_track_pack>(c, grid_for(cap, d_track_pack::BLOCK), 0u, ukey, ustart, uend, cnt, cnt + 1, jb, (uint32_t)cap, out);
     if ((rc = flush(b))) return rc;
     HIPCHECK(hipMemcpyAsync(t->h_out, out, (TRK_HEAD + 3 * cap) * 4, hipMemcpyDeviceToHost, b.st));
     HIPCHECK(timed_sync(b.st));
@@ -2611,7 +2609,7 @@ extern "C" int f3ds_tracker_update(f3ds_tracker* t, const f3ds_rgbd_format* fmt_
         cap = (size_t)total * 2;
         if ((rc = trk_pinned(&t->h_out, &t->out_cap, TRK_HEAD + 3 * cap))) return rc;
         ENSURE(c->trk_out, TRK_HEAD + 3 * cap, out);
-        rec<d_track_pack>(c, grid_for(cap, 256), 0u, ukey, ustart, uend, cnt, cnt + 1, jb, (uint32_t)cap, out);
+        rec<d_track_pack>(c, grid_for(cap, d_track_pack::BLOCK), 0u, ukey, ustart, uend, cnt, cnt + 1, jb, (uint32_t)cap, out);
         if ((rc = flush(b))) return rc;
         HIPCHECK(hipMemcpyAsync(t->h_out, out, (TRK_HEAD + 3 * (size_t)total) * 4, hipMemcpyDeviceToHost, b.st));
         HIPCHECK(timed_sync(b.st));
@@ -2631,7 +2629,7 @@ extern "C" int f3ds_tracker_update(f3ds_tracker* t, const f3ds_rgbd_format* fmt_
     r.first_frame = t->have_prev ? 0u : 1u;
     if ((rc = trk_pinned(&t->h_id, &t->id_cap, Kc))) return rc;
     if (Kc) { memcpy(t->h_id, ids.data(), (size_t)Kc * 4); HIPCHECK(hipMemcpyAsync(d_id, t->h_id, (size_t)Kc * 4, hipMemcpyHostToDevice, b.st)); }
-    rec<d_track_apply>(c, grid_for(n, 256), 0u, d_lab, n, d_id, Kc, ids_on_device ? track_ids : tid);
+    rec<d_track_apply>(c, grid_for(n, d_track_apply::BLOCK), 0u, d_lab, n, d_id, Kc, ids_on_device ? track_ids : tid);
     if ((rc = flush(b))) return rc;
     if (!ids_on_device) {
         hipStream_t dl;      // (queued on the copy stream only once the ids exist, as the labels of f3ds_segment_batch)
@@ -2676,9 +2674,9 @@ int rg_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& 
     a.width = fmt.width; a.n = n; a.depth_pitch = lay.depth_pitch; a.color_pitch = lay.color_pitch; a.depth_f32 = fmt.depth_type == F3DS_DEPTH_F32 ? 1 : 0;
     a.color_format = im.color ? fmt.color_format : -1; a.K = K; a.copies = copies;
     a.depth_scale = fmt.depth_scale; a.fx = fmt.fx; a.fy = fmt.fy; a.cx = fmt.cx; a.cy = fmt.cy;
-    rec<d_region_init>(c, grid_for((size_t)K * copies * RG_WORDS, 256), 0u, reinterpret_cast<uint32_t*>(acc), K * copies, head);
-    rec<d_region_accum>(c, grid_for((n + LI_TRIPS - 1u) / LI_TRIPS, 256), 0u, im.depth, im.color, im.labels, a, acc, head);
-    rec<d_region_finish>(c, grid_for(K, 256), 0u, acc, K, copies, head, d_rows);
+    rec<d_region_init>(c, grid_for((size_t)K * copies * RG_WORDS, d_region_init::BLOCK), 0u, reinterpret_cast<uint32_t*>(acc), K * copies, head);
+    rec<d_region_accum>(c, grid_for((n + LI_TRIPS - 1u) / LI_TRIPS, d_region_accum::BLOCK), 0u, im.depth, im.color, im.labels, a, acc, head);
+    rec<d_region_finish>(c, grid_for(K, d_region_finish::BLOCK), 0u, acc, K, copies, head, d_rows);
     return F3DS_OK;
 }
 }  // namespace
@@ -2749,13 +2747,13 @@ int pair_record(f3ds_ctx* c, const PairScratch& s, size_t words, const PairArgs&
     ENSURE(c->hist, (size_t)RS_BINS * ((rec_cap + RS_TILE - 1) / RS_TILE + 1), hist); ENSURE(c->tiles, (rec_cap + SCAN_TILE - 1) / SCAN_TILE + 1, tiles);
     const uint64_t hole = ct_hole(a.K, a.kb);
     int rc;
-    rec<d_pair_init>(c, grid_for(rec_cap, 256), 0u, k0, v0, rec_cap, head);
+    rec<d_pair_init>(c, grid_for(rec_cap, d_pair_init::BLOCK), 0u, k0, v0, rec_cap, head);
     accum(k0, rec_words);
     uint64_t* ks; uint32_t* vs;
     if ((rc = radix_sort(c, k0, v0, k1, v1, rec_cap, sort_bits, &ks, &vs))) return rc;
-    rec<d_evl_heads>(c, grid_for(rec_cap, 256), 0u, ks, rec_cap, hole, flag);
+    rec<d_evl_heads>(c, grid_for(rec_cap, d_evl_heads::BLOCK), 0u, ks, rec_cap, hole, flag);
     if ((rc = scan_u32(c, flag, flag, rec_cap))) return rc;
-    rec<d_track_runs>(c, grid_for(rec_cap, 256), 0u, ks, rec_cap, hole, flag, ukey, ustart, uend, cnt);
+    rec<d_track_runs>(c, grid_for(rec_cap, d_track_runs::BLOCK), 0u, ks, rec_cap, hole, flag, ukey, ustart, uend, cnt);
     finish(ukey, ustart, uend, cnt, vs, rec_words);
     return F3DS_OK;
 }
@@ -2821,9 +2819,9 @@ int ct_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& 
     const PairArgs a = pair_args(fmt, lay, K, depth_tol, rec_cap);
     const uint32_t n = a.n;
     return pair_record(c, rgc_scratch(c), CT_WORDS, a, sort_bits, head,
-        [&](uint64_t* k0, uint32_t* rec_words) { rec<d_contact_accum>(c, grid_for((n + RGC_TRIPS - 1u) / RGC_TRIPS, 256), 0u, im.depth, im.labels, a, k0, rec_words, head); },
+        [&](uint64_t* k0, uint32_t* rec_words) { rec<d_contact_accum>(c, grid_for((n + RGC_TRIPS - 1u) / RGC_TRIPS, d_contact_accum::BLOCK), 0u, im.depth, im.labels, a, k0, rec_words, head); },
         [&](uint64_t* ukey, uint32_t* ustart, uint32_t* uend, uint32_t* cnt, uint32_t* vs, uint32_t* rec_words) {
-            rec<d_contact_finish>(c, grid_for((size_t)(rec_cap < 8192u ? rec_cap : 8192u) * 64u, 256), 0u, ukey, ustart, uend, cnt, vs, rec_words, a.kb, rec_cap, head, d_rows, (uint64_t)cap);
+            rec<d_contact_finish>(c, grid_for((size_t)(rec_cap < 8192u ? rec_cap : 8192u) * 64u, d_contact_finish::BLOCK), 0u, ukey, ustart, uend, cnt, vs, rec_words, a.kb, rec_cap, head, d_rows, (uint64_t)cap);
         });
 }
 }  // namespace
@@ -2870,9 +2868,9 @@ int sh_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& 
     const uint32_t n = a.n;
     ShAcc* acc;
     ENSURE(accs, K ? (size_t)K * a.copies : 1u, acc);
-    rec<d_shape_init>(c, grid_for((size_t)K * a.copies * SH_WORDS, 256), 0u, reinterpret_cast<uint32_t*>(acc), K * a.copies, head);
-    rec<d_shape_accum>(c, grid_for((n + LI_TRIPS - 1u) / LI_TRIPS, 256), 0u, im.depth, im.labels, a, acc, head);
-    rec<d_shape_finish>(c, grid_for(K, 256), 0u, acc, K, a.copies, head, d_rows);
+    rec<d_shape_init>(c, grid_for((size_t)K * a.copies * SH_WORDS, d_shape_init::BLOCK), 0u, reinterpret_cast<uint32_t*>(acc), K * a.copies, head);
+    rec<d_shape_accum>(c, grid_for((n + LI_TRIPS - 1u) / LI_TRIPS, d_shape_accum::BLOCK), 0u, im.depth, im.labels, a, acc, head);
+    rec<d_shape_finish>(c, grid_for(K, d_shape_finish::BLOCK), 0u, acc, K, a.copies, head, d_rows);
     return F3DS_OK;
 }
 }  // namespace
@@ -2915,16 +2913,16 @@ int bx_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& 
               f3ds_region_shape* d_shapes /* NULL: the context's scratch */) {
     const ShapeArgs a = sh_args(fmt, lay, K);
     const uint32_t n = a.n;
-    const uint32_t accum_grid = grid_for((n + LI_TRIPS - 1u) / LI_TRIPS, 256);      // (pass one, sh_record, asks for the same)
+    const uint32_t accum_grid = grid_for((n + LI_TRIPS - 1u) / LI_TRIPS, d_box_accum::BLOCK);      // (pass one, sh_record, asks for the same)
     BxAcc* acc2; BxFrame* frames; uint32_t* head2;
     ENSURE(c->rgx_acc, K ? (size_t)K * a.copies : 1u, acc2);
     ENSURE(c->rgx_frame, K ? K : 1u, frames);
     ENSURE(c->rgx_head, LI_HEAD_WORDS, head2);
     if (!d_shapes) ENSURE(c->rgx_shape, K ? K : 1u, d_shapes);
     if (const int rc = sh_record(c, fmt, lay, im, K, head, d_shapes, c->rgs_acc)) return rc;      // (rgs_acc is ensured before its first rec<>, and nothing recorded refers to it yet)
-    rec<d_box_frame>(c, grid_for(K, 256), 0u, d_shapes, K, a.copies, plane_tol, head, frames, acc2, head2);
+    rec<d_box_frame>(c, grid_for(K, d_box_frame::BLOCK), 0u, d_shapes, K, a.copies, plane_tol, head, frames, acc2, head2);
     rec<d_box_accum>(c, accum_grid, 0u, im.depth, im.labels, a, frames, acc2, head, head2);
-    rec<d_box_finish>(c, grid_for(K, 256), 0u, acc2, frames, K, a.copies, head, d_rows);
+    rec<d_box_finish>(c, grid_for(K, d_box_finish::BLOCK), 0u, acc2, frames, K, a.copies, head, d_rows);
     return F3DS_OK;
 }
 }  // namespace
@@ -2985,7 +2983,7 @@ int jt_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& 
     return pair_record(c, rgj_scratch(c), JT_WORDS, a, sort_bits, head,
         [&](uint64_t* k0, uint32_t* rec_words) { rec<d_joint_accum>(c, grid_for((n + RGJ_TRIPS - 1u) / RGJ_TRIPS, RGJ_BLOCK), 0u, im.depth, im.labels, a, k0, rec_words, head); },
         [&](uint64_t* ukey, uint32_t* ustart, uint32_t* uend, uint32_t* cnt, uint32_t* vs, uint32_t* rec_words) {
-            rec<d_joint_finish>(c, grid_for((size_t)(rec_cap < 8192u ? rec_cap : 8192u) * 64u, 256), 0u, ukey, ustart, uend, cnt, vs, rec_words, d_shapes, prm, a.kb, rec_cap, head, d_rows,
+            rec<d_joint_finish>(c, grid_for((size_t)(rec_cap < 8192u ? rec_cap : 8192u) * 64u, d_joint_finish::BLOCK), 0u, ukey, ustart, uend, cnt, vs, rec_words, d_shapes, prm, a.kb, rec_cap, head, d_rows,
                                 (uint64_t)cap);
         });
 }
@@ -3040,12 +3038,12 @@ int cc_record(f3ds_ctx* c, const f3ds_rgbd_format& fmt, const f3ds::RgbdLayout& 
     a.depth_scale = fmt.depth_scale; a.depth_tol = prm.depth_tol;
     const size_t seams = (size_t)(a.tiles_x - 1u) * fmt.height + (size_t)(a.tiles_y - 1u) * fmt.width;
     rec_fill(c, head, 0u, LI_HEAD_BYTES);
-    rec<d_comp_local>(c, grid_for((size_t)a.tiles_x * a.tiles_y, 1), 0u, im.depth, im.labels, a, parent, cnt, head);
-    rec<d_comp_seam>(c, grid_for(seams, 256), 0u, im.depth, im.labels, a, parent);
-    rec<d_comp_flatten>(c, grid_for(n, 256), 0u, n, parent, cnt);
-    rec<d_comp_flag>(c, grid_for(n, 256), 0u, n, parent, cnt, a.min_pixels, flag, head);
+    rec<d_comp_local>(c, grid_for((size_t)a.tiles_x * a.tiles_y, CC_TILES_PER_WG), 0u, im.depth, im.labels, a, parent, cnt, head);
+    rec<d_comp_seam>(c, grid_for(seams, d_comp_seam::BLOCK), 0u, im.depth, im.labels, a, parent);
+    rec<d_comp_flatten>(c, grid_for(n, d_comp_flatten::BLOCK), 0u, n, parent, cnt);
+    rec<d_comp_flag>(c, grid_for(n, d_comp_flag::BLOCK), 0u, n, parent, cnt, a.min_pixels, flag, head);
     if (const int rc = scan_u32(c, flag, flag, n)) return rc;
-    rec<d_comp_write>(c, grid_for(n, 256), 0u, n, im.labels, parent, cnt, flag, a.min_pixels, head, d_comp, d_rows, (uint64_t)cap);
+    rec<d_comp_write>(c, grid_for(n, d_comp_write::BLOCK), 0u, n, im.labels, parent, cnt, flag, a.min_pixels, head, d_comp, d_rows, (uint64_t)cap);
     return F3DS_OK;
 }
 }  // namespace
@@ -3116,7 +3114,8 @@ int cd_record(f3ds_ctx* c, const P16* pts, const uint32_t* labels, uint32_t n, u
     CloudArgs a;
     memset(&a, 0, sizeof a);
     a.n = n; a.K = K; a.copies = rgt_copies(K); a.idx_bits = idx_bits; a.fold_negative_z = prm.fold_negative_z; a.ordered = ordered ? 1 : 0;
-    const uint32_t walk_grid = grid_for(((size_t)n + LI_TRIPS - 1u) / LI_TRIPS, 256);      // (both walks, both passes: LI_TRIPS trips a workgroup, as the image family)
+    static_assert(d_cloud_accum::BLOCK == d_cloud_box_accum::BLOCK, "one grid for both walks");
+    const uint32_t walk_grid = grid_for(((size_t)n + LI_TRIPS - 1u) / LI_TRIPS, d_cloud_accum::BLOCK);      // (both walks, both passes: LI_TRIPS trips a workgroup, as the image family)
     CdAcc* acc; uint64_t *k0 = nullptr, *k1 = nullptr, *ks = nullptr;
     f3ds_region_shape* shapes = nullptr; BxFrame* frames = nullptr; BxAcc* acc2 = nullptr; uint32_t* head2 = nullptr;
     ENSURE(c->rgp_acc, K ? (size_t)K * a.copies : 1u, acc);
@@ -3125,17 +3124,17 @@ int cd_record(f3ds_ctx* c, const P16* pts, const uint32_t* labels, uint32_t n, u
         ENSURE(c->rgp_shape, K ? K : 1u, shapes); ENSURE(c->rgp_frame, K ? K : 1u, frames);
         ENSURE(c->rgp_bacc, K ? (size_t)K * a.copies : 1u, acc2); ENSURE(c->rgp_head, LI_HEAD_WORDS, head2);
     }
-    rec<d_cloud_init>(c, grid_for((size_t)K * a.copies * CD_WORDS, 256), 0u, reinterpret_cast<uint32_t*>(acc), K * a.copies, head);
+    rec<d_cloud_init>(c, grid_for((size_t)K * a.copies * CD_WORDS, d_cloud_init::BLOCK), 0u, reinterpret_cast<uint32_t*>(acc), K * a.copies, head);
     if (ordered) {
-        rec<d_cloud_keys>(c, grid_for(n, 256), 0u, labels, a, k0, head);
+        rec<d_cloud_keys>(c, grid_for(n, d_cloud_keys::BLOCK), 0u, labels, a, k0, head);
         if (const int rc = radix_sort(c, k0, nullptr, k1, nullptr, n, label_bits, &ks, nullptr, (int)idx_bits)) return rc;
     }
     rec<d_cloud_accum>(c, walk_grid, 0u, pts, labels, ks, a, acc, head);
-    rec<d_cloud_finish>(c, grid_for(K, 256), 0u, acc, K, a.copies, head, d_rows, shapes);
+    rec<d_cloud_finish>(c, grid_for(K, d_cloud_finish::BLOCK), 0u, acc, K, a.copies, head, d_rows, shapes);
     if (d_boxes) {
-        rec<d_box_frame>(c, grid_for(K, 256), 0u, shapes, K, a.copies, prm.plane_tol, head, frames, acc2, head2);
+        rec<d_box_frame>(c, grid_for(K, d_box_frame::BLOCK), 0u, shapes, K, a.copies, prm.plane_tol, head, frames, acc2, head2);
         rec<d_cloud_box_accum>(c, walk_grid, 0u, pts, labels, ks, a, frames, acc2, head, head2);
-        rec<d_box_finish>(c, grid_for(K, 256), 0u, acc2, frames, K, a.copies, head, d_boxes);
+        rec<d_box_finish>(c, grid_for(K, d_box_finish::BLOCK), 0u, acc2, frames, K, a.copies, head, d_boxes);
     }
     c->cloud_path = ordered ? CD_PATH_ORDERED : CD_PATH_DIRECT;
     return F3DS_OK;
@@ -3212,4 +3211,89 @@ extern "C" int f3ds_cloud_regions_batch(f3ds_ctx** ctxs, int nctx, const void* c
 extern "C" int f3ds_cloud_regions(f3ds_ctx* c, const void* points16, size_t n, const uint32_t* labels, uint32_t n_regions, const f3ds_cloud_params* params, int inputs_on_device,
                                   f3ds_cloud_region* rows, f3ds_region_box* boxes, int rows_on_device, f3ds_cloud_regions_result* result) {
     return f3ds_cloud_regions_batch(&c, 1, &points16, &n, &labels, &n_regions, params, inputs_on_device, &rows, boxes ? &boxes : nullptr, rows_on_device, result, nullptr);
+}
+
+// ---- The limits by name: every number a test is sized by, from the constant the code itself uses (kernel limits: f3ds_kernels.inc, f3ds_algo.h and the region
+// includes; host policy: f3ds_batch_policy.h; a kernel's workgroup size under "<kernel>::BLOCK").  Host arithmetic only, no HIP call.  X(name, value), B(kernel).
+#define F3DS_CONSTANTS(X, B) \
+    X(NT_TILE, NT_TILE) X(NT_RING1, NT_RING1) X(NT_SLOTS, NT_SLOTS) X(VL_MAX_RUN, VL_MAX_RUN) X(VT_TILE, VT_TILE) X(VT_TAB, VT_TAB) X(VT_ENT_MAX, VT_ENT_MAX) \
+    X(VT_CNT_BITS, VT_CNT_BITS) X(VG_CHUNK, VG_CHUNK) X(RL_LDS_CAP, RL_LDS_CAP) X(HT_CAP, HT_CAP) X(HT_ROW, HT_ROW) X(QL, QL) X(BY_WAVE_RATIO, BY_WAVE_RATIO) \
+    X(SW_TILE_NONE, SW_TILE_NONE) X(N_BLOCK_DEPTH_MAX, N_BLOCK_DEPTH_MAX) X(R_STACK, F3DS_R_STACK) X(R_ROUNDS, F3DS_R_ROUNDS) X(TAG_PERIOD, A_TAG_PERIOD) \
+    X(MAX_SEED_EVENTS, F3DS_MAX_SEED_EVENTS) X(SEED_CHUNK, SEED_CHUNK) X(SEED_CELLS_PER_WG, SEED_CELLS_PER_WG) X(SEED_CAND_STRIDE, SEED_CAND_STRIDE) \
+    X(SEED_NN_MARGIN, double_bits(SEED_NN_MARGIN)) X(SEED_NN_ULP, double_bits(SEED_NN_ULP)) X(SEED_PRUNE_MARGIN, double_bits(SEED_PRUNE_MARGIN)) \
+    X(MC_TL_CAP, MC_TL_CAP) X(MC_SP_TL, MC_SP_TL) X(MC_SP_LEAVES, MC_SP_LEAVES) X(MC_GROUP, MC_GROUP) X(MC_LDS_LIMIT, MC_LDS_LIMIT) X(MC_LDS_STATIC, MC_LDS_STATIC) \
+    X(MC_CH_ROWS4, MC_CH_ROWS4) X(MC_CH_ROWS8, MC_CH_ROWS8) X(MC_SP_ROWS_MIN, MC_SP_ROWS_MIN) X(MC_SP_ROWS8, F3DS_SP_ROWS8) X(MC_SP_REST_TRIES, MC_SP_REST_TRIES) \
+    X(MC_SP_REST_DIV, F3DS_SP_REST_DIV) X(MC_SP_REST_EPOCHS, MC_SP_REST_EPOCHS) \
+    X(LI_SLOTS, LI_SLOTS) X(LI_PROBES, LI_PROBES) X(LI_TRIPS, LI_TRIPS) X(RGT_MAX_COPIES, RGT_MAX_COPIES) X(RGT_COPY_BUDGET, RGT_COPY_BUDGET) X(RGC_SLOTS, RGC_SLOTS) \
+    X(RGC_TRIPS, RGC_TRIPS) X(CC_TILE_W, CC_TILE_W) X(CC_TILE_H, CC_TILE_H) X(CC_TILES_PER_WG, CC_TILES_PER_WG) \
+    X(OVF_EVENTS, F3DS_OVF_EVENTS) X(OVF_LEAF_POOL, F3DS_OVF_LEAF_POOL) X(OVF_EDGE_LIST, F3DS_OVF_EDGE_LIST) X(OVF_ILIST_POOL, F3DS_OVF_ILIST_POOL) \
+    X(OVF_DENSE_VOXEL, F3DS_OVF_DENSE_VOXEL) X(OVF_TILE_VOXELS, F3DS_OVF_TILE_VOXELS) \
+    X(KEY_BITS, f3ds_policy::KEY_BITS) X(TILE_MIN_CONTEXTS, f3ds_policy::TILE_MIN_CONTEXTS) X(EV_MULT, f3ds_policy::EV_MULT) X(EV_EXTRA, f3ds_policy::EV_EXTRA) \
+    X(EDGE_MULT, f3ds_policy::EDGE_MULT) X(EDGE_EXTRA, f3ds_policy::EDGE_EXTRA) X(GROW, f3ds_policy::GROW) X(EV_MULT_CAP, f3ds_policy::EV_MULT_CAP) \
+    X(POOL_MULT_CAP, f3ds_policy::POOL_MULT_CAP) X(ILIST_MULT_CAP, f3ds_policy::ILIST_MULT_CAP) X(EDGE_MULT_CAP, f3ds_policy::EDGE_MULT_CAP) \
+    X(ILIST_SLACK, f3ds_policy::ILIST_SLACK) X(ILIST_EXTRA_SHORT, f3ds_policy::ILIST_EXTRA_SHORT) X(ILIST_EXTRA, f3ds_policy::ILIST_EXTRA) \
+    X(DENSE_PENALTY, f3ds_policy::DENSE_PENALTY) X(DENSE_PENALTY_STEP, f3ds_policy::DENSE_PENALTY_STEP) X(DENSE_PENALTY_CAP, f3ds_policy::DENSE_PENALTY_CAP) \
+    X(NORMALS_256_FRAMES, f3ds_policy::NORMALS_256_FRAMES) X(GRID_TARGET, f3ds_policy::GRID_TARGET) X(GRID_MIN, f3ds_policy::GRID_MIN) X(WIDE_CAP, f3ds_policy::WIDE_CAP) \
+    B(d_seed_grow) B(d_seed_nn) B(d_seed_filter) B(d_reseed) B(d_region_accum) B(d_shape_accum) B(d_box_accum) B(d_contact_accum) B(d_comp_local) B(d_comp_seam) B(d_track_keys)
+namespace {
+uint64_t double_bits(double v) { uint64_t b; memcpy(&b, &v, 8); return b; }
+struct NamedConstant { const char* name; uint64_t value; };
+const NamedConstant* constant_table(size_t* count) {
+#define F3DS_X(name, value) {#name, (uint64_t)(value)},
+#define F3DS_B(kernel) {#kernel "::BLOCK", (uint64_t)kernel::BLOCK},
+    static const NamedConstant table[] = {F3DS_CONSTANTS(F3DS_X, F3DS_B)};
+#undef F3DS_X
+#undef F3DS_B
+    *count = sizeof table / sizeof table[0];
+    return table;
+}
+}  // namespace
+extern "C" int f3ds_constant(const char* name, uint64_t* value) {
+    size_t n; const NamedConstant* t = constant_table(&n);
+    if (!name || !value) return F3DS_ERR_ARG;
+    for (size_t i = 0; i < n; ++i) if (!strcmp(t[i].name, name)) { *value = t[i].value; return F3DS_OK; }
+    return F3DS_ERR_ARG;
+}
+extern "C" const char* f3ds_constant_name(size_t index) {
+    size_t n; const NamedConstant* t = constant_table(&n);
+    return index < n ? t[index].name : nullptr;
+}
+extern "C" int f3ds_stage0_plan(int max_depth, uint32_t max_points, int n_contexts, int vox_tiles, int sort_pairs, int32_t out[4]) {
+    if (!out || max_depth < 0 || max_depth > 21 || n_contexts < 1 || vox_tiles < 0 || vox_tiles > 2) return F3DS_ERR_ARG;
+    const bool wanted = f3ds_policy::tile_path_wanted(n_contexts, vox_tiles != 0 && !sort_pairs, vox_tiles == 2);      // (Switches::read: F3DS_SORT_PAIRS implies the sort path)
+    const f3ds_policy::Stage0Plan p = f3ds_policy::stage0_plan(max_depth, max_points, wanted, sort_pairs != 0, VT_LIMITS);
+    out[0] = p.tiles ? 1 : 0; out[1] = p.tile_bits; out[2] = p.idxbits; out[3] = p.sort_bits;
+    return F3DS_OK;
+}
+extern "C" int f3ds_policy_capacity(int what, uint32_t count, uint32_t n_seeds, uint32_t mult, uint32_t slack, uint32_t* out) {
+    if (!out) return F3DS_ERR_ARG;
+    switch (what) {
+        case F3DS_CAP_EDGES: *out = f3ds_policy::edge_capacity(count, mult); return F3DS_OK;
+        case F3DS_CAP_EVENTS: *out = f3ds_policy::event_capacity(count, mult); return F3DS_OK;
+        case F3DS_CAP_LEAF_POOL: *out = f3ds_policy::leaf_pool_capacity(count, mult); return F3DS_OK;
+        case F3DS_CAP_ILIST: *out = f3ds_policy::ilist_capacity(count, n_seeds, slack, mult, MC_TL_CAP); return F3DS_OK;
+    }
+    return F3DS_ERR_ARG;
+}
+extern "C" int f3ds_policy_grow(uint32_t mult, uint32_t cap, uint32_t* out) {
+    if (!out) return F3DS_ERR_ARG;
+    f3ds_policy::grow(&mult, cap);
+    *out = mult;
+    return F3DS_OK;
+}
+extern "C" int f3ds_policy_launch(int frames, int normals_forced, uint32_t grid_target, uint32_t grid_cap_forced, uint32_t out[3]) {
+    if (!out) return F3DS_ERR_ARG;
+    out[0] = (uint32_t)f3ds_policy::normals_threads(frames, normals_forced);
+    out[1] = (uint32_t)f3ds_policy::grid_cap_for_batch(frames, grid_target, grid_cap_forced);
+    out[2] = (uint32_t)f3ds_policy::wide_cap(grid_cap_forced);
+    return F3DS_OK;
+}
+extern "C" uint32_t f3ds_policy_dense_penalty(uint32_t penalty) { return f3ds_policy::next_dense_penalty(penalty); }
+extern "C" int f3ds_policy_stage_layout(size_t n_frames, const size_t* fixed_bytes, const size_t* stage_rows, size_t row_bytes, size_t first_rows, size_t* slots, size_t* first_bytes, size_t* total) {
+    if (!n_frames || !fixed_bytes || !slots || !first_bytes || !total) return F3DS_ERR_ARG;
+    static_assert(sizeof(LiSlot) == 3 * sizeof(size_t), "a slot is (at, rows_at, first)");
+    std::vector<LiSlot> slot(n_frames);
+    *total = li_stage_layout(n_frames, fixed_bytes, stage_rows, row_bytes, first_rows, slot.data(), first_bytes);
+    memcpy(slots, slot.data(), n_frames * sizeof(LiSlot));
+    return F3DS_OK;
 }

@@ -33,7 +33,7 @@ struct DevCounters {
     uint32_t n_changed;      // voxels whose (owner, distance) changed in the current sweep
     uint32_t sweep_full;     // t+1 while sweep t has to evaluate every voxel (no dirty-tile skipping)
     uint32_t sweep_marks;    // t+1 while sweep t records which tiles the next sweep has to look at
-    int ev_overflow;         // the merge loop ran out of weight-history events (1), of leaf pool (2) or of incident-list pool (4), the adjacency pass of list room (3): the host reruns the stage with more
+    int ev_overflow;         // an F3dsOverflow (f3ds_algo.h): what the kernel that set error = F3DS_ERR_UNSUPPORTED ran out of; the host reruns the stage with more of it, or on another path
     uint32_t sweep_pre;      // t+1 when sweep t was full from its start, i.e. its R pre-pass ran (an incremental sweep whose rounds do not converge turns full later: d_sweep_R)
     uint32_t pad_to_line_[1];         // rq[] starts a 128-byte line of its own: the chain walker's list counters are bumped by atomics from every workgroup, as n_changed (above) is by the claim kernel
     uint32_t rq[F3DS_R_PASSES + 1];   // chain walker lists of a full sweep: rq[0] voxels from the pre-pass, rq[p] voxels whose
@@ -832,7 +832,7 @@ struct d_tile_keys {
             }
             __syncthreads();
             if (tid == 0) { atomicMax(&dc->vox_max_tile, s_ent); if (s_dis) dc->vox_disorder = 1u; }
-            if (s_over[0] | s_over[1]) { if (tid == 0) { dc->error = F3DS_ERR_UNSUPPORTED; dc->ev_overflow = 7; } return; }
+            if (s_over[0] | s_over[1]) { if (tid == 0) { dc->error = F3DS_ERR_UNSUPPORTED; dc->ev_overflow = F3DS_OVF_TILE_VOXELS; } return; }
             // ---- one descriptor per live entry: (code << tile_bits | tile, tile * VT_TAB + entry), its count beside it
             if (tid == 0) s_base = s_ent ? atomicAdd(&dc->seg_count, s_ent) : 0u;      // (one atomic per tile on the frame's descriptor counter)
             __syncthreads();
@@ -857,7 +857,7 @@ struct d_tile_keys {
                         if (fa.leaf_order == 1) code = (~code) & code_mask;
                         dkeys[d] = (((code << tile_bits) | (uint64_t)tile) << VT_CNT_BITS) | (uint64_t)tcnt[e];      // (the count rides below the sorted bits: the descriptor pass needs no second array)
                         dvals[d] = tile * VT_TAB + e;
-                    } else { dc->error = F3DS_ERR_UNSUPPORTED; dc->ev_overflow = 7; }
+                    } else { dc->error = F3DS_ERR_UNSUPPORTED; dc->ev_overflow = F3DS_OVF_TILE_VOXELS; }
                 }
             }
             __syncthreads();
@@ -940,7 +940,7 @@ struct d_desc_offsets {
         }
         if (threadIdx.x == 0) {
             dc->n_voxels = ch; dc->n_valid = cc;
-            if (ch <= capV) seg_start[ch] = cc; else { dc->error = F3DS_ERR_UNSUPPORTED; dc->ev_overflow = 7; }
+            if (ch <= capV) seg_start[ch] = cc; else { dc->error = F3DS_ERR_UNSUPPORTED; dc->ev_overflow = F3DS_OVF_TILE_VOXELS; }
         }
     }
 };
@@ -1084,7 +1084,7 @@ struct d_voxel_list_accum {
             const bool mine = v < V;
             const uint32_t s = mine ? seg_start[v] : 0u, e = mine ? seg_start[v + 1] : 0u;
             const uint32_t p0 = seg_start[vb], p1 = seg_start[vb + 256u < V ? vb + 256u : V];      // (uniform)
-            if (__syncthreads_or(e - s > VL_MAX_RUN)) { if (tid == 0) { dc->error = F3DS_ERR_UNSUPPORTED; dc->ev_overflow = 6; } return; }      // a dense voxel: sort path (host)
+            if (__syncthreads_or(e - s > VL_MAX_RUN)) { if (tid == 0) { dc->error = F3DS_ERR_UNSUPPORTED; dc->ev_overflow = F3DS_OVF_DENSE_VOXEL; } return; }      // a dense voxel: sort path (host)
             if (disorder) {
                 for (uint32_t a = s + 1u; a < e; ++a) {
                     const uint32_t x = list[a];
@@ -1197,6 +1197,9 @@ constexpr int NT_HCAP = 2048;       // hash entries
 #endif
 constexpr int NT_SLOTS = F3DS_NT_SLOTS;      // distinct voxels in the two-ring union
 constexpr int NT_RING1 = F3DS_NT_RING1;      // distinct voxels in the one-ring union
+// whether slot sl (counted from 0) lies in a tile's table: a ring of exactly NT_RING1 / NT_SLOTS voxels fits, one more makes the tile overflow
+__host__ __device__ constexpr bool nt_ring1_holds(uint32_t sl) { return sl < (uint32_t)NT_RING1; }
+__host__ __device__ constexpr bool nt_slots_hold(uint32_t sl) { return sl < (uint32_t)NT_SLOTS; }
 constexpr uint16_t NT_NONE = 0xFFFFu;
 constexpr uint32_t NT_HNONE = 0x3FFu;              // slot field of a tile-hash entry that has not been numbered yet (NT_SLOTS < 1023)
 constexpr uint32_t NT_ORD_LIMIT = (1u << 22) - 2u; // voxel ordinals + 1 must fit the 22 bits above the slot field
@@ -1357,7 +1360,7 @@ struct d_normals_t {
 #pragma unroll
             for (int r = 0; r < NI; ++r) {
                 const int i = r * NTT + (int)threadIdx.x;
-                if (key[r]) { const uint32_t sl = first + (uint32_t)__popcll(mask[r] & lanemask_lt()); if (sl < NT_RING1) { hw[i] = (key[r] & ~NT_HNONE) | sl; sord[sl] = (key[r] >> 10) - 1u; } else overflow = 1; }
+                if (key[r]) { const uint32_t sl = first + (uint32_t)__popcll(mask[r] & lanemask_lt()); if (nt_ring1_holds(sl)) { hw[i] = (key[r] & ~NT_HNONE) | sl; sord[sl] = (key[r] >> 10) - 1u; } else overflow = 1; }
                 first += (uint32_t)__popcll(mask[r]);
             }
         }
@@ -1427,7 +1430,7 @@ struct d_normals_t {
 #pragma unroll
             for (int r = 0; r < NI; ++r) {
                 const int i = r * NTT + (int)threadIdx.x;
-                if (key[r]) { const uint32_t sl = first + (uint32_t)__popcll(mask[r] & lanemask_lt()); if (sl < NT_SLOTS) { hw[i] = (key[r] & ~NT_HNONE) | sl; sord[sl] = (key[r] >> 10) - 1u; } else overflow = 1; }
+                if (key[r]) { const uint32_t sl = first + (uint32_t)__popcll(mask[r] & lanemask_lt()); if (nt_slots_hold(sl)) { hw[i] = (key[r] & ~NT_HNONE) | sl; sord[sl] = (key[r] >> 10) - 1u; } else overflow = 1; }
                 first += (uint32_t)__popcll(mask[r]);
             }
         }
@@ -1758,6 +1761,12 @@ struct d_cell_hash {
         }
     }
 };
+constexpr uint32_t SEED_CELLS_PER_WG = 4;      // seed cells per workgroup of d_seed_nn / d_seed_filter, a wave each (their launches: seed_cell_grid)
+constexpr uint32_t SEED_CAND_STRIDE = 256;     // list entries a wave takes per round of their candidate loops (four per lane)
+constexpr double SEED_NN_MARGIN = 1e-3;        // d_seed_nn: the own-cell shortcut holds below (half cell)^2 * (1 - this) ...
+constexpr double SEED_NN_ULP = 0x1p-23;        // ... the half cell less this much of the centre's largest coordinate
+constexpr double SEED_PRUNE_MARGIN = 1.001;    // d_seed_filter: a cell is looked up when its box is within r2 * this of the seed voxel
+static_assert(SEED_CELLS_PER_WG * 64u == 256u && SEED_CAND_STRIDE == 4u * 64u, "a wave per cell in a 256-thread workgroup, four entries per lane and round");
 // one wave per occupied seed cell: exact nearest voxel to the cell centre (3x3x3 cell block)
 // (four seed cells per workgroup, a wave each: one-wave workgroups -- ~1 500 per frame, 290 k per batched launch -- were bound by the rate at which workgroups are dispatched)
 struct d_seed_nn {
@@ -1765,7 +1774,7 @@ struct d_seed_nn {
     __device__ void operator()(const float* vf, const uint32_t* ckey, const uint32_t* sorted_vox, const uint32_t* cell_start,
                                                const DevCounters* dc, const SeedGrid* gp, const uint64_t* hkeys, const uint32_t* hvals, uint32_t hmask,
                                                int* seed_orig) const {
-        const uint32_t c = BIX * 4u + (threadIdx.x >> 6);
+        const uint32_t c = BIX * SEED_CELLS_PER_WG + (threadIdx.x >> 6);
         if (c >= dc->n_cells) return;
         const uint32_t v0 = sorted_vox[cell_start[c]];
         const unsigned key[3] = {ckey[v0 * 3], ckey[v0 * 3 + 1], ckey[v0 * 3 + 2]};
@@ -1777,7 +1786,7 @@ struct d_seed_nn {
         // voxel nearer than that is the answer -- 27 cells are only searched when the surface cuts a corner of the cell.  Same (distance, ordinal) minimum.
         {
             const uint32_t b0 = cell_start[c], e0 = cell_start[c + 1];
-            for (uint32_t i0 = b0; i0 < e0; i0 += 256u) {
+            for (uint32_t i0 = b0; i0 < e0; i0 += SEED_CAND_STRIDE) {
                 int j[4]; bool ok[4];
     #pragma unroll
                 for (int u = 0; u < 4; ++u) { const uint32_t i = i0 + 64u * (uint32_t)u + (uint32_t)lane; ok[u] = i < e0; j[u] = (int)sorted_vox[ok[u] ? i : b0]; }
@@ -1801,14 +1810,14 @@ struct d_seed_nn {
             // nearer than half a cell.  The half cell gives up twice that before it is squared (the 1e-3 is for the roundings of a_sqdist alone, 2.4e-7 relative), and where
             // that takes more than half of it away (coordinates beyond 2^21 cells) no shortcut is taken: DESIGN.md 7.
             const float cmax = fmaxf(fabsf(centre[0]), fmaxf(fabsf(centre[1]), fabsf(centre[2])));
-            const double half = 0.5 * gp->res - (double)cmax * 0x1p-23;
-            const float near = half > 0.25 * gp->res ? (float)(half * half * (1.0 - 1e-3)) : 0.0f;
+            const double half = 0.5 * gp->res - (double)cmax * SEED_NN_ULP;
+            const float near = half > 0.25 * gp->res ? (float)(half * half * (1.0 - SEED_NN_MARGIN)) : 0.0f;
             if (best != 0x7fffffff && bd < near) { if (lane == 0) seed_orig[c] = best; return; }      // (uniform: every lane holds the wave's minimum)
             bd = F3DS_FLT_MAX; best = 0x7fffffff;
         }
         // lanes 0..26 look up the 27 cells at the same time; their voxels are then visited as one flat list
         // (the nearest voxel under the (distance, ordinal) order does not depend on the visiting order)
-        __shared__ uint32_t s_beg4[4][28], s_pre4[4][28];
+        __shared__ uint32_t s_beg4[SEED_CELLS_PER_WG][28], s_pre4[SEED_CELLS_PER_WG][28];
         uint32_t* s_beg = s_beg4[threadIdx.x >> 6]; uint32_t* s_pre = s_pre4[threadIdx.x >> 6];
         uint32_t beg = 0, cnt = 0;
         if (lane < 27) {
@@ -1826,7 +1835,7 @@ struct d_seed_nn {
         wave_lds_sync();
         // (four rounds of 64 list entries at a time: their ordinals, then their centroids, are requested together -- entry by entry the ~1 300 voxels of the 27 cells
         // were ~20 rounds of two dependent trips to L2 per wave)
-        for (uint32_t i0 = 0; i0 < total; i0 += 256u) {
+        for (uint32_t i0 = 0; i0 < total; i0 += SEED_CAND_STRIDE) {
             int j[4]; bool ok[4];
     #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -1864,9 +1873,9 @@ struct d_seed_filter {
     __device__ void operator()(const float* vf, const uint32_t* ckey, const uint32_t* sorted_vox, const uint32_t* cell_start,
                                                    const DevCounters* dc, const SeedGrid* gp, const uint64_t* hkeys, const uint32_t* hvals, uint32_t hmask,
                                                    const int* seed_orig, float r2, float min_points, uint32_t* keep) const {
-        __shared__ uint32_t s_beg4[4][28], s_pre4[4][28];
+        __shared__ uint32_t s_beg4[SEED_CELLS_PER_WG][28], s_pre4[SEED_CELLS_PER_WG][28];
         uint32_t* s_beg = s_beg4[threadIdx.x >> 6]; uint32_t* s_pre = s_pre4[threadIdx.x >> 6];
-        const uint32_t c = BIX * 4u + (threadIdx.x >> 6);
+        const uint32_t c = BIX * SEED_CELLS_PER_WG + (threadIdx.x >> 6);
         if (c >= dc->n_cells) return;
         const int lane = lane_id();
         const int s0 = seed_orig[c];
@@ -1886,7 +1895,7 @@ struct d_seed_filter {
                 if (t < 0.0) t = 0.0;
                 far2 += t * t;
             }
-            if (x >= 0 && y >= 0 && z >= 0 && far2 <= (double)r2 * 1.001) {
+            if (x >= 0 && y >= 0 && z >= 0 && far2 <= (double)r2 * SEED_PRUNE_MARGIN) {
                 const int cc = hash_find(hkeys, hvals, hmask, n_pack_key((unsigned)x, (unsigned)y, (unsigned)z));
                 if (cc >= 0) { beg = cell_start[cc]; cnt = cell_start[cc + 1] - beg; }
             }
@@ -1899,7 +1908,7 @@ struct d_seed_filter {
         if (lane == 27) s_pre[27] = total;
         wave_lds_sync();
         uint32_t num = 0;
-        for (uint32_t i0 = 0; i0 < total; i0 += 256u) {       // (four rounds at a time: d_seed_nn)
+        for (uint32_t i0 = 0; i0 < total; i0 += SEED_CAND_STRIDE) {       // (four rounds at a time: d_seed_nn)
             uint32_t vv[4]; bool ok[4];
     #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -1948,6 +1957,11 @@ struct d_seed_compact {
 // ordinal window: d_centroid was 12 ms of that frame's 18 ms of sweeps); up to 64 DISTINCT tiles are visited through the list,
 // more than that, or more than HT_CAP raw entries: the ordinal window [lo, hi].
 constexpr uint32_t HT_CAP = 256;
+// the row path of d_centroid / d_sv_fill (four helpers per wave, 16 lanes each) takes a helper of at most HT_ROW tile-list entries and QL leaves; a frame of more
+// than BY_WAVE_RATIO voxels per seed goes straight to the wave-wide path
+constexpr uint32_t HT_ROW = 16;
+constexpr uint32_t QL = 64;
+constexpr uint32_t BY_WAVE_RATIO = 48;
 struct d_helper_own {
     static constexpr int BLOCK = 256;
     __device__ void operator()(const int* seed_kept, uint32_t S0, uint32_t* owner) const {
@@ -2015,8 +2029,8 @@ struct d_refine_normals {
 struct d_reseed {
     static constexpr int BLOCK = 256;
     __device__ void operator()(const float* vf, uint32_t V, uint32_t S0, const uint32_t* hcount, const float* hc, int* seed) const {
-        __shared__ float sd[256];
-        __shared__ int sv[256];
+        __shared__ float sd[BLOCK];
+        __shared__ int sv[BLOCK];
         const uint32_t h = BIX + 1u;
         if (h > S0) return;
         if (hcount[h] == 0u) { if (threadIdx.x == 0) seed[h - 1u] = -1; return; }
@@ -2030,7 +2044,7 @@ struct d_reseed {
         }
         sd[threadIdx.x] = bd; sv[threadIdx.x] = best;
         __syncthreads();
-        for (int w = 128; w > 0; w >>= 1) {
+        for (int w = BLOCK / 2; w > 0; w >>= 1) {
             if ((int)threadIdx.x < w) {
                 const int ob = sv[threadIdx.x + w]; const float od = sd[threadIdx.x + w];
                 const int mb = sv[threadIdx.x]; const float md = sd[threadIdx.x];
@@ -2627,7 +2641,6 @@ struct d_centroid {
 #define F3DS_CENTROID_WPS 5
 #endif
     static constexpr int WAVES_PER_SIMD = F3DS_CENTROID_WPS;
-    static constexpr uint32_t QL = 64;      // leaves a row-path helper may have
     __device__ void operator()(SweepFrame f, uint32_t t) const {
         __shared__ __attribute__((aligned(16))) float tiles[4][64][12];              // (wave-wide path: feature rows of up to 64 leaves)
         __shared__ uint32_t srts[4][64], leafs[4][64];
@@ -2648,7 +2661,7 @@ struct d_centroid {
         // takes is the chain of dependent loads behind one helper -- the 27 + 54 accesses of mark_tiles per leaf on top of the sums --, and a row walks it four
         // times slower than a wave (measured per launch of 192 frames, sweeps 9..15: 70-210 us a wave per helper, 160-280 us four per wave).
         // (and so do frames of big supervoxels -- 48 voxels and more on average, BASELINE config 4 has 190: most helpers would overflow a row's 64 leaves)
-        const bool by_wave = a_sweep_marks_after_claim(sweep_ctl(f.dc), t, f.thr) || (uint32_t)f.sv.V > 48u * f.S0;
+        const bool by_wave = a_sweep_marks_after_claim(sweep_ctl(f.dc), t, f.thr) || (uint32_t)f.sv.V > BY_WAVE_RATIO * f.S0;
         if (by_wave) {
             // (neighbouring labels are neighbours in space and change together: the four helpers of a group go to the four waves of a workgroup, side by side)
             const uint32_t bix = BIX, stp = gridDim.x;
@@ -2697,7 +2710,7 @@ struct d_centroid {
         const uint32_t tl_ = tl[l16];
         const bool gact = live && ga_ != 0 && !gd_;
         const int gv = gact ? gvx_ : -1;
-        const bool fits = live && cnt + (gv >= 0 ? 1u : 0u) <= 16u;      // (row-uniform; a list that overflowed reads HT_CAP + 1)
+        const bool fits = live && cnt + (gv >= 0 ? 1u : 0u) <= HT_ROW;      // (row-uniform; a list that overflowed reads HT_CAP + 1)
         uint32_t tid = 0xFFFFFFFFu;
         if (fits) { if (l16 < cnt) tid = tl_; else if (l16 == cnt && gv >= 0) tid = (uint32_t)gv >> 6; }
         uint32_t nd, keptbits;
@@ -2858,7 +2871,6 @@ struct d_centroid {
 // does not fit a row (more than 16 list entries, more than 64 leaves) takes the wave-wide path `one_helper`.
 struct d_sv_fill {
     static constexpr int BLOCK = 64;
-    static constexpr uint32_t QL = 64;
     __device__ void operator()(const float* vf, const uint32_t* owner, uint32_t S0, const uint32_t* hlo, const uint32_t* hhi,
                                                const int* ghost_vox, const unsigned char* ghost_active, const uint32_t* hcount, const uint32_t* loff,
                                                const float* hc, float* rows, int* row_voxel, float* racc0, uint32_t* rcnt0, float* rrec0,
@@ -2881,7 +2893,7 @@ struct d_sv_fill {
             rrec0[(size_t)h * 16 + l16] = 0.0f;
         }
         const bool active = live && len != 0u;
-        const bool fits = active && cnt + (gv >= 0 ? 1u : 0u) <= 16u && V <= 48u * S0;      // (frames of big supervoxels -- 48 voxels and more on average -- go straight to the wave-wide path)
+        const bool fits = active && cnt + (gv >= 0 ? 1u : 0u) <= HT_ROW && V <= BY_WAVE_RATIO * S0;      // (frames of big supervoxels -- 48 voxels and more on average -- go straight to the wave-wide path)
         uint32_t tid = 0xFFFFFFFFu;
         if (fits) { if (l16 < cnt) tid = tl_; else if (l16 == cnt && gv >= 0) tid = (uint32_t)gv >> 6; }
         uint32_t nd, keptbits;
@@ -3111,7 +3123,7 @@ __device__ inline void edge_insert(uint64_t key, uint64_t* hkeys, uint32_t hmask
         if (old == key) return;
         if (old == HASH_EMPTY) {
             uint32_t pos = atomicAdd(&dc->n_edges, 1u);
-            if (pos < ecap) ekeys[pos] = key; else { dc->error = F3DS_ERR_UNSUPPORTED; dc->ev_overflow = 3; }      // adjacency list full: the host reruns the stage with more room
+            if (pos < ecap) ekeys[pos] = key; else { dc->error = F3DS_ERR_UNSUPPORTED; dc->ev_overflow = F3DS_OVF_EDGE_LIST; }      // adjacency list full: the host reruns the stage with more room
             return;
         }
         hh = (hh + 1u) & hmask;
@@ -3403,7 +3415,7 @@ struct d_merge {
                 const float w = a_edge_weight(mp, m.rrec + (size_t)lo * 16, m.rrec + (size_t)hi * 16, &err);
                 if (err) m.dc->error = err;
                 const uint32_t ev = atomicAdd(&s_nevents, 1u);
-                if (ev >= m.ev_cap) { m.dc->error = F3DS_ERR_UNSUPPORTED; m.dc->ev_overflow = 1; continue; }
+                if (ev >= m.ev_cap) { m.dc->error = F3DS_ERR_UNSUPPORTED; m.dc->ev_overflow = F3DS_OVF_EVENTS; continue; }
                 const uint32_t ku = n_weight_key(w);
                 m.ev_epoch[ev] = epoch; m.ev_key[ev] = ku; m.ev_prev[ev] = m.ehist[e];
                 m.ea[e] = lo; m.eb[e] = hi; m.ew[e] = w; m.eku[e] = ku; m.ehist[e] = (int)ev;
@@ -3423,7 +3435,11 @@ constexpr uint32_t MC_TL_CAP = 1024;      // edges incident to the two regions o
 // voxel rows the speculative second merge of an epoch may fold: 128, staged one per lane by waves 2 and 3, in the 4-wave layout (the other two carry the first merge's
 // folds); in the 8-wave layout as many of 1024 / 512 / 256 / 128 as the frame's LDS layout has room for, staged one per lane by the whole workgroup, 512 rows a round (BASELINE
 // config 4: supervoxels of ~190 voxels -- at 128 rows one runner-up in seven was small enough and the speculation rested; at 512 five in six are)
-constexpr uint32_t MC_LDS_LIMIT = 160u * 1024u - 2560u;      // dynamic LDS a workgroup may ask for (2.5 KB: the kernel's static LDS)
+constexpr uint32_t MC_LDS_STATIC = 2560;      // bytes of the 160 KB kept back for the kernel's static LDS
+constexpr uint32_t MC_LDS_LIMIT = 160u * 1024u - MC_LDS_STATIC;      // dynamic LDS a workgroup may ask for
+constexpr uint32_t MC_CH_ROWS4 = 128, MC_CH_ROWS8 = 256;      // rows per staging buffer of the 4-wave / 8-wave layout
+constexpr uint32_t MC_SP_ROWS_MIN = 128;      // rows the speculative second merge may fold at the least (the 4-wave layout: always)
+constexpr uint32_t MC_SP_REST_TRIES = 64, MC_SP_REST_EPOCHS = 256;      // the speculation's rest rule: judged every 64 attempts, a rest lasts 256 epochs (F3DS_SP_REST_DIV)
 constexpr uint32_t MC_SP_TL = 256;        // and adjacencies it may touch (its own touched list)
 #ifndef F3DS_SP_REST_DIV
 #define F3DS_SP_REST_DIV 4u      // the speculation rests for 256 epochs when fewer than one in F3DS_SP_REST_DIV of the last 64 attempts were committed
@@ -3451,7 +3467,7 @@ struct MergeIlLayout {
 __host__ __device__ inline MergeIlLayout merge_il_offsets(uint32_t E, int nw, int res) {
     MergeIlLayout L;
     const uint32_t T = (uint32_t)nw * 64u;
-    L.CH = nw == 4 ? 128u : 256u;                                           // rows per staging buffer
+    L.CH = nw == 4 ? MC_CH_ROWS4 : MC_CH_ROWS8;                                           // rows per staging buffer
     L.Ecap = (E + 63u) & ~63u; if (!L.Ecap) L.Ecap = 64u;                    // whole waves of slots
     const uint32_t NG = L.Ecap / MC_GROUP;
     L.NGcap = (NG + T - 1u) / T * T;                                        // every thread reads whole rounds of group minima: no bounds tests
@@ -3468,8 +3484,8 @@ __host__ __device__ inline MergeIlLayout merge_il_offsets(uint32_t E, int nw, in
     L.off_lsrc = o; o += T * 4u;
     o = (o + 15u) & ~15u;
     L.off_stage = o; o += 2u * L.CH * 52u + 64u;                            // two row buffers + 1 / count per row (+ 64: the fold loops read up to 16 rows ahead)
-    L.sp_rows = 128u;
-    if (nw == 8) for (uint32_t r = F3DS_SP_ROWS8; r > 128u; r >>= 1) if (o + r * 52u + MC_SP_TL * 8u + 64u <= MC_LDS_LIMIT) { L.sp_rows = r; break; }
+    L.sp_rows = MC_SP_ROWS_MIN;
+    if (nw == 8) for (uint32_t r = F3DS_SP_ROWS8; r > MC_SP_ROWS_MIN; r >>= 1) if (o + r * 52u + MC_SP_TL * 8u + 64u <= MC_LDS_LIMIT) { L.sp_rows = r; break; }
     L.off_stage2 = o; o += L.sp_rows * 52u + MC_SP_TL * 8u + 64u;               // the speculative second merge: rows, 1 / count, its touched list
     L.total = o;
     return L;
@@ -3921,7 +3937,7 @@ struct d_merge_il_t {
             const bool in_place = na + nb <= cap_a;
             const uint32_t new_start = in_place ? a_start : s_pool_end;
             const uint32_t new_cap = in_place ? cap_a : 2u * (na + nb);
-            if (!in_place && new_start + new_cap > x.pool_cap) { if (tid == 0) { DevCounters* dcp = s_cold.dc; dcp->error = F3DS_ERR_UNSUPPORTED; dcp->ev_overflow = 2; } break; }      // (uniform) leaf pool full: rerun with a larger one
+            if (!in_place && new_start + new_cap > x.pool_cap) { if (tid == 0) { DevCounters* dcp = s_cold.dc; dcp->error = F3DS_ERR_UNSUPPORTED; dcp->ev_overflow = F3DS_OVF_LEAF_POOL; } break; }      // (uniform) leaf pool full: rerun with a larger one
             if (in_place) { for (uint32_t i = tid; i < nb; i += T) x.pool[a_start + na + i] = i < T ? leaf0 : x.pool[b_start + i]; }
             else { for (uint32_t i = tid; i < na + nb; i += T) x.pool[new_start + i] = i < na ? x.pool[a_start + i] : x.pool[b_start + (i - na)]; }
             TPH(7);
@@ -3975,7 +3991,7 @@ struct d_merge_il_t {
             const uint32_t il_pool_end = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_ipool_end);
             const uint32_t il_new = il_in_place ? il_a : il_pool_end;
             const uint32_t il_newcap = il_in_place ? il_ca : nt + (nt >> 1) + 4u;
-            if (!il_in_place && il_new + il_newcap > x.ilist_cap) { if (tid == 0) { DevCounters* dcp = s_cold.dc; dcp->error = F3DS_ERR_UNSUPPORTED; dcp->ev_overflow = 4; } break; }      // (uniform) list pool full: rerun with a larger one (its own multiplier: f3ds_ctx::ilist_mult)
+            if (!il_in_place && il_new + il_newcap > x.ilist_cap) { if (tid == 0) { DevCounters* dcp = s_cold.dc; dcp->error = F3DS_ERR_UNSUPPORTED; dcp->ev_overflow = F3DS_OVF_ILIST_POOL; } break; }      // (uniform) list pool full: rerun with a larger one (its own multiplier: f3ds_ctx::ilist_mult)
             for (uint32_t i = tid; i < nt; i += T) x.ilist[il_new + i] = tl[i];
             bool il_in_place2 = true; uint32_t il_new2 = 0u, il_newcap2 = 0u;
             if constexpr (SPEC) {
@@ -4267,7 +4283,7 @@ struct d_merge_il_t {
             };
             auto publish_edge = [&](uint32_t e, uint32_t lo, uint32_t hi, int hprev, uint32_t ku, uint32_t ep, uint32_t kold) {      // the new weight enters the edge's history and the order keys
                 const uint32_t ev = atomicAdd(&s_nevents, 1u);
-                if (ev >= ev_cap) { DevCounters* dcp = s_cold.dc; dcp->error = F3DS_ERR_UNSUPPORTED; dcp->ev_overflow = 1; s_err = 1; return; }
+                if (ev >= ev_cap) { DevCounters* dcp = s_cold.dc; dcp->error = F3DS_ERR_UNSUPPORTED; dcp->ev_overflow = F3DS_OVF_EVENTS; s_err = 1; return; }
                 s_cold.ev_epoch[ev] = ep; s_cold.ev_key[ev] = ku; s_cold.ev_prev[ev] = hprev;
                 s_cold.ehist[e] = (int)ev;
                 akey[e] = ku; eab[e] = (lo << 16) | hi;
@@ -4404,7 +4420,7 @@ struct d_merge_il_t {
                     if (tid == 0) { s_nt2 = 0u; s_cross = 0u; s_min1 = KEY_DEAD; }
                 } else if (tid == 0 && (s_nt2 | s_cross)) { s_nt2 = 0u; s_cross = 0u; }      // (a speculation given up after the scan)
             }
-            if (SPEC && sp_try >= 64u) { if (sp_hit * F3DS_SP_REST_DIV < sp_try) sp_rest = 256u; sp_try = 0u; sp_hit = 0u; }
+            if (SPEC && sp_try >= MC_SP_REST_TRIES) { if (sp_hit * F3DS_SP_REST_DIV < sp_try) sp_rest = MC_SP_REST_EPOCHS; sp_try = 0u; sp_hit = 0u; }
             for (uint32_t i = tid; i < 2u * MC_TL_CAP; i += T) hsh[i] = 0u;
             __syncthreads();
             TPH(4);

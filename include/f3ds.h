@@ -769,6 +769,32 @@ int f3ds_get_debug(f3ds_ctx* ctx, int what, void* dst, size_t cap_bytes, size_t*
  * speculative second merge of an epoch may absorb (128; 256, 512 or 1024 in the 8-wave layout where LDS has room), out[2] = edge slots, out[3] = 1 if the layout fits a
  * compute unit's LDS (else the cluster stage takes the next layout, at last d_merge).  waves: 4 or 8; keys_in_lds: 2 or 0.  Returns F3DS_ERR_ARG otherwise. */
 int f3ds_merge_layout_info(uint32_t n_edges, int waves, int keys_in_lds, uint32_t out[4]);
+/* The limits of the kernels and of the host's batch-wide decisions, by name (diagnostics and tests; host arithmetic only, no device needed).  Each value is the
+ * constant the code itself uses: NT_RING1, VL_MAX_RUN, MC_TL_CAP, EDGE_MULT, WIDE_CAP, ...; a kernel's workgroup size is "<kernel>::BLOCK"; the reasons for a
+ * rerun in F3DS_TRACE_ERR output are OVF_*; the three floating margins of the seed kernels (SEED_NN_MARGIN, SEED_NN_ULP, SEED_PRUNE_MARGIN) come as the bit
+ * pattern of the double.  f3ds_constant returns F3DS_ERR_ARG for a name it does not know; f3ds_constant_name(i) is the i-th name, NULL behind the last. */
+int f3ds_constant(const char* name, uint64_t* value);
+const char* f3ds_constant_name(size_t index);
+/* What stage 0 of a batch call does for fresh contexts whose live frames have at most max_depth octree levels (0 .. 21) and max_points points, n_contexts
+ * contexts in the call, F3DS_VOX_TILES = vox_tiles (0, 1 = unset, 2) and F3DS_SORT_PAIRS = sort_pairs: out[0] = 1 the tile path / 0 the point sort, out[1] = bits of
+ * a tile's number in a descriptor key, out[2] = bits of a point's index in a one-word sort key (-1: the sort moves (key, index) pairs), out[3] = bits of the
+ * sort key without the index.  The function segment_batch calls (csrc/f3ds_batch_policy.h); host arithmetic only. */
+int f3ds_stage0_plan(int max_depth, uint32_t max_points, int n_contexts, int vox_tiles, int sort_pairs, int32_t out[4]);
+/* The other batch-wide decisions, the same way.  f3ds_policy_capacity: entries of a growing buffer -- F3DS_CAP_EDGES: the adjacency list of count seeds at
+ * edge_mult = mult; F3DS_CAP_EVENTS: the weight history of count edges at ev_mult = mult; F3DS_CAP_LEAF_POOL: the leaf pool of count seeds at pool_mult = mult;
+ * F3DS_CAP_ILIST: the incident-list pool of count edges and n_seeds seeds at ilist_mult = mult under F3DS_ILIST_SLACK = slack.  f3ds_policy_grow: a multiplier
+ * after an overflow, given its cap.  f3ds_policy_dense_penalty: the calls a context stays off the tile path after its next refusal.  f3ds_policy_launch:
+ * out[0] = threads of the normals kernel in a call of `frames` frames (normals_forced: F3DS_NORMALS_THREADS, 0 unset), out[1] = workgroups per frame of a
+ * streaming kernel (grid_target: F3DS_GRID_TARGET; grid_cap_forced: F3DS_GRID_CAP, 0 unset), out[2] = of a gathering kernel. */
+enum { F3DS_CAP_EDGES = 0, F3DS_CAP_EVENTS = 1, F3DS_CAP_LEAF_POOL = 2, F3DS_CAP_ILIST = 3 };
+int f3ds_policy_capacity(int what, uint32_t count, uint32_t n_seeds, uint32_t mult, uint32_t slack, uint32_t* out);
+int f3ds_policy_grow(uint32_t mult, uint32_t cap, uint32_t* out);
+uint32_t f3ds_policy_dense_penalty(uint32_t penalty);
+int f3ds_policy_launch(int frames, int normals_forced, uint32_t grid_target, uint32_t grid_cap_forced, uint32_t out[3]);
+/* Where a batch form of the label-image family puts the outputs of its frames in the staging buffer it downloads (csrc/f3ds_label_image.h, li_stage_layout): frame i
+ * has fixed_bytes[i] bytes of fixed size and, with stage_rows, stage_rows[i] rows of row_bytes bytes whose count the device decides.  slots[3 i ..] = (offset of the
+ * fixed bytes, offset of the rows, rows the first download brings); *first_bytes = the length of that download; *total = the bytes in all. */
+int f3ds_policy_stage_layout(size_t n_frames, const size_t* fixed_bytes, const size_t* stage_rows, size_t row_bytes, size_t first_rows, size_t* slots, size_t* first_bytes, size_t* total);
 
 /* ---- the VCCS result itself: what main() reads back from pcl::SupervoxelClustering after extract()
  * (src/supervoxel_clustering.cpp:359-367).  All valid after f3ds_segment; call with NULL outputs for the count. */

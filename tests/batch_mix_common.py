@@ -4,26 +4,22 @@ remembers of a refusal, frames that leave the batch, the adjacency pass and the 
 the normals kernel.
 
 Plain numpy, no GPU.  MIXES lists every batch: its frames (lattice clouds of vccs_clouds_common.py at voxel_res = R), one set of parameters, the environment of the call,
-the condition that makes it the mix it is named for, and what the call has to show.  A condition is checked from the oracle's lone runs of the frames and from constants
-read out of the sources by regular expression (read_host_constants), never from the code under test: tests/test_batch_mix_cpu.py asserts every condition and that the
+the condition that makes it the mix it is named for, and what the call has to show.  A condition is checked from the oracle's lone runs of the frames and from the constants
+restated below (HOST_CONSTANTS: test_batch_mix_cpu.py compares each with the library's own, P.constant(name)), never from the code under test: tests/test_batch_mix_cpu.py asserts every condition and that the
 emulation equals the oracle on every frame, tests/test_batch_mix_gpu.py runs every mix through segment_batch and compares every frame with its lone oracle run.
 
 The reference of a frame is oracle.segment(frame, prm) on that frame alone.  Its arrays are copied when the run is made (Snapshot): a later cluster() on the oracle's
 handle, which the tests of the contexts' state need, leaves them as they were."""
 import collections
-import os
-import re
 
 import numpy as np
 
 import vccs_clouds_common as C
-from conftest import ALL_DEBUG, ROOT
+from conftest import ALL_DEBUG
 from merge_graphs_common import FIT_EDGES
 from vccs_clouds_common import R, _count_frame, _one_dense, _with_far, block, census, cloud
 
-CSRC = os.path.join(ROOT, "fast-3d-pointcloud-segmentation_amd", "csrc")
-
-# ---- the constants of the host logic the mixes are sized by (checked against the sources by test_batch_mix_cpu.py)
+# ---- the constants of the host logic the mixes are sized by (checked against the library's own by test_batch_mix_cpu.py)
 VT_CNT_BITS = 14            # bits of a tile descriptor's key that hold the entry's point count
 VT_TILE = 4096              # points per tile of stage 0's tile path
 N_BLOCK_DEPTH_MAX = 12      # deepest grid whose neighbour search goes through the 4x4x4 block table
@@ -39,36 +35,18 @@ TILE_MIN_FRAMES = 4         # a call of fewer contexts takes the sort path
 KEY_BITS = 64               # a sort key is one 64-bit word
 ILIST_SHORT_EXTRA = 16      # entries of the incident-list pool of a frame without adjacencies under F3DS_ILIST_SLACK < 32 (2 E + slack * E * mult + 16)
 
-HOST_CONSTANT_PATTERNS = {       # file -> [(regular expression with one group, value it has to give)]
-    "f3ds_kernels.inc": [(r"constexpr int VT_CNT_BITS = (\d+);", VT_CNT_BITS), (r"#define F3DS_VT_TILE (\d+)\n", VT_TILE)],
-    "f3ds_numerics.h": [(r"#define N_BLOCK_DEPTH_MAX (\d+)\n", N_BLOCK_DEPTH_MAX)],
-    "f3ds_hip.hip": [
-        (r"uint32_t vox_dense_wait = 0, vox_dense_penalty = (\d+);", DENSE_PENALTY),
-        (r"c->vox_dense_penalty = std::min\(2u \* c->vox_dense_penalty, (\d+)u\);", DENSE_PENALTY_CAP),
-        (r"c->vox_dense_penalty = std::min\((\d+)u \* c->vox_dense_penalty, \d+u\);", 2),
-        (r"uint32_t edge_mult = (\d+);", EDGE_MULT), (r"\(uint64_t\)S0 \* c->edge_mult \+ (\d+)u, 0x7fffffffu\)", EDGE_EXTRA),
-        (r"c->h_dc->ev_overflow == 3 && c->edge_mult < \(1u << 14\)\) \{ c->edge_mult \*= (\d+)u; again = true; \}", EDGE_GROW),
-        (r"if \(nthr_env \? nthr_env == 256 : g_batch_frames >= (\d+)\)\n\s+rec<d_normals_t<256>>", NORMALS_256_FRAMES),
-        (r"atol\(dev_getenv\(\"F3DS_GRID_TARGET\"\)\) : (\d+);", GRID_TARGET), (r"return cap < 8 \? 8 : \(cap > (\d+) \? \d+ : cap\);", WIDE_CAP),
-        (r"g_wide_cap = g_sw\.grid_cap \? \(size_t\)g_sw\.grid_cap : (\d+);", WIDE_CAP),
-        (r"bool hashed = g_sw\.vox_hash && \(nctx >= (\d+) \|\| g_sw\.vox_tiles_forced\);", TILE_MIN_FRAMES),
-        (r"\(uint64_t\)g_sw\.ilist_slack \* E \* c->ilist_mult \+ \(g_sw\.ilist_slack < 32u \? (\d+)u : 1024u\);", ILIST_SHORT_EXTRA),
-        (r"if \(code_bits \+ tile_bits \+ VT_CNT_BITS > (\d+) \|\|", KEY_BITS), (r"if \(3 \* maxd \+ 1 \+ idxbits > (\d+) \|\| g_sw\.sort_pairs\) idxbits = -1;", KEY_BITS),
-        (r"return seg_vox_tiles\(c, (3 \* maxd), tile_bits\);", "3 * maxd"), (r"return seg_sort\(c, (3 \* maxd \+ 1), idxbits\);", "3 * maxd + 1"),
-        (r"const int tile_bits = bits_for\(\(uint64_t\)(maxtiles - 1u)\);", "maxtiles - 1u"), (r"int idxbits = bits_for\(\(uint64_t\)(maxn - 1u)\);", "maxn - 1u")],
+HOST_CONSTANTS = {       # name of P.constant() -> the value the mixes assume
+    "VT_CNT_BITS": VT_CNT_BITS, "VT_TILE": VT_TILE, "N_BLOCK_DEPTH_MAX": N_BLOCK_DEPTH_MAX, "DENSE_PENALTY": DENSE_PENALTY, "DENSE_PENALTY_STEP": 2,
+    "DENSE_PENALTY_CAP": DENSE_PENALTY_CAP, "EDGE_MULT": EDGE_MULT, "EDGE_EXTRA": EDGE_EXTRA, "GROW": EDGE_GROW, "EDGE_MULT_CAP": 1 << 14, "EV_MULT_CAP": 16384,
+    "POOL_MULT_CAP": 64, "ILIST_MULT_CAP": 4096, "NORMALS_256_FRAMES": NORMALS_256_FRAMES, "GRID_TARGET": GRID_TARGET, "GRID_MIN": 8, "WIDE_CAP": WIDE_CAP,
+    "TILE_MIN_CONTEXTS": TILE_MIN_FRAMES, "ILIST_SLACK": 32, "ILIST_EXTRA_SHORT": ILIST_SHORT_EXTRA, "ILIST_EXTRA": 1024, "KEY_BITS": KEY_BITS,
+    "OVF_EDGE_LIST": 3, "OVF_DENSE_VOXEL": 6, "OVF_TILE_VOXELS": 7,      # the reasons the F3DS_TRACE_ERR lines of the reruns carry
 }
-
-
-def read_host_constants(csrc_dir=CSRC):
-    """[(file, pattern, value found or None, value expected)] for every constant above, from its defining line."""
-    out = []
-    for name, pats in HOST_CONSTANT_PATTERNS.items():
-        text = open(os.path.join(csrc_dir, name)).read()
-        for pat, want in pats:
-            m = re.findall(pat, text)
-            have = m[0] if len(m) == 1 else None
-            out.append((name, pat, int(have) if have is not None and isinstance(want, int) else have, want))
-    return out
+# the grid P.stage0_plan is compared with predict_stage0 on (test_batch_mix_cpu.py)
+PLAN_DEPTHS = tuple(range(1, 22))
+PLAN_POINTS = (1, 2, 515, 4095, 4096, 4097, 4618, 1 << 20)
+PLAN_CONTEXTS = (1, 3, 4, 16)
+PLAN_VOX_TILES = (None, "0", "2")      # F3DS_VOX_TILES: unset, the sort path, the tile path for calls of any size
 
 
 # ------------------------------------------------------------------------------------------------ the two formulas of segment_batch_from
@@ -88,12 +66,14 @@ def sort_key_bits(depths, n_points):
     return 3 * max(depths) + 1 + bits_for(max(1, max(n_points)) - 1)
 
 
-def predict_stage0(depths, n_points, n_contexts, vox_tiles):
+def predict_stage0(depths, n_points, n_contexts, vox_tiles, sort_pairs=False):
     """(stage0_path() of every live frame, form of the point sort or None) for a batch whose live frames have these octree depths and point counts; vox_tiles: the value
-    of F3DS_VOX_TILES (None: unset).  No frame of the batch may be one the tile path refuses after it ran (a dense voxel, a tile of too many voxels)."""
-    if vox_tiles != "0" and n_contexts >= TILE_MIN_FRAMES and tile_key_bits(depths, n_points) <= KEY_BITS:
+    of F3DS_VOX_TILES (None: unset; "2": the tile path for calls of fewer than four contexts too); sort_pairs: F3DS_SORT_PAIRS, which implies the sort path.  No frame of
+    the batch may be one the tile path refuses after it ran (a dense voxel, a tile of too many voxels)."""
+    wanted = vox_tiles != "0" and not sort_pairs and (n_contexts >= TILE_MIN_FRAMES or vox_tiles == "2")
+    if wanted and tile_key_bits(depths, n_points) <= KEY_BITS:
         return "tiles", None
-    return "sort", "pairs" if sort_key_bits(depths, n_points) > KEY_BITS else "one-word"
+    return "sort", "pairs" if sort_pairs or sort_key_bits(depths, n_points) > KEY_BITS else "one-word"
 
 
 def predict_batch_path(runs, n_contexts, vox_tiles=None):
@@ -282,7 +262,7 @@ def runs_of(oracle, P, m):
 
 
 def adjacency_room(S0, mult):
-    return S0 * mult + EDGE_EXTRA
+    return min(S0 * mult + EDGE_EXTRA, 0x7FFFFFFF)
 
 
 def regrows_needed(E, S0, mult):

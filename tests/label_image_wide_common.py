@@ -2,8 +2,8 @@
 _contacts, _shapes, _boxes, _components) at frames WIDER than a workgroup.  Nothing here is a new reference: the references are those of
 region_table_common, region_contacts_common, region_shapes_common, region_boxes_common, region_components_common and track_common, and the scenes are their
 generators at new sizes.  What this file adds is the list of cases, each with the classes of control flow it is for, and a CENSUS: the launch arithmetic of
-csrc/f3ds_hip.hip and the span arithmetic of label_accum_span / pair_accum_span restated in plain Python from the kernels' constants (read from their
-defining lines, KERNEL_CONSTANT_PATTERNS), so that a CPU test can assert that every case reaches what it claims.
+csrc/f3ds_hip.hip and the span arithmetic of label_accum_span / pair_accum_span restated in plain Python from the kernels' constants (KERNEL_CONSTANTS,
+compared with the library's own by name), so that a CPU test can assert that every case reaches what it claims.
 
 Shapes (width x height, depth, layout) and what they reach -- a trip of a 256-thread workgroup moves a lane sv = 256 // width rows and su = 256 - sv * width
 columns on, with one carry:
@@ -20,8 +20,6 @@ Scenes: the region table's 1 (ordinary), 2 (one region: copies = 32, every flush
 Classes (CLASSES): a case lists the ones it is for, census() says which ones it reaches, and the CPU test asserts that the first is a subset of the second and
 that no class is left without a case."""
 import ctypes
-import os
-import re
 
 import numpy as np
 
@@ -44,44 +42,18 @@ RGC_SLOTS, RGC_TRIPS = 256, 8                 # csrc/f3ds_contacts.inc
 RGT_MAX_COPIES, RGT_COPY_BUDGET = 32, 2048    # csrc/f3ds_regions.inc: rgt_copies
 CC_TILE_W, CC_TILE_H = 64, 16                 # csrc/f3ds_components.h
 GRID_CAP = 2048                               # csrc/f3ds_hip.hip: grid_for()'s cap for a lone frame unless F3DS_GRID_CAP narrows it
-KERNEL_CONSTANT_PATTERNS = {       # file -> [(regular expression with one group, value it has to give)]
-    "f3ds_regions.inc": [
-        (r"constexpr int LI_SLOT_BITS = (\d+), LI_SLOTS = 1 << LI_SLOT_BITS;", LI_SLOTS.bit_length() - 1), (r"constexpr int LI_PROBES = (\d+);", LI_PROBES),
-        (r"constexpr uint32_t LI_TRIPS = (\d+);", LI_TRIPS), (r"constexpr uint32_t RGT_MAX_COPIES = (\d+), RGT_COPY_BUDGET = \d+;", RGT_MAX_COPIES),
-        (r"constexpr uint32_t RGT_MAX_COPIES = \d+, RGT_COPY_BUDGET = (\d+);", RGT_COPY_BUDGET),
-        (r"struct d_region_accum \{\n    static constexpr int BLOCK = (\d+);", BLOCK),
-        (r"acc \+= \(size_t\)\(BIX (%) a\.copies\) \* a\.K;", "%"),
-        (r"if \(u (>=) a\.width\) \{ u -= a\.width; \+\+v; \}", ">=")],
-    "f3ds_shapes.inc": [(r"struct d_shape_accum \{\n    static constexpr int BLOCK = (\d+);", BLOCK)],
-    "f3ds_boxes.inc": [(r"struct d_box_accum \{\n    static constexpr int BLOCK = (\d+);", BLOCK)],
-    "f3ds_contacts.inc": [
-        (r"constexpr int RGC_SLOT_BITS = (\d+), RGC_SLOTS = 1 << RGC_SLOT_BITS;", RGC_SLOTS.bit_length() - 1), (r"constexpr uint32_t RGC_TRIPS = (\d+);", RGC_TRIPS),
-        (r"struct d_contact_accum \{\n    static constexpr int BLOCK = (RGC_SLOTS);", "RGC_SLOTS")],
-    "f3ds_components.h": [(r"constexpr uint32_t CC_TILE_W = (\d+), CC_TILE_H = \d+;", CC_TILE_W), (r"constexpr uint32_t CC_TILE_W = \d+, CC_TILE_H = (\d+);", CC_TILE_H)],
-    "f3ds_components.inc": [(r"struct d_comp_local \{\n    static constexpr int BLOCK = (\d+);", BLOCK), (r"struct d_comp_seam \{\n    static constexpr int BLOCK = (\d+);", BLOCK)],
-    "f3ds_track.inc": [(r"struct d_track_keys \{\n    static constexpr int BLOCK = (\d+);", BLOCK)],
-    "f3ds_hip.hip": [      # the launches the census restates
-        (r"thread_local size_t g_grid_cap = (\d+);", GRID_CAP),
-        (r"rec<d_region_accum>\(c, grid_for\(\(n \+ LI_TRIPS - 1u\) / LI_TRIPS, (\d+)\), 0u,", BLOCK),
-        (r"rec<d_shape_accum>\(c, grid_for\(\(n \+ LI_TRIPS - 1u\) / LI_TRIPS, (\d+)\), 0u,", BLOCK),
-        (r"const uint32_t accum_grid = grid_for\(\(n \+ LI_TRIPS - 1u\) / LI_TRIPS, (\d+)\);", BLOCK),
-        (r"rec<d_contact_accum>\(c, grid_for\(\(n \+ RGC_TRIPS - 1u\) / RGC_TRIPS, (\d+)\), 0u,", BLOCK),
-        (r"rec<d_comp_local>\(c, grid_for\(\(size_t\)a\.tiles_x \* a\.tiles_y, (\d+)\), 0u,", 1),
-        (r"rec<d_comp_seam>\(c, grid_for\(seams, (\d+)\), 0u,", BLOCK),
-        (r"rec<d_track_keys>\(c, grid_for\(n, (\d+)\), 0u,", BLOCK)],
+KERNEL_CONSTANTS = {       # name of P.constant() -> the value the census assumes
+    "LI_SLOTS": LI_SLOTS, "LI_PROBES": LI_PROBES, "LI_TRIPS": LI_TRIPS, "RGT_MAX_COPIES": RGT_MAX_COPIES, "RGT_COPY_BUDGET": RGT_COPY_BUDGET, "RGC_SLOTS": RGC_SLOTS,
+    "RGC_TRIPS": RGC_TRIPS, "CC_TILE_W": CC_TILE_W, "CC_TILE_H": CC_TILE_H, "WIDE_CAP": GRID_CAP,
+    # the launches the census restates pass the kernel's own BLOCK to grid_for(); d_comp_local takes a tile per workgroup
+    "d_region_accum::BLOCK": BLOCK, "d_shape_accum::BLOCK": BLOCK, "d_box_accum::BLOCK": BLOCK, "d_contact_accum::BLOCK": RGC_SLOTS, "d_comp_local::BLOCK": BLOCK,
+    "d_comp_seam::BLOCK": BLOCK, "d_track_keys::BLOCK": BLOCK, "CC_TILES_PER_WG": 1,
 }
-
-
-def read_kernel_constants(csrc_dir):
-    """[(file, pattern, value found or None, value expected)] for every constant above, from its defining line."""
-    out = []
-    for name, pats in KERNEL_CONSTANT_PATTERNS.items():
-        text = open(os.path.join(csrc_dir, name)).read()
-        for pat, want in pats:
-            m = re.findall(pat, text)
-            have = m[0] if len(m) == 1 else None
-            out.append((name, pat, int(have) if have is not None and isinstance(want, int) else have, want))
-    return out
+# What the two operators of the span walk decide, by the classes of CLASSES that sit on them from both sides (test_label_image_wide_cpu.py asserts that each class has a
+# case): acc += (BIX % copies) * K -- "wrap32" (more workgroups than accumulator sets: 36 and 39 onto 32) against every case of at most 32 workgroups; several workgroups onto
+# as many sets or more (no wrap); the carry u >= width -- su = 1 (width 255: u reaches the width exactly, one trip in 255), su = 0 (256 and 128: never) and sv = 0 (257
+# and wider: a carry on every trip that crosses a row end, u landing on the width exactly at 512 = two blocks).
+OPERATOR_CLASSES = {"BIX % a.copies": ("wrap32", "several_workgroups"), "u >= a.width": ("below_block", "su0_sv1", "su0_sv2", "sv0")}
 
 
 # ---- the launch and span arithmetic, restated -----------------------------------------------------------------------------------------------------------------

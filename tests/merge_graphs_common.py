@@ -15,12 +15,10 @@ lambda * CIEDE2000(mean colours) / range: the colours decide the order.  Two edg
 Under ADAPTIVE_LAMBDA identical normals give lambda = 0 and every initial weight 0 (a mass tie); identical normals AND colours give lambda = NaN and no merge."""
 import collections
 import functools
-import os
-import re
 
 import numpy as np
 
-# ---- the constants of the merge kernels the cases are sized by (checked against the sources by test_merge_graphs_cpu.py)
+# ---- the constants of the merge kernels the cases are sized by (checked against the library's own by test_merge_graphs_cpu.py)
 MC_TL_CAP = 1024        # adjacencies the two regions of one merge may touch in d_merge_il_t; also equal minimum keys its tie path takes
 MC_SP_TL = 256          # adjacencies a speculative second merge may touch
 MC_SP_LEAVES = 8        # supervoxels the region a speculative second merge absorbs may consist of
@@ -32,26 +30,12 @@ SP_REST_TRIES, SP_REST_DIV, SP_REST_EPOCHS = 64, 4, 256      # the speculation r
 EV_MULT, EV_EXTRA = 64, 4096       # weight-history events a frame starts with: E * 64 + 4096
 LANES = 64
 
-KERNEL_CONSTANT_PATTERNS = {       # file -> [(regular expression with one group, value it has to give)]
-    "f3ds_kernels.inc": [
-        (r"constexpr uint32_t MC_TL_CAP = (\d+);", MC_TL_CAP), (r"constexpr uint32_t MC_SP_TL = (\d+);", MC_SP_TL), (r"#define F3DS_SP_LEAVES (\d+)\n", MC_SP_LEAVES),
-        (r"constexpr uint32_t MC_GROUP = (\d+);", MC_GROUP), (r"#define F3DS_SP_ROWS8 (\d+)u", SP_ROWS8_MAX), (r"#define F3DS_SP_REST_DIV (\d+)u", SP_REST_DIV),
-        (r"L\.CH = nw == 4 \? (\d+)u : \d+u;", CHUNK_ROWS[4]), (r"L\.CH = nw == 4 \? \d+u : (\d+)u;", CHUNK_ROWS[8]), (r"L\.sp_rows = (\d+)u;", 128),
-        (r"if \(SPEC && sp_try >= (\d+)u\)", SP_REST_TRIES), (r"if \(sp_hit \* F3DS_SP_REST_DIV < sp_try\) sp_rest = (\d+)u;", SP_REST_EPOCHS),
-        (r"constexpr uint32_t MC_LDS_LIMIT = 160u \* 1024u - (\d+)u;", 2560)],
-    "f3ds_hip.hip": [(r"uint32_t ev_mult = (\d+);", EV_MULT), (r"\(uint64_t\)E \* c->ev_mult \+ (\d+)u;", EV_EXTRA)],
+KERNEL_CONSTANTS = {       # name of P.constant() -> the value the cases assume
+    "MC_TL_CAP": MC_TL_CAP, "MC_SP_TL": MC_SP_TL, "MC_SP_LEAVES": MC_SP_LEAVES, "MC_GROUP": MC_GROUP, "MC_SP_ROWS8": SP_ROWS8_MAX, "MC_SP_REST_DIV": SP_REST_DIV,
+    "MC_CH_ROWS4": CHUNK_ROWS[4], "MC_CH_ROWS8": CHUNK_ROWS[8], "MC_SP_ROWS_MIN": 128, "MC_SP_REST_TRIES": SP_REST_TRIES, "MC_SP_REST_EPOCHS": SP_REST_EPOCHS,
+    "MC_LDS_STATIC": 2560, "MC_LDS_LIMIT": MC_LDS_LIMIT, "EV_MULT": EV_MULT, "EV_EXTRA": EV_EXTRA,
+    "OVF_EVENTS": 1, "OVF_LEAF_POOL": 2, "OVF_ILIST_POOL": 4,      # the reasons for a rerun of the merge stage
 }
-
-
-def read_kernel_constants(csrc_dir):
-    """[(file, pattern, value found or None, value expected)] for every constant above, from its defining line."""
-    out = []
-    for name, pats in KERNEL_CONSTANT_PATTERNS.items():
-        text = open(os.path.join(csrc_dir, name)).read()
-        for pat, want in pats:
-            m = re.findall(pat, text)
-            out.append((name, pat, int(m[0]) if len(m) == 1 else None, want))
-    return out
 
 
 # ------------------------------------------------------------------------------------------------ building blocks

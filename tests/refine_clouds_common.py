@@ -35,8 +35,6 @@ without sweeps never ran updateCentroid: every centroid is still the zero it sta
 """
 import collections
 import ctypes
-import os
-import re
 
 import numpy as np
 
@@ -44,23 +42,7 @@ import vccs_clouds_common as C
 from conftest import first_mismatch, same_bits
 
 RESEED_BLOCK = 256      # d_reseed::BLOCK: thread t scans the voxels t, t + 256, ...; the reduction halves 256 threads down to one
-RESEED_PATTERNS = [     # (regular expression with one group, value it has to give) in f3ds_kernels.inc
-    (r"struct d_reseed \{\n    static constexpr int BLOCK = (\d+);", RESEED_BLOCK),
-    (r"__shared__ float sd\[(\d+)\];\n        __shared__ int sv\[\d+\];\n        const uint32_t h = BIX \+ 1u;", RESEED_BLOCK),
-    (r"__shared__ float sd\[\d+\];\n        __shared__ int sv\[(\d+)\];\n        const uint32_t h = BIX \+ 1u;", RESEED_BLOCK),
-    (r"for \(int w = (\d+); w > 0; w >>= 1\) \{\n            if \(\(int\)threadIdx\.x < w\) \{\n                const int ob = sv\[threadIdx\.x \+ w\];", RESEED_BLOCK // 2),
-]
 REFINE_KEYS = ("voxel_label", "label", "n_voxels", "voxel_normal", "xyz", "rgb", "normal")      # the seven arrays of a refine call
-
-
-def read_reseed_constants(csrc_dir):
-    """[(pattern, value found or None, value expected)] from the defining lines of d_reseed."""
-    text = open(os.path.join(csrc_dir, "f3ds_kernels.inc")).read()
-    out = []
-    for pat, want in RESEED_PATTERNS:
-        m = re.findall(pat, text)
-        out.append((pat, int(m[0]) if len(m) == 1 else None, want))
-    return out
 
 
 # ------------------------------------------------------------------------------------------------ the cases

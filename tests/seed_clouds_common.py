@@ -13,15 +13,13 @@ float32 holds exactly: ties and the bounds r^2 and res^2 / 4 are hit bit for bit
 import collections
 import functools
 import math
-import os
-import re
 
 import numpy as np
 
 import vccs_clouds_common as V
 from conftest import ALL_DEBUG, first_mismatch
 
-# ---- the constants of the seed kernels the cases are sized by (checked against the sources by test_seed_clouds_cpu.py)
+# ---- the constants of the seed kernels the cases are sized by (checked against the library's own by test_seed_clouds_cpu.py)
 SEED_CHUNK = 256            # voxels per box of d_chunkbox; d_seed_grow looks at 256 chunk boxes per trip
 CAND_STRIDE = 256           # list entries a wave of d_seed_nn / d_seed_filter takes per round
 CELLS_PER_WG = 4            # seed cells per workgroup of d_seed_nn / d_seed_filter (a wave each)
@@ -30,31 +28,15 @@ NN_MARGIN = 1e-3            # d_seed_nn: own-cell shortcut below res^2 / 4 * (1 
 PRUNE_MARGIN = 1.001        # d_seed_filter: a cell is looked up when its box is within r2 * 1.001 of the seed voxel
 FLT_EPS = float(np.finfo(np.float32).eps)
 
-SEED_CONSTANT_PATTERNS = {
-    "f3ds_kernels.inc": [
-        (r"constexpr int SEED_CHUNK = (\d+);", 1, SEED_CHUNK),
-        (r"for \(uint32_t c = c0 \+ threadIdx\.x; c < C; c \+= \(uint32_t\)(BLOCK)\)", 1, "BLOCK"),
-        (r"for \(uint32_t i0 = (?:b0|0); i0 < (?:e0|total); i0 \+= (\d+)u\)", 3, CAND_STRIDE),      # own cell and 27 cells of d_seed_nn, d_seed_filter
-        (r"const uint32_t c = BIX \* (\d+)u \+ \(threadIdx\.x >> 6\);", 2, CELLS_PER_WG),
-        (r"\(float\)\(half \* half \* \(1\.0 - (1e-3)\)\)", 1, "1e-3"),
-        (r"const double half = 0\.5 \* gp->res - \(double\)cmax \* (0x1p-23);", 1, "0x1p-23"),
-        (r"far2 <= \(double\)r2 \* (1\.001)\)", 1, "1.001"),
-        (r"if \(lane == 0\) keep\[c\] = \(\(float\)num (>) min_points\)", 1, ">"),
-        (r"a_sqdist\(sp, pp\) (<) r2\) num\+\+", 1, "<")],
-    "f3ds_algo.h": [(r"#define F3DS_MAX_SEED_EVENTS (\d+)\n", 1, MAX_SEED_EVENTS)],
-    "f3ds_hip.hip": [(r"rec<d_seed_nn>\(c, \(C \+ 3u\) / (\d+)u,", 1, CELLS_PER_WG), (r"rec<d_seed_filter>\(c, \(C \+ 3u\) / (\d+)u,", 1, CELLS_PER_WG)],
+SEED_ULP = 2.0 ** -23       # d_seed_nn: the half cell gives up this much of the centre's largest coordinate before it is squared
+SEED_CONSTANTS = {       # name of P.constant() -> the value the cases assume
+    "SEED_CHUNK": SEED_CHUNK, "d_seed_grow::BLOCK": SEED_CHUNK, "SEED_CAND_STRIDE": CAND_STRIDE, "SEED_CELLS_PER_WG": CELLS_PER_WG, "d_seed_nn::BLOCK": 64 * CELLS_PER_WG,
+    "d_seed_filter::BLOCK": 64 * CELLS_PER_WG, "MAX_SEED_EVENTS": MAX_SEED_EVENTS, "SEED_NN_MARGIN": NN_MARGIN, "SEED_NN_ULP": SEED_ULP, "SEED_PRUNE_MARGIN": PRUNE_MARGIN,
 }
-
-
-def read_seed_constants(csrc_dir):
-    """[(file, pattern, values found, values expected)] for every constant above, from its defining lines."""
-    out = []
-    for name, pats in SEED_CONSTANT_PATTERNS.items():
-        text = open(os.path.join(csrc_dir, name)).read()
-        for pat, times, want in pats:
-            m = re.findall(pat, text)
-            out.append((name, pat, [int(x) if isinstance(want, int) else x for x in m], [want] * times))
-    return out
+# The two strict comparisons of d_seed_filter, by the cases that sit on them from both sides (test_seed_clouds_cpu.py asserts they are in the list; their conditions in
+# check_condition say what they hold): (float)num > min_points -- c9-min-points-exactly-2 has seeds with exactly min_points = 2 neighbours (dropped) and with more (kept);
+# a_sqdist < r2 -- c2-at-the-radius has voxels at exactly the radius (not counted) beside voxels inside it (counted), both deciding whether a seed is kept.
+FILTER_BOUNDARY_CASES = {"num > min_points": "c9-min-points-exactly-2", "a_sqdist < r2": "c2-at-the-radius"}
 
 
 # ------------------------------------------------------------------------------------------------ the reference

@@ -1,10 +1,9 @@
-"""The label-image calls at frames wider than a workgroup (tests/label_image_wide_common.py), without a GPU: the CENSUS -- the kernels' constants as their
-defining lines state them, every case reaching the classes of control flow it is for, every class populated -- and the `_host` form of every call against
+"""The label-image calls at frames wider than a workgroup (tests/label_image_wide_common.py), without a GPU: the CENSUS -- the kernels' constants as the
+library itself names them (P.constant), every case reaching the classes of control flow it is for, every class populated -- and the `_host` form of every call against
 its Python reference at every case, bit for bit: f3ds_region_table_host, _contacts_host, _shapes_host, _boxes_host, _components_host,
 f3ds_region_components_tiled (the kernels' union-find steps, sequentially) at tile sizes 64 x 16 and 3 x 5, and the tracker's update composed from
 f3ds_deproject, f3ds_track_reproject and f3ds_track_assign as tests/test_track_cpu.py composes it.  This is what shows that the references are right at the new
 shapes before a GPU sees them; tests/test_label_image_wide_gpu.py compares the device with the same cached references."""
-import os
 
 import numpy as np
 import pytest
@@ -24,9 +23,13 @@ IDS = [c.id for c in W.CASES]
 # ---- the census -----------------------------------------------------------------------------------------------------------------------------------------------
 
 def test_the_kernels_constants_are_the_census_constants(P):
-    csrc = os.path.join(os.path.dirname(os.path.abspath(P.__file__)), "csrc")
-    for name, pat, have, want in W.read_kernel_constants(csrc):
-        assert have == want, "%s: %r gives %r, the census assumes %r" % (name, pat, have, want)
+    got = [(name, P.constant(name), want) for name, want in W.KERNEL_CONSTANTS.items()]
+    assert len(got) == 18
+    for name, have, want in got:
+        assert have == want, "%s is %r, the census assumes %r" % (name, have, want)
+    # the remainder of the accumulator sets and the carry of the span walk: the classes that sit on either side of them all have cases
+    sides = [cl for classes in W.OPERATOR_CLASSES.values() for cl in classes]
+    assert len(sides) == 6 and all(any(cl in c.classes for c in W.CASES) for cl in sides)
     assert W.rgt_copies(1) == 32 and W.rgt_copies(64) == 32 and W.rgt_copies(65) == 31 and W.rgt_copies(2049) == 1 and W.rgt_copies(0) == 32
 
 

@@ -1,18 +1,16 @@
 """The synthetic merge graphs of merge_graphs_common.py, checked without a GPU: the generator is deterministic, the oracle's run of every case meets the structural
 condition the case is for (so no case can stop exercising its path unnoticed), the replay accepts every oracle log and refuses a damaged one, the oracle is invariant
-under other keys and row orders, and the kernel constants the cases are sized by are the ones in the sources.
+under other keys and row orders, and the kernel constants the cases are sized by are the library's own (P.constant).
 
 Oracle seconds per case on the development machine (each run is made once per process and shared): star400-to-the-end 1.1 - 1.3, star1099 0.6, grid30-all-equal 0.5,
 chain-E8191 / E8192 / E8193 0.5 - 0.6 each, the three grids of 12 096 / 12 160 edges 0.7 - 0.8 each, the six tie17-lane chains (3 147 edges) 0.1 - 0.6 each (equalization the
 most), chain-E4095 .. E4097 0.2 each, grid22-all-equal 0.2, star1024 .. star1026 and hubs 0.2 each, rest-and-resume 0.15, star1099-all-equal 0.1, everything else under 0.1:
 about 10 s for the 109 cases, and 3 s more for the nine runs under other keys."""
-import os
 
 import numpy as np
 import pytest
 
 import merge_graphs_common as G
-from conftest import ROOT
 from test_cluster_supervoxels import map_labels, relabel
 
 NAMES = [c.name for c in G.CASES]
@@ -43,12 +41,17 @@ def test_every_supervoxel_of_every_case_is_a_plane_patch():
         assert (np.linalg.norm(np.cross(u, v), axis=1) > 0).all(), name
 
 
-def test_kernel_constants_the_cases_are_sized_by():
-    """MC_TL_CAP, MC_SP_TL, MC_SP_LEAVES, MC_GROUP, the staging chunks, the speculation's rest counter and the initial event room, read from their defining lines."""
-    got = G.read_kernel_constants(os.path.join(ROOT, "fast-3d-pointcloud-segmentation_amd", "csrc"))
-    assert len(got) == 14
-    for name, pat, have, want in got:
-        assert have == want, "%s: %s gives %r, the tests assume %r" % (name, pat, have, want)
+def test_kernel_constants_the_cases_are_sized_by(P):
+    """MC_TL_CAP, MC_SP_TL, MC_SP_LEAVES, MC_GROUP, the staging chunks, the speculation's rest counter, the LDS limit, the initial event room and the reasons for a rerun
+    of the stage: the library's own constants by name -- and the event room as the host computes it from them."""
+    got = [(name, P.constant(name), want) for name, want in G.KERNEL_CONSTANTS.items()]
+    assert len(got) == 18
+    for name, have, want in got:
+        assert have == want, "%s is %r, the tests assume %r" % (name, have, want)
+    for E in (0, 1, 63, 4096, 12096, 1 << 20, 1 << 28):
+        for mult in (G.EV_MULT, 4 * G.EV_MULT, 16384):
+            assert P.policy_capacity(P.CAP_EVENTS, E, mult) == min(E * mult + G.EV_EXTRA, 0x7FFFFFFF), (E, mult)
+    assert P.policy_grow(G.EV_MULT, P.constant("EV_MULT_CAP")) == 4 * G.EV_MULT
 
 
 def test_largest_edge_count_whose_keys_fit_lds(P):

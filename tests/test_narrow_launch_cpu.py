@@ -50,9 +50,8 @@ def test_case_tables_are_consistent():
 
 
 def test_every_listed_kernel_exists():
-    src = open(os.path.join(ROOT, "fast-3d-pointcloud-segmentation_amd", "csrc", "f3ds_kernels.inc")).read()
-    src += open(os.path.join(ROOT, "fast-3d-pointcloud-segmentation_amd", "csrc", "f3ds_eval_levels.inc")).read()
-    src += open(os.path.join(ROOT, "fast-3d-pointcloud-segmentation_amd", "csrc", "f3ds_levels.inc")).read()
+    csrc = os.path.join(ROOT, "fast-3d-pointcloud-segmentation_amd", "csrc")
+    src = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".inc", ".hip")))      # (wherever a kernel lives)
     for fam in FAMILIES:
         for k in re.findall(r"\bd_\w+", fam.kernels):
             assert re.search(r"struct %s\b" % k, src), (fam.name, k)

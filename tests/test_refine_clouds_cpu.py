@@ -12,24 +12,23 @@ d-deep-chain-cold, n-line-V127, s-voxel-of-256-points, g-seed-ghosts-one-sweep a
 k = 2, 3 -- the cases and iterations whose census counts reduction_ties, r-helpers-of-64-and-65-leaves excepted (its ties lie inside isolated 2 x 2 crumbs that regrow
 alike from any of their four voxels).  With `d <= bd` in a thread's scan (the last minimum stays) it fails on r-holes-same-thread-tie at every k and passes everywhere
 else: no other case has two tied voxels in one thread."""
-import os
 
 import numpy as np
 import pytest
 
 import refine_clouds_common as RC
 import vccs_clouds_common as C
-from conftest import ROOT
 
 PAIRS = [(c.name, k) for c in RC.CASES for k in c.ks]
 
 
-def test_reseed_block_is_the_one_in_the_source():
-    """d_reseed::BLOCK, the two LDS arrays and the first stride of the reduction: the census sorts ties by ordinal % 256."""
-    got = RC.read_reseed_constants(os.path.join(ROOT, "fast-3d-pointcloud-segmentation_amd", "csrc"))
-    assert len(got) == 4
-    for pat, have, want in got:
-        assert have == want, "%s gives %r, the census assumes %r" % (pat, have, want)
+def test_reseed_block_is_the_one_in_the_source(P):
+    """d_reseed::BLOCK: the census sorts ties by ordinal % 256.  The kernel sizes its two LDS arrays by BLOCK and starts its reduction at BLOCK / 2, so the one number
+    is all there is to restate; that the reduction halves down to one thread needs a power of two, and what the scan stride and the reduction's tie clause decide is
+    held by the cases whose census counts two tied voxels in one thread (256 apart) and ties the reduction decides."""
+    facts = [P.constant("d_reseed::BLOCK") == RC.RESEED_BLOCK, RC.RESEED_BLOCK & (RC.RESEED_BLOCK - 1) == 0,
+             "r-holes-same-thread-tie" in RC.CASE, "n-line-V127" in RC.CASE and "r-tiny-supervoxels-desc" in RC.CASE]
+    assert len(facts) == 4 and all(facts), facts
 
 
 def test_the_case_list_is_the_one_the_issue_names():

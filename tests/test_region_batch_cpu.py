@@ -111,11 +111,13 @@ def test_the_staging_layout_keeps_the_frames_apart(P):
 
 
 def test_the_layout_in_the_header_is_the_one_restated(P):
-    """the defining lines of li_stage_layout say what stage_layout() above says"""
-    import os
-    src = open(os.path.join(os.path.dirname(os.path.abspath(P.__file__)), "csrc", "f3ds_label_image.h")).read()
-    for line in ("size_t off = nctx * LI_HEAD_BYTES;", "slot[i].at = off; off += li_align8(fixed[i]);",
-                 "if (stage_rows && stage_rows[i] <= first_rows) { slot[i].first = stage_rows[i]; off += li_align8(stage_rows[i] * row_bytes); }",
-                 "if (first_long) { slot[i].first = first_rows; *first_bytes = off + first_rows * row_bytes; first_long = false; }",
-                 "inline size_t li_align8(size_t x) { return (x + 7u) & ~(size_t)7u; }"):
-        assert line in src, line
+    """li_stage_layout computes what stage_layout() above says, on the batches of the test before this one and at the rows either side of the first download"""
+    rng = np.random.default_rng(5)
+    cases = [([4 * 5917], [5000], 12, 2048), ([0], None, 12, 2048), ([4, 12], [2048, 2049], 40, 2048), ([72, 0, 4], [2049, 2049, 0], 12, 2048)]
+    for trial in range(200):
+        n = int(rng.integers(1, 9))
+        fixed = [int(x) for x in rng.choice([0, 4, 12, 72, 84 * 23, 4 * 5917], n)]
+        rows = None if trial % 3 == 0 else [int(x) for x in rng.choice([0, 1, 64, 2048, 2049, 11834], n)]
+        cases.append((fixed, rows, int(rng.choice([12, 40])), 2048))
+    for fixed, rows, rb, first_rows in cases:
+        assert P.policy_stage_layout(fixed, rows, rb, first_rows) == stage_layout(fixed, rows, rb, first_rows), (fixed, rows, rb)

@@ -1,14 +1,13 @@
 """The seed-stage clouds of seed_clouds_common.py, checked without a GPU: the brute-force reference gives what a hand count gives, the census of every case (taken from the
 reference alone) meets the condition the case is for, reference = oracle = emulation on SEED_ORIG, SEED_KEPT and n_seed_cells -- which is the check that the oracle's
 restriction to 27 cells is sound on these clouds --, the emulation equals the oracle on every debug array, and the constants and margins of the seed kernels the cases are
-sized by are the ones in the sources."""
-import os
+sized by are the library's own (P.constant)."""
 
 import numpy as np
 import pytest
 
 import seed_clouds_common as S
-from conftest import ALL_DEBUG, ROOT, first_mismatch
+from conftest import ALL_DEBUG, first_mismatch
 
 _emul = {}
 
@@ -37,16 +36,17 @@ def test_reference_gives_what_a_hand_count_gives():
     assert S.morton(np.array([[1, 0, 0], [0, 1, 0], [0, 0, 1], [2, 0, 0]]), 2).tolist() == [4, 2, 1, 32]
 
 
-def test_seed_kernel_constants_the_cases_are_sized_by():
-    """SEED_CHUNK = 256 and the 256 chunk boxes of a trip of d_seed_grow (its BLOCK), the 256u stride of the three candidate loops, four cells per workgroup in the kernels
-    and in their launches, F3DS_MAX_SEED_EVENTS, the margins 1e-3 and 1.001, the 2^-23 of its largest coordinate the half cell gives up, and the two strict comparisons of the filter."""
-    got = S.read_seed_constants(os.path.join(ROOT, "fast-3d-pointcloud-segmentation_amd", "csrc"))
-    assert len(got) == 12
-    for name, pat, have, want in got:
-        assert have == want, "%s: %s gives %r, the tests assume %r" % (name, pat, have, want)
-    text = open(os.path.join(ROOT, "fast-3d-pointcloud-segmentation_amd", "csrc", "f3ds_kernels.inc")).read()
-    grow = text[text.index("struct d_seed_grow {"):text.index("struct d_seed_keys {")]
-    assert "static constexpr int BLOCK = 256;" in grow
+def test_seed_kernel_constants_the_cases_are_sized_by(P):
+    """SEED_CHUNK = 256 and the 256 chunk boxes of a trip of d_seed_grow (its BLOCK), the stride 256 of the three candidate loops, four cells per workgroup (a wave each
+    of the kernels' 256 threads; their launches divide by the same constant), F3DS_MAX_SEED_EVENTS, the margins 1e-3 and 1.001 and the 2^-23 of its largest coordinate
+    the half cell gives up -- the library's own constants by name, the margins bit for bit as doubles --, and the two strict comparisons of the filter by the cases that
+    sit on them from both sides."""
+    got = [(name, P.constant(name), want) for name, want in S.SEED_CONSTANTS.items()]
+    assert len(got) == 10
+    for name, have, want in got:
+        assert have == want and type(have) is type(want), "%s is %r, the tests assume %r" % (name, have, want)
+    assert len(S.FILTER_BOUNDARY_CASES) == 2 and set(S.FILTER_BOUNDARY_CASES.values()) <= set(S.NAMES)
+    assert S.CASE["c9-min-points-exactly-2"].cond == ("exact_min_points", 2) and S.CASE["c2-at-the-radius"].cond == ("at_r2",)
 
 
 def test_the_case_list():

@@ -9,7 +9,6 @@ import pytest
 import sweep_states_common as S
 from conftest import ROOT, same_bits
 from test_kernprobe_cpu import EARG, kp_built, kp_nogpu  # noqa: F401  (fixtures)
-from vccs_clouds_common import read_kernel_constants
 
 
 @pytest.mark.parametrize("case", S.CASES, ids=lambda c: c.name)
@@ -109,15 +108,10 @@ def contract_breach(st):
     return None
 
 
-def test_kernel_constants_the_cases_are_sized_by():
-    csrc = os.path.join(ROOT, "fast-3d-pointcloud-segmentation_amd", "csrc")
-    found = read_kernel_constants(csrc)
-    need = {"HT_CAP": S.HT_CAP, "F3DS_R_STACK": S.R_STACK, "F3DS_R_ROUNDS": S.R_ROUNDS, "NT_TILE": S.NT_TILE, "<= (\\d+)u;": S.HT_ROW, "QL = ": S.QL, "V > (\\d+)u": S.BY_WAVE_RATIO}
-    for key, want in need.items():
-        hits = [(have, w) for _, pat, have, w in found if key in pat]
-        assert hits, key
-        for have, w in hits:
-            assert have == w and (w == want or w == [want, want]), (key, have, w, want)
+def test_kernel_constants_the_cases_are_sized_by(P):
+    need = {"HT_CAP": S.HT_CAP, "R_STACK": S.R_STACK, "R_ROUNDS": S.R_ROUNDS, "NT_TILE": S.NT_TILE, "HT_ROW": S.HT_ROW, "QL": S.QL, "BY_WAVE_RATIO": S.BY_WAVE_RATIO}
+    for name, want in need.items():
+        assert P.constant(name) == want, (name, P.constant(name), want)
     assert (S.HT_CAP, S.R_STACK, S.R_ROUNDS, S.NT_TILE, S.HT_ROW, S.QL, S.BY_WAVE_RATIO) == (256, 24, 4, 128, 16, 64, 48)
     # the emulation's census names the same limits
     text = open(os.path.join(ROOT, "tests", "emul", "f3ds_emul.cpp")).read()

@@ -1,7 +1,7 @@
 """The synthetic lattice clouds of vccs_clouds_common.py, checked without a GPU: the generator is deterministic and puts every point a quarter of a cell inside its
 voxel, the census counts what a hand count gives, the oracle's run of every case meets the condition the case is for (so no case can stop exercising its path
 unnoticed), the emulation of the device pipeline equals the oracle byte for byte on every case -- once more with every sweep full where sweeps are the subject --, the
-kernel constants the cases are sized by are the ones in the sources, and the golden cases reach none of these paths (when one starts to, that test says so and the case
+kernel constants the cases are sized by are the library's own (P.constant), and the golden cases reach none of these paths (when one starts to, that test says so and the case
 list can shrink).
 
 Oracle seconds on the development machine: 1.4 s for the 50 cases together (r-tiny-supervoxels-desc 0.3, the blocks of 4 000 to 8 000 voxels 0.06 - 0.11 each, everything else
@@ -65,14 +65,28 @@ def test_census_counts_what_a_hand_count_gives(oracle, P):
     assert cen.disorder
 
 
-def test_kernel_constants_the_cases_are_sized_by():
+def test_kernel_constants_the_cases_are_sized_by(P):
     """NT_RING1, NT_SLOTS, VL_MAX_RUN, VT_ENT_MAX, F3DS_VT_TILE, VG_CHUNK, RL_LDS_CAP, HT_CAP, QL, the 63 of a_sweep_tag, F3DS_R_STACK, F3DS_R_ROUNDS and the 48 of the
-    wave-per-helper switch, read from their defining lines -- and the comparisons at the four table limits (> / >= / <), which decide on which side 256, 1280, 448 and 896 fall."""
-    got = C.read_kernel_constants(os.path.join(ROOT, "fast-3d-pointcloud-segmentation_amd", "csrc"))
-    assert len(got) == 24
-    for name, pat, have, want in got:
-        assert have == want, "%s: %s gives %r, the tests assume %r" % (name, pat, have, want)
+    wave-per-helper switch: the library's own constants by name -- and the side of the four table limits 256, 1280, 448 and 896 fall on: the first two (and the relabel
+    table's 12288) by the pair of cases that sits on the limit from both sides, whose conditions predict the path the GPU test then sees; the two ring tables, which no
+    lattice block sits on from both sides, by the one-line predicates beside their constants."""
+    got = [(name, P.constant(name), want) for name, want in C.KERNEL_CONSTANTS.items()]
+    assert len(got) == 17
+    for name, have, want in got:
+        assert have == want, "%s is %r, the tests assume %r" % (name, have, want)
     assert C.VT_ENT_MAX == C.VT_TILE // 2 * 5 // 8
+    sides = 0
+    for limit, (fits, over) in sorted(C.BOUNDARY_CASES.items()):
+        assert fits in C.CASE and over in C.CASE, limit
+        a, b = C.CASE[fits].cond, C.CASE[over].cond
+        assert a[0] == b[0] and a[1] == C.KERNEL_CONSTANTS[limit] - (limit == "RL_LDS_CAP") and b[1] == a[1] + 1, (limit, a, b)      # (S0 + 1 labels: 12287 seeds fill the table)
+        sides += 2
+    assert sides == 6
+    preds = C.read_predicates(os.path.join(ROOT, "fast-3d-pointcloud-segmentation_amd", "csrc"))
+    assert len(preds) == 2
+    for pat, have, want in preds:
+        assert have == [want], "%s gives %r, the tests assume %r" % (pat, have, want)
+    assert "n-ring2-896-fits" in C.CASE and C.CASE["n-ring2-896-fits"].cond[2] == C.NT_SLOTS      # (the side a behavioural case does sit on: a two-ring of exactly 896 fits)
 
 
 def test_the_case_list_is_the_one_the_issue_names():

@@ -21,7 +21,7 @@ import numpy as np
 
 from conftest import ALL_DEBUG, first_mismatch
 
-# ---- the constants of the kernels the cases are sized by (checked against the sources by test_vccs_clouds_cpu.py)
+# ---- the constants of the kernels the cases are sized by (checked against the library's own by test_vccs_clouds_cpu.py)
 NT_TILE = 128           # voxels per tile of d_normals_t (leaf order)
 NT_RING1 = 448          # distinct voxels a tile's one-ring may hold (a ring of exactly 448 fits)
 NT_SLOTS = 896          # ... and its two-ring
@@ -39,37 +39,30 @@ R_ROUNDS = 4            # F3DS_R_ROUNDS
 BY_WAVE_RATIO = 48      # d_centroid: V > 48 * S0 -> a wave per helper
 TILE_NONE = 0xFFFFFFFF  # SW_TILE_NONE / Context.tile_list_lengths() of a tile that overflowed
 
-KERNEL_CONSTANT_PATTERNS = {       # file -> [(regular expression with one group, value it has to give)]
-    "f3ds_kernels.inc": [
-        (r"constexpr int NT_TILE = (\d+);", NT_TILE), (r"#define F3DS_NT_RING1 (\d+)\n", NT_RING1), (r"#define F3DS_NT_SLOTS (\d+)\n", NT_SLOTS),
-        (r"constexpr uint32_t VL_MAX_RUN = (\d+);", VL_MAX_RUN), (r"#define F3DS_VT_TILE (\d+)\n", VT_TILE), (r"constexpr uint32_t VT_TAB = VT_TILE / (\d+);", 2),
-        (r"constexpr uint32_t VT_ENT_MAX = VT_TAB \* (\d+) / 8;", 5), (r"constexpr uint32_t VG_CHUNK = (\d+);", VG_CHUNK), (r"constexpr uint32_t RL_LDS_CAP = (\d+);", RL_LDS_CAP),
-        (r"constexpr uint32_t HT_CAP = (\d+);", HT_CAP), (r"\(uint32_t\)f\.sv\.V > (\d+)u \* f\.S0;", BY_WAVE_RATIO), (r"&& V <= (\d+)u \* S0;", BY_WAVE_RATIO),
-        (r"const bool fits = active && cnt \+ \(gv >= 0 \? 1u : 0u\) <= (\d+)u && V", HT_ROW), (r"const bool fits = live && cnt \+ \(gv >= 0 \? 1u : 0u\) <= (\d+)u;", HT_ROW),
-        (r"__syncthreads_or\(e - s (>) VL_MAX_RUN\)", ">"), (r"atomicAdd\(&s_ent, 1u\) (>=) VT_ENT_MAX", ">="),
-        (r"if \(sl (<) NT_RING1\) \{ hw\[i\]", "<"), (r"if \(sl (<) NT_SLOTS\) \{ hw\[i\]", "<"),
-        (r"constexpr uint32_t SW_TILE_NONE = 0x(FFFFFFFF)u;", "FFFFFFFF")],
-    "f3ds_algo.h": [
-        (r"#define F3DS_R_STACK (\d+)\n", R_STACK), (r"#define F3DS_R_ROUNDS (\d+) ", R_ROUNDS),
-        (r"a_sweep_tag\(unsigned sweep\) \{ return \(unsigned char\)\(\(sweep % (\d+)u\) \+ 1u\); \}", TAG_PERIOD),
-        (r"a_sweep_needs_clear\(unsigned sweep\) \{ return sweep % (\d+)u == 0u; \}", TAG_PERIOD)],
+KERNEL_CONSTANTS = {       # name of P.constant() -> the value the cases assume
+    "NT_TILE": NT_TILE, "NT_RING1": NT_RING1, "NT_SLOTS": NT_SLOTS, "VL_MAX_RUN": VL_MAX_RUN, "VT_TILE": VT_TILE, "VT_TAB": VT_TILE // 2, "VT_ENT_MAX": VT_ENT_MAX,
+    "VG_CHUNK": VG_CHUNK, "RL_LDS_CAP": RL_LDS_CAP, "HT_CAP": HT_CAP, "HT_ROW": HT_ROW, "QL": QL, "TAG_PERIOD": TAG_PERIOD, "R_STACK": R_STACK, "R_ROUNDS": R_ROUNDS,
+    "BY_WAVE_RATIO": BY_WAVE_RATIO, "SW_TILE_NONE": TILE_NONE,
 }
-QL_PATTERN = r"static constexpr uint32_t QL = (\d+);"      # (defined in two kernels: both have to say 64)
+# The side of each limit the limit itself falls on, by the cases that sit on it from both sides (name of the limit -> (the case that still fits, the first that does not)):
+# what the comparison operators of the kernels decide.  test_vccs_clouds_cpu.py asserts that the pairs are in the case list with the conditions that say so.
+BOUNDARY_CASES = {
+    "VL_MAX_RUN": ("s-voxel-of-256-points", "s-voxel-of-257-points"),       # e - s > VL_MAX_RUN: a voxel of exactly 256 points stays on the tile path
+    "VT_ENT_MAX": ("s-tile-of-1280-voxels", "s-tile-of-1281-voxels"),       # the entry after the 1280th is refused (>=, counted from 0)
+    "RL_LDS_CAP": ("r-every-voxel-a-seed-12287", "r-every-voxel-a-seed-12288"),
+}
+# The two limits no lattice block sits on from both sides (no block gives a largest one-ring of 443..455 with every two-ring fitting, nor a two-ring of 897..900): their
+# comparisons are one-line predicates beside the constants, and these patterns are aimed at those definition lines of f3ds_kernels.inc.
+PREDICATE_PATTERNS = [
+    (r"__host__ __device__ constexpr bool nt_ring1_holds\(uint32_t sl\) \{ return sl (<) \(uint32_t\)NT_RING1; \}", "<"),
+    (r"__host__ __device__ constexpr bool nt_slots_hold\(uint32_t sl\) \{ return sl (<) \(uint32_t\)NT_SLOTS; \}", "<"),
+]
 
 
-def read_kernel_constants(csrc_dir):
-    """[(file, pattern, value found or None, value expected)] for every constant above, from its defining line."""
-    out = []
-    for name, pats in KERNEL_CONSTANT_PATTERNS.items():
-        text = open(os.path.join(csrc_dir, name)).read()
-        for pat, want in pats:
-            m = re.findall(pat, text)
-            have = m[0] if len(m) == 1 else None
-            out.append((name, pat, int(have) if have is not None and isinstance(want, int) else have, want))
+def read_predicates(csrc_dir):
+    """[(pattern, operators found, operator expected)] of the predicate definitions above."""
     text = open(os.path.join(csrc_dir, "f3ds_kernels.inc")).read()
-    m = re.findall(QL_PATTERN, text)
-    out.append(("f3ds_kernels.inc", QL_PATTERN, [int(x) for x in m], [QL, QL]))
-    return out
+    return [(pat, re.findall(pat, text), want) for pat, want in PREDICATE_PATTERNS]
 
 
 # ------------------------------------------------------------------------------------------------ the generator
